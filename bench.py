@@ -25,6 +25,18 @@ Extra objects on the JSON line:
 config.tflop_per_sample is the dense algorithmic count; config.tflop_per_sample_executed subtracts the
 work whose result is exactly zero and therefore skipped (MLM-head backward of unlabelled rows, backward of rows behind a
 sequence's last unmasked key, attention over masked-out keys: DESIGN.md S2/S3); step_mfma_frac uses the executed count.
+
+--dump-outputs DIR writes what the LAST timed step of the headline returned -- the forward's losses, prediction scores and
+relation outputs, the heads' logits -- and the parameters after its AdamW update, as DIR/<name>.npy (float32; float64 where
+the tensor is), rank 0 only.  An array of more than 2^20 elements is a seeded sample of 2^20 of its elements (the positions
+depend on the array's name and shape only), so the files stay below 64 MB and two builds run with the same arguments can be
+compared output for output: the inputs (weights, batches, dropout seeds) are fixed by the arguments, and the headline runs
+in deterministic mode, so the step computes the same bits from them every run.
+
+The headline step forms every fp32 sum in a fixed order (model.deterministic = True).  With fp32 atomics instead
+(--atomic-sums) each step differs from run to run in the last bits; through the bf16 weight copies those differences grow
+over the warm-up and timed steps until whole outputs differ by bf16 ulps.  The ordered sums cost a few tenths of a percent
+of the step, inside the run-to-run spread; the secondary leg `atomic_sums` times the other mode.
 """
 import argparse
 import json
@@ -177,8 +189,8 @@ def main():
     ap.add_argument("--sync-prologue", action="store_true", help="A/B: the step prologue on the compute stream (model.async_prologue = False)")
     ap.add_argument("--scores-fp32", action="store_true", help="return the prediction scores as fp32 (model.scores_dtype = torch.float32)")
     ap.add_argument("--no-dp-reference-legs", action="store_true", help="skip the N > 1 readiness legs (paired weight gradients on the plain step; bf16 wire under the wrapper)")
-    ap.add_argument("--no-deterministic", action="store_true", help="skip the secondary measurement in deterministic mode")
-    ap.add_argument("--deterministic", action="store_true", help="run the HEADLINE in deterministic mode (model.deterministic = True)")
+    ap.add_argument("--no-deterministic", action="store_true", help="skip the secondary measurement in the summation mode the headline does not use")
+    ap.add_argument("--atomic-sums", action="store_true", help="run the HEADLINE with fp32 atomics (model.deterministic = False): outputs differ run to run")
     ap.add_argument("--no-scores-fp32", action="store_true", help="skip the secondary measurement with fp32 prediction scores (the reference's dtype)")
     ap.add_argument("--no-reference-default", action="store_true", help="skip the secondary measurement of the reference's own default model "
                     "(bert-large: 24-layer d=1024, T=P=40, batch 32: REF:train.py:28,32,38)")
@@ -186,7 +198,13 @@ def main():
                     help="reference-default: measure ONLY the reference's default model and print its record (tools; never the driver's line)")
     ap.add_argument("--no-box-probe", action="store_true", help="skip the three fixed yardstick launches in front of the headline (the `box` object)")
     ap.add_argument("--rank-report", action="store_true", help="N > 1 diagnostics even on one process: per-rank step times, exposed tail (on by default for N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (and the parameters after it) "
+                    "as DIR/<name>.npy: float32 / float64, a seeded sample of arrays above 2^20 elements")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.preset != "headline":
+        ap.error("--dump-outputs writes the headline step's outputs: --preset headline only")
     # (rocm-smi is a child process: started before anything here initialises HIP, and only with the box yardstick)
     smi = smi_readings() if (int(os.environ.get("RANK", 0)) == 0 and not a.no_box_probe) else None
 
@@ -286,8 +304,7 @@ def main():
     model.return_scores = True            # the reference returns the six score tensors; keep them materialised
     if a.scores_fp32:
         model.scores_dtype = torch.float32
-    if a.deterministic:
-        model.deterministic = True
+    model.deterministic = not a.atomic_sums           # (process-wide: every leg below runs in the headline's mode unless it says otherwise)
     targs = default_args(train_batch_size=a.batch, learning_rate=5e-5)
     opt, sched = build_optimizer(model, targs, num_train_optimization_steps=10 * (a.steps + a.warmup))
     dp = (parallel.DataParallel(model, opt, bucket_mb=a.bucket_mb, force_dynamic_queue=a.force_dp, wire_dtype=torch.bfloat16 if a.dp_wire == "bf16" else None,
@@ -297,8 +314,10 @@ def main():
     row_frac = []
     tail_events = []       # instrumented leg only: (before, after) finish_backward on the compute stream = the EXPOSED part of the exchange
 
-    def step(i):
-        out, _ = model(**pool[i % len(pool)])
+    def step(i, keep=None):
+        out, logits = model(**pool[i % len(pool)])
+        if keep is not None:                              # (--dump-outputs: the last timed step's returned tensors, read after the timed region)
+            keep.append((out, logits))
         out[0].mean().backward()
         row_frac.append(getattr(model, "last_backward_row_fraction", 1.0))      # (known on the host once backward has sized its launches)
         if dp is not None:
@@ -323,10 +342,11 @@ def main():
         step(i)
     torch.cuda.synchronize()
     barrier()
+    kept = []
     t0 = time.perf_counter()
     last = None
     for i in range(a.steps):
-        last = step(a.warmup + i)
+        last = step(a.warmup + i, keep=kept if (a.dump_outputs and i == a.steps - 1) else None)
     host_enqueued = time.perf_counter() - t0              # every call of the K steps has RETURNED: the host's side of the region (queue busy)
     torch.cuda.synchronize()
     own_done = time.perf_counter() - t0                   # this rank's GPU is done (the contract's value is taken behind the barrier)
@@ -348,6 +368,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t)
     loss = float(last.detach())
+    dumped = dump_outputs(a.dump_outputs, *kept[0], model) if (kept and rank == 0) else None
+    kept.clear()
     # The roofline leg: the SAME K steps once more, bracketed the same way, with a HIP event pair around every GEMM / attention launch
     # on the launch stream.  Kept out of the headline region because the instrumentation is not free: ~340 event records per step
     # are ~340 extra packets in the queue between kernels (round 2 timed both in one pass: 16.4 ms per step against 15.9 without the
@@ -408,18 +430,20 @@ def main():
         scores_fp32 = leg_record(sel, note="model.scores_dtype = torch.float32: the six returned prediction-score tensors in the reference's dtype "
                                            "(REF:MMBertForPretraining.py:445-449); same losses and gradients as the headline step")
 
-    # Secondary: model.deterministic = True -- ordered sums instead of fp32 atomics (CE loss sums, the heads' skinny products, bias /
-    # LayerNorm partial sums, the embedding scatter through per-id run sums): bit-identical losses and gradients run to run
-    # (tests/test_train_gpu.py::test_deterministic_mode_gives_bit_identical_steps); what it costs in the step is this leg against the headline.
+    # Secondary: the other summation mode.  model.deterministic = True forms the sums that fp32 atomics would make (CE loss sums, the
+    # heads' skinny products, bias / LayerNorm partial sums, the embedding scatter through per-id run sums) in a fixed order:
+    # bit-identical losses and gradients run to run (tests/test_train_gpu.py::test_deterministic_mode_gives_bit_identical_steps).
+    # What one mode costs against the other is this leg against the headline.
     det_leg = None
     if not a.no_deterministic:
         was_det = model.deterministic
-        model.deterministic = True
+        model.deterministic = not was_det
         try:
             dl = timed_leg(step)
         finally:
             model.deterministic = was_det
-        det_leg = leg_record(dl, note="model.deterministic = True (mmbert_set_deterministic): every fp32 sum in a schedule-independent order; "
+        det_leg = leg_record(dl, note="model.deterministic = False: fp32 atomics, sums in schedule order, not reproducible run to run" if was_det else
+                                      "model.deterministic = True (mmbert_set_deterministic): every fp32 sum in a schedule-independent order; "
                                       "bit-identical losses and gradients run to run")
 
     # Secondary (N > 1 readiness): the weight gradients per layer PAIR instead of all layers in one call -- the form the data-parallel
@@ -550,12 +574,14 @@ def main():
     if scores_fp32 is not None:
         res["scores_fp32"] = scores_fp32
     if det_leg is not None:
-        res["deterministic"] = det_leg
+        res["atomic_sums" if not a.atomic_sums else "deterministic"] = det_leg
     if paired is not None:
         res["paired_wgrads"] = paired
     if wire_leg is not None:
         res["dp_wire_bf16"] = wire_leg
-    res["config"]["deterministic"] = bool(a.deterministic)
+    res["config"]["deterministic"] = not a.atomic_sums
+    if dumped is not None:
+        res["outputs_dumped"] = dumped
     if train_only is not None:
         res["train_only"] = train_only
     if fused is not None:
@@ -679,6 +705,45 @@ def reference_default_leg(a, dev, ops, wrap_state):
     del model, opt, pool
     torch.cuda.empty_cache()
     return rec
+
+
+# names of the forward's 13-tuple (REF:MMBertForPretraining.py:445-449; the text / visual / speech loss slots are None)
+OUTPUT_NAMES = ("joint_loss", None, None, None, "ap_loss", "label_loss", "nce", "text_scores", "text_rel",
+                "visual_scores", "visual_rel", "speech_scores", "speech_rel")
+DUMP_ELEMENTS = 1 << 20          # per file: 12 files at most, float32 -> about 50 MB in all
+
+
+def sample_array(t, name, n=DUMP_ELEMENTS):
+    """``t`` on the host as float32 (float64 if it is): whole up to ``n`` elements, else the elements at ``n`` positions drawn from a
+    generator seeded by ``name`` (same name and shape -> same positions; drawn with replacement, in increasing order)."""
+    import zlib
+    t = t.detach()
+    if t.numel() > n:
+        g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+        pos = torch.randint(0, t.numel(), (n,), generator=g).sort().values
+        t = t[tuple(ix.to(t.device) for ix in torch.unravel_index(pos, t.shape))]
+    return t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+
+
+def dump_outputs(path, out, logits, model):
+    """--dump-outputs: the 13-tuple and the heads' logits one step returned, and every parameter after that step's update
+    (``params_after_step``: a share of DUMP_ELEMENTS per parameter by size, in parameter-name order), as ``path/<name>.npy``.
+    Returns the record's description of the files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: t for name, t in zip(OUTPUT_NAMES, out) if name is not None and t is not None}
+    if logits is not None:
+        arrays["logits"] = logits
+    desc = {}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), sample_array(t, name))
+        desc[name] = {"shape": list(t.shape), "sampled": t.numel() > DUMP_ELEMENTS}
+    params = sorted(model.named_parameters(), key=lambda kv: kv[0])
+    total = sum(p.numel() for _, p in params)
+    parts = [sample_array(p, n, n=max(1, DUMP_ELEMENTS * p.numel() // total)).reshape(-1) for n, p in params]
+    np.save(os.path.join(path, "params_after_step.npy"), np.concatenate(parts))
+    desc["params_after_step"] = {"shape": [total], "sampled": True, "parameters": len(params)}
+    return {"dir": path, "arrays": desc}
 
 
 def exposed_tail(events, world, dev):
