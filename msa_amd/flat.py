@@ -17,6 +17,7 @@ embeddings; the tied word embedding last) so buckets can be reduced while backwa
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, List, Tuple
 
 import numpy as np
@@ -149,6 +150,7 @@ class FlatParams:
         self._ndesc, self._ntiles = len(descs), tile0
         self._version = -1
         self.grads_dirty = False             # set by backward, cleared by the fused zero_grad in AdamW
+        self._owner = weakref.ref(model)     # (join_side_writers)
         # ---- lazy zero (round 4): gradients that ONE weight-gradient launch per backward produces whole (the encoder's dense weights,
         # the tied word-embedding table) need no zero fill between optimizer steps -- the first launch of the next backward overwrites
         # them (accumulate = 0) instead of reading zeros and adding.  What torch does with zero_grad(set_to_none=True): the old gradient
@@ -267,6 +269,14 @@ class FlatParams:
         ev = self.__dict__.pop("_t_event", None)
         if ev is not None:
             torch.cuda.current_stream().wait_event(ev)
+
+    def join_side_writers(self):
+        """Before the optimizer writes ``grads`` (update, zero fill): the current stream waits for gradient launches the owning model still
+        has on its side streams -- a backward pass that raised between their fork and their join leaves them running
+        (model._join_side_writers)."""
+        m = self._owner()
+        if m is not None:
+            m._join_side_writers()
 
     def mark_synced(self):
         """The bf16 copies were just refreshed by the optimizer kernel itself."""

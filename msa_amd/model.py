@@ -295,19 +295,38 @@ def _late_wgrad(top, prob, defer: bool):
     of 9 - 360 short tiles on the serial tail of backward.  Otherwise (a gradient hook wants final gradients early, or no trunk backward
     follows): launched here."""
     if defer:
-        pend = top.__dict__.setdefault("_late_wgrads", [])
+        pend = _late_pending(top)
         if any(q[2] is prob[2] for q in pend):                  # a second backward stage writing the same gradient: never two writers in one launch
             _flush_late_wgrads(top)
-            pend = top.__dict__.setdefault("_late_wgrads", [])
+            pend = []
+        if not pend:
+            top.__dict__["_late_wgrads"] = (torch._C._current_graph_task_id(), pend)
         pend.append(prob)
     else:
         _wgrad(top, [prob])
 
 
+def _late_pending(top):
+    """The few-row problems queued in ``top._late_wgrads`` = (backward pass, [problems]) by THIS backward pass.  Each entry is tagged with
+    the autograd graph task that queued it: two graphs differentiated in one backward pass share it (their problems are this pass's), while
+    a list left by a backward pass that raised before the trunk flushed it belongs to another one -- it is never flushed into a later
+    pass's gradients (_take_late_wgrads drops it)."""
+    pend = top.__dict__.get("_late_wgrads")
+    return pend[1] if pend is not None and pend[0] == torch._C._current_graph_task_id() else []
+
+
+def _take_late_wgrads(top):
+    """Pops ``top._late_wgrads``: this backward pass's problems, or [] (a stale list is dropped)."""
+    late = _late_pending(top)
+    top.__dict__.pop("_late_wgrads", None)
+    return late
+
+
 def _flush_late_wgrads(top, long_probs=(), deferred=False):
-    """The deferred dense problems (``long_probs``, all of the backward's row count) and whatever waits in ``top._late_wgrads``: as ONE
-    call per 12 layers when ``deferred`` (the few-row problems behind the last one's), else the few-row problems one launch each."""
-    late = top.__dict__.pop("_late_wgrads", None) or []
+    """The deferred dense problems (``long_probs``, all of the backward's row count) and whatever this backward pass queued in
+    ``top._late_wgrads``: as ONE call per 12 layers when ``deferred`` (the few-row problems behind the last one's), else the few-row
+    problems one launch each."""
+    late = _take_late_wgrads(top)
     long_probs = list(long_probs)
     if not deferred or not long_probs:
         for c in range(0, len(long_probs), 48):
@@ -819,7 +838,7 @@ class _TrunkFn(torch.autograd.Function):
         compact, t.compact = t.compact, None                      # (rows in the caller's order, their gradients): set by the MLM head
         # no MLM-head launch has overwritten a dropped table gradient (no labelled row): zero it before the embedding rows are added / the
         # slice is reduced -- unless that launch waits in the deferred call (then after the encoder's backward, below: a no-op)
-        if not any(q[2] is w["g_word_pad"] for q in (top.__dict__.get("_late_wgrads") or ())):
+        if not any(q[2] is w["g_word_pad"] for q in _late_pending(top)):
             top._flat.settle([w["g_word_pad"]])
         # ONE collector for the LayerNorm' gamma / beta sums of the whole backward -- the MLM head's call (already in it), the sparse top
         # layer's two, the dense layers', the embedding stage's: one reduce launch at the end instead of seven (a data-parallel hook
@@ -925,7 +944,9 @@ class _ScalarLoss(torch.Tensor):
     0-dim tensor ``mean()`` is the identity, yet torch launches a reduction for it, a fill for the implicit unit gradient and a division in
     ``MeanBackward`` -- three ATen launches per step in front of the heads' backward.  Here ``mean()`` of the scalar returns the scalar and
     ``backward()`` without a gradient seeds a cached device-side 1.0: the same graph, the same values, no launch.  Everything else is
-    ``torch.Tensor`` (``.item()``, arithmetic, ``.detach()``, a ``mean`` with arguments)."""
+    ``torch.Tensor`` (``.item()``, arithmetic, ``.detach()``, a ``mean`` with arguments).  The cached seed never reaches user code: a tensor
+    hook on the loss receives the root gradient itself (and may change it in place), ``.grad`` of a leaf or after ``retain_grad()`` may
+    keep it -- then the seed is a fresh tensor, as torch makes it."""
 
     def mean(self, *args, **kwargs):
         if self.dim() == 0 and not args and not kwargs:
@@ -933,11 +954,16 @@ class _ScalarLoss(torch.Tensor):
         return super().mean(*args, **kwargs)
 
     def backward(self, gradient=None, retain_graph=None, create_graph=False, inputs=None):
-        if gradient is None and self.dim() == 0 and not create_graph:
-            key = (self.dtype, self.device)
-            gradient = _ones.get(key)
-            if gradient is None:
-                gradient = _ones[key] = torch.ones((), dtype=self.dtype, device=self.device)
+        if gradient is None and not create_graph:
+            with torch._C.DisableTorchFunctionSubclass():       # (plain attribute reads: no __torch_function__ round trip for each)
+                if self.dim() == 0:
+                    if self._backward_hooks or self.retains_grad or self.grad_fn is None:
+                        gradient = torch.ones((), dtype=self.dtype, device=self.device)
+                    else:
+                        key = (self.dtype, self.device)
+                        gradient = _ones.get(key)
+                        if gradient is None:
+                            gradient = _ones[key] = torch.ones((), dtype=self.dtype, device=self.device)
         return torch.autograd.backward(self, gradient, retain_graph, create_graph, inputs=inputs)
 
 
@@ -1088,7 +1114,9 @@ class _MLMHeadFn(torch.autograd.Function):
         # the few-row weight gradients wait for the trunk's backward (which follows in this pass) unless a hook wants them final before it
         late = (ctx.trunk is not None and ctx.needs_input_grad[0] and ctx.top.grad_hook is None and ctx.top.head_grad_hook is None
                 and getattr(ctx.top, "late_wgrads", True))
-        if ctx.top.__dict__.get("_late_wgrads"):                 # (left by a backward whose trunk stage never ran)
+        if ctx.top.__dict__.get("_late_wgrads"):
+            # queued by another graph's MLM head in this backward pass (two graphs, one backward): launched now; a list that a backward
+            # pass which raised left behind is dropped instead (_late_pending)
             _flush_late_wgrads(ctx.top)
         if ctx.compact:
             y_c, pre_c, t0_c, mean_c, rstd_c, t_c, logits_c, labels_c, bounds_c, inv, lse, sel = ctx.saved_tensors
@@ -1191,6 +1219,24 @@ class _GpuModelBase(nn.Module):
     def _next_seed(self) -> int:
         self._calls += 1
         return self._seed * 1000003 + self._calls
+
+    def _join_side_writers(self):
+        """The current stream waits for the gradient launches this model queued on side streams and has not joined yet (the deferred
+        weight-gradient call, the heads' backward levels).  A backward pass joins them itself; one that raised between the fork and the
+        join leaves them running, so the optimizer calls this (flat.FlatParams.join_side_writers) before it writes the gradients, and so
+        does the next forward pass."""
+        _join_wgrads(self)
+        _join_heads(self)
+
+    def _drop_leftovers(self):
+        """At a forward pass, no backward pass is in flight: what one that raised half-way left behind goes -- side-stream launches are
+        joined, the few-row weight-gradient problems it had queued and the [CLS]-row records of a forward pass that stopped before the
+        heads are dropped (the LayerNorm' collector: see _encode)."""
+        self._join_side_writers()
+        d = self.__dict__
+        d.pop("_late_wgrads", None)
+        d.pop("_heads_src", None)
+        d.pop("_heads_pre", None)
 
     def _layer_grads_done(self, i: int):
         if self.grad_hook is not None:
@@ -1338,6 +1384,7 @@ class _GpuModelBase(nn.Module):
         lnd = self.__dict__.get("_lnd")
         if lnd is not None and lnd.items and torch.is_grad_enabled():
             lnd.drop()                 # a backward pass that raised half-way left its LayerNorm' sums behind: no pass is in flight at a forward
+        self._drop_leftovers()
         B, T = passes[0]["ids"].shape
         cfg = self.config
         if T > cfg.max_position_embeddings:
@@ -2111,16 +2158,22 @@ class MMBertForPretraining(_GpuModelBase):
                     and self.config.hidden_size % 16 == 0
                     and all(q.grad is not None for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight)))
 
-    def _run_heads(self, first, ap_v, ap_s, sentiment, dev, B, mlm=None):
+    def _run_heads(self, first, ap_v, ap_s, sentiment, dev, B, mlm=None, coop=False):
         """The heads on the [3B, H] [CLS] rows: the fused kernels (csrc/heads.hip) where they apply, else the eager form.
+        ``coop``: the forward pass's _coop_heads_apply() -- the ONE decision the MLM head acted on too (it then left the rows in the encoder
+        output and ``first`` is a placeholder): not evaluated a second time here.
         (A captured hipGraph of the eager [B,H]-sized glue -- forward and backward, ~200 dependent launches -- was built and
         measured in round 1: no gain; the device time of the tiny kernels, not their dispatch, is the cost.)"""
         src = self.__dict__.pop("_heads_src", None)
         grads_ok = all(q.grad is not None for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight))
-        fused = self.fused_heads and sentiment is not None and first.is_cuda and self.num_labels in (1, 7) and grads_ok
-        coop = fused and getattr(self, "coop_heads", True) and B <= 128 and first.shape[1] % 16 == 0
+        fused = coop or (self.fused_heads and sentiment is not None and first.is_cuda and self.num_labels in (1, 7) and grads_ok)
         if src is not None and not (coop and src[2] == first.data_ptr()):
-            first = src[0].index_select(0, src[1]).float()      # (the rows were left to a path that does not run after all: gather them now)
+            # the rows were left to the level-launch heads, which do not run on this placeholder after all: gathered into it now, in place --
+            # ``first`` is what carries the heads' gradient back to the [CLS] rows (a fresh gather would have no autograd edge to the trunk)
+            if src[2] != first.data_ptr():
+                raise RuntimeError("msa_amd: the [CLS] rows left for the heads belong to another forward pass")
+            with torch.no_grad():
+                first.copy_(src[0].index_select(0, src[1]))
             src = None
         if fused and not coop and B > 32:
             fused = False
@@ -2179,15 +2232,15 @@ class MMBertForPretraining(_GpuModelBase):
         want_rows = torch.is_grad_enabled() and getattr(self, "sparse_mlm_backward", True) and labels.is_cuda
         y, plan, lens, rows = self._encode(passes, labels, want_rows, packed=pk)
         trunk, self._last_trunk = self._last_trunk, None
-        self._heads_read_rows = self._coop_heads_apply(sentiment, B)
-        if self._heads_read_rows and getattr(self, "heads_side_stream", True) and y.is_cuda and y.is_contiguous():
+        coop = self._heads_read_rows = self._coop_heads_apply(sentiment, B)
+        if coop and getattr(self, "heads_side_stream", True) and y.is_cuda and y.is_contiguous():
             # the heads' forward levels below the losses go out NOW, on the side stream, beside the MLM head's launches (_HeadsStepFn.prelaunch)
             _HeadsStepFn.prelaunch(self, y, plan["first"], (ap_v.to(dev).view(-1).long(), ap_s.to(dev).view(-1).long()),
                                    sentiment.to(dev).view(-1).float())
         # first = [3B, H]: the [CLS] rows of every sequence; joint_loss = alpha * (mlm_t + mlm_v + mlm_s) / 3 + heads_loss  (:427, :443)
         mlm, logits, first = _MLMHeadFn.apply(y, self.cls.predictions.transform.LayerNorm.weight, self, labels, plan["bounds"], plan["bounds_dev"],
                                               self.return_scores, rows, plan["first"], trunk)
-        joint_loss, ap_loss, label_loss, nce, logits_out, t_rel, v_rel, s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=mlm)
+        joint_loss, ap_loss, label_loss, nce, logits_out, t_rel, v_rel, s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=mlm, coop=coop)
         scores = (None, None, None)
         if logits is not None:
             b = plan["bounds"]
@@ -2234,10 +2287,10 @@ class MMBertForPretraining(_GpuModelBase):
         # the visual padding sits in the MIDDLE of the fused sequence: valid-first packing over the row set, not over a prefix
         y, plan, lens, rows = self._encode(passes, labels, want_rows, rowset=getattr(self, "fused_rowset_packing", True), packed=pk)
         trunk, self._last_trunk = self._last_trunk, None
-        self._heads_read_rows = self._coop_heads_apply(sentiment, B)
+        coop = self._heads_read_rows = self._coop_heads_apply(sentiment, B)
         mlm, logits, first = _MLMHeadFn.apply(y, self.cls.predictions.transform.LayerNorm.weight, self, labels, plan["bounds"], plan["bounds_dev"],
                                               self.return_scores, rows, plan["first"].repeat(3), trunk)   # the one [CLS] row in the t / v / s slots
-        joint_loss, ap_loss, label_loss, nce, logits_out, _t_rel, v_rel, _s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=mlm)
+        joint_loss, ap_loss, label_loss, nce, logits_out, _t_rel, v_rel, _s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=mlm, coop=coop)
         scores = None if logits is None else logits.view(B, lens[0], -1)[:, :, :V]
         if scores is not None and self.scores_dtype != scores.dtype:
             scores = scores.to(self.scores_dtype)

@@ -109,6 +109,7 @@ class AdamW:
             self._bind()
         flat = self._flat
         self._steps += 1
+        flat.join_side_writers()             # (left by a backward that raised: nothing may still add into the gradients the kernel reads and zeroes)
         flat.wait_transposes()               # (a step without a backward in between: the last step's transposed copies still read the bf16 copy)
         flat.settle()                        # a lazy gradient no backward has written since the last step counts as zero
         flat.attach_lazy()
@@ -124,11 +125,17 @@ class AdamW:
     def zero_grad(self, set_to_none: bool = False):
         flat = self._flat
         if flat is None:
+            # (not bound before the first step(); the parameters may already live in a model's flat storage: join its side streams first)
+            refs = (getattr(p, "_mmb_flat", None) for g in self.param_groups for p in g["params"])
+            storage = next((r[0] for r in refs if r is not None), None)
+            if storage is not None:
+                storage.join_side_writers()
             for g in self.param_groups:
                 for p in g["params"]:
                     if p.grad is not None:
                         p.grad.zero_()
             return
+        flat.join_side_writers()             # (left by a backward that raised: see step())
         if flat.grads_dirty:                 # step() already zeroed the buffer in the same kernel
             flat.grads.zero_()
             flat.grads_dirty = False

@@ -493,3 +493,30 @@ def test_inputs_embeds_alone_raises_like_the_reference_does():
         m(input_ids=torch.zeros(2, 5, dtype=torch.long), inputs_embeds=x)
     with pytest.raises(ValueError, match="either input_ids or inputs_embeds"):
         m()
+
+
+def test_scalar_loss_seed_is_never_handed_to_user_code():
+    """model._ScalarLoss seeds backward() with a cached 1.0 (no fill launch per step).  User code that sees the root gradient must get a
+    fresh one: a hook on the loss that changes its gradient in place, or a retained ``loss.grad`` zeroed afterwards, would otherwise change
+    the seed of every later step.  Each step's gradient is compared with the plain tensor's (implicit ones seed) exactly."""
+    from msa_amd.model import _ScalarLoss
+    x = torch.tensor([0.5, -1.25, 2.0, 3.0], dtype=torch.float32, requires_grad=True)
+    f = lambda: (x * x * x).sum() * 0.75
+    (ref,) = torch.autograd.grad(f(), x)
+    assert float(ref.abs().min()) > 0
+    for _ in range(3):                                     # hooked: doubled, every time (not 2x, 4x, 8x)
+        x.grad = None
+        loss = f().as_subclass(_ScalarLoss)
+        loss.register_hook(lambda g: g.mul_(2.0))
+        loss.backward()
+        assert torch.equal(x.grad, 2.0 * ref), (x.grad, ref)
+    for _ in range(3):                                     # retained and zeroed: the next step still gets a unit seed
+        x.grad = None
+        loss = f().as_subclass(_ScalarLoss)
+        loss.retain_grad()
+        loss.mean().backward()
+        assert torch.equal(x.grad, ref) and float(loss.grad) == 1.0
+        loss.grad.zero_()
+    x.grad = None                                          # and the plain (cached) path afterwards
+    f().as_subclass(_ScalarLoss).backward()
+    assert torch.equal(x.grad, ref)

@@ -1477,6 +1477,48 @@ def test_level_launch_heads_equal_the_multi_launch_heads_and_read_their_rows_fro
     assert all(torch.equal(viay["grads"][n], new["grads"][n]) for n in names)
 
 
+@pytest.mark.parametrize("patched", ["decision", "heads_site"])
+def test_the_cls_rows_gradient_reaches_the_trunk_whichever_heads_run(patched):
+    """The level-launch heads read the [CLS] rows from the encoder output themselves; the MLM head then hands out only a placeholder
+    ``first`` that carries the autograd edge.  Whether that happens and which heads run must be ONE decision (model._coop_heads_apply,
+    taken once per forward pass): if the heads that run are not the ones the rows were left to, the heads' gradient wrt the [CLS] rows
+    must still reach the trunk.  decision: the decision says "level-launch heads" although model.coop_heads is off -- they run, the same
+    step as the default one; heads_site: the heads are told not to run the level-launch form (the rows were left for it) -- the rows are
+    gathered into the placeholder and the multi-launch heads run: the same step as model.coop_heads = False.  Deterministic mode: every
+    parameter gradient BIT-identical to that reference (a dropped edge changes the whole trunk's)."""
+    from msa_amd import ops as _ops
+    cfg = dict(hidden=256, layers=2, heads=4, intermediate=1024, vocab=4096, dataset="mosei", alpha=1.0, beta=1.0)
+    batch = batch_to(synthetic_batch(4, 24, 90, 70, dataset="mosei", vocab=cfg["vocab"], seed=45), DEV)
+    res = {}
+    was = _ops.deterministic()
+    try:
+        _ops.set_deterministic(True)
+        for run in ("warm-up", "patched", "reference"):        # (warm-up: process-wide workspaces that grow on demand take their size)
+            m = build(cfg)
+            if run != "patched":
+                m.coop_heads = patched == "decision"
+            elif patched == "decision":
+                m.coop_heads = False
+                m._coop_heads_apply = lambda sentiment, B: True
+            else:
+                orig = m._run_heads
+                m._run_heads = lambda *a, _o=orig, **k: _o(*a, **dict(k, coop=False))
+            out, _ = m(**batch)
+            read_rows = m._heads_read_rows
+            out[0].mean().backward()
+            torch.cuda.synchronize()
+            res[run] = (read_rows, out[0].detach().clone(), {n: q.grad.float().clone() for n, q in m.named_parameters() if q.grad is not None})
+    finally:
+        _ops.set_deterministic(was)
+    assert res["patched"][0] and res["reference"][0] == (patched == "decision")      # the rows were left in the encoder output
+    assert torch.equal(res["patched"][1], res["reference"][1])
+    g, ref = res["patched"][2], res["reference"][2]
+    assert g.keys() == ref.keys()
+    diff = [n for n in ref if not torch.equal(g[n], ref[n])]
+    assert not diff, diff[:8]
+    assert float(ref["bert.encoder.layer.0.attention.self.query.weight"].abs().max()) > 0
+
+
 def test_scores_dtype_float32_for_numpy_consumers():
     """outputs[7/9/11] are bf16 views by default (documented deviation); ``model.scores_dtype = torch.float32`` hands out what the
     reference does -- fp32 tensors, straight from the vocabulary GEMM's accumulators -- that ``.cpu().numpy()`` accepts

@@ -917,3 +917,148 @@ def test_deterministic_mode_gives_bit_identical_steps(size):
             close(run(dict(ev, skip_padded_backward=False, sparse_top_layer_backward=False)), run(ev), "short cuts off (eval)")
     finally:
         _ops.set_deterministic(was)
+
+
+# What a backward pass leaves on the model between its autograd nodes (round 6): the few-row weight-gradient problems waiting for the
+# trunk's deferred call, the two side streams' joins, and the [CLS]-row record the MLM head hands to the level-launch heads.
+_LEFTOVERS = ("_late_wgrads", "_wgrad_join", "_heads_join", "_heads_src")
+
+
+def _queued_late_wgrads(m):
+    """The few-row weight-gradient problems waiting in model._late_wgrads = (backward pass, problems)."""
+    pend = m.__dict__.get("_late_wgrads")
+    return [] if pend is None else pend[1]
+
+
+@pytest.mark.parametrize("where,size,zero_grad", [("trunk_entry", "small", True), ("after_trunk", "small", True), ("in_mlm_head", "small", True),
+                                                  ("trunk_entry", "small", False), ("in_mlm_head", "small", False), ("trunk_entry", "base2", True)])
+def test_a_backward_that_raised_leaks_nothing_into_the_next_step(where, size, zero_grad):
+    """A training loop that catches an exception raised in backward (an out-of-memory error, say), skips the batch and trains on: the next
+    step must be exactly the step a model that never saw the failed backward takes.  Twins with the same weights and seeds: A runs forward
+    on batch 1, a backward that raises (an ordinary Python exception between launches, injected at ``where``), [zero_grad], then a full
+    step on batch 2; B runs the same batch-1 forward with its loss discarded, [zero_grad], and the same batch-2 step.  Deterministic mode,
+    so the flat gradient buffer before the update and the parameters after it are compared BIT for bit.  Injection points, each with the
+    state it leaves asserted at injection time:
+      trunk_entry  -- the start of _EncoderFn.run_backward: the MLM head's tied-decoder and transform problems are queued, not launched;
+      after_trunk  -- behind run_backward: the deferred call (all layers' weight gradients + the few-row ones) is still on its side stream;
+      in_mlm_head  -- between the MLM head's two few-row problems: one is queued, and the heads' backward is still on its side stream.
+    Without zero_grad the failed pass's own launches stay in the buffer (as torch keeps them): the entries it had not written must still
+    be the twin's.  The paths are forced on (the shape rule must not switch them off under the test); base2 = the headline width, so the
+    30 522-row tied decoder's gradient is among the leftovers."""
+    from msa_amd import model as M
+    from msa_amd import ops as _ops
+    from msa_amd import trainer as T_
+    if size == "small":
+        cfg = dict(hidden=256, layers=3, heads=4, intermediate=1024, vocab=4096, dataset="mosei", alpha=1.0, beta=1.0)
+    else:
+        cfg = dict(hidden=768, layers=2, heads=12, intermediate=3072, vocab=30522, dataset="mosei", alpha=1.0, beta=1.0)
+    b1 = batch_to(synthetic_batch(4, 24, 200, 130, dataset="mosei", vocab=cfg["vocab"], seed=81), DEV)
+    b2 = batch_to(synthetic_batch(4, 24, 200, 130, dataset="mosei", vocab=cfg["vocab"], seed=82), DEV)
+    orig_rb, orig_lw = M._EncoderFn.__dict__["run_backward"], M._late_wgrad
+    at_raise = {}
+
+    def state(m):
+        d = m.__dict__
+        return dict(late=len(_queued_late_wgrads(m)), wgrad_join="_wgrad_join" in d, heads_join=bool(d.get("_heads_join")))
+
+    def inject(m):
+        if where == "trunk_entry":
+            def rb(*a, **k):
+                at_raise.update(state(m))
+                raise RuntimeError("injected failure")
+        elif where == "after_trunk":
+            def rb(*a, **k):
+                orig_rb.__func__(*a, **k)
+                at_raise.update(state(m))
+                raise RuntimeError("injected failure")
+        else:
+            calls = []
+
+            def lw(top, prob, defer):
+                if calls:
+                    at_raise.update(state(m))
+                    raise RuntimeError("injected failure")
+                calls.append(prob)
+                return orig_lw(top, prob, defer)
+            M._late_wgrad = lw
+            return
+        M._EncoderFn.run_backward = staticmethod(rb)
+
+    runs = {}
+    was = _ops.deterministic()
+    try:
+        _ops.set_deterministic(True)
+        for twin in ("warm-up", "failed", "clean"):             # (warm-up: process-wide workspaces that grow on demand -- the LayerNorm'
+            m = build(cfg, dropout=0.1)                         # collector's flushes early as it grows -- take their size first)
+            m.train()
+            m.manual_seed(17)
+            m.defer_wgrads = m.late_wgrads = m.wgrad_side_stream = m.coop_heads = m.heads_side_stream = True
+            opt, sched = T_.build_optimizer(m, T_.default_args(train_batch_size=4, learning_rate=1e-3), 10, mode="hf")
+            sched.step()
+            if twin == "warm-up":
+                for b in (b1, b2):
+                    o, _ = m(**b)
+                    o[0].mean().backward()
+                opt.step()
+                del m, o
+                continue
+            o1, _ = m(**b1)
+            assert m._heads_read_rows                            # the level-launch heads run (and read the [CLS] rows beside the graph)
+            partial = None
+            if twin == "failed":
+                inject(m)
+                try:
+                    with pytest.raises(RuntimeError, match="injected failure"):
+                        o1[0].mean().backward()
+                finally:
+                    M._EncoderFn.run_backward, M._late_wgrad = orig_rb, orig_lw
+                if not zero_grad:
+                    torch.cuda.synchronize()
+                    partial = {n: q.grad.detach().clone() for n, q in m.named_parameters() if q.grad is not None}
+            del o1
+            if zero_grad:
+                opt.zero_grad()
+            after_zero_grad = [k for k in _LEFTOVERS if m.__dict__.get(k)]
+            o2, _ = m(**b2)
+            after_forward = [k for k in _LEFTOVERS if m.__dict__.get(k)]
+            o2[0].mean().backward()
+            torch.cuda.synchronize()
+            grads = {n: q.grad.detach().clone() for n, q in m.named_parameters() if q.grad is not None}
+            flat_grads = m._flat.grads.clone()
+            opt.step()
+            torch.cuda.synchronize()
+            runs[twin] = dict(grads=grads, flat_grads=flat_grads, params={n: q.detach().clone() for n, q in m.named_parameters()},
+                              partial=partial, after_zero_grad=after_zero_grad, after_forward=after_forward, loss=o2[0].detach().clone())
+    finally:
+        _ops.set_deterministic(was)
+        M._EncoderFn.run_backward, M._late_wgrad = orig_rb, orig_lw
+    # the injection really left work pending
+    if where == "trunk_entry":
+        assert at_raise["late"] == 2, at_raise                   # tied decoder + MLM transform
+    elif where == "after_trunk":
+        assert at_raise["wgrad_join"], at_raise
+    else:
+        assert at_raise["late"] == 1 and at_raise["heads_join"], at_raise
+    a, b = runs["failed"], runs["clean"]
+    assert torch.equal(a["loss"], b["loss"])
+    assert a["grads"].keys() == b["grads"].keys()
+    if zero_grad:
+        diff = [n for n in b["grads"] if not torch.equal(a["grads"][n], b["grads"][n])]
+        assert not diff, diff[:8]
+        assert torch.equal(a["flat_grads"], b["flat_grads"])
+        diff = [n for n in b["params"] if not torch.equal(a["params"][n], b["params"][n])]
+        assert not diff, diff[:8]
+    else:
+        part = a["partial"]
+        for n in ("bert.embeddings.word_embeddings.weight", "cls.predictions.transform.dense.weight", "cls.predictions.bias"):
+            assert n not in part or not bool(part[n].any()), n  # what the failed pass had queued but not launched is compared whole
+        diff = []
+        for n in b["grads"]:
+            untouched = part[n] == 0 if n in part else torch.ones_like(b["grads"][n], dtype=torch.bool)
+            if not (torch.equal(a["grads"][n][untouched], b["grads"][n][untouched]) and torch.equal(a["params"][n][untouched], b["params"][n][untouched])):
+                diff.append(n)
+        assert not diff, diff[:8]
+    # nothing of the failed pass survives the optimizer's zero_grad (the side streams joined) or the next forward pass
+    if zero_grad:
+        assert not [k for k in a["after_zero_grad"] if k != "_late_wgrads"], a["after_zero_grad"]
+    assert not a["after_forward"] and not b["after_forward"], (a["after_forward"], b["after_forward"])
