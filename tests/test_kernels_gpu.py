@@ -658,6 +658,8 @@ def ref_attention(q, k, v, bias, drop_mask=None, drop_scale=1.0):
 
 @pytest.mark.parametrize("lens,heads,p", [([50], 2, 0.0), ([64, 128], 2, 0.0), ([50, 114, 550], 2, 0.0), ([37, 200], 3, 0.1), ([1425], 1, 0.0)])
 def test_attention_fwd_bwd(ops, lens, heads, p):
+    """ctx, LSE, dQ, dK, dV against the float64 reference, every (sequence, head) block (tests/attention_ref.check)."""
+    from tests import attention_ref as A
     H = heads * 64
     M = sum(lens)
     qkv = bf(rnd(M, 3 * H, seed=40))
@@ -669,22 +671,13 @@ def test_attention_fwd_bwd(ops, lens, heads, p):
     drop = ops.make_drop(p, 777, 3)
     ctx, lse = ops.attn_fwd(qkv.to(DEV), bias.to(DEV), layout, H, drop=drop)
     dqkv = ops.attn_bwd(qkv.to(DEV), ctx, dctx.to(DEV), lse, bias.to(DEV), layout, H, drop=drop)
-    s = 0
-    for i, n in enumerate(lens):
-        x = qkv[s:s + n].float().requires_grad_(True)
-        q, k, v = (x[:, j * H:(j + 1) * H].view(n, heads, 64).transpose(0, 1)[None] for j in range(3))
-        mask = None
-        if p > 0:
-            mask = torch.stack([ops.attn_dropout_mask(n, layout.elem_base_host[i], h, drop, DEV).float().cpu() for h in range(heads)])[None]
-            assert 0.85 < float(mask.mean()) < 0.95
-        out = ref_attention(q, k, v, bias[s:s + n], mask, drop[2])          # [1, heads, n, 64]
-        ref = out[0].transpose(0, 1).reshape(n, H)
-        ref.backward(dctx[s:s + n].float())
-        assert_close(ctx[s:s + n], ref, 2e-2, 2e-2, f"ctx seq{i}")
-        sc = (q @ k.transpose(-1, -2)) * 0.125 + bias[s:s + n][None, None, :]
-        assert_close(lse[s:s + n], torch.logsumexp(sc, -1)[0].t(), 1e-3, 2e-2, f"lse seq{i}")
-        assert_close(dqkv[s:s + n], x.grad, 3e-2, 3e-2, f"dqkv seq{i}")
-        s += n
+    masks = None
+    if p > 0:
+        masks = [torch.stack([ops.attn_dropout_mask(n, layout.elem_base_host[i], h, drop, DEV) for h in range(heads)]).cpu()
+                 for i, n in enumerate(lens)]
+        assert all(0.85 < float(m.float().mean()) < 0.95 for m in masks)
+    ref = A.reference(qkv, bias, lens, heads, masks, drop[2], dctx)
+    A.check(A.outputs(ctx, lse, dqkv), ref, lens, heads, f"lens {lens} heads {heads} p {p}")
 
 
 @pytest.mark.parametrize("lens", [[64], [128, 256], [50, 114, 114, 50, 114], [128, 50]])
@@ -866,16 +859,17 @@ def test_device_split_layout_equals_host_form(ops, heads):
 
 
 def test_attention_rescale_branch(ops):
-    """Force the running max to jump at a later key tile (guide rule 26): spike one key."""
+    """Force the running max to jump at a later key tile (guide rule 26): spike one key; ctx and LSE against the float64
+    reference (tests/attention_ref.check)."""
+    from tests import attention_ref as A
     n, heads, H = 200, 1, 64
     qkv = bf(rnd(n, 3 * H, seed=42) * 0.3)
     qkv[150, H:2 * H] = qkv[3, 0:H] * 40.0          # key 150 aligned with query 3 -> huge score in tile 2
     layout = ops.SeqLayout([n], heads, DEV)
     bias = torch.zeros(n)
-    ctx, _ = ops.attn_fwd(qkv.to(DEV), bias.to(DEV), layout, H)
-    x = qkv.float()
-    ref = ref_attention(x[None, None, :, :H], x[None, None, :, H:2 * H], x[None, None, :, 2 * H:], bias)[0, 0]
-    assert_close(ctx, ref, 2e-2, 2e-2, "rescale")
+    ctx, lse = ops.attn_fwd(qkv.to(DEV), bias.to(DEV), layout, H)
+    ref = A.reference(qkv, bias, [n], heads)
+    A.check(A.outputs(ctx, lse), ref, [n], heads, "rescale")
 
 
 # ------------------------------------------------------------------------- embeddings, CE, AdamW
