@@ -5,6 +5,8 @@ import math
 import pytest
 import torch
 
+from tests import rowwise_ref as RW
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -570,6 +572,13 @@ def test_ln_fwd_bwd(ops, M, H, eps):
     assert_close(dx, xr.grad, 1e-2, 1e-2, "ln dx")
     assert_close(dgamma, g_.grad, 1e-3, 1e-3 * math.sqrt(M), "dgamma")
     assert_close(dbeta, b_.grad, 1e-3, 1e-3 * math.sqrt(M), "dbeta")
+    # the float64 reference (tests/rowwise_ref.py): y, mean, rstd, dx and the gamma / beta sums within their calibrated bounds
+    ref = RW.ln_fwd(x, gamma, beta, eps)
+    for k, got in (("y", out), ("mean", mean), ("rstd", rstd)):
+        RW.check(got, ref[k], f"ln {k}")
+    refb = RW.ln_bwd(dy, x, mean.cpu(), rstd.cpu(), gamma, adds=8)
+    for k, got in (("dx", dx), ("dgamma", dgamma), ("dbeta", dbeta)):
+        RW.check(got, refb[k], f"ln {k}")
 
 
 def test_ln_bwd_deferred_reduce_over_calls_of_different_row_counts(ops):
@@ -606,8 +615,9 @@ def test_ln_bwd_deferred_reduce_over_calls_of_different_row_counts(ops):
 @pytest.mark.parametrize("M,H,n", [(40, 128, 24), (40, 768, 24), (3000, 256, 2500), (2100, 1024, 2050)])
 def test_ln_row_maps_and_dropouts(ops, M, H, n):
     """Row maps on every operand, the post-LN dropout (embedding form) and the branch dropout + second output + bias gradient (encoder
-    form) against torch, masks replayed from mmbert_dropout_mask.  H = 128: the generic kernels; H = 256 k: the lean ones (several
-    trips per wave at the larger row counts: the request-ahead pipeline and the scalar row records)."""
+    form) against torch and the float64 reference, masks replayed from mmbert_dropout_mask.  H = 128: the generic kernels; H = 256 k:
+    the lean ones.  The forward runs one trip here (the lean forward covers 4096 rows per trip); the lean backward runs two at n > 2048
+    (2048 rows per trip).  Row maps over several forward trips: tests/test_rowwise_gpu.py."""
     x, gamma, beta = bf(rnd(M, H, seed=34)), 1 + 0.1 * rnd(H, seed=35), 0.1 * rnd(H, seed=36)
     in_rows = torch.randperm(M, generator=torch.Generator().manual_seed(1))[:n].int()
     out_rows = torch.randperm(M, generator=torch.Generator().manual_seed(2))[:n].int()
@@ -637,6 +647,14 @@ def test_ln_row_maps_and_dropouts(ops, M, H, n):
     xh = (xs.detach() - xs.detach().mean(1, keepdim=True)) * torch.rsqrt(xs.detach().var(1, unbiased=False, keepdim=True) + 1e-5)
     assert_close(dgamma, (g_ref * xh).sum(0), 2e-3, 2e-3 * math.sqrt(n), "dgamma")
     assert_close(dbeta, g_ref.sum(0), 2e-3, 2e-3 * math.sqrt(n), "dbeta")
+    ref = RW.ln_fwd(x, gamma, beta, 1e-5, in_rows=in_rows, out_rows=out_rows, keep=mask.to(torch.uint8), dscale=post[2])
+    RW.check(out, ref["y"], "mapped ln + post dropout")
+    RW.check(mean, ref["mean"], "mapped mean")
+    RW.check(rstd, ref["rstd"], "mapped rstd")
+    refb = RW.ln_bwd(dy, x, mean.cpu(), rstd.cpu(), gamma, dy_rows=out_rows, x_rows=in_rows, post_keep=mask.to(torch.uint8),
+                     post_scale=post[2], pre_keep=m2.to(torch.uint8), pre_scale=pre[2], dx2=True, dbias2=True, adds=8)
+    for k, got in (("dx", dx), ("dx2", dx2), ("dgamma", dgamma), ("dbeta", dbeta), ("dbias2", dbias2)):
+        RW.check(got, refb[k], f"mapped ln bwd {k}")
     # the rows the dy map leaves out (dy_row_limit): zero gradient, nothing read
     lim = int(out_rows.max()) // 2
     dgamma.zero_(); dbeta.zero_()
@@ -958,6 +976,12 @@ def test_cross_entropy_segments(ops):
         valid = labels[a:b] != -100
         assert_close(lse[a:b][valid.to(DEV)], torch.logsumexp(lg.detach(), -1)[valid], 1e-4, 1e-3, "row lse")
     assert float(dl[:, V:].abs().max()) == 0.0
+    # the float64 reference (tests/rowwise_ref.py): losses, row_lse and dlogits within their calibrated bounds
+    ref = RW.ce_fwd(logits, labels, V, bounds, 3)
+    RW.check(loss, ref["loss"], "ce loss")
+    RW.check(lse, ref["row_lse"], "ce row lse")
+    for j, r in RW.ce_bwd(logits, labels, V, bounds, 3, g, lse.cpu(), count=ref["count"]):
+        RW.check(dl[j.to(DEV)], r, "ce dlogits", gathered=True)
     # in-place form (dlogits aliases logits)
     lg_dev = logits.to(DEV).clone()
     ops.ce_bwd(lg_dev, V, labels.to(DEV), bounds.to(DEV), 3, inv, g.to(DEV), lse, lg_dev)
