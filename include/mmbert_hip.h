@@ -416,6 +416,29 @@ int mmbert_id_runs_sum_rows(mmbert_stream_t stream, const void* src, int src_bf1
 int mmbert_adamw(mmbert_stream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags, size_t n,
                  double lr, double beta1, double beta2, double eps, double wd, int step, double gscale, int mode, int zero_grad);
 
+/* The same update with the gradient scale read from the DEVICE scalar coef[0] (one scalar load per wave) instead of a host gscale:
+ * the clip coefficient mmbert_grad_norm writes to out + 2, so that a clipped step neither syncs with the host nor rewrites g.
+ * Same preconditions and writes as mmbert_adamw; coef != NULL. */
+int mmbert_adamw_devscale(mmbert_stream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags, size_t n,
+                          double lr, double beta1, double beta2, double eps, double wd, int step, const float* coef, int mode, int zero_grad);
+
+/* ---- global gradient-norm clipping (torch.nn.utils.clip_grad_norm_) ----
+ * segs: device int64 array of nseg pairs (offset, length) in elements of g[0..n): the elements the norm covers, any offsets and lengths
+ * (0 <= offset, offset + length <= n; parameters pack inside 256-element blocks).  g 16-byte aligned.  Two launches, no float atomics:
+ * every workgroup stores a double partial into workspace (>= MMBERT_GRAD_NORM_WORKSPACE bytes, caller-owned, no other use during the
+ * call), one workgroup folds them in a fixed order -- the result's bits depend on the data alone (deterministic mode or not).
+ * Writes three fp32 device scalars:
+ *   out[0] = the norm of gscale * g over the segments (norm_type 2.0 or +INFINITY; anything else returns -1),
+ *   out[1] = min(1, max_norm / (out[0] + 1e-6)) formed in fp32 as torch does (max_norm / inf = 0; a NaN norm gives NaN),
+ *   out[2] = out[1] * gscale (what mmbert_adamw_devscale applies to g).
+ * max_norm >= 0.  Nothing is read back: the launch is graph-capturable and syncs nothing. */
+#define MMBERT_GRAD_NORM_WORKSPACE 8192
+int mmbert_grad_norm(mmbert_stream_t stream, const float* g, size_t n, const int64_t* segs, int nseg, double norm_type, double max_norm,
+                     double gscale, void* workspace, float* out);
+/* g[e] *= coef[0] for every element e of the segments (same segs / n / alignment rules as mmbert_grad_norm; elements outside them are
+ * not written).  The torch-semantics drop-in msa_amd.optim.clip_grad_norm_ scales .grad in place with out + 1. */
+int mmbert_grad_scale(mmbert_stream_t stream, float* g, size_t n, const int64_t* segs, int nseg, const float* coef);
+
 /* du = dy * gelu_erf'(u), contiguous bf16 (BertPredictionHeadTransform backward, HF:476-480) */
 int mmbert_gelu_bwd(mmbert_stream_t stream, const void* dy, const void* u, void* du, size_t n);
 

@@ -81,6 +81,9 @@ SIGNATURES = {
     "mmbert_id_runs_sum_rows": (I, [P, P, I, I, P, I, I, I, P, I, P, I]),
     "mmbert_skinny_wgrad": (I, [P, I, P]),
     "mmbert_adamw": (I, [P, P, P, P, P, P, P, SZ, D, D, D, D, D, I, D, I, I]),
+    "mmbert_adamw_devscale": (I, [P, P, P, P, P, P, P, SZ, D, D, D, D, D, I, P, I, I]),
+    "mmbert_grad_norm": (I, [P, P, SZ, P, I, D, D, D, P, P]),
+    "mmbert_grad_scale": (I, [P, P, SZ, P, I, P]),
     "mmbert_gelu_bwd": (I, [P, P, P, P, SZ]),
     "mmbert_cast_f32_bf16": (I, [P, P, P, SZ]),
     "mmbert_cast_bf16_f32": (I, [P, P, P, SZ]),

@@ -1378,6 +1378,202 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
 }
 
+// adamw_kernel with the gradient scale read from the DEVICE scalar *coef (the clip coefficient of mmbert_grad_norm with the 1/world
+// average folded in; one scalar load per wave) in place of the host gscale.  Otherwise line for line adamw_kernel: a shared inline body
+// or a template changed adamw_kernel's register allocation and schedule (or its name in the traces), so the measured kernel stays as it was.
+__global__ __launch_bounds__(256) void adamw_devscale_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                             bf16_t* __restrict__ pb, const uint8_t* __restrict__ flags, size_t n,
+                                                             float beta1, float beta2, float omb1, float omb2, float eps, float step_size, float rsbc2,
+                                                             float lrwd, const float* __restrict__ coef, int mode, int zero_grad) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float gscale = *coef;
+    const uint8_t fb = flags[i >> 8];
+    const uint8_t f = fb & 3;
+    float4 P = *(float4*)(p + i);
+    if (f != 2) {
+        float4 G = *(float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i);
+        float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w}, ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
+        const float decay = (f == 1) ? lrwd : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float gr = ga[r] * gscale;
+            if (mode == 1) pa[r] *= (1.0f - decay);
+            ma[r] = beta1 * ma[r] + omb1 * gr;
+            va[r] = beta2 * va[r] + omb2 * gr * gr;
+            if (mode == 0) {
+                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) + eps);
+                pa[r] -= decay * pa[r];
+            } else {
+                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) * rsbc2 + eps);
+            }
+        }
+        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
+        *(float4*)(p + i) = P;
+        *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
+        *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
+    }
+    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+}
+
+// --------------------------------------------------------------------------------------------
+// Global gradient norm over a list of element segments of a flat fp32 buffer (torch.nn.utils.clip_grad_norm_: the reference
+// never clips; BERT's recipe and HF Trainer clip at 1.0).  segs[2 s], segs[2 s + 1] = offset, length of
+// segment s in elements -- any offset, any length: parameters pack inside 256-element blocks (flat.py ALIGN).
+// Every access is a 16-byte load of the aligned float4 that holds the elements; the lanes outside the segment are masked
+// (a straddling float4 at a segment edge is read whole, its foreign elements select 0).  Only the buffer's own last partial float4
+// (n % 4 != 0) is read element by element, clamped to n - 1.
+// Two launches, no float atomics, no in-launch hand-off between workgroups (the per-XCD L2s are not coherent: DESIGN 3.5,
+// tools/ubench/exchange_check.py): every
+// workgroup STORES its partial (double) into its own slot; one workgroup then folds the slots in slot order.  Squares are summed in
+// fp32 per lane (GN_UNROLL x 4 independent accumulators, ~30 terms each at the headline size), in double from there on.  The grid
+// depends on n alone (sized for 256 CUs, not from a device query), so the bits depend on the data alone.
+// --------------------------------------------------------------------------------------------
+#define GN_THREADS 256
+#define GN_UNROLL 4
+#define GN_MAX_WG 1024                   // 256 CUs x 4; == MMBERT_GRAD_NORM_WORKSPACE / sizeof(double)
+
+template <bool INF>
+__device__ __forceinline__ double gn_combine(double a, double b) {
+    if (!INF) return a + b;
+    return (b > a || __builtin_isnan(b)) ? b : a;               // max that keeps a NaN (torch's amax / clamp propagate it)
+}
+
+template <bool INF>
+__device__ __forceinline__ float gn_acc(float a, float x) {
+    if (!INF) return fmaf(x, x, a);
+    const float ax = fabsf(x);
+    return (ax > a || __builtin_isnan(ax)) ? ax : a;
+}
+
+// lane -> wave (xor butterfly, fixed order) -> workgroup (4 waves, slot order); the result is valid in thread 0
+template <bool INF>
+__device__ __forceinline__ double gn_block_reduce(double a) {
+    __shared__ double red[GN_THREADS / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a = gn_combine<INF>(a, __shfl_xor(a, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = red[0];
+#pragma unroll
+        for (int w = 1; w < GN_THREADS / 64; ++w) a = gn_combine<INF>(a, red[w]);
+    }
+    return a;
+}
+
+template <bool INF>
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_partial_kernel(const float* __restrict__ g, size_t n, const long long* __restrict__ segs,
+                                                                       int nseg, double* __restrict__ part) {
+    const size_t T = (size_t)gridDim.x * GN_THREADS, t = (size_t)blockIdx.x * GN_THREADS + threadIdx.x;
+    const size_t nfull = n >> 2;                                 // float4s wholly inside the buffer
+    float acc[GN_UNROLL][4];
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[u][r] = 0.f;
+    for (int s = 0; s < nseg; ++s) {
+        const size_t lo = min((size_t)segs[2 * s], n), hi = min(lo + (size_t)segs[2 * s + 1], n);
+        const size_t c0 = lo >> 2, c1 = min((hi + 3) >> 2, nfull);
+        for (size_t c = c0 + t; c < c1; c += GN_UNROLL * T) {
+            float4 x[GN_UNROLL];
+#pragma unroll
+            for (int u = 0; u < GN_UNROLL; ++u) x[u] = *(const float4*)(g + 4 * min(c + u * T, c1 - 1));       // issued together
+#pragma unroll
+            for (int u = 0; u < GN_UNROLL; ++u) {
+                const size_t e = 4 * (c + u * T);
+                const bool live = c + u * T < c1;
+                const float xs[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[u][r] = gn_acc<INF>(acc[u][r], (live && e + r >= lo && e + r < hi) ? xs[r] : 0.f);
+            }
+        }
+        if (t == 0 && hi > 4 * nfull && lo < hi) {               // the buffer's last partial float4 (n % 4 != 0)
+            float xs[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) xs[r] = g[min(4 * nfull + r, n - 1)];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const size_t e = 4 * nfull + r;
+                acc[0][r] = gn_acc<INF>(acc[0][r], (e >= lo && e < hi) ? xs[r] : 0.f);
+            }
+        }
+    }
+    double a = 0.0;
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a = gn_combine<INF>(a, (double)acc[u][r]);
+    a = gn_block_reduce<INF>(a);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// out[0] = ||gscale g|| (fp32), out[1] = min(1, max_norm / (out[0] + 1e-6)) in fp32 as torch forms it (NaN stays NaN, max_norm / inf = 0),
+// out[2] = out[1] * gscale (the factor the AdamW kernel applies to the raw gradient)
+template <bool INF>
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_finalize_kernel(const double* __restrict__ part, int nparts, float max_norm, double gscale,
+                                                                        float* __restrict__ out) {
+    double x[GN_MAX_WG / GN_THREADS];
+#pragma unroll
+    for (int k = 0; k < GN_MAX_WG / GN_THREADS; ++k) x[k] = part[min((int)threadIdx.x + k * GN_THREADS, nparts - 1)];     // issued together
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < GN_MAX_WG / GN_THREADS; ++k) a = gn_combine<INF>(a, (int)threadIdx.x + k * GN_THREADS < nparts ? x[k] : 0.0);
+    a = gn_block_reduce<INF>(a);
+    if (threadIdx.x == 0) {
+        // torch: clamp(max_norm / (norm + 1e-6), max = 1) on an fp32 tensor, where scalar / tensor is tensor.reciprocal() * scalar --
+        // the same three fp32 roundings here.  The reciprocal goes through double (the library builds with -ffast-math: an fp32 1 / x
+        // is v_rcp_f32, up to 1 ulp off; a double quotient rounded to fp32 is the IEEE fp32 quotient -- torch's device reciprocal was
+        // measured up to 1 ulp away from it, tests/test_clip_gpu.py)
+        const float norm = (float)((INF ? a : sqrt(a)) * fabs(gscale));
+        float c = (float)(1.0 / (double)(norm + 1e-6f)) * max_norm;
+        c = c > 1.f ? 1.f : c;
+        out[0] = norm;
+        out[1] = c;
+        out[2] = (float)((double)c * gscale);
+    }
+}
+
+// g[seg] *= *coef over the same segment list (the torch-semantics clip_grad_norm_ drop-in: it scales .grad in place)
+__global__ __launch_bounds__(GN_THREADS) void grad_scale_kernel(float* __restrict__ g, size_t n, const long long* __restrict__ segs, int nseg,
+                                                                const float* __restrict__ coef) {
+    const float k = *coef;
+    const size_t T = (size_t)gridDim.x * GN_THREADS, t = (size_t)blockIdx.x * GN_THREADS + threadIdx.x;
+    const size_t nfull = n >> 2;
+    for (int s = 0; s < nseg; ++s) {
+        const size_t lo = min((size_t)segs[2 * s], n), hi = min(lo + (size_t)segs[2 * s + 1], n);
+        const size_t c0 = lo >> 2, c1 = min((hi + 3) >> 2, nfull);
+        for (size_t c = c0 + t; c < c1; c += GN_UNROLL * T) {
+            float4 x[GN_UNROLL];
+#pragma unroll
+            for (int u = 0; u < GN_UNROLL; ++u) x[u] = *(const float4*)(g + 4 * min(c + u * T, c1 - 1));
+#pragma unroll
+            for (int u = 0; u < GN_UNROLL; ++u) {
+                const size_t e = 4 * (c + u * T);
+                if (c + u * T >= c1) continue;
+                if (e >= lo && e + 4 <= hi) {
+                    *(float4*)(g + e) = make_float4(x[u].x * k, x[u].y * k, x[u].z * k, x[u].w * k);
+                } else {                                         // a float4 across a segment edge: only the segment's own elements
+                    const float xs[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) if (e + r >= lo && e + r < hi) g[e + r] = xs[r] * k;
+                }
+            }
+        }
+        if (t == 0 && hi > 4 * nfull && lo < hi) {               // the buffer's last partial float4 (n % 4 != 0)
+            float xs[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) xs[r] = g[min(4 * nfull + r, n - 1)];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const size_t e = 4 * nfull + r;
+                if (e >= lo && e < hi) g[e] = xs[r] * k;
+            }
+        }
+    }
+}
+
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, size_t n) {
     for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * blockDim.x * 4) {
         const float4 a = *(const float4*)(x + i);
@@ -2059,6 +2255,48 @@ int mmbert_adamw(hipStream_t stream, float* p, float* g, float* m, float* v, voi
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, n,
                        (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size, (float)(1.0 / sqrt(bc2)),
                        (float)(lr * wd), (float)gscale, mode, zero_grad);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+int mmbert_adamw_devscale(hipStream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags, size_t n,
+                          double lr, double beta1, double beta2, double eps, double wd, int step, const float* coef, int mode, int zero_grad) {
+    if (n == 0) return 0;
+    if ((n & 255) || !coef) return -1;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double step_size = mode == 0 ? lr * sqrt(bc2) / bc1 : lr / bc1;
+    hipLaunchKernelGGL(adamw_devscale_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, n,
+                       (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size, (float)(1.0 / sqrt(bc2)),
+                       (float)(lr * wd), coef, mode, zero_grad);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+static unsigned grad_norm_grid(size_t n) {
+    const size_t per = (size_t)GN_THREADS * GN_UNROLL, wg = ((n + 3) / 4 + per - 1) / per;
+    return (unsigned)std::max<size_t>(1, std::min<size_t>(GN_MAX_WG, wg));
+}
+
+int mmbert_grad_norm(hipStream_t stream, const float* g, size_t n, const int64_t* segs, int nseg, double norm_type, double max_norm,
+                     double gscale, void* workspace, float* out) {
+    const bool inf = norm_type == INFINITY;
+    if ((!inf && norm_type != 2.0) || nseg < 0 || (nseg > 0 && !segs) || !workspace || !out || ((uintptr_t)g & 15) || !(max_norm >= 0.0))
+        return -1;
+    const unsigned grid = grad_norm_grid(n);
+    double* part = (double*)workspace;
+    if (inf) hipLaunchKernelGGL(grad_norm_partial_kernel<true>, dim3(grid), dim3(GN_THREADS), 0, stream, g, n, (const long long*)segs, nseg, part);
+    else hipLaunchKernelGGL(grad_norm_partial_kernel<false>, dim3(grid), dim3(GN_THREADS), 0, stream, g, n, (const long long*)segs, nseg, part);
+    MMB_CHECK_LAUNCH();
+    if (inf) hipLaunchKernelGGL(grad_norm_finalize_kernel<true>, dim3(1), dim3(GN_THREADS), 0, stream, (const double*)part, (int)grid, (float)max_norm, gscale, out);
+    else hipLaunchKernelGGL(grad_norm_finalize_kernel<false>, dim3(1), dim3(GN_THREADS), 0, stream, (const double*)part, (int)grid, (float)max_norm, gscale, out);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+int mmbert_grad_scale(hipStream_t stream, float* g, size_t n, const int64_t* segs, int nseg, const float* coef) {
+    if (nseg < 0 || (nseg > 0 && !segs) || !coef || ((uintptr_t)g & 15)) return -1;
+    if (nseg == 0 || n == 0) return 0;
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(grad_norm_grid(n)), dim3(GN_THREADS), 0, stream, g, n, (const long long*)segs, nseg, coef);
     MMB_CHECK_LAUNCH();
     return 0;
 }

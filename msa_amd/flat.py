@@ -35,6 +35,21 @@ def _round_up(x: int, a: int) -> int:
     return (x + a - 1) // a * a
 
 
+def grad_segments(offset: Dict[str, int], numel: Dict[str, int], names, exclude=()) -> List[Tuple[int, int]]:
+    """The (offset, length) element segments of ``grads`` that the parameters ``names`` cover, in buffer order, parameters whose name
+    starts with an ``exclude`` prefix left out, each parameter once, adjacent ones merged into one segment.  A pure function of the
+    storage's ``offset`` / ``numel`` maps (the global-norm kernel, mmbert_grad_norm, takes the list as it is: any offsets, any lengths)."""
+    spans = sorted({(offset[n], numel[n]) for n in set(names) if not any(n.startswith(e) for e in exclude) and numel[n] > 0})
+    segs: List[Tuple[int, int]] = []
+    for o, k in spans:
+        if segs and segs[-1][0] + segs[-1][1] >= o:
+            lo, ln = segs[-1]
+            segs[-1] = (lo, max(lo + ln, o + k) - lo)
+        else:
+            segs.append((o, k))
+    return segs
+
+
 class FlatParams:
     def __init__(self, model: torch.nn.Module, cfg, device):
         self.device = device
@@ -158,6 +173,11 @@ class FlatParams:
         self.lazy: Dict[int, Tuple[torch.Tensor, List[str]]] = {}
         self.stale: set = set()
         self.lazy_detached = False
+        # the factor the optimizer applies to ``grads`` (1 / world under parallel.DataParallel, which sets it): the torch-semantics
+        # clip (optim.clip_grad_norm_) measures the gradient the step will apply, the mean over ranks
+        self.grad_scale = 1.0
+        self._segments: Dict[Tuple[frozenset, tuple], Tuple[torch.Tensor, int]] = {}
+        self._norm_ws = None
         self.refresh()
 
     # ------------------------------------------------------------------------------------------
@@ -226,6 +246,22 @@ class FlatParams:
                     o = self.offset[n]
                     p.grad = self.grads[o:o + self.numel[n]].view(p.shape)
         self.lazy_detached = False
+
+    def segments(self, names, exclude=()) -> Tuple[torch.Tensor, int]:
+        """(device int64 [nseg, 2] of (offset, length), nseg) of grad_segments(names, exclude), built once per parameter set."""
+        key = (frozenset(names), tuple(exclude))
+        hit = self._segments.get(key)
+        if hit is None:
+            segs = grad_segments(self.offset, self.numel, key[0], exclude)
+            t = torch.tensor(segs if segs else [(0, 0)], dtype=torch.int64).to(self.device)
+            hit = self._segments[key] = (t, len(segs))
+        return hit
+
+    def norm_workspace(self) -> torch.Tensor:
+        """The global-norm kernel's partial-sum slots (ops.GRAD_NORM_WORKSPACE bytes), one per storage: clips run on the current stream."""
+        if self._norm_ws is None:
+            self._norm_ws = torch.empty(ops.GRAD_NORM_WORKSPACE // 8, dtype=torch.float64, device=self.device)
+        return self._norm_ws
 
     def view32(self, name: str, shape=None) -> torch.Tensor:
         o, k = self.offset[name], self.numel[name]

@@ -908,6 +908,39 @@ def adamw(p, g, m, v, p_bf16, flags, *, lr, beta1=0.9, beta2=0.999, eps=1e-6, wd
                                 1 if zero_grad else 0), "mmbert_adamw")
 
 
+def adamw_devscale(p, g, m, v, p_bf16, flags, coef, *, lr, beta1=0.9, beta2=0.999, eps=1e-6, wd=0.01, step=1, mode=0, zero_grad=True):
+    """ops.adamw with the gradient scale read from the device scalar ``coef`` (fp32, e.g. grad_norm's out[2:3])."""
+    lib = _lib.load()
+    _lib.check(lib.mmbert_adamw_devscale(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16), flags.data_ptr(),
+                                         p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(wd), int(step), coef.data_ptr(),
+                                         int(mode), 1 if zero_grad else 0), "mmbert_adamw_devscale")
+
+
+GRAD_NORM_WORKSPACE = 8192          # MMBERT_GRAD_NORM_WORKSPACE (include/mmbert_hip.h), bytes
+
+
+def grad_norm(g, segs, nseg, *, max_norm, norm_type=2.0, gscale=1.0, workspace=None, out=None):
+    """fp32 [3] on the device: (||gscale g[segs]||, min(1, max_norm / (norm + 1e-6)), that coefficient * gscale) -- mmbert_grad_norm.
+    ``segs``: device int64 [nseg, 2] of (offset, length) in elements of the contiguous fp32 ``g``; ``workspace``: >= GRAD_NORM_WORKSPACE
+    bytes of device memory (allocated here when None).  No host sync."""
+    assert g.dtype == torch.float32 and g.is_contiguous() and segs.dtype == torch.int64 and segs.is_contiguous()
+    if workspace is None:
+        workspace = torch.empty(GRAD_NORM_WORKSPACE // 8, dtype=torch.float64, device=g.device)
+    assert workspace.numel() * workspace.element_size() >= GRAD_NORM_WORKSPACE
+    if out is None:
+        out = torch.empty(3, dtype=torch.float32, device=g.device)
+    _lib.check(_lib.load().mmbert_grad_norm(_stream(), g.data_ptr(), g.numel(), segs.data_ptr(), int(nseg), float(norm_type), float(max_norm),
+                                            float(gscale), workspace.data_ptr(), out.data_ptr()), "mmbert_grad_norm")
+    return out
+
+
+def grad_scale_(g, segs, nseg, coef):
+    """g[segs] *= coef[0] in place (device fp32 scalar; mmbert_grad_scale)."""
+    assert g.dtype == torch.float32 and g.is_contiguous() and segs.dtype == torch.int64 and coef.dtype == torch.float32
+    _lib.check(_lib.load().mmbert_grad_scale(_stream(), g.data_ptr(), g.numel(), segs.data_ptr(), int(nseg), coef.data_ptr()), "mmbert_grad_scale")
+    return g
+
+
 def gelu_bwd(dy, u, du=None):
     if du is None:
         du = torch.empty_like(dy)

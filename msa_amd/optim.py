@@ -8,12 +8,23 @@ imports (eps 1e-6, bias correction, decay applied after the update); ``mode="tor
 """
 from __future__ import annotations
 
+import math
 from typing import Iterable, List, Union
 
 import torch
 
 from . import ops
 from .flat import FROZEN
+
+
+def _clip_args(max_norm, norm_type):
+    """(max_norm, norm_type) as floats for the native clip; norm_type other than 2 and inf: NotImplementedError."""
+    max_norm, norm_type = float(max_norm), float(norm_type)
+    if not max_norm >= 0.0:
+        raise ValueError(f"clip_grad_norm_: max_norm must be >= 0, got {max_norm}")
+    if norm_type != 2.0 and norm_type != math.inf:
+        raise NotImplementedError(f"clip_grad_norm_: the native clip takes norm_type 2 or inf, got {norm_type}")
+    return max_norm, norm_type
 
 
 class AdamW:
@@ -35,6 +46,7 @@ class AdamW:
         self._lazy_zero = True
         self._flat = None
         self._steps = 0
+        self._clip = None                   # clip_grad_norm_'s device scalars until the next step() applies them (or zero_grad() drops them)
 
     # The dense weights' gradients (3/4 of the parameters) are not zero-filled between steps: the next backward's weight-gradient
     # launches overwrite them (flat.FlatParams lazy zero; torch's zero_grad(set_to_none=True) semantics).  False: fill with zeros.
@@ -102,7 +114,27 @@ class AdamW:
         self._m = torch.zeros_like(flat.params)
         self._v = torch.zeros_like(flat.params)
         self._flat = flat
+        self._names = [flat.name_at(p._mmb_flat[1]) for g in self.param_groups for p in g["params"]]
         self._build_flags()
+
+    def clip_grad_norm_(self, max_norm, norm_type=2.0) -> torch.Tensor:
+        """Global gradient-norm clipping fused into the next ``step()``: returns the total norm (0-d fp32 device tensor) of the gradient
+        that step will apply -- this optimizer's parameters except flat.FROZEN, times ``grad_scale`` (under DataParallel the mean over
+        ranks) -- and has the step multiply every gradient by ``min(1, max_norm / (norm + 1e-6))`` as the AdamW kernel reads it.
+        Unlike ``torch.nn.utils.clip_grad_norm_``, ``.grad`` is NOT modified: the coefficient stays on the device until ``step()``
+        applies it (one reduction pass, no host sync, no write pass).  A second call before ``step()`` replaces the coefficient;
+        ``zero_grad()`` without a step drops it.  norm_type: 2 or inf."""
+        max_norm, norm_type = _clip_args(max_norm, norm_type)
+        if self._flat is None:
+            self._bind()
+        flat = self._flat
+        flat.join_side_writers()             # (see step(): nothing may still add into the gradients read here)
+        flat.settle()                        # a dropped lazy gradient counts as zero
+        segs, nseg = flat.segments(self._names, FROZEN)
+        out = ops.grad_norm(flat.grads, segs, nseg, max_norm=max_norm, norm_type=norm_type, gscale=self.grad_scale,
+                            workspace=flat.norm_workspace())
+        self._clip = out
+        return out[0]
 
     def step(self):
         if self._flat is None:
@@ -113,9 +145,15 @@ class AdamW:
         flat.wait_transposes()               # (a step without a backward in between: the last step's transposed copies still read the bf16 copy)
         flat.settle()                        # a lazy gradient no backward has written since the last step counts as zero
         flat.attach_lazy()
-        ops.adamw(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, lr=self.lr, beta1=self.betas[0],
-                  beta2=self.betas[1], eps=self.eps, wd=self.wd, step=self._steps, gscale=self.grad_scale, mode=self.mode,
-                  zero_grad=True)
+        clip, self._clip = self._clip, None
+        if clip is None:
+            ops.adamw(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, lr=self.lr, beta1=self.betas[0],
+                      beta2=self.betas[1], eps=self.eps, wd=self.wd, step=self._steps, gscale=self.grad_scale, mode=self.mode,
+                      zero_grad=True)
+        else:                                # clip_grad_norm_ ran: its coefficient (x grad_scale) from the device
+            ops.adamw_devscale(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, clip[2:3], lr=self.lr,
+                               beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, wd=self.wd, step=self._steps, mode=self.mode,
+                               zero_grad=True)
         flat.refresh_transposes(side=True)
         flat.mark_synced()
         flat.grads_dirty = False
@@ -123,6 +161,7 @@ class AdamW:
             flat.drop_lazy()
 
     def zero_grad(self, set_to_none: bool = False):
+        self._clip = None                    # a clip coefficient no step() applied belongs to the gradients dropped here
         flat = self._flat
         if flat is None:
             # (not bound before the first step(); the parameters may already live in a model's flat storage: join its side streams first)
@@ -157,6 +196,46 @@ class AdamW:
             self._v.copy_(sd["v"])
         for g, lr in zip(self.param_groups, sd["lrs"]):
             g["lr"] = lr
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` with torch's signature and semantics -- ``.grad`` is scaled in place, the total norm (0-d fp32
+    device tensor) returned, parameters whose ``.grad`` is None skipped -- on the HIP global-norm kernel when every parameter is backed
+    by ONE msa_amd flat storage (two launches for the norm, one for the scaling, no host sync).
+    When a parallel.DataParallel drives that storage, ``.grad`` holds the SUM over ranks (the 1/world average is applied inside the
+    AdamW kernel): the norm here is the norm of the averaged gradient, the one the step applies -- which torch's own clip, measuring the
+    sum, gets ``world`` times too large.  ``error_if_nonfinite=True`` reads the norm back to the host (one sync).  ``foreach`` is
+    accepted for compatibility and ignored.  Anything else (parameters outside a flat storage, or spread over several) goes to torch's
+    clip unchanged; on the native path norm_type is 2 or inf.  ``AdamW.clip_grad_norm_`` is the fused form that leaves ``.grad`` alone."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = [p for p in parameters if p.grad is not None]
+    flat, names = None, []
+    for p in params:
+        ref = getattr(p, "_mmb_flat", None)
+        if ref is None or (flat is not None and ref[0] is not flat):
+            flat = None
+            break
+        flat = ref[0]
+        o = ref[1]
+        if p.grad.data_ptr() != flat.grads.data_ptr() + 4 * o or not p.grad.is_contiguous() or p.data_ptr() != flat.params.data_ptr() + 4 * o:
+            flat = None                      # (a .grad the caller replaced, or a re-materialised parameter: not the flat buffer's view)
+            break
+        names.append(flat.name_at(o))
+    if flat is None:
+        return torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite, foreach=foreach)
+    max_norm, norm_type = _clip_args(max_norm, norm_type)
+    flat.join_side_writers()
+    flat.settle()                            # (a dropped lazy gradient counts as zero, as its .grad view would read it)
+    segs, nseg = flat.segments(names)
+    out = ops.grad_norm(flat.grads, segs, nseg, max_norm=max_norm, norm_type=norm_type, gscale=flat.grad_scale,
+                        workspace=flat.norm_workspace())
+    norm = out[0]
+    if error_if_nonfinite and not bool(torch.isfinite(norm)):
+        raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be clipped. "
+                           "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    ops.grad_scale_(flat.grads, segs, nseg, out[1:2])
+    return norm
 
 
 class LinearWarmupSchedule:

@@ -206,6 +206,7 @@ class DataParallel:
             model.head_grad_hook = self._on_heads_done
             model.defer_embed_rows = True
             model.embed_ids_hook = self._on_ids
+        flat.grad_scale = 1.0 / self.world                            # (read by optim.clip_grad_norm_: the norm of the averaged gradient)
         if optimizer is not None:
             optimizer.grad_scale = 1.0 / self.world
         self.optimizer = optimizer

@@ -14,9 +14,11 @@ buffers) and does not pay the dispatcher per launch.
     l = torch.ops.mmbert.mlm_head_ce(logits, labels, vocab)                                             # CE(ignore_index=-100), mean
     torch.ops.mmbert.adamw_multi_tensor(p, g, m, v, p_bf16, flags, lr, b1, b2, eps, wd, step, 1.0, "hf", True)   # in place
     labels = torch.ops.mmbert.mlm_mask_rng(ids, 0.15, seed, [101, 102], 103)                            # ids masked in place
+    r = torch.ops.mmbert.grad_norm(g, segs, 1.0, 2.0, 1.0)          # [norm, min(1, 1 / (norm + 1e-6)), that * grad_scale] (fp32)
 
 One operator per kernel family of SURVEY.md S8(b): linear (gemm nt/tn + epilogues), layer_norm, attention, embed_ln, joint_embed,
-mlm_head_ce, adamw_multi_tensor, mlm_mask_rng; the differentiable ones carry their autograd formulas.
+mlm_head_ce, adamw_multi_tensor, mlm_mask_rng; the differentiable ones carry their autograd formulas.  grad_norm: the global
+gradient norm of clip_grad_norm_ (not in the reference).
 
 No CPU implementation is registered: calling an operator with CPU tensors raises (there is no fallback path).
 """
@@ -205,6 +207,7 @@ _lib.define("mlm_head_ce_bwd(Tensor dloss, Tensor logits, Tensor labels, int voc
 _lib.define("adamw_multi_tensor(Tensor(a!) p, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!)? p_bf16, Tensor flags, float lr, float beta1, "
             "float beta2, float eps, float weight_decay, int step, float grad_scale=1.0, str mode='hf', bool zero_grad=True) -> ()")
 _lib.define("mlm_mask_rng(Tensor(a!) ids, float p, int seed, int[] special_ids, int mask_id=103) -> Tensor")
+_lib.define("grad_norm(Tensor g, Tensor segments, float max_norm, float norm_type=2.0, float grad_scale=1.0) -> Tensor")
 
 _DROP_SITE_EMB, _DROP_SITE_JOINT = 78, 79
 
@@ -304,13 +307,22 @@ def _adamw(p, g, m, v, p_bf16, flags, lr, beta1, beta2, eps, weight_decay, step,
               mode={"hf": 0, "torch": 1}[mode], zero_grad=zero_grad)
 
 
+def _grad_norm(g, segments, max_norm, norm_type=2.0, grad_scale=1.0):
+    """Global norm of grad_scale * g over the (offset, length) element segments (int64 [nseg, 2]) of the flat fp32 g, as
+    clip_grad_norm_ forms it: fp32 [3] = (norm, min(1, max_norm / (norm + 1e-6)), that coefficient * grad_scale).  norm_type 2 or inf;
+    the bits depend on the data alone (no float atomics).  No host sync."""
+    segs = segments.to(torch.int64).reshape(-1, 2).contiguous()
+    return ops.grad_norm(g.contiguous(), segs, segs.shape[0], max_norm=max_norm, norm_type=norm_type, gscale=grad_scale)
+
+
 def _mlm_mask(ids, p, seed, special_ids, mask_id=103):
     return ops.mlm_mask(ids, float(p), int(seed), special_ids=tuple(special_ids), mask_id=int(mask_id))
 
 
 for _name, _fn in (("embed_ln", _emb), ("embed_ln_fwd", _emb_fwd), ("embed_ln_bwd", _emb_bwd), ("joint_embed", _joint),
                    ("joint_embed_fwd", _joint_fwd), ("joint_embed_bwd", _joint_bwd), ("mlm_head_ce", _ce), ("mlm_head_ce_fwd", _ce_fwd),
-                   ("mlm_head_ce_bwd", _ce_bwd), ("adamw_multi_tensor", _adamw), ("mlm_mask_rng", _mlm_mask)):
+                   ("mlm_head_ce_bwd", _ce_bwd), ("adamw_multi_tensor", _adamw), ("mlm_mask_rng", _mlm_mask),
+                   ("grad_norm", _grad_norm)):
     _lib.impl(_name, _fn, "CUDA")
 
 

@@ -144,13 +144,16 @@ def train_epoch(args, model, traindata, optimizer, scheduler, tokenizer=None, *,
     """One epoch.  ``traindata``: a Dataset of the reference's 16-tuples (collated here), or pass
     ``batches`` = an iterable of ready model-kwargs dicts (the synthetic generator).
     Returns the reference's 6-tuple (REF:trainer.py:101): (train_loss, text_loss, visual_loss,
-    speech_loss, ap_loss_of_the_LAST_step, label_loss) each divided by the number of steps."""
+    speech_loss, ap_loss_of_the_LAST_step, label_loss) each divided by the number of steps.
+    ``args.max_grad_norm`` (optional; the reference has no such argument and ``default_args()`` leaves it out): clip the accumulated
+    gradient to that global L2 norm in every optimizer step, fused into the step (``AdamW.clip_grad_norm_``)."""
     if batches is None:
         from torch.utils.data import DataLoader, RandomSampler, SequentialSampler
         sampler = RandomSampler(traindata) if shuffle else SequentialSampler(traindata)
         loader = DataLoader(traindata, sampler=sampler, batch_size=args.train_batch_size, collate_fn=collate)
         batches = (pack_step_inputs(b, args, device, generator) for b in loader)
     gas = args.gradient_accumulation_step
+    max_grad_norm = getattr(args, "max_grad_norm", None)                   # (not a reference argument: None = no clipping)
     model.train()
     train_loss = torch.zeros((), device=device)
     label_loss = torch.zeros((), device=device)
@@ -170,6 +173,8 @@ def train_epoch(args, model, traindata, optimizer, scheduler, tokenizer=None, *,
         if stepping:                                                         # REF:trainer.py:96-99
             if dp is not None:
                 dp.finish_backward()
+            if max_grad_norm is not None:                                    # the accumulated gradient, once per step
+                optimizer.clip_grad_norm_(max_grad_norm)
             optimizer.step()
             scheduler.step()
             optimizer.zero_grad()
@@ -346,6 +351,7 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
     reference's checkpoint format = its state-dict keys) whenever the TEST accuracy improves; after ``patience_limit`` epochs
     without improvement the best predictions / targets go to ``predict.npy`` / ``target.npy`` and the loop stops.
     ``epoch_batches``: optional callable ``(split, epoch) -> iterable of model kwargs`` replacing the datasets (synthetic data).
+    ``args.max_grad_norm``, when present, reaches every epoch's train_epoch (global-norm clipping).
     Returns a dict with the best epoch's numbers and the per-epoch history."""
     import os
     import numpy as np
