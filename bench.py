@@ -11,7 +11,12 @@ batches already resident in HBM.  Workload = BASELINE.json configs[1]: 12 layers
 T=50, A=V=500, batch 16 per GPU, bf16 MFMA compute (fp32 master weights / accumulation).
 Weak scaling: per-GPU batch is fixed, global batch = 16*N.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  With --full it
+also measures what follows (each part still subject to its --no-* flag, see EXTRAS) and adds it to the line.
+
+Extra objects on the JSON line (--full only):
+  box          -- three fixed yardstick launches in front of the headline and the GPU's clock and power readings (box_probe below);
+                  `value_normalised` = value / box.index.
   roofline     -- the dominant kernel (gemm_nt: forward projections + input gradients, 2/3 of the
                   step's FLOPs): algorithmic FLOPs of its launches / their summed durations, taken live
                   with HIP events on the launch stream over a timed region of the SAME K steps that follows
@@ -22,6 +27,9 @@ Extra objects on the JSON line:
                   fwd+bwd steps, plus BASELINE configs[0] exactly.
   fused1050    -- secondary: the same train step on ONE sequence text|visual|speech (S = 1050), a declared extension
                   (model.forward_fused); never the headline value.
+  dense_backward_reference, scores_fp32, atomic_sums / deterministic, paired_wgrads, dp_wire_bf16, train_only,
+  reference_default -- secondary legs, each the same K steps under another setting (see main()); config.dp.rccl and
+                  config.dp.exposed_tail_us under the data-parallel wrapper.
 config.tflop_per_sample is the dense algorithmic count; config.tflop_per_sample_executed subtracts the
 work whose result is exactly zero and therefore skipped (MLM-head backward of unlabelled rows, backward of rows behind a
 sequence's last unmasked key, attention over masked-out keys: DESIGN.md S2/S3); step_mfma_frac uses the executed count.
@@ -159,7 +167,17 @@ def box_probe(dev, ops, smi):
     return out
 
 
-def main():
+# what a --full run measures besides the headline, each named after the --no-* flag that leaves it out
+EXTRAS = ("box_probe", "kernel_timing", "dense_reference", "scores_fp32", "deterministic", "dp_reference_legs", "train_only", "fused",
+          "reference_default", "cpu_baseline")
+
+
+def extras(a):
+    """The parts of EXTRAS this run measures: none without --full."""
+    return frozenset(k for k in EXTRAS if a.full and not getattr(a, "no_" + k))
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -171,6 +189,8 @@ def main():
     ap.add_argument("--hidden", type=int, default=768)
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--vocab", type=int, default=30522)
+    ap.add_argument("--full", action="store_true", help="also measure everything besides the headline (EXTRAS: the box yardstick, the per-kernel "
+                    "roofline pass, the secondary legs, the CPU baseline, RCCL's own account under N > 1); the --no-* flags below leave parts out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-fused", action="store_true", help="skip the secondary fused-sequence (S = T+V+A) measurement")
@@ -200,13 +220,19 @@ def main():
     ap.add_argument("--rank-report", action="store_true", help="N > 1 diagnostics even on one process: per-rank step times, exposed tail (on by default for N > 1)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (and the parameters after it) "
                     "as DIR/<name>.npy: float32 / float64, a seeded sample of arrays above 2^20 elements")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.dump_outputs and a.preset != "headline":
         ap.error("--dump-outputs writes the headline step's outputs: --preset headline only")
+    return a
+
+
+def main():
+    a = parse_args()
+    ex = extras(a)
     # (rocm-smi is a child process: started before anything here initialises HIP, and only with the box yardstick)
-    smi = smi_readings() if (int(os.environ.get("RANK", 0)) == 0 and not a.no_box_probe) else None
+    smi = smi_readings() if (int(os.environ.get("RANK", 0)) == 0 and "box_probe" in ex) else None
 
     from msa_amd import ops, parallel
     from msa_amd.data import synthetic_batch, batch_to, to_fused
@@ -221,8 +247,8 @@ def main():
         saved_stdout = os.dup(1)
         os.dup2(2, 1)
     rccl_log = None
-    if (int(os.environ.get("WORLD_SIZE", 1)) > 1 or a.force_dp) and os.environ.get("NCCL_DEBUG", "VERSION").upper() in ("VERSION", "WARN", ""):
-        # N > 1 must be diagnosable from ONE run: RCCL's own account of what it built (rings / trees, channels, transport per peer) and
+    if a.full and (int(os.environ.get("WORLD_SIZE", 1)) > 1 or a.force_dp) and os.environ.get("NCCL_DEBUG", "VERSION").upper() in ("VERSION", "WARN", ""):
+        # N > 1 must be diagnosable from ONE --full run: RCCL's own account of what it built (rings / trees, channels, transport per peer) and
         # of what it picked per message size (algorithm / protocol / channels) goes to a per-process file; rank 0 condenses it into
         # config.dp.rccl and onto stderr at the end (the full file stays in /tmp).  (An NCCL_DEBUG of VERSION / WARN from the image's
         # environment is raised to INFO; an INFO / TRACE the caller set is left alone -- it then goes wherever the caller sent it.)
@@ -234,7 +260,7 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
 
-    box = box_probe(dev, ops, smi) if (rank == 0 and not a.no_box_probe) else None
+    box = box_probe(dev, ops, smi) if (rank == 0 and "box_probe" in ex) else None
 
     timing = {"nt": [], "tn": [], "attn_fwd": [], "attn_bwd": []}
     record = [False]
@@ -254,8 +280,10 @@ def main():
     # The per-launch wrappers are installed only around the instrumented legs: the headline region runs the model's default host path
     # (one composite C call per encoder layer, mmbert_layer_fwd / _bwd), the instrumented region the per-launch path -- the same kernels
     # with the same arguments (tests/test_model_gpu.py::test_composite_layer_calls_are_bit_identical), each launch between two events.
+    # (--preset reference-default is a measurement of its own: its per-shape pass follows --no-kernel-timing alone)
+    kernel_timing = ("kernel_timing" in ex) if a.preset == "headline" else not a.no_kernel_timing
     originals, wrappers = {}, {}
-    if not a.no_kernel_timing:
+    if kernel_timing:
         originals = dict(gemm_nt=ops.gemm_nt, gemm_tn=ops.gemm_tn, gemm_tn_grouped=ops.gemm_tn_grouped, attn_fwd=ops.attn_fwd, attn_bwd=ops.attn_bwd)
         wrappers["gemm_nt"] = wrap("nt", ops.gemm_nt, lambda A, B, **kw: 2.0 * A.shape[0] * A.shape[1] * B.shape[0],
                                    lambda A, B, **kw: (A.shape[0], B.shape[0], A.shape[1]))
@@ -277,7 +305,7 @@ def main():
         record[0] = bool(on)
 
     if a.preset == "reference-default":
-        rec = reference_default_leg(a, dev, ops, wrap_state=(timing, instrument))
+        rec = reference_default_leg(a, dev, ops, wrap_state=(timing, instrument), kernel_timing=kernel_timing)
         if saved_stdout is not None:
             if torch.distributed.is_initialized():
                 torch.distributed.destroy_process_group()
@@ -375,7 +403,7 @@ def main():
     # are ~340 extra packets in the queue between kernels (round 2 timed both in one pass: 16.4 ms per step against 15.9 without the
     # events, same box, same process); `ms_per_step_instrumented` reports what this leg took.
     elapsed_instr = None
-    if not a.no_kernel_timing:
+    if kernel_timing:
         instrument(True)
         ti0 = time.perf_counter()
         for i in range(a.steps):
@@ -410,7 +438,7 @@ def main():
     # For reference: the same step with every exact-zero short cut switched off (attention visits the masked-out keys, backward
     # runs on all rows and densely through the top layer); identical gradients up to fp32 summation order, never the headline.
     dense_ref = None
-    if not a.no_dense_reference and (model.skip_masked_keys or model.skip_padded_backward or model.sparse_top_layer_backward):
+    if "dense_reference" in ex and (model.skip_masked_keys or model.skip_padded_backward or model.sparse_top_layer_backward):
         saved_flags = (model.skip_masked_keys, model.skip_padded_backward, model.sparse_top_layer_backward)
         model.skip_masked_keys = model.skip_padded_backward = model.sparse_top_layer_backward = False
         delapsed = timed_leg(step)
@@ -422,7 +450,7 @@ def main():
     # vocabulary GEMM store its fp32 accumulators instead: bit-identical losses and gradients (test_scores_dtype_float32_for_numpy_consumers),
     # twice the bytes written by that launch.
     scores_fp32 = None
-    if not a.no_scores_fp32 and model.scores_dtype != torch.float32:
+    if "scores_fp32" in ex and model.scores_dtype != torch.float32:
         saved_dtype = model.scores_dtype
         model.scores_dtype = torch.float32
         sel = timed_leg(step)
@@ -435,7 +463,7 @@ def main():
     # bit-identical losses and gradients run to run (tests/test_train_gpu.py::test_deterministic_mode_gives_bit_identical_steps).
     # What one mode costs against the other is this leg against the headline.
     det_leg = None
-    if not a.no_deterministic:
+    if "deterministic" in ex:
         was_det = model.deterministic
         model.deterministic = not was_det
         try:
@@ -450,7 +478,7 @@ def main():
     # wrapper has to use (its hook needs a layer's gradient slice when the layer is done), measured on the plain step so that a SCALE
     # point can be read against a world-1 number of the same code path.
     paired = None
-    if not a.no_dp_reference_legs and dp is None:
+    if "dp_reference_legs" in ex and dp is None:
         was_defer = getattr(model, "defer_wgrads", None)
         model.defer_wgrads = False
         pel = timed_leg(step)
@@ -462,7 +490,7 @@ def main():
     # (only in the forced single-process form by default: at N > 1 the headline's collectives are the ones to be measured, and a leg that
     # switches the exchange protocol between timed regions is one more thing that could go wrong on the first real multi-GPU run;
     # --dp-wire bf16 measures that protocol as the headline of its own run)
-    if not a.no_dp_reference_legs and dp is not None and a.dp_wire == "fp32" and world == 1:
+    if "dp_reference_legs" in ex and dp is not None and a.dp_wire == "fp32" and world == 1:
         bk = dp.bucketer
         saved_wire = (bk.wire_dtype, bk.force_wire_path)
         bk.wire_dtype, bk.force_wire_path = torch.bfloat16, world == 1
@@ -478,7 +506,7 @@ def main():
     # only (forward too) and the encoder leaves out the rows that only those scores would read.  Same losses and gradients
     # (tests/test_model_gpu.py); not the headline, which keeps every returned tensor.
     train_only = None
-    if not a.no_train_only:
+    if "train_only" in ex:
         model.return_scores = False
         telapsed = timed_leg(step)
         model.return_scores = True
@@ -488,7 +516,7 @@ def main():
     # BASELINE.json's metric name quotes.  The reference never builds that sequence (its step is the three passes above), so
     # this is a declared extension (model.forward_fused, checked against oracle.fused_forward) and never the headline value.
     fused = None
-    if not a.no_fused:
+    if "fused" in ex:
         fpool = [to_fused(b) for b in pool]
 
         def fstep(i):
@@ -509,8 +537,8 @@ def main():
     # Secondary: the reference's OWN default model (REF:train.py:28,32,38,70 -- bert-large-uncased: 24 layers, d = 1024, 16 heads, I = 4096,
     # max_seq_length 40, pair length == text length, train_batch_size 32), same train step.  Never the headline (BASELINE.json quotes d = 768).
     ref_default = None
-    if not a.no_reference_default and world == 1 and dp is None:
-        ref_default = reference_default_leg(a, dev, ops, wrap_state=(timing, instrument))
+    if "reference_default" in ex and world == 1 and dp is None:
+        ref_default = reference_default_leg(a, dev, ops, wrap_state=(timing, instrument), kernel_timing=kernel_timing)
 
     samples = a.steps * a.batch * world
     value = samples / elapsed
@@ -600,7 +628,7 @@ def main():
     if dp is not None and rccl_log is not None and rank == 0:
         res["config"]["dp"]["rccl"] = rccl_summary(rccl_log)
     if rank == 0:
-        if not a.no_kernel_timing and timing["nt"]:
+        if kernel_timing and timing["nt"]:
             kern = {}
             for k, lst in timing.items():
                 if lst:
@@ -626,12 +654,12 @@ def main():
                     fl2, ms2, n2 = kern[k]
                     res["roofline"]["gemm_tn" if k == "tn" else k] = {"achieved": round(fl2 / (ms2 * 1e-3) / 1e12, 1), "launches": n2,
                                                                       "share_of_step_time": round(ms2 * 1e-3 / elapsed_instr, 3)}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and "cpu_baseline" in ex:
             res["cpu_baseline"] = cpu_baseline(a, L, H, I, V)
         print(json.dumps(res), flush=True)
 
 
-def reference_default_leg(a, dev, ops, wrap_state):
+def reference_default_leg(a, dev, ops, wrap_state, kernel_timing):
     """The reference's default configuration (bert-large, T = P = 40, batch 32) through the same train step: samples/s, the persistent NT
     family's in-situ rate at its {1024, 3072, 4096} shapes (HIP events, a second pass like the headline's roofline leg) and which
     kernel / tile / tile walk every shape was dispatched to (mmbert_gemm_nt_describe)."""
@@ -676,7 +704,7 @@ def reference_default_leg(a, dev, ops, wrap_state):
     fwd = 2 * S3 * L * (4 * H * H + 2 * H * I) + 4 * (T * T + 2 * (2 * T) ** 2) * H * L + 2 * S3 * H * H + 2 * S3 * H * V + 2 * T * (35 + 74) * H
     rec["tflop_per_sample"] = round(3.0 * fwd / 1e12, 4)
     rec["step_mfma_frac_dense"] = round(3.0 * fwd * rec["value"] / 2.5e15, 4)
-    if not a.no_kernel_timing:
+    if kernel_timing:
         marks = {k: len(v) for k, v in timing.items()}
         mark = marks["nt"]
         instrument(True)
