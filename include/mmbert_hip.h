@@ -422,6 +422,20 @@ int mmbert_adamw(mmbert_stream_t stream, float* p, float* g, float* m, float* v,
 int mmbert_adamw_devscale(mmbert_stream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags, size_t n,
                           double lr, double beta1, double beta2, double eps, double wd, int step, const float* coef, int mode, int zero_grad);
 
+/* The same update with per-parameter-group hyper-parameters (torch / transformers param groups).  group_of_block[i/256] (device uint8,
+ * the granularity of flags) is the group of each 256-element block; hyper is a HOST array of ngroups x {lr, beta1, beta2, eps,
+ * weight_decay} in double, read during the call only (no pointer is kept).  Groups with equal tuples share one slot; each slot's
+ * coefficients are formed in double and rounded to fp32 once, as in mmbert_adamw, and travel by value in the kernel arguments: no
+ * device allocation, no copy, no sync, graph-capturable.  A block flagged "decay" applies its own slot's lr * weight_decay.
+ * coef == NULL: the host gscale scales the gradient; else the device scalar coef[0] does (as in mmbert_adamw_devscale).
+ * Flags, modes, bf16 refresh and zero_grad as in mmbert_adamw; n % 256 == 0.  Returns -1 when ngroups is outside
+ * [1, MMBERT_ADAMW_MAX_GROUPS] or the groups hold more than MMBERT_ADAMW_MAX_SLOTS distinct tuples. */
+#define MMBERT_ADAMW_MAX_GROUPS 255
+#define MMBERT_ADAMW_MAX_SLOTS 64      /* distinct (lr, beta1, beta2, eps, weight_decay) per call */
+int mmbert_adamw_grouped(mmbert_stream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags,
+                         const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale,
+                         const float* coef, int mode, int zero_grad);
+
 /* ---- global gradient-norm clipping (torch.nn.utils.clip_grad_norm_) ----
  * segs: device int64 array of nseg pairs (offset, length) in elements of g[0..n): the elements the norm covers, any offsets and lengths
  * (0 <= offset, offset + length <= n; parameters pack inside 256-element blocks).  g 16-byte aligned.  Two launches, no float atomics:

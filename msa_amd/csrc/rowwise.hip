@@ -7,6 +7,7 @@
 // Conventions: one wave (64 lanes) per row, 8-byte bf16x4 accesses, fp32 statistics, row-index
 // maps (int32) where a kernel gathers or scatters rows of the packed token matrix.
 #include "common.h"
+#include <cstring>
 
 std::atomic<int> g_mmb_deterministic{0};     // mmbert_set_deterministic (common.h: every translation unit of the library reads it)
 
@@ -1417,6 +1418,62 @@ __global__ __launch_bounds__(256) void adamw_devscale_kernel(float* __restrict__
     if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
 }
 
+// Per-parameter-group AdamW (torch / transformers param groups with their own lr, betas, eps, weight_decay).  group_of_block[i / 256]
+// names each 256-element block's group, at the granularity of flags; slot[group] picks one of the de-duplicated coefficient sets that
+// mmbert_adamw_grouped formed in double and rounded to fp32 once.  The whole table travels BY VALUE in the kernel arguments: no device
+// allocation, no copy per step (the host runs a step ahead), nothing to sync, graph-capturable.  One wave = 64 lanes x 4 floats = one
+// block, so the group is wave-uniform: readfirstlane makes that provable and the slot word and the 8 coefficients come in as scalar
+// loads from the argument segment, once per wave.  The element loop is adamw_kernel's (same traffic + 1 byte per block).
+#define ADAMW_MAX_GROUPS 255             // == MMBERT_ADAMW_MAX_GROUPS (include/mmbert_hip.h)
+#define ADAMW_MAX_SLOTS 64               // == MMBERT_ADAMW_MAX_SLOTS
+struct AdamWSlots {
+    float c[ADAMW_MAX_SLOTS][8];         // beta1, beta2, 1 - beta1, 1 - beta2, eps, step_size, 1 / sqrt(bc2), lr * wd
+    uint32_t slot4[64];                  // group k -> slot in byte k & 3 of word k >> 2 (a word: one scalar load; 256 entries = every
+                                         // value of a group byte, so a stray index reads slot 0, never past the table)
+};
+static_assert(sizeof(AdamWSlots) == 2304, "AdamWSlots layout");
+static_assert(sizeof(AdamWSlots) + 128 <= 4096, "adamw_grouped_kernel's arguments must fit the 4 KiB kernel-argument segment");
+
+template <bool DEVSCALE>
+__global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                            bf16_t* __restrict__ pb, const uint8_t* __restrict__ flags,
+                                                            const uint8_t* __restrict__ group_of_block, size_t n, const AdamWSlots a,
+                                                            float host_gscale, const float* __restrict__ coef, int mode, int zero_grad) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float gscale = DEVSCALE ? *coef : host_gscale;
+    const uint8_t fb = flags[i >> 8];
+    const uint8_t f = fb & 3;
+    const int grp = __builtin_amdgcn_readfirstlane((int)group_of_block[i >> 8]);
+    float4 P = *(float4*)(p + i);
+    if (f != 2) {
+        const float* c = a.c[(a.slot4[grp >> 2] >> ((grp & 3) * 8)) & 255u];
+        const float beta1 = c[0], beta2 = c[1], omb1 = c[2], omb2 = c[3], eps = c[4], step_size = c[5], rsbc2 = c[6], lrwd = c[7];
+        float4 G = *(float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i);
+        float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w}, ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
+        const float decay = (f == 1) ? lrwd : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float gr = ga[r] * gscale;
+            if (mode == 1) pa[r] *= (1.0f - decay);
+            ma[r] = beta1 * ma[r] + omb1 * gr;
+            va[r] = beta2 * va[r] + omb2 * gr * gr;
+            if (mode == 0) {
+                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) + eps);
+                pa[r] -= decay * pa[r];
+            } else {
+                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) * rsbc2 + eps);
+            }
+        }
+        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
+        *(float4*)(p + i) = P;
+        *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
+        *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
+    }
+    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+}
+
 // --------------------------------------------------------------------------------------------
 // Global gradient norm over a list of element segments of a flat fp32 buffer (torch.nn.utils.clip_grad_norm_: the reference
 // never clips; BERT's recipe and HF Trainer clip at 1.0).  segs[2 s], segs[2 s + 1] = offset, length of
@@ -2268,6 +2325,45 @@ int mmbert_adamw_devscale(hipStream_t stream, float* p, float* g, float* m, floa
     hipLaunchKernelGGL(adamw_devscale_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, n,
                        (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size, (float)(1.0 / sqrt(bc2)),
                        (float)(lr * wd), coef, mode, zero_grad);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+int mmbert_adamw_grouped(hipStream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags,
+                         const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale, const float* coef,
+                         int mode, int zero_grad) {
+    if (n == 0) return 0;
+    if ((n & 255) || !hyper || ngroups < 1 || ngroups > ADAMW_MAX_GROUPS) return -1;
+    AdamWSlots a;
+    memset(&a, 0, sizeof(a));
+    double key[ADAMW_MAX_SLOTS][5];      // (lr, beta1, beta2, eps, weight_decay) of each slot, in first-seen order
+    int nslot = 0;
+    for (int k = 0; k < ngroups; ++k) {
+        const double* h = hyper + 5 * k;
+        int s = 0;
+        while (s < nslot && !(key[s][0] == h[0] && key[s][1] == h[1] && key[s][2] == h[2] && key[s][3] == h[3] && key[s][4] == h[4])) ++s;
+        if (s == nslot) {
+            if (nslot == ADAMW_MAX_SLOTS) return -1;
+            for (int j = 0; j < 5; ++j) key[s][j] = h[j];
+            ++nslot;
+        }
+        a.slot4[k >> 2] |= (uint32_t)s << ((k & 3) * 8);
+    }
+    for (int s = 0; s < nslot; ++s) {    // mmbert_adamw's coefficients, slot by slot: formed in double, rounded to fp32 once
+        const double lr = key[s][0], beta1 = key[s][1], beta2 = key[s][2], eps = key[s][3], wd = key[s][4];
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        const double step_size = mode == 0 ? lr * sqrt(bc2) / bc1 : lr / bc1;
+        const float c[8] = {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size,
+                            (float)(1.0 / sqrt(bc2)), (float)(lr * wd)};
+        for (int j = 0; j < 8; ++j) a.c[s][j] = c[j];
+    }
+    const dim3 grid((unsigned)((n / 4 + 255) / 256));
+    if (coef)
+        hipLaunchKernelGGL(adamw_grouped_kernel<true>, grid, dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, group_of_block, n, a,
+                           1.0f, coef, mode, zero_grad);
+    else
+        hipLaunchKernelGGL(adamw_grouped_kernel<false>, grid, dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, group_of_block, n, a,
+                           (float)gscale, (const float*)nullptr, mode, zero_grad);
     MMB_CHECK_LAUNCH();
     return 0;
 }

@@ -916,6 +916,21 @@ def adamw_devscale(p, g, m, v, p_bf16, flags, coef, *, lr, beta1=0.9, beta2=0.99
                                          int(mode), 1 if zero_grad else 0), "mmbert_adamw_devscale")
 
 
+ADAMW_MAX_GROUPS, ADAMW_MAX_SLOTS = 255, 64      # MMBERT_ADAMW_MAX_GROUPS / _SLOTS (include/mmbert_hip.h)
+
+
+def adamw_grouped(p, g, m, v, p_bf16, flags, group_of_block, hyper, *, step=1, gscale=1.0, coef=None, mode=0, zero_grad=True):
+    """ops.adamw with per-group hyper-parameters (mmbert_adamw_grouped): ``group_of_block`` device uint8 [n / 256], ``hyper`` a host
+    sequence of (lr, beta1, beta2, eps, weight_decay) per group; ``coef`` (device fp32 scalar) replaces ``gscale`` when given."""
+    hyper = [tuple(float(x) for x in h) for h in hyper]
+    assert all(len(h) == 5 for h in hyper) and group_of_block.dtype == torch.uint8 and group_of_block.numel() * 256 >= p.numel()
+    arr = (ctypes.c_double * (5 * max(1, len(hyper))))(*[x for h in hyper for x in h])
+    _lib.check(_lib.load().mmbert_adamw_grouped(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16),
+                                                flags.data_ptr(), group_of_block.data_ptr(), p.numel(), arr, len(hyper), int(step),
+                                                float(gscale), None if coef is None else coef.data_ptr(), int(mode),
+                                                1 if zero_grad else 0), "mmbert_adamw_grouped")
+
+
 GRAD_NORM_WORKSPACE = 8192          # MMBERT_GRAD_NORM_WORKSPACE (include/mmbert_hip.h), bytes
 
 

@@ -27,6 +27,22 @@ def _clip_args(max_norm, norm_type):
     return max_norm, norm_type
 
 
+def adamw_slots(hyper):
+    """What mmbert_adamw_grouped does with the groups' (lr, beta1, beta2, eps, weight_decay) tuples: groups with equal tuples share a
+    slot.  Returns (slot of each group, the distinct tuples in first-seen order); more than ops.ADAMW_MAX_GROUPS groups or
+    ops.ADAMW_MAX_SLOTS distinct tuples raise NotImplementedError."""
+    hyper = [tuple(float(x) for x in h) for h in hyper]
+    if len(hyper) > ops.ADAMW_MAX_GROUPS:
+        raise NotImplementedError(f"AdamW: {len(hyper)} param groups, the fused step takes at most {ops.ADAMW_MAX_GROUPS}: "
+                                  "merge the groups that share lr, betas, eps and weight_decay")
+    index = {}
+    slots = [index.setdefault(h, len(index)) for h in hyper]
+    if len(index) > ops.ADAMW_MAX_SLOTS:
+        raise NotImplementedError(f"AdamW: {len(index)} distinct (lr, betas, eps, weight_decay) combinations in one step, the fused step "
+                                  f"takes at most {ops.ADAMW_MAX_SLOTS}: merge groups (e.g. coarser layer-wise lr decay)")
+    return slots, list(index)
+
+
 class AdamW:
     def __init__(self, params: Union[Iterable[torch.nn.Parameter], List[dict]], lr=1e-3, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, correct_bias=True, mode="hf"):
@@ -38,6 +54,8 @@ class AdamW:
         for g in self.param_groups:
             g.setdefault("weight_decay", weight_decay)
             g.setdefault("lr", lr)
+            g.setdefault("betas", tuple(betas))
+            g.setdefault("eps", eps)
             g["initial_lr"] = g["lr"]
         if not correct_bias:
             raise NotImplementedError("correct_bias=False is not used by the reference")
@@ -73,10 +91,21 @@ class AdamW:
             flags |= lazy                        # + 4: the fused zero_grad leaves these blocks to the next backward's overwriting launches
         self._flags = flags.to(self._flat.device)
 
-    # the scheduler scales every group's lr by the same factor; the kernel takes one lr
     @property
     def lr(self) -> float:
         return self.param_groups[0]["lr"]
+
+    def _hyper(self):
+        """(lr, beta1, beta2, eps, weight_decay) of every group, read afresh (schedulers and users change them between steps); keys that
+        would change the update but are not implemented raise."""
+        out = []
+        for i, g in enumerate(self.param_groups):
+            for key, bad in (("amsgrad", True), ("maximize", True), ("correct_bias", False)):
+                if key in g and bool(g[key]) == bad:
+                    raise NotImplementedError(f"AdamW: param group {i} sets {key}={bad}, which the fused AdamW does not implement")
+            b1, b2 = g["betas"]
+            out.append((float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"])))
+        return out
 
     def _bind(self):
         flat = None
@@ -92,30 +121,52 @@ class AdamW:
                     raise RuntimeError("AdamW: parameters belong to different flat storages")
         if not flat.owns_any():
             raise RuntimeError("AdamW: the model was re-materialised (e.g. moved) after this storage was created")
-        wds = sorted({float(g["weight_decay"]) for g in self.param_groups if g["weight_decay"] > 0})
-        if len(wds) > 1:
-            raise NotImplementedError("one non-zero weight_decay value is supported (the reference uses 0.01 / 0.0)")
-        self.wd = wds[0] if wds else 0.0
+        if len(self.param_groups) > ops.ADAMW_MAX_GROUPS:
+            raise NotImplementedError(f"AdamW: {len(self.param_groups)} param groups, the fused step takes at most {ops.ADAMW_MAX_GROUPS}: "
+                                      "merge the groups that share lr, betas, eps and weight_decay")
+        self._build_maps(flat)               # (first: a refused grouping leaves the optimizer unbound)
+        self._m = torch.zeros_like(flat.params)
+        self._v = torch.zeros_like(flat.params)
+        self._flat = flat
+        self._names = [flat.name_at(p._mmb_flat[1]) for g in self.param_groups for p in g["params"]]
+        self._build_flags()
+
+    def _build_maps(self, flat):
+        """The kernel's per-block maps: flags (decay bit from each group's weight_decay > 0; blocks this optimizer does not step are
+        frozen) and group_of_block.  A 256-element block holds one group: packed neighbours that share a block (the q/k/v biases, a
+        LayerNorm's weight and bias; the q/k/v weights when H * H % 256 != 0) in different groups raise."""
         flags = flat.flags.clone().cpu()
         flags[flags != 2] = 3                # 3 = not owned by this optimizer -> treated as frozen below
-        for g in self.param_groups:
-            f = 1 if g["weight_decay"] > 0 else 0
+        group = torch.zeros_like(flags)
+        owner = torch.full(flags.shape, -1, dtype=torch.int64)      # index into ``names`` of a parameter in the block
+        names, gidx, active, decay = [], [], set(), []
+        for gi, g in enumerate(self.param_groups):
+            decay.append(g["weight_decay"] > 0)
+            f = 1 if decay[-1] else 0
             for p in g["params"]:
                 _, off = p._mmb_flat
                 name = flat.name_at(off)
                 if any(name.startswith(fr) for fr in FROZEN):
                     continue                 # grad is always None in the reference -> optimizer skips it
                 b0, b1 = off // 256, (off + p.numel() + 255) // 256
-                if ((flags[b0:b1] != 3) & (flags[b0:b1] != f)).any():
-                    raise NotImplementedError(f"{name}: packed neighbours must share one weight-decay setting")
+                prev = owner[b0:b1]
+                for j in sorted(set(prev[prev >= 0].tolist())):
+                    if names[j] == name:
+                        raise ValueError(f"AdamW: {name} appears in more than one parameter group")
+                    if gidx[j] != gi:
+                        raise NotImplementedError(f"AdamW: {names[j]} (param group {gidx[j]}) and {name} (param group {gi}) share a 256-element "
+                                                  "block of the flat buffer (packed neighbours): put them in the same param group")
+                names.append(name)
+                gidx.append(gi)
+                owner[b0:b1] = len(names) - 1
                 flags[b0:b1] = f
+                group[b0:b1] = gi
+                active.add(gi)
         flags[flags == 3] = 2
         self._base_flags = flags
-        self._m = torch.zeros_like(flat.params)
-        self._v = torch.zeros_like(flat.params)
-        self._flat = flat
-        self._names = [flat.name_at(p._mmb_flat[1]) for g in self.param_groups for p in g["params"]]
-        self._build_flags()
+        self._group_of_block = group.to(flat.device)
+        self._active = sorted(active)
+        self._decay = tuple(decay)
 
     def clip_grad_norm_(self, max_norm, norm_type=2.0) -> torch.Tensor:
         """Global gradient-norm clipping fused into the next ``step()``: returns the total norm (0-d fp32 device tensor) of the gradient
@@ -137,8 +188,19 @@ class AdamW:
         return out[0]
 
     def step(self):
+        hyper = self._hyper()
         if self._flat is None:
             self._bind()
+        if tuple(h[4] > 0 for h in hyper) != self._decay:
+            self._build_maps(self._flat)     # a group's weight_decay turned on or off since the flags were built
+            self._build_flags()
+        act = [hyper[i] for i in self._active] or hyper[:1]
+        wds = {h[4] for h in act if h[4] > 0}
+        grouped = any(h[:4] != act[0][:4] for h in act) or len(wds) > 1
+        if grouped:
+            adamw_slots(hyper)               # (the limits: raise before anything is launched)
+        lr, beta1, beta2, eps, _ = act[0]
+        wd = wds.pop() if wds else 0.0
         flat = self._flat
         self._steps += 1
         flat.join_side_writers()             # (left by a backward that raised: nothing may still add into the gradients the kernel reads and zeroes)
@@ -146,14 +208,16 @@ class AdamW:
         flat.settle()                        # a lazy gradient no backward has written since the last step counts as zero
         flat.attach_lazy()
         clip, self._clip = self._clip, None
-        if clip is None:
-            ops.adamw(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, lr=self.lr, beta1=self.betas[0],
-                      beta2=self.betas[1], eps=self.eps, wd=self.wd, step=self._steps, gscale=self.grad_scale, mode=self.mode,
-                      zero_grad=True)
+        if grouped:                          # per-group hyper-parameters: each block reads its own group's coefficients
+            ops.adamw_grouped(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, self._group_of_block, hyper,
+                              step=self._steps, gscale=self.grad_scale, coef=None if clip is None else clip[2:3], mode=self.mode,
+                              zero_grad=True)
+        elif clip is None:                   # one set for every group (the reference's two groups): the single-set kernel
+            ops.adamw(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd,
+                      step=self._steps, gscale=self.grad_scale, mode=self.mode, zero_grad=True)
         else:                                # clip_grad_norm_ ran: its coefficient (x grad_scale) from the device
-            ops.adamw_devscale(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, clip[2:3], lr=self.lr,
-                               beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, wd=self.wd, step=self._steps, mode=self.mode,
-                               zero_grad=True)
+            ops.adamw_devscale(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, clip[2:3], lr=lr, beta1=beta1,
+                               beta2=beta2, eps=eps, wd=wd, step=self._steps, mode=self.mode, zero_grad=True)
         flat.refresh_transposes(side=True)
         flat.mark_synced()
         flat.grads_dirty = False
@@ -196,6 +260,37 @@ class AdamW:
             self._v.copy_(sd["v"])
         for g, lr in zip(self.param_groups, sd["lrs"]):
             g["lr"] = lr
+
+
+_NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight")               # REF:train.py:78 (trainer.build_optimizer)
+
+
+def layerwise_param_groups(model, lr, *, weight_decay=0.01, layer_decay=1.0, head_lr=None):
+    """AdamW param groups for fine-tuning from a BERT checkpoint with layer-wise learning-rate decay.  Encoder layer i of L gets
+    ``lr * layer_decay ** (L - i)``, ``bert.embeddings.*`` ``lr * layer_decay ** (L + 1)``, ``bert.pooler.*`` ``lr``; everything a BERT
+    checkpoint does not carry (``bert.jointEmbeddings.*``, ``cls.*``, the fusion head ``classifier1_*`` / ``attn`` / ``vt`` / ``vv`` /
+    ``vs``, the ``cpc_*`` nets) gets ``head_lr`` (default ``lr``).  Weight decay follows the reference's rule by name (none for biases
+    and LayerNorm parameters).  Parameters with the same (lr, weight_decay) share one group, in the order of ``named_parameters()``:
+    with the defaults that is exactly trainer.build_optimizer's two groups."""
+    import re
+    named = list(model.named_parameters())
+    layer = re.compile(r"bert\.encoder\.layer\.(\d+)\.")
+    L = 1 + max((int(m.group(1)) for m in (layer.match(n) for n, _ in named) if m), default=-1)
+    head_lr = lr if head_lr is None else head_lr
+    groups = {}
+    for n, p in named:
+        m = layer.match(n)
+        if m:
+            glr = lr * layer_decay ** (L - int(m.group(1)))
+        elif n.startswith("bert.embeddings."):
+            glr = lr * layer_decay ** (L + 1)
+        elif n.startswith("bert.pooler."):
+            glr = lr
+        else:
+            glr = head_lr
+        wd = 0.0 if any(nd in n for nd in _NO_DECAY) else weight_decay
+        groups.setdefault((glr, wd), []).append(p)
+    return [{"params": ps, "lr": glr, "weight_decay": wd} for (glr, wd), ps in groups.items()]
 
 
 def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None) -> torch.Tensor:

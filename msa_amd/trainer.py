@@ -244,12 +244,18 @@ def default_args(**kw):
 
 def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
     """REF:train.py:76-97: two parameter groups by NAME substring, AdamW, linear warm-up with
-    warmup = N and total = warmup_proportion * N."""
-    from .optim import AdamW, get_linear_schedule_with_warmup
-    no_decay = ["bias", "LayerNorm.bias", "LayerNorm.weight"]
-    named = list(model.named_parameters())
-    groups = [{"params": [p for n, p in named if not any(nd in n for nd in no_decay)], "weight_decay": 0.01},
-              {"params": [p for n, p in named if any(nd in n for nd in no_decay)], "weight_decay": 0.0}]
+    warmup = N and total = warmup_proportion * N.
+    ``args.layer_lr_decay`` / ``args.head_learning_rate`` (optional; not reference arguments, ``default_args()`` leaves them out): the
+    groups of optim.layerwise_param_groups (layer-wise lr decay, a learning rate of its own for the parts a BERT checkpoint lacks)."""
+    from .optim import AdamW, get_linear_schedule_with_warmup, layerwise_param_groups
+    layer_decay, head_lr = getattr(args, "layer_lr_decay", None), getattr(args, "head_learning_rate", None)
+    if layer_decay is not None or head_lr is not None:
+        groups = layerwise_param_groups(model, args.learning_rate, layer_decay=1.0 if layer_decay is None else layer_decay, head_lr=head_lr)
+    else:
+        no_decay = ["bias", "LayerNorm.bias", "LayerNorm.weight"]
+        named = list(model.named_parameters())
+        groups = [{"params": [p for n, p in named if not any(nd in n for nd in no_decay)], "weight_decay": 0.01},
+                  {"params": [p for n, p in named if any(nd in n for nd in no_decay)], "weight_decay": 0.0}]
     opt = AdamW(groups, lr=args.learning_rate, mode=mode)
     sched = get_linear_schedule_with_warmup(opt, num_warmup_steps=num_train_optimization_steps,
                                             num_training_steps=args.warmup_proportion * num_train_optimization_steps)
