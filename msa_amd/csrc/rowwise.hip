@@ -2154,7 +2154,10 @@ int mmbert_pair_proj_fwd(hipStream_t stream, const void* feat, int feat_f64, int
     if (D < 1 || H < 1) return -1;
     const int KC = D < 128 ? (D + 3) & ~3 : 128;                 // k chunk in LDS (a multiple of 4); row pitch = 2 mod 16 floats
     const int pitch = KC + ((18 - (KC & 15)) & 15);
-    const int lds = 192 * pitch * (int)sizeof(float);             // <= 99 840 bytes
+    // the operand tiles, and the output tile the full-tile store stages through the same LDS ([64][136] bf16: 17 408 bytes, more
+    // than the operand tiles of D <= 16 take -- rows 51-63 of every such tile were lost)
+    const int ops_lds = 192 * pitch * (int)sizeof(float), out_lds = 64 * 136 * (int)sizeof(bf16_t);
+    const int lds = ops_lds > out_lds ? ops_lds : out_lds;       // <= 99 840 bytes
     return feat_f64 ? pair_proj_fwd_launch(stream, (const double*)feat, n, P, D, W, bias, H, out, ldo, T, KC, pitch, lds)
                     : pair_proj_fwd_launch(stream, (const float*)feat, n, P, D, W, bias, H, out, ldo, T, KC, pitch, lds);
 }

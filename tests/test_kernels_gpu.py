@@ -912,6 +912,12 @@ def test_embed_gather_scatter(ops):
     assert_close(gw, rw, 1e-4, 1e-4, "word grad")
     assert_close(gt, rt, 1e-4, 1e-3, "type grad")
     assert_close(gp, rp, 1e-4, 1e-4, "pos grad")
+    # and against the float64 reference's bounds (tests/embed_ref.py)
+    from tests import embed_ref as E
+    E.check(out, E.gather(ids, tts, word, typ, pos, T), "gather")
+    ref = E.scatter(ids, tts, d, T, torch.zeros(V, H), torch.zeros(2, H), torch.zeros(64, H), det=ops.deterministic())
+    for nm, got in (("gword", gw), ("gtype", gt), ("gpos", gp)):
+        E.check(got, ref[nm], nm)
 
 
 @pytest.mark.parametrize("D", [35, 74, 371])
@@ -934,6 +940,14 @@ def test_pair_proj(ops, D):
     ops.pair_proj_bwd(feat.to(DEV), out, dJ.to(DEV), T, dW, db)
     assert_close(dW, Wr.grad, 1e-3, 1e-3, "pair dW")
     assert_close(db, br.grad, 1e-3, 1e-3, "pair db")
+    # and against the float64 reference's bounds (tests/embed_ref.py)
+    from tests import embed_ref as E
+    rows = E.pair_rows(B, P, T)
+    E.check(out, E.pair_fwd(feat, W, b, rows=rows), "pair fwd")
+    rb = E.pair_bwd(feat, out[rows.to(DEV)].cpu(), dJ[rows], torch.zeros(H, D), torch.zeros(H),
+                    cus=torch.cuda.get_device_properties(0).multi_processor_count)
+    E.check(dW, rb["dW"], "pair dW")
+    E.check(db, rb["db"], "pair db")
     dW2, db2 = torch.zeros(H, D, device=DEV), torch.zeros(H, device=DEV)      # per-row-range slabs added in range order: reproducible
     ops.pair_proj_bwd(feat.to(DEV), out, dJ.to(DEV), T, dW2, db2)
     assert torch.equal(dW, dW2) and torch.equal(db, db2)
