@@ -1806,6 +1806,11 @@ __device__ __forceinline__ float mask_value(const MaskSeg& g, int b, int p) {
     }
 }
 
+// (1 - m) * -10000 with the reference's two fp32 roundings.  Written as plain operators, -ffast-math let hipcc distribute it into ONE
+// fma(m, 10000, -10000): one rounding, so m = 3e-8 read as a masked key (-10000) where the reference's -9999.999 is a live one, and
+// m = 1 gave +0 where the reference gives -0.  The round-to-nearest library forms are never reassociated or contracted.
+__device__ __forceinline__ float key_bias_of(float m) { return __ocml_mul_rte_f32(__ocml_sub_rte_f32(1.0f, m), -10000.0f); }
+
 __global__ __launch_bounds__(256) void prologue_seq_kernel(const PrologueArgs a) {
     __shared__ int red[4][5];
     const int s = blockIdx.x, p = s / a.B, b = s - p * a.B;
@@ -1821,7 +1826,7 @@ __global__ __launch_bounds__(256) void prologue_seq_kernel(const PrologueArgs a)
                 const MaskSeg& g = a.seg[q];
                 if (g.pass == p && pos >= g.offset && pos < g.offset + g.len) { m = mask_value(g, b, pos - g.offset); break; }
             }
-            bias = (1.0f - m) * -10000.0f;
+            bias = key_bias_of(m);
             if (bias > -10000.0f) last_key = pos;
             if (a.labels) {
                 const int64_t lab = a.labels[row0 + pos];
