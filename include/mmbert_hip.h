@@ -180,6 +180,16 @@ int mmbert_attn_kv_len(mmbert_stream_t stream, const float* key_bias, const int*
 int mmbert_attn_fwd(mmbert_stream_t stream, const void* qkv, void* ctx, float* lse, const float* key_bias, const int* bias_start, int H, int heads,
                     const int* seq_start, const int* seq_len, const unsigned* elem_base, const int* tile_seq, const int* tile_r0, int ntiles,
                     uint32_t dstream, uint32_t dthr, float dscale, const int* kv_len, const int* tile_qshift, const int* tile_qend);
+/* Attention forward for ONE query row per sequence -- inference only (no dropout, no LSE, nothing kept for a backward pass): the top
+ * encoder layer of a label-free prediction, whose output is read at the [CLS] rows alone.  Reads K and V of every row of the packed
+ * qkv matrix [tokens, 3H] (keys / values of sequence s at rows seq_start[s] + index, as in mmbert_attn_fwd) and the query of row
+ * q_row[s] -- a packed row of the same matrix, wherever the caller's packing put the sequence's query (its [CLS] row).  key_bias,
+ * bias_start: the padded per-sequence layout of mmbert_attn_fwd (entries past a sequence's length <= -1e30); kv_len (may be null):
+ * trailing masked keys are skipped, exact as there.  ctx: COMPACT output [nseq, H] bf16, row s = sequence s.
+ * softmax(q.k^T / 8 + key_bias) . v with fp32 scores, softmax and accumulation, one bf16 rounding at the store; a fully masked sequence
+ * is a softmax over equally biased keys.  One workgroup per (sequence, head), no atomics: bitwise reproducible.  nseq <= 65535. */
+int mmbert_attn_fwd_first(mmbert_stream_t stream, const void* qkv, void* ctx, const float* key_bias, const int* bias_start, int H, int heads,
+                          const int* seq_start, const int* seq_len, const int* q_row, int nseq, const int* kv_len);
 int mmbert_attn_bwd(mmbert_stream_t stream, const void* qkv, const void* ctx, const void* dctx, void* dqkv, const float* lse, float* delta,
                     const float* key_bias, const int* bias_start, int H, int heads, const int* seq_start, const int* seq_len, const unsigned* elem_base,
                     const int* qtile_seq, const int* qtile_r0, int nqtiles,      /* query tiles: mmbert_attn_tile_rows(0) rows */
@@ -328,6 +338,14 @@ int mmbert_heads_step_bwd(mmbert_stream_t stream, const mmbert_heads_step* p);
  * beside the MLM head's launches on a side stream; forward level 7 (the losses; the only one that reads `mlm`) behind both. */
 int mmbert_heads_step_fwd_levels(mmbert_stream_t stream, const mmbert_heads_step* p, int lo, int hi);
 int mmbert_heads_step_bwd_levels(mmbert_stream_t stream, const mmbert_heads_step* p, int lo, int hi);
+/* Prediction without labels -- inference only: forward levels 1 .. 5 (pooler, align / seq_relationship scores, gates, gated concatenation,
+ * classifier1_1 / 1_2; the same kernels as mmbert_heads_step_fwd_levels(p, 1, 5), the same bits).  Reads `first` (or y + first_rows), the
+ * parameters and tanh_lo; writes logits [B], t_rel [B,2], rel [2B,2] and ws.  ap, ap2, sent, mlm, loss, aux, out5, sync and every gradient
+ * pointer are NOT read and may be null.  B <= 128 (no level couples samples: a larger batch is run in chunks), H % 16 == 0.
+ * mmbert_heads_step_outputs: where, in floats from the start of ws, forward leaves the pooler outputs P [3B, H] (text, visual, speech)
+ * and the classifier1_1 output T [B, H] (same B, H as the call that wrote ws); returns 0, or -1 for B, H <= 0. */
+int mmbert_heads_predict(mmbert_stream_t stream, const mmbert_heads_step* p);
+int mmbert_heads_step_outputs(int B, int H, size_t* pooled_offset, size_t* fused_offset);
 /* dmlm[i] = dloss * alpha / nmlm alone (backward level 6 writes the same): the MLM head's backward needs nothing else of the heads' to start */
 int mmbert_heads_step_dmlm(mmbert_stream_t stream, const mmbert_heads_step* p);
 

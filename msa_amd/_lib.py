@@ -47,6 +47,7 @@ SIGNATURES = {
     "mmbert_attn_tile_rows": (I, [I]),
     "mmbert_attn_kv_len": (I, [P, P, P, P, I, P]),
     "mmbert_attn_fwd": (I, [P, P, P, P, P, P, I, I, P, P, P, P, P, I, U32, U32, F, P, P, P]),
+    "mmbert_attn_fwd_first": (I, [P, P, P, P, P, I, I, P, P, P, I, P]),
     "mmbert_attn_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, I, P, P, I, U32, U32, F, P, P, P, I, P]),
     "mmbert_attn_q_limit": (I, [P, P, I, P, I, P]),
     "mmbert_attn_dropout_mask": (I, [P, P, I, C.c_uint, I, U32, U32]),
@@ -73,6 +74,8 @@ SIGNATURES = {
     "mmbert_heads_step_fwd_levels": (I, [P, P, I, I]),
     "mmbert_heads_step_bwd_levels": (I, [P, P, I, I]),
     "mmbert_heads_step_dmlm": (I, [P, P]),
+    "mmbert_heads_predict": (I, [P, P]),
+    "mmbert_heads_step_outputs": (I, [I, I, P, P]),
     "mmbert_layer_fwd": (I, [P, P, P]),
     "mmbert_layer_bwd": (I, [P, P, P]),
     "mmbert_layer_struct_sizes": (I, [P]),

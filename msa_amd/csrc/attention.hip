@@ -770,6 +770,122 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
     }
 }
 
+// =============================================================================================
+// forward for ONE query row per sequence (inference: the top encoder layer of a label-free prediction, whose output is read at the
+// [CLS] rows only).  Workgroup = one (sequence, head), 4 waves; 8 consecutive lanes own one key: lane c of the group holds dims
+// 8c .. 8c+7 of the query (fp32, times 1/8), loads the same 16 bytes of the key's K and V rows straight to registers, the score is its
+// partial dot product summed over the group (three shuffles).  A group walks keys g, g + 32, ... four at a time (eight 16-byte loads
+// in flight per lane) with its own running maximum / denominator / fp32 output slice; the 32 groups are merged at the end in a fixed
+// order (shuffles, then 1.3 KB of LDS): no atomics, the same bits every run.  No MFMA: 2 flops per loaded byte, bound by the K / V read.
+// fp32 scores, fp32 softmax, fp32 P.V, one bf16 rounding at the store; no dropout, no LSE.
+// =============================================================================================
+struct AttnFirstArgs {
+    const bf16_t* qkv; int ld_qkv;
+    bf16_t* ctx;             // [nseq, H]
+    const float* key_bias; const int* bias_start; const int* kv_len;
+    const int* seq_start; const int* seq_len; const int* q_row;
+    int H; float scale;
+};
+
+struct AfState { float m, l, o[8]; };
+__device__ __forceinline__ void af_merge(AfState& a, const AfState& b) {
+    const float M = fmaxf(a.m, b.m);
+    const float wa = a.m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f((a.m - M) * LOG2E);
+    const float wb = b.m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f((b.m - M) * LOG2E);
+    a.m = M; a.l = a.l * wa + b.l * wb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a.o[j] = a.o[j] * wa + b.o[j] * wb;
+}
+
+__global__ __launch_bounds__(256) void attn_fwd_first_kernel(const AttnFirstArgs a) {
+    __shared__ float part[4][8][10];
+    const int head = blockIdx.x, seq = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 7, grp = wave * 8 + (lane >> 3);
+    const int start = a.seq_start[seq], S = a.seq_len[seq];
+    const int Skv = a.kv_len ? min(S, a.kv_len[seq]) : S;               // keys at and past Skv are all masked out (probability exactly 0)
+    bf16_t* orow = a.ctx + (size_t)seq * a.H + head * 64;
+    if (Skv <= 0) {                                                       // an empty sequence has no keys: a zero row
+        if (threadIdx.x < 8) *(bf16x8*)(orow + 8 * threadIdx.x) = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+        return;
+    }
+    const bf16_t* kbase = a.qkv + (size_t)start * a.ld_qkv + a.H + head * 64 + 8 * c;
+    const bf16_t* vbase = kbase + a.H;
+    const float* bbase = a.key_bias + a.bias_start[seq];
+    float q[8];
+    {
+        const bf16x8 qv = *(const bf16x8*)(a.qkv + (size_t)a.q_row[seq] * a.ld_qkv + head * 64 + 8 * c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q[j] = bf2f(qv[j]) * a.scale;
+    }
+    AfState st;
+    st.m = -INFINITY; st.l = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) st.o[j] = 0.f;
+
+    for (int k0 = grp; k0 < Skv; k0 += 128) {                            // (k0 < Skv: at least one key of the four is real, the maximum stays finite)
+        bf16x8 kf[4], vf[4];
+        float b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = min(k0 + 32 * u, Skv - 1);                     // clamped address; the score of a key past the end is set to -inf below
+            kf[u] = *(const bf16x8*)(kbase + (size_t)k * a.ld_qkv);
+            vf[u] = *(const bf16x8*)(vbase + (size_t)k * a.ld_qkv);
+            b[u] = bbase[k];
+        }
+        float s[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float d = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], bf2f(kf[u][j]), d);
+            d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64); d += __shfl_xor(d, 4, 64);
+            s[u] = k0 + 32 * u < Skv ? d + b[u] : -INFINITY;
+        }
+        const float mnew = fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), st.m);
+        const float alpha = __builtin_amdgcn_exp2f((st.m - mnew) * LOG2E);            // first batch: exp2(-inf) = 0
+        st.m = mnew; st.l *= alpha;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) st.o[j] *= alpha;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float p = __builtin_amdgcn_exp2f((s[u] - mnew) * LOG2E);
+            st.l += p;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) st.o[j] = __builtin_fmaf(p, bf2f(vf[u][j]), st.o[j]);
+        }
+    }
+    // the 8 key groups of a wave (lanes with equal c), then the 4 waves
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+        AfState o2;
+        o2.m = __shfl_xor(st.m, off, 64); o2.l = __shfl_xor(st.l, off, 64);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o2.o[j] = __shfl_xor(st.o[j], off, 64);
+        af_merge(st, o2);
+    }
+    if (lane < 8) {
+        part[wave][lane][0] = st.m; part[wave][lane][1] = st.l;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) part[wave][lane][2 + j] = st.o[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            AfState o2;
+            o2.m = part[w][c][0]; o2.l = part[w][c][1];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o2.o[j] = part[w][c][2 + j];
+            af_merge(st, o2);
+        }
+        const float inv = 1.0f / st.l;
+        const bf16x8 ov = {f2bf(st.o[0] * inv), f2bf(st.o[1] * inv), f2bf(st.o[2] * inv), f2bf(st.o[3] * inv),
+                           f2bf(st.o[4] * inv), f2bf(st.o[5] * inv), f2bf(st.o[6] * inv), f2bf(st.o[7] * inv)};
+        *(bf16x8*)(orow + 8 * c) = ov;
+    }
+}
+
 // test/debug: the keep mask of one (sequence, head) as bytes [S, S]
 __global__ void attn_mask_kernel(uint8_t* out, int S, unsigned elem_base, int head, uint32_t stream, uint32_t thr) {
     const int Spad = (S + 3) & ~3;
@@ -857,6 +973,18 @@ int mmbert_attn_fwd(hipStream_t stream, const void* qkv, void* ctx, float* lse, 
     constexpr int extra_lds = 0;
     if (dthr) hipLaunchKernelGGL(attn_fwd_kernel<true>, a.head_fast ? dim3(heads, ntiles) : dim3(ntiles, heads), dim3(256), extra_lds, stream, a);
     else hipLaunchKernelGGL(attn_fwd_kernel<false>, a.head_fast ? dim3(heads, ntiles) : dim3(ntiles, heads), dim3(256), extra_lds, stream, a);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+int mmbert_attn_fwd_first(hipStream_t stream, const void* qkv, void* ctx, const float* key_bias, const int* bias_start, int H, int heads,
+                          const int* seq_start, const int* seq_len, const int* q_row, int nseq, const int* kv_len) {
+    if (nseq <= 0) return 0;
+    if (heads <= 0 || H != heads * 64 || nseq > 65535 || !qkv || !ctx || !key_bias || !bias_start || !seq_start || !seq_len || !q_row) return -1;
+    AttnFirstArgs a;
+    a.qkv = (const bf16_t*)qkv; a.ld_qkv = 3 * H; a.ctx = (bf16_t*)ctx; a.key_bias = key_bias; a.bias_start = bias_start; a.kv_len = kv_len;
+    a.seq_start = seq_start; a.seq_len = seq_len; a.q_row = q_row; a.H = H; a.scale = 0.125f;
+    hipLaunchKernelGGL(attn_fwd_first_kernel, dim3(heads, nseq), dim3(256), 0, stream, a);
     MMB_CHECK_LAUNCH();
     return 0;
 }

@@ -620,6 +620,32 @@ int mmbert_heads_step_fwd_levels(hipStream_t stream, const mmbert_heads_step* p,
 
 int mmbert_heads_step_fwd(hipStream_t stream, const mmbert_heads_step* p) { return mmbert_heads_step_fwd_levels(stream, p, 1, 7); }
 
+// prediction without labels: levels 1 .. 5 read the [CLS] rows, the parameters and the workspace -- labels, losses and the loss level's counter
+// are level 7's (so they are not asked for here); same kernels, grids and bits as mmbert_heads_step_fwd_levels(p, 1, 5)
+int mmbert_heads_predict(hipStream_t stream, const mmbert_heads_step* p) {
+    if (!p || p->B <= 0 || p->B > 128 || p->H < 16 || (p->H & 15) || !p->ws || (!p->first && (!p->y || !p->first_rows || (p->ldy & 3)))) return -1;
+    if (!p->logits || !p->t_rel || !p->rel) return -1;
+    if (!p->Wp || !p->bp || !p->Wal || !p->bal || !p->Wsr || !p->bsr || !p->Wat || !p->bat || !p->Wc1 || !p->bc1 || !p->Wc2 || !p->bc2) return -1;
+    for (int m = 0; m < 3; ++m) if (!p->vw[m] || !p->vb[m] || !p->Wq[m] || !p->bq[m]) return -1;
+    const int cus = mmb_device_cus();
+    const int B = p->B, H = p->H, R = 3 * B, tH = H >> 4, tB = (B + 15) >> 4, tR = (R + 15) >> 4, t2B = (2 * B + 15) >> 4;
+    const int red = HC_WAVES * 256 * (int)sizeof(float);
+    HC_LAUNCH(heads_fwd_level_kernel, 1, hc_grid(tR * tH + t2B, p->first ? 0 : R, cus, 1), red);
+    HC_LAUNCH(heads_fwd_level_kernel, 2, hc_grid(tR * tH + tB, 0, cus, 1), red);
+    HC_LAUNCH(heads_fwd_level_kernel, 3, hc_grid(0, R, cus, 1), red);
+    HC_LAUNCH(heads_fwd_level_kernel, 4, hc_grid(tB * tH, 0, cus, 1), red);
+    HC_LAUNCH(heads_fwd_level_kernel, 5, hc_grid(tB * 3 * tH + tB, 0, cus, 1), red);
+    return 0;
+}
+
+int mmbert_heads_step_outputs(int B, int H, size_t* pooled_offset, size_t* fused_offset) {
+    if (B <= 0 || H <= 0) return -1;
+    const HcWs w = hc_ws(B, H, nullptr, nullptr);
+    if (pooled_offset) *pooled_offset = (size_t)((uintptr_t)w.P / sizeof(float));      // (base 0: the fields are the offsets)
+    if (fused_offset) *fused_offset = (size_t)((uintptr_t)w.T / sizeof(float));
+    return 0;
+}
+
 int mmbert_heads_step_bwd_levels(hipStream_t stream, const mmbert_heads_step* p, int lo, int hi) {
     int cus;
     if (hc_check(p, &cus)) return -1;

@@ -385,12 +385,14 @@ class _EncoderFn:
     autograd between its stages)."""
 
     @staticmethod
-    def run_forward(top, x, layout, key_bias, seed, kv_len, keep, y_out=None, y_rows=None):
+    def run_forward(top, x, layout, key_bias, seed, kv_len, keep, y_out=None, y_rows=None, stop=None, train=None):
         """Returns (y, saved).  ``y_out`` / ``y_rows``: the LAST layer's LayerNorm writes row i of its output to y_out[y_rows[i]] --
-        the un-packing of the valid-first layout (ops.SplitLayout.perm32) rides on that store instead of a [tokens, H] gather."""
+        the un-packing of the valid-first layout (ops.SplitLayout.perm32) rides on that store instead of a [tokens, H] gather.
+        ``stop``: run layers 0 .. stop - 1 only; ``train``: the dropout decision, when it is not the module's mode (both: predict())."""
         cfg = top.config
         H, L = cfg.hidden_size, cfg.num_hidden_layers
-        train = top.training
+        nl = L if stop is None else stop
+        train = top.training if train is None else train
         ph = cfg.hidden_dropout_prob if train else 0.0
         pa = cfg.attention_probs_dropout_prob if train else 0.0
         saved = []
@@ -405,7 +407,7 @@ class _EncoderFn:
             heads = layout.heads
             bf, f32 = torch.bfloat16, torch.float32
             tq = ops._tile_queue(dev)
-            for i in range(L):
+            for i in range(nl):
                 lw = top._lw[i]
                 d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
                 last = i == L - 1 and y_out is not None
@@ -437,7 +439,7 @@ class _EncoderFn:
                     saved.append((x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2))
                 x = y2
             return x, saved
-        for i in range(L):
+        for i in range(nl):
             lw = top._lw[i]
             d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
             qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
@@ -456,6 +458,28 @@ class _EncoderFn:
             if top.debug_hidden is not None:
                 top.debug_hidden.setdefault("_layers_packed", []).append(None if last else y2.detach())
         return x, saved
+
+    @staticmethod
+    def run_top_first(top, x, layout, key_bias, kv_len, q_rows):
+        """The TOP layer for a label-free prediction (inference arithmetic, no dropout): its output is read at one row per sequence only
+        (``q_rows`` int32: the packed row of each sequence's [CLS] query), so only that query attends (ops.attn_fwd_first) and everything
+        behind the attention runs on the gathered [sequences, H] rows.  The QKV projection stays the existing full launch: K and V are
+        needed for every row, and leaving the Q third out (N = 2H plus a Q product on the gathered rows) cannot win -- at the headline shape
+        the full launch takes 58 us, so a third is 19 us, and a 48-row product on the small-shape kernel takes 19 - 36 us (the three behind
+        the attention, profiles/predict_ab.txt); the split form itself was not built.  Returns [sequences, H] bf16."""
+        cfg = top.config
+        H = cfg.hidden_size
+        lw = top._lw[cfg.num_hidden_layers - 1]
+        qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
+        actx = ops.attn_fwd_first(qkv, key_bias, layout, H, q_rows, kv_len=kv_len)
+        del qkv
+        xr = ops.gather_rows([x], q_rows)[0]
+        z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=xr)
+        y1, _, _ = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=False)
+        g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True)
+        z2 = ops.gemm_nt(g, lw["W2"], bias=lw["b2"], resid=y1)
+        y2, _, _ = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=False)
+        return y2
 
     @staticmethod
     def run_backward(top, layout, key_bias, kv_len, saved, dy, dy_rows, top_rows, compact=None, lnd=None):
@@ -719,7 +743,7 @@ def _trunk_static(plan, B, T, lens, joff, dev):
 class _Trunk:
     """What one _TrunkFn call works on (plain attributes; built by _encode)."""
     __slots__ = ("ids", "tts", "B", "T", "lens", "pair_info", "feats", "feat_versions", "plan", "layout", "split", "key_bias", "kv_len", "seed", "top_rows",
-                 "d_emb", "d_joint", "infer", "late_split", "compact", "J_pre")
+                 "d_emb", "d_joint", "infer", "late_split", "compact", "J_pre", "predict")
 
 
 class _TrunkFn(torch.autograd.Function):
@@ -816,6 +840,16 @@ class _TrunkFn(torch.autograd.Function):
         if split is not None and not t.infer:
             y_out = (torch.zeros if dropped else torch.empty)((tokens, H), device=dev, dtype=torch.bfloat16)
             y_rows = split.perm32
+        if t.predict:
+            # label-free prediction: layers 0 .. L - 2 as always, the top layer for the [CLS] query of every sequence only; no [tokens, H]
+            # un-packing -- the output is the compact [sequences, H] matrix of those rows, in the caller's sequence order
+            kvl = None if split is not None else t.kv_len
+            y, _ = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, kvl, False, stop=cfg.num_hidden_layers - 1, train=False)
+            first32 = plan.get("first32")
+            if first32 is None:
+                first32 = plan["first32"] = plan["first"].to(torch.int32)
+            q_rows = split.inv32.index_select(0, plan["first"]) if split is not None else first32
+            return _EncoderFn.run_top_first(top, y, layout, t.key_bias, kvl, q_rows)
         y, saved = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, None if split is not None else t.kv_len, keep, y_out, y_rows)
         if split is not None and t.infer:
             y = y.index_select(0, split.inv)                      # every masked-out row reads its sequence's representative
@@ -1370,26 +1404,32 @@ class _GpuModelBase(nn.Module):
         n = len(passes) * B * T
         return packed[:n], packed[n:2 * n], (packed[2 * n:] if label_parts else None)
 
-    def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None):
+    def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None, predict=False):
         """passes: list of dict(ids[B,T], tt[B,T]|None, mask, pair[B,P,D]|None, pair_mask|None).
         Returns (Y [tokens,H] bf16, plan, lens_per_pass, rows) -- ``rows`` = (labelled-row list, host words, event) when asked for.
         ``rowset``: the valid-first packing over a row SET instead of a prefix per sequence (the prologue's row-set mode): for
         sequences whose masked-out rows do not sit at the end -- the fused text | visual | speech sequence has its visual padding in
         the middle.  Every sequence is then run in its own valid-first order (active rows = unmasked keys and labelled rows, first):
         attention is invariant under a permutation of the keys that carries the key bias along, every other operator is row-wise,
-        and the un-packing gather restores the caller's order.  Only with a backward pass to save (labels, autograd on)."""
+        and the un-packing gather restores the caller's order.  Only with a backward pass to save (labels, autograd on).
+        ``predict`` (predict(): no labels, under no_grad): inference arithmetic whatever the module's mode is -- no dropout, the
+        inference packing -- with the top layer run for the [CLS] rows only; Y is then the compact [sequences, H] matrix of those rows.
+        Such a call takes nothing from and leaves nothing in the model's per-step state: no dropout seed is drawn, the prologue runs
+        on the current stream into buffers of its own (the alternating sets of ``async_prologue`` stay as they are), the leftovers of
+        a train step are not touched and no trunk record is kept."""
         bert = self._bert()
         dev = passes[0]["ids"].device
         self._ensure_ready(dev)
-        lnd = self.__dict__.get("_lnd")
-        if lnd is not None and lnd.items and torch.is_grad_enabled():
-            lnd.drop()                 # a backward pass that raised half-way left its LayerNorm' sums behind: no pass is in flight at a forward
-        self._drop_leftovers()
+        if not predict:
+            lnd = self.__dict__.get("_lnd")
+            if lnd is not None and lnd.items and torch.is_grad_enabled():
+                lnd.drop()             # a backward pass that raised half-way left its LayerNorm' sums behind: no pass is in flight at a forward
+            self._drop_leftovers()
         B, T = passes[0]["ids"].shape
         cfg = self.config
         if T > cfg.max_position_embeddings:
             raise ValueError("text length exceeds max_position_embeddings")
-        seed = self._next_seed()
+        seed = 0 if predict else self._next_seed()         # (predict: no dropout site is live, the seed is never read)
         je = bert.jointEmbeddings
         rowset = bool(rowset and labels is not None and torch.is_grad_enabled() and getattr(self, "skip_padded_backward", True)
                       and getattr(self, "skip_masked_keys", True))
@@ -1397,7 +1437,7 @@ class _GpuModelBase(nn.Module):
         # lengths, the rows backward must visit and the labelled-row list, and starts the one device -> host copy of the step
         # (the embedding kernels below keep the GPU busy while it travels and the host packs the layout)
         segs, lens, pair_info = [], [], []
-        side = self._prologue_stream(passes[0]["ids"])
+        side = None if predict else self._prologue_stream(passes[0]["ids"])
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):     # (a 3-D text mask is reduced by a kernel)
             for k, p in enumerate(passes):
                 segs.append((self._mask2d(p["mask"], False, dev), k, 0))
@@ -1449,13 +1489,15 @@ class _GpuModelBase(nn.Module):
             marks[k % 2] = mark
             main.wait_event(ev)
         key_bias = pro.key_bias                                       # per-sequence padded layout, -1e30 = "no such key"
-        self._last_valid_dev = pro.valid
+        if not predict:
+            self._last_valid_dev = pro.valid
         rows = (pro.idx, host[nseq:], ev) if want_rows else None
         # padded pair rows are masked-out keys at the tail of every joint sequence: the attention kernels skip them (exact)
         kv_len = pro.kv_len if getattr(self, "skip_masked_keys", True) else None
         # inference (no dropout, no autograd): the masked-out rows of a sequence are identical in every layer -> one stands for all
-        infer = (not self.training) and (not torch.is_grad_enabled()) and getattr(self, "dedupe_masked_rows", True)
-        self.last_backward_row_fraction = 1.0                            # (bookkeeping for bench.py: share of rows backward visits)
+        infer = (predict or ((not self.training) and (not torch.is_grad_enabled()))) and getattr(self, "dedupe_masked_rows", True)
+        if not predict:
+            self.last_backward_row_fraction = 1.0                        # (bookkeeping for bench.py: share of rows backward visits)
         pending = None
         if kv_len is not None:
             if infer:
@@ -1477,10 +1519,11 @@ class _GpuModelBase(nn.Module):
                 with torch.cuda.stream(side):
                     early_ids = torch.cat([p["ids"].reshape(-1).long() for p in passes])
             self.embed_ids_hook(early_ids, side)
-        p_emb = cfg.hidden_dropout_prob if self.training else 0.0
-        p_joint = je.dropout_prob if (self.training and je.training) else 0.0
+        p_emb = cfg.hidden_dropout_prob if (self.training and not predict) else 0.0
+        p_joint = je.dropout_prob if (self.training and je.training and not predict) else 0.0
         t = _Trunk()
         t.compact = None
+        t.predict = bool(predict)
         t.ids, t.tts, t.B, t.T, t.lens, t.pair_info, t.plan = ids, tts, B, T, lens, pair_info, plan
         t.feats = [None if info is None else tuple(_pair_features(f, dev) for f in info[0]) for info in pair_info]
         t.feat_versions = [None if fs is None else tuple(f._version for f in fs) for fs in t.feats]
@@ -1531,6 +1574,8 @@ class _GpuModelBase(nn.Module):
         t.layout = get_split                                      # (late: _TrunkFn calls it once the embedding kernels are queued)
         y = _TrunkFn.apply(bert.embeddings.LayerNorm.weight, self, t)
         split = t.split
+        if predict:
+            return y, plan, lens, rows
         self._last_trunk = t                                       # (forward() hands it to the MLM head: compact output gradient)
         if self.debug_hidden is not None:
             packed = self.debug_hidden.pop("_layers_packed", [])
@@ -1724,6 +1769,44 @@ class _HeadsStepFn(torch.autograd.Function):
     ``first``: fp32 [3B, H]; or, with ``src = (y bf16 [tokens, H], rows int64 [3B])``, a placeholder whose rows the kernel reads from y."""
 
     @staticmethod
+    def _set_params(top, a):
+        """The heads' parameter pointers of the argument record (shared by the train step and predict())."""
+        pool, al, sr, at = top.bert.pooler.dense, top.cls.align, top.cls.seq_relationship, top.attn
+        vs3 = (top.vt, top.vv, top.vs)
+        c1, c2 = top.classifier1_1, top.classifier1_2
+        qs = (top.cpc_zt.net, top.cpc_zv.net, top.cpc_za.net)
+        assert c2.weight.shape[0] == 1 and at.weight.is_contiguous()
+        a.Wp, a.bp, a.Wal, a.bal, a.Wsr, a.bsr = (t.data_ptr() for t in (pool.weight, pool.bias, al.weight, al.bias, sr.weight, sr.bias))
+        a.Wat, a.bat, a.Wc1, a.bc1, a.Wc2, a.bc2 = (t.data_ptr() for t in (at.weight, at.bias, c1.weight, c1.bias, c2.weight, c2.bias))
+        for m in range(3):
+            a.vw[m], a.vb[m], a.Wq[m], a.bq[m] = vs3[m].weight.data_ptr(), vs3[m].bias.data_ptr(), qs[m].weight.data_ptr(), qs[m].bias.data_ptr()
+
+    @staticmethod
+    def predict(top, y, B):
+        """The heads of a label-free prediction on the compact [3B, H] bf16 [CLS] rows ``y`` (text, visual, speech): forward levels 1 - 5
+        (mmbert_heads_predict: no labels, no losses), in chunks of <= 128 samples -- without the loss level nothing couples the samples of
+        a batch, so any B goes through the level-launch kernels.  Returns (logits [B,1], t_rel, v_rel, s_rel [B,2], pooled [3,B,H], fused [B,H])."""
+        H, dev, f32 = y.shape[1], y.device, torch.float32
+        assert y.dtype == torch.bfloat16 and y.is_contiguous() and y.shape[0] == 3 * B
+        parts = []
+        for b0 in range(0, B, 128):
+            n = min(128, B - b0)
+            a = ops.heads_step_struct()
+            a.B, a.H, a.tanh_lo = n, H, 1 if top.num_labels == 1 else 0
+            rows = (torch.arange(b0, b0 + n, device=dev, dtype=torch.int64)[None, :] + torch.arange(3, device=dev, dtype=torch.int64)[:, None] * B).reshape(-1)
+            a.first, a.y, a.first_rows, a.ldy = None, y.data_ptr(), rows.data_ptr(), y.stride(0)
+            _HeadsStepFn._set_params(top, a)
+            logits, t_rel, rel = torch.empty((n, 1), device=dev, dtype=f32), torch.empty((n, 2), device=dev, dtype=f32), torch.empty((2 * n, 2), device=dev, dtype=f32)
+            ws = ops.heads_step_workspace(n, H, dev)
+            a.logits, a.t_rel, a.rel, a.ws = logits.data_ptr(), t_rel.data_ptr(), rel.data_ptr(), ws.data_ptr()
+            ops.heads_predict(a)
+            P, T = ops.heads_step_outputs(ws, n, H)
+            parts.append((logits, t_rel, rel[:n], rel[n:], P, T))
+        if len(parts) == 1:
+            return parts[0]
+        return tuple(torch.cat([q[i] for q in parts], dim=1 if i == 4 else 0) for i in range(6))
+
+    @staticmethod
     def _setup(top, B, H, dev, ap, sent, first=None, src=None):
         """The argument record of a forward pass (everything but the MLM losses) and its output tensors: (a, outs, keep)."""
         a = ops.heads_step_struct()
@@ -1736,15 +1819,7 @@ class _HeadsStepFn(torch.autograd.Function):
         else:
             assert first.dtype == torch.float32 and first.is_contiguous()
             a.first = first.data_ptr()
-        pool, al, sr, at = top.bert.pooler.dense, top.cls.align, top.cls.seq_relationship, top.attn
-        vs3 = (top.vt, top.vv, top.vs)
-        c1, c2 = top.classifier1_1, top.classifier1_2
-        qs = (top.cpc_zt.net, top.cpc_zv.net, top.cpc_za.net)
-        assert c2.weight.shape[0] == 1 and at.weight.is_contiguous()
-        a.Wp, a.bp, a.Wal, a.bal, a.Wsr, a.bsr = (t.data_ptr() for t in (pool.weight, pool.bias, al.weight, al.bias, sr.weight, sr.bias))
-        a.Wat, a.bat, a.Wc1, a.bc1, a.Wc2, a.bc2 = (t.data_ptr() for t in (at.weight, at.bias, c1.weight, c1.bias, c2.weight, c2.bias))
-        for m in range(3):
-            a.vw[m], a.vb[m], a.Wq[m], a.bq[m] = vs3[m].weight.data_ptr(), vs3[m].bias.data_ptr(), qs[m].weight.data_ptr(), qs[m].bias.data_ptr()
+        _HeadsStepFn._set_params(top, a)
         if isinstance(ap, tuple):                              # (visual labels [B], speech labels [B]): no concatenation launch
             ap = tuple(t.contiguous() for t in ap)
             assert all(t.dtype == torch.int64 and t.numel() == B for t in ap)
@@ -2250,6 +2325,41 @@ class MMBertForPretraining(_GpuModelBase):
         self.outputs = (_scalar_loss(joint_loss), None, None, None, ap_loss, label_loss, nce,
                         scores[0], t_rel, scores[1], v_rel, scores[2], s_rel)
         return self.outputs, logits_out
+
+    def predict(self, input_ids, token_type_ids, attention_mask, return_pooled=False):
+        """DECLARED EXTENSION, not in the reference (its ``sampling.py`` does not run against its own model's signature): the sentiment
+        prediction WITHOUT labels.  The first three arguments are ``forward``'s.  Returns ``logits`` [B, 1] fp32 -- what ``forward``
+        returns as its second value in eval mode, classifier1_2(classifier1_1(gated concat)), through tanh when ``num_labels == 1``
+        (REF:MMBertForPretraining.py:406-415, 431-436) -- and, with ``return_pooled``, also a dict: ``pooled`` [3, B, H] (text, visual,
+        speech pooler outputs), ``fused`` [B, H] (the classifier1_1 output), ``t_rel`` / ``v_rel`` / ``s_rel`` [B, 2] (forward's outputs
+        8 / 10 / 12).
+
+        Always inference arithmetic (no dropout, no autograd graph, inside or outside ``torch.no_grad()``) without changing
+        ``self.training``; runs on the current stream; takes nothing from and leaves nothing in the model's per-step state (dropout
+        seed sequence, prologue buffers, pending gradients), so it can sit between two train steps.  What it does not run: the MLM
+        transform, the vocabulary GEMM (no [tokens, vocab] buffer), any cross-entropy, and the top encoder layer on any row but the 3 B
+        [CLS] rows -- only those are read by the pooler (REF :297, :406-415; HF pooler): one-query attention (ops.attn_fwd_first), then
+        out-projection / LayerNorm / FFN / LayerNorm on 3 B rows, then the heads' forward levels 1 - 5 (any B: chunks of 128)."""
+        if self.num_labels not in (1, 7):
+            raise NotImplementedError(f"predict(): num_labels = {self.num_labels} -- only the regression head (num_labels 1 or 7) is implemented; "
+                                      "classifier1_2 has one output whatever num_labels says (REF:MMBertForPretraining.py:369)")
+        text_ids, visual, speech, twv, tws = input_ids
+        tt_t = token_type_ids[0]
+        am_t, am_v, am_s = attention_mask
+        dev = text_ids.device
+        if self.config.hidden_size % 16 != 0:
+            raise RuntimeError(f"predict(): hidden_size {self.config.hidden_size} is not a multiple of 16 (the level-launch heads)")
+        with torch.no_grad():
+            self._ensure_ready(dev)                               # (CPU tensors: the "no CPU path" error, before anything is moved)
+            B = text_ids.shape[0]
+            passes = [dict(ids=text_ids, tt=tt_t, mask=am_t),
+                      dict(ids=twv, tt=None, mask=am_v[0].to(dev), pair=visual, pair_mask=am_v[1].to(dev)),
+                      dict(ids=tws, tt=None, mask=am_s[0].to(dev), pair=speech, pair_mask=am_s[1].to(dev))]
+            y, _plan, _lens, _ = self._encode(passes, None, False, predict=True)
+            logits, t_rel, v_rel, s_rel, pooled, fused = _HeadsStepFn.predict(self, y, B)
+        if return_pooled:
+            return logits, dict(pooled=pooled, fused=fused, t_rel=t_rel, v_rel=v_rel, s_rel=s_rel)
+        return logits
 
     def forward_fused(self, input_ids, token_type_ids, attention_mask, masked_labels, ap_label, sentiment):
         """DECLARED EXTENSION, not in the reference (SURVEY S8(d) mode ``fused1050``; BASELINE.json quotes its metric on a "fused

@@ -823,6 +823,27 @@ def attn_fwd(qkv, key_bias, layout: SeqLayout, H, *, drop: Drop = None, ctx=None
     return ctx, lse
 
 
+def attn_fwd_first(qkv, key_bias, layout: SeqLayout, H, q_rows, *, kv_len=None):
+    """Attention forward for ONE query row per sequence (mmbert_attn_fwd_first; inference only: no dropout, no LSE): ``q_rows`` int32
+    [sequences] = the packed row of ``qkv`` that holds each sequence's query (its [CLS] row, wherever the packing put it); keys and
+    values are the sequence's rows as ``attn_fwd`` reads them under the same ``layout`` / ``kv_len``.  Returns the COMPACT context
+    [sequences, H] bf16.  ``key_bias``: padded layout (pad_key_bias); a [tokens] vector is padded on the fly."""
+    lib = _lib.load()
+    M = qkv.shape[0]
+    if key_bias.numel() != layout.bias_len or layout.bias_len == M:
+        key_bias = pad_key_bias(key_bias, layout) if key_bias.numel() == M else key_bias
+    assert qkv.shape[1] == 3 * H and qkv.is_contiguous() and qkv.dtype == torch.bfloat16
+    if getattr(layout, "split", False):
+        kv_len = layout.kv_len                           # keys of a sequence = its region-A rows
+    ns = layout.seq_len.numel()
+    assert q_rows.dtype == torch.int32 and q_rows.is_contiguous() and q_rows.numel() == ns and key_bias.dtype == torch.float32
+    ctx = torch.empty((ns, H), device=qkv.device, dtype=torch.bfloat16)
+    _lib.check(lib.mmbert_attn_fwd_first(_stream(), qkv.data_ptr(), ctx.data_ptr(), key_bias.data_ptr(), layout.bias_start.data_ptr(), H, layout.heads,
+                                         layout.seq_start.data_ptr(), layout.seq_len.data_ptr(), q_rows.data_ptr(), ns, _ptr(kv_len)),
+               "mmbert_attn_fwd_first")
+    return ctx
+
+
 def attn_q_limit(rows32, layout):
     """Per sequence of ``layout``: 1 + the largest query index among the packed rows ``rows32`` (int32) -- what ``attn_bwd(q_limit=...)``
     takes when only those rows have a non-zero output gradient (mmbert_attn_q_limit)."""
@@ -1201,6 +1222,18 @@ def heads_step_fwd(a: "_HeadsStep", lo: int = 1, hi: int = 7):
     _lib.check(_lib.load().mmbert_heads_step_fwd_levels(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_fwd_levels")
 
 
+def heads_predict(a: "_HeadsStep"):
+    """Forward levels 1 - 5 without labels (mmbert_heads_predict): logits, t_rel, rel and the workspace's P / T (heads_step_outputs)."""
+    _lib.check(_lib.load().mmbert_heads_predict(_stream(), ctypes.addressof(a)), "mmbert_heads_predict")
+
+
+def heads_step_outputs(ws: torch.Tensor, B: int, H: int):
+    """Views of a heads workspace a forward call has written: (pooler outputs P [3, B, H], classifier1_1 output T [B, H])."""
+    po, fo = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(_lib.load().mmbert_heads_step_outputs(int(B), int(H), ctypes.byref(po), ctypes.byref(fo)), "mmbert_heads_step_outputs")
+    return ws[po.value:po.value + 3 * B * H].view(3, B, H), ws[fo.value:fo.value + B * H].view(B, H)
+
+
 def heads_step_dmlm(a: "_HeadsStep"):
     _lib.check(_lib.load().mmbert_heads_step_dmlm(_stream(), ctypes.addressof(a)), "mmbert_heads_step_dmlm")
 
@@ -1348,7 +1381,7 @@ def layer_bwd(L: _AttnLayout, a: _LayerBwd):
 
 # the per-launch wrappers as defined here: model.py takes the composite path only while nobody has wrapped them (bench.py's per-launch
 # event timing, tests that spy on launches)
-_UNWRAPPED = dict(gemm_nt=gemm_nt, attn_fwd=attn_fwd, attn_bwd=attn_bwd, ln_fwd=ln_fwd, ln_bwd=ln_bwd)
+_UNWRAPPED = dict(gemm_nt=gemm_nt, attn_fwd=attn_fwd, attn_fwd_first=attn_fwd_first, attn_bwd=attn_bwd, ln_fwd=ln_fwd, ln_bwd=ln_bwd)
 
 
 def launches_unwrapped() -> bool:

@@ -298,6 +298,38 @@ def eval_epoch(args, model, valdata, tokenizer=None, *, device="cuda", generator
     return (float(dev_loss) / n, 0.0, 0.0, 0.0, float(ap_loss) / n, float(label_loss) / n, preds, labels)
 
 
+def pack_predict_inputs(batch, device):
+    """The three arguments of ``model.predict`` from one ``collate`` batch: the utterance as it is (no MLM masking), no labels."""
+    text_batch, visual_batch, speech_batch, attention_batch = batch[:4]
+    dev = torch.device(device)
+    return dict(
+        input_ids=(text_batch[0].to(dev), visual_batch[1].to(dev), speech_batch[1].to(dev), visual_batch[0].to(dev), speech_batch[0].to(dev)),
+        token_type_ids=(text_batch[2].to(dev), visual_batch[3].to(dev), speech_batch[3].to(dev)),
+        attention_mask=(text_batch[3].to(dev), (attention_batch[0].to(dev), visual_batch[4].to(dev)),
+                        (attention_batch[1].to(dev), speech_batch[4].to(dev))),
+    )
+
+
+def predict_epoch(args, model, data, *, device="cuda", batches=None):
+    """The label-free counterpart of ``eval_epoch`` (what the reference's ``sampling.py`` is for; that script does not run against its
+    own model's signature): ``model.predict`` over ``data`` in SEQUENTIAL order -- row i of the result is item i of the dataset -- on the
+    utterances as they are (no MLM masking: ``eval_epoch`` masks because the reference's evaluation does; a prediction does not).
+    ``data``: a Dataset of the reference's 16-tuples (collated here, ``args.test_batch_size``, else ``args.val_batch_size``), or pass
+    ``batches`` = an iterable of model-kwargs dicts (keys other than ``input_ids`` / ``token_type_ids`` / ``attention_mask``, such as
+    labels, are ignored).  Returns the predictions as one float32 array [N, 1]: one device->host transfer at the end.  Leaves
+    ``model.training`` as it found it."""
+    import numpy as np
+    if batches is None:
+        from torch.utils.data import DataLoader, SequentialSampler
+        bs = getattr(args, "test_batch_size", None) or args.val_batch_size
+        loader = DataLoader(data, sampler=SequentialSampler(data), batch_size=bs, collate_fn=collate)
+        batches = (pack_predict_inputs(b, device) for b in loader)
+    preds = [model.predict(kw["input_ids"], kw["token_type_ids"], kw["attention_mask"]) for kw in batches]
+    if not preds:
+        return np.zeros((0, 1), dtype=np.float32)
+    return torch.cat(preds).float().cpu().numpy()
+
+
 def _weighted_f1(y_true, y_pred):
     """F1 per class weighted by the class's support in ``y_true`` (sklearn ``f1_score(average="weighted")``)."""
     import numpy as np

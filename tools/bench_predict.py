@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""What a prediction costs: ``model.predict`` against what had to be called before it existed, same process, alternating order.
+
+    python tools/bench_predict.py [--calls 50] [--rounds 3] [--shapes headline,refdef32,refdef256] [--kernel]
+
+Shapes: ``headline`` (12 layers, d = 768, T = 50, A = V = 500, B = 16) and the reference's default model (bert-large, T = P = 40:
+REF:train.py:28,32,38) at B = 32 and B = 256.  Legs, ms per call (device events around ``--calls`` calls, every shape and leg warmed
+up first, ``--rounds`` alternating rounds: median, and the spread max - min over the rounds of the SAME leg):
+  (a) model.eval() + no_grad + forward with dummy labels          -- the only way to predictions without predict()
+  (b) the same with return_scores = False                         -- expected equal to (a): the dense MLM head runs under no_grad anyway
+  (c) model.predict                                               -- no labels, [CLS]-only top layer, no MLM head
+plus the peak allocation of each above the level before the call (torch.cuda.max_memory_allocated).
+``--kernel``: the stand-alone time of ops.attn_fwd_first at the headline layout (16 x 50 + 32 x 550 rows, 12 heads; device events
+around 200 launches) and the bytes it reads (K and V of every row once, one query row and the key bias per (sequence, head)) over
+that time, as a share of the 6.3 TB/s a long copy reaches (a bandwidth share: the kernel has no MFMA work).
+The last line of the output is one JSON object with every number."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from msa_amd.data import synthetic_batch, batch_to
+from msa_amd.model import MMBertConfig, MMBertForPretraining
+
+SHAPES = {
+    "headline": dict(L=12, H=768, heads=12, I=3072, V=30522, T=50, Pv=500, Pa=500, B=16),
+    "refdef32": dict(L=24, H=1024, heads=16, I=4096, V=30522, T=40, Pv=40, Pa=40, B=32),
+    "refdef256": dict(L=24, H=1024, heads=16, I=4096, V=30522, T=40, Pv=40, Pa=40, B=256),
+}
+COPY_BW = 6.3e12          # bytes/s of a long device copy on this part
+
+
+def timed(fn, calls):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def peak_of(fn):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    del out
+    return peak
+
+
+def bench_shape(name, s, calls, rounds, dev):
+    torch.manual_seed(0)
+    model = MMBertForPretraining(MMBertConfig(vocab_size=s["V"], hidden_size=s["H"], num_hidden_layers=s["L"], num_attention_heads=s["heads"],
+                                              intermediate_size=s["I"]))
+    model.bert.set_joint_embeddings("mosei")
+    model.set_alpha_beta(1.0, 1.0)
+    model.to(dev).eval()
+    batch = batch_to(synthetic_batch(s["B"], s["T"], s["Pv"], s["Pa"], vocab=s["V"], seed=50), dev)
+    args3 = (batch["input_ids"], batch["token_type_ids"], batch["attention_mask"])
+
+    def forward(scores):
+        def f():
+            model.return_scores = scores
+            with torch.no_grad():
+                return model(**batch)[1]
+        return f
+    legs = [("a_forward", forward(True)), ("b_forward_no_scores", forward(False)), ("c_predict", lambda: model.predict(*args3))]
+    for _, fn in legs:                                        # warm-up of every leg at this shape
+        for _ in range(3):
+            fn()
+    times = {n: [] for n, _ in legs}
+    for r in range(rounds):
+        order = legs if r % 2 == 0 else legs[::-1]
+        for n, fn in order:
+            fn()
+            times[n].append(timed(fn, calls))
+    res = {}
+    for n, fn in legs:
+        t = sorted(times[n])
+        res[n] = dict(ms=t[len(t) // 2], spread_ms=t[-1] - t[0], peak_bytes=peak_of(fn))
+    model.return_scores = True
+    base = min(res["a_forward"]["ms"], res["b_forward_no_scores"]["ms"])
+    res["predict_over_forward"] = res["c_predict"]["ms"] / base
+    for n, _ in legs:
+        print(f"{name:10s} {n:22s} {res[n]['ms']:9.3f} ms/call  spread {res[n]['spread_ms']:.3f} ms  peak {res[n]['peak_bytes'] / 2 ** 20:9.1f} MiB")
+    print(f"{name:10s} predict / min(a, b) = {res['predict_over_forward']:.4f}")
+    del model
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_kernel(dev):
+    from msa_amd import ops
+    heads, H = 12, 768
+    lens = [50] * 16 + [550] * 32
+    M = sum(lens)
+    layout = ops.SeqLayout(lens, heads, dev)
+    g = torch.Generator().manual_seed(1)
+    qkv = torch.randn(M, 3 * H, generator=g).to(torch.bfloat16).to(dev)
+    kb = ops.pad_key_bias(torch.zeros(M, device=dev), layout)
+    q_rows = layout.seq_start.to(torch.int32).contiguous()
+    fn = lambda: ops.attn_fwd_first(qkv, kb, layout, H, q_rows)
+    for _ in range(10):
+        fn()
+    ts = sorted(timed(fn, 200) for _ in range(3))
+    ms = ts[1]
+    nbytes = M * 2 * H * 2 + len(lens) * H * 2 * 2 + M * 4 * heads          # K, V | query rows, output | key bias per head
+    res = dict(ms=ms, spread_ms=ts[-1] - ts[0], bytes=nbytes, bytes_per_s=nbytes / (ms * 1e-3), share_of_copy_bandwidth=nbytes / (ms * 1e-3) / COPY_BW)
+    print(f"attn_fwd_first headline layout: {ms * 1e3:.1f} us (spread {res['spread_ms'] * 1e3:.1f} us), {nbytes / 1e6:.1f} MB read -> "
+          f"{res['bytes_per_s'] / 1e12:.2f} TB/s = {100 * res['share_of_copy_bandwidth']:.1f} % of the 6.3 TB/s of a long copy (bandwidth share)")
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--shapes", default="headline,refdef32,refdef256")
+    ap.add_argument("--kernel", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_predict.py needs the GPU: there is no CPU path and no number to report without one")
+    dev = torch.device("cuda", 0)
+    out = dict(calls=a.calls, rounds=a.rounds, shapes={})
+    for name in [x for x in a.shapes.split(",") if x]:
+        out["shapes"][name] = bench_shape(name, SHAPES[name], a.calls, a.rounds, dev)
+    if a.kernel:
+        out["attn_fwd_first"] = bench_kernel(dev)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
