@@ -306,13 +306,20 @@ int mmbert_heads_colsum(mmbert_stream_t stream, int nseg, const float* const* sr
  * gated concatenation, classifier1_1 / 1_2, losses; CPC REF:MMBertEmbedding.py:21-32) from ONE call that issues seven launches, and its whole
  * backward -- the gradient of the [CLS] rows and of every head parameter -- from one more call (six launches).
  * fp32 throughout (products on the fp32 MFMA), no data atomics: results do not depend on scheduling.
- * Row order of every [3B, H] array: modality-major (text, visual, speech).  B <= 128, H % 16 == 0, the regression head (one output).
+ * Row order of every [3B, H] array: modality-major (text, visual, speech).  B <= 128, H % 16 == 0.  The label head is the regression head
+ * (one output, MSE; ncls = 0) or -- a declared extension -- a C-class head (ncls = C, 2 <= C <= 16: one 16-wide fp32 MFMA tile; mean C-way
+ * cross-entropy in place of the MSE, REF:MMBertForPretraining.py:438-443).
  *   first      fp32 [3B, H] (ld H) -- or NULL: row i is row first_rows[i] of the bf16 matrix y (ldy elements per row; ldy % 4 == 0)
  *   ap         int64 [2B] alignment labels (visual rows, then speech rows) -- or ap [B] (visual) and ap2 [B] (speech) when ap2 != NULL; sent fp32 [B]; mlm fp32 [nmlm] per-pass MLM losses (nmlm may be 0)
+ *   ncls       0: regression (sent is read; sent_cls, pred are not and may be null).  C in 2 .. 16: Wc2 is [C, H], bc2 [C], gWc2 [C, H], gbc2 [C];
+ *              sent_cls int64 [B] class labels in [0, C) (sent is not read) -- a label outside the range is clamped into it, so nothing is read
+ *              or written out of bounds, and the label loss and its gradients are then unspecified; logits is [B, C], RAW (tanh_lo is not read);
+ *              pred int64 [B] = index of the largest raw logit, the lowest index on an exact tie (written by forward level 5).
+ *              Anything else (negative, 1, > 16), or ncls > 0 with a null sent_cls / pred, is refused (-1, nothing launched)
  *   parameters fp32 in PyTorch's Linear layout [out, in]: Wp (pooler), Wal (align [2,H]), Wsr (seq_relationship [2,H]), Wat (attn [H,2H]),
- *              vw[m] / vb[m] (vt, vv, vs: [H] / [1]), Wc1 (classifier1_1 [H,3H]), Wc2 (classifier1_2 [1,H]), Wq[m] (cpc_z{t,v,a}.net [H,H])
+ *              vw[m] / vb[m] (vt, vv, vs: [H] / [1]), Wc1 (classifier1_1 [H,3H]), Wc2 (classifier1_2 [1,H]; [ncls,H] when ncls > 0), Wq[m] (cpc_z{t,v,a}.net [H,H])
  *   forward    loss[1] = alpha * mean(mlm) + ap_loss + label_loss - beta * nce (REF :427,:443), aux[3] = {ap_loss, label_loss, nce},
- *              out5[5] = {ap, label, nce, heads, joint}, logits[B] (tanh applied when tanh_lo), t_rel [B,2], rel [2B,2]
+ *              out5[5] = {ap, label, nce, heads, joint}, logits[B] (tanh applied when tanh_lo; [B, ncls] raw when ncls > 0), t_rel [B,2], rel [2B,2]
  *   ws         mmbert_heads_step_workspace(B, H) bytes; written by forward, read and extended by backward (same B, H)
  *   backward   dloss: device scalar (upstream gradient of `loss`); dfirst fp32 [3B, H]; dmlm [nmlm] = dloss * alpha / nmlm;
  *              g*: the parameters' gradients, ACCUMULATED (+=); gWat has row pitch 2H like Wat
@@ -321,7 +328,7 @@ int mmbert_heads_colsum(mmbert_stream_t stream, int nseg, const float* const* sr
 typedef struct {
     int B, H, tanh_lo, nmlm;
     float alpha, beta;
-    const float* first; const void* y; const int64_t* first_rows; int ldy, pad0_;
+    const float* first; const void* y; const int64_t* first_rows; int ldy, ncls;
     const int64_t* ap; const int64_t* ap2; const float* sent; const float* mlm;
     const float *Wp, *bp, *Wal, *bal, *Wsr, *bsr, *Wat, *bat, *vw[3], *vb[3], *Wc1, *bc1, *Wc2, *bc2, *Wq[3], *bq[3];
     float *loss, *aux, *out5, *logits, *t_rel, *rel;
@@ -329,6 +336,7 @@ typedef struct {
     const float* dloss; float* dfirst; float* dmlm;
     float *gWp, *gbp, *gWal, *gbal, *gWat, *gbat, *gvw[3], *gvb[3], *gWc1, *gbc1, *gWc2, *gbc2, *gWq[3], *gbq[3];
     unsigned* sync;
+    const int64_t* sent_cls; int64_t* pred;          /* ncls > 0 only (appended: the offsets of every field above are those of the regression-only struct) */
 } mmbert_heads_step;
 int mmbert_heads_step_struct_size(void);          /* sizeof(mmbert_heads_step): bindings check their mirror of the struct against it */
 size_t mmbert_heads_step_workspace(int B, int H);
@@ -340,7 +348,8 @@ int mmbert_heads_step_fwd_levels(mmbert_stream_t stream, const mmbert_heads_step
 int mmbert_heads_step_bwd_levels(mmbert_stream_t stream, const mmbert_heads_step* p, int lo, int hi);
 /* Prediction without labels -- inference only: forward levels 1 .. 5 (pooler, align / seq_relationship scores, gates, gated concatenation,
  * classifier1_1 / 1_2; the same kernels as mmbert_heads_step_fwd_levels(p, 1, 5), the same bits).  Reads `first` (or y + first_rows), the
- * parameters and tanh_lo; writes logits [B], t_rel [B,2], rel [2B,2] and ws.  ap, ap2, sent, mlm, loss, aux, out5, sync and every gradient
+ * parameters and tanh_lo; writes logits [B], t_rel [B,2], rel [2B,2] and ws -- with ncls > 0, raw logits [B, ncls] and pred [B] (required then),
+ * by the classifier tile's own workgroup: no extra launch.  ap, ap2, sent, sent_cls, mlm, loss, aux, out5, sync and every gradient
  * pointer are NOT read and may be null.  B <= 128 (no level couples samples: a larger batch is run in chunks), H % 16 == 0.
  * mmbert_heads_step_outputs: where, in floats from the start of ws, forward leaves the pooler outputs P [3B, H] (text, visual, speech)
  * and the classifier1_1 output T [B, H] (same B, H as the call that wrote ws); returns 0, or -1 for B, H <= 0. */

@@ -15,6 +15,13 @@
 // sum has ONE owner and a fixed order, so the results do not depend on scheduling -- there is no separate deterministic form.  Every parameter
 // gradient is ACCUMULATED (+=) into the caller's buffers (views of the flat gradient buffer).
 //
+// The label head is the reference's regression head (one output, MSE; p.ncls == 0) or a C-class head (declared extension: classifier1_2 [C, H],
+// 2 <= C <= 16, mean C-way cross-entropy, REF:MMBertForPretraining.py:438-443).  The class head is a COMPILE-TIME property of the level kernels
+// (template parameter CLS): the regression instantiation is the code it was before the class head existed.  What differs: forward level 5 (the
+// classifier tile loads row min(n, C - 1) of Wc2 -- one 16-wide MFMA tile covers C <= 16 --, stores columns n < C, and its workgroup then takes
+// the argmax of its own 16 rows: `pred`, in the train step and in mmbert_heads_predict alike, no launch of its own), forward level 7 (the label
+// loss and its seed dlo [B, C]), backward level 2 (dT += dlo Wc2) and backward level 3 (gWc2 [C, H], gbc2 [C]).
+//
 // MEASURED AND WITHDRAWN (same round, profiles/r6_heads_persistent_kernel.txt): the same levels inside ONE persistent kernel per direction with grid
 // barriers between them.  An MI355X has one L2 per XCD, so data exchanged between levels inside a launch needs agent-scope ("sc1") stores and
 // loads, or cache-wide fences: a fence pair by one thread per workgroup costs 8 us per barrier, by every thread 131 us (!), agent-scope accesses
@@ -148,7 +155,7 @@ __device__ __forceinline__ float4 hc_col4_lim(const float* W, int ld, int k, int
     return make_float4(k < lim ? v0 : 0.f, k + 1 < lim ? v1 : 0.f, k + 2 < lim ? v2 : 0.f, k + 3 < lim ? v3 : 0.f);
 }
 
-// workspace layout (floats); R = 3 B
+// workspace layout (floats); R = 3 B.  lo / dlo: [B] (regression) or [B, ncls]; sized for 16 classes always, so that the size depends on (B, H) alone
 struct HcWs {
     float *first, *P, *Apre, *XP, *T, *g, *nx, *ny, *lo, *S, *dS, *rsum, *csum, *part, *drel, *dlo;       // forward (kept for backward)
     float *dPc, *dXP, *dT, *dC, *dP0, *dA, *E, *dpre, *dgv;                                               // backward scratch
@@ -159,7 +166,7 @@ __host__ __device__ __forceinline__ HcWs hc_ws(int B, int H, float* base, size_t
     HcWs t;
 #define HC_TAKE(field, n) t.field = base + o; o += ((size_t)(n) + 3) & ~(size_t)3;
     HC_TAKE(first, RH) HC_TAKE(P, RH) HC_TAKE(Apre, RH) HC_TAKE(XP, RH) HC_TAKE(T, BH) HC_TAKE(g, R) HC_TAKE(nx, R) HC_TAKE(ny, R)
-    HC_TAKE(lo, B) HC_TAKE(S, BB) HC_TAKE(dS, BB) HC_TAKE(rsum, R) HC_TAKE(csum, R) HC_TAKE(part, 8) HC_TAKE(drel, 4 * (size_t)B) HC_TAKE(dlo, B)
+    HC_TAKE(lo, 16 * (size_t)B) HC_TAKE(S, BB) HC_TAKE(dS, BB) HC_TAKE(rsum, R) HC_TAKE(csum, R) HC_TAKE(part, 8) HC_TAKE(drel, 4 * (size_t)B) HC_TAKE(dlo, 16 * (size_t)B)
     HC_TAKE(dPc, RH) HC_TAKE(dXP, RH) HC_TAKE(dT, BH) HC_TAKE(dC, 3 * BH) HC_TAKE(dP0, RH) HC_TAKE(dA, RH) HC_TAKE(E, RH) HC_TAKE(dpre, RH) HC_TAKE(dgv, R)
 #undef HC_TAKE
     if (total) *total = o;
@@ -182,7 +189,7 @@ struct HcFirst {
 // =====================================================================================================================================
 // forward
 // =====================================================================================================================================
-template <int LEVEL>
+template <int LEVEL, bool CLS>
 __global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmbert_heads_step p) {
 #if defined(__gfx950__)
     extern __shared__ __attribute__((aligned(16))) float hc_sm[];
@@ -266,6 +273,24 @@ __global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmber
                 hc_wg_tile(c, tb, tn, H, [&](int b, int k) { return mem.ld4(w.T + (size_t)min(b, B - 1) * H + k); },
                            [&](int n, int k) { return hc_ld4(Wq + (size_t)(n - m * H) * H + k); },
                            [&](int b, int n, float s) { if (b < B) hc_stc(w.XP + ((size_t)m * B + b) * H + (n - m * H), s + bq[n - m * H]); });
+            } else if constexpr (CLS) {
+                // (class head: lo [B, C] raw; the tile's 16 x 16 values also go to LDS, and 16 threads then take their rows' argmax -- the
+                //  largest raw logit, the lowest index on an exact tie)
+                const int C = p.ncls, tb = t - nX;
+                hc_wg_tile(c, tb, 0, H, [&](int b, int k) { return mem.ld4(w.T + (size_t)min(b, B - 1) * H + k); },
+                           [&](int n, int k) { return hc_ld4(p.Wc2 + (size_t)min(n, C - 1) * H + k); },
+                           [&](int b, int n, float s) {
+                               const float v = s + p.bc2[min(n, C - 1)];
+                               lds2[(b & 15) * 16 + n] = v;
+                               if (b < B && n < C) { hc_stc(w.lo + (size_t)b * C + n, v); p.logits[(size_t)b * C + n] = v; }
+                           });
+                const int b = tb * 16 + tid;
+                if (tid < 16 && b < B) {
+                    int best = 0; float bv = lds2[tid * 16];
+                    for (int n = 1; n < C; ++n) { const float v = lds2[tid * 16 + n]; if (v > bv) { bv = v; best = n; } }
+                    p.pred[b] = (long long)best;
+                }
+                __syncthreads();                                          // (lds2 is free for this workgroup's next tile)
             } else {
                 hc_wg_tile(c, t - nX, 0, H, [&](int b, int k) { return mem.ld4(w.T + (size_t)min(b, B - 1) * H + k); },
                            [&](int n, int k) { return hc_ld4(p.Wc2 + k); },
@@ -356,12 +381,30 @@ __global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmber
             w.drel[i * 2] = sc * (expf(a - lse) - (y == 0 ? 1.f : 0.f));
             w.drel[i * 2 + 1] = sc * (expf(cc - lse) - (y == 1 ? 1.f : 0.f));
         }
+        if constexpr (CLS) {
+            // mean C-way cross-entropy (REF :438-441) and its seed dlo[b][c] = (softmax_c - [c == y_b]) / B; `se` carries the label loss.
+            // A label outside [0, C) is clamped (nothing out of bounds; the loss is then unspecified)
+            const int C = p.ncls;
+            for (int b = tid; b < B; b += HC_THREADS) {
+                const float* l = w.lo + (size_t)b * C;
+                const long long yl = p.sent_cls[b];
+                const int y = (int)(yl < 0 ? 0 : (yl > C - 1 ? C - 1 : yl));
+                float mx = hc_ldc(l);
+                for (int q = 1; q < C; ++q) mx = fmaxf(mx, hc_ldc(l + q));
+                float sx = 0.f;
+                for (int q = 0; q < C; ++q) sx += expf(hc_ldc(l + q) - mx);
+                const float lse = mx + logf(sx);
+                se += (lse - hc_ldc(l + y)) / (float)B;
+                for (int q = 0; q < C; ++q) w.dlo[(size_t)b * C + q] = (expf(hc_ldc(l + q) - lse) - (q == y ? 1.f : 0.f)) / (float)B;
+            }
+        } else {
         for (int b = tid; b < B; b += HC_THREADS) {
             const float lo = hc_ldc(w.lo + b);
             const float v = p.tanh_lo ? tanhf(lo) : lo;
             const float d = v - p.sent[b];
             se += d * d / (float)B;
             w.dlo[b] = 2.f * d / (float)B * (p.tanh_lo ? 1.f - v * v : 1.f);
+        }
         }
         ce = wave_sum(ce); se = wave_sum(se);
         if (lane == 0) { red[wave] = ce; red[HC_WAVES + wave] = se; }
@@ -399,7 +442,7 @@ __global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmber
 //   dA = dg v_m (Apre > 0)                E = dg relu(Apre)  dP = dP0 + dA (W1 + W2)           dpre = dP (1 - P^2)
 //   dfirst = dpre Wp + [rows >= B] drel Wal
 // =====================================================================================================================================
-template <int LEVEL>
+template <int LEVEL, bool CLS>
 __global__ __launch_bounds__(HC_THREADS) void heads_bwd_level_kernel(const mmbert_heads_step p) {
 #if defined(__gfx950__)
     extern __shared__ __attribute__((aligned(16))) float hc_sm[];
@@ -457,7 +500,15 @@ __global__ __launch_bounds__(HC_THREADS) void heads_bwd_level_kernel(const mmber
             hc_wg_tile<12>(c, t / tH, t % tH, 3 * H,
                        [&](int b, int k) { const int m = k / H; return mem.ld4(w.dXP + ((size_t)m * B + min(b, B - 1)) * H + (k - m * H)); },
                        [&](int n, int k) { const int m = k / H; return hc_col4(hc_pick(p.Wq, m), H, k - m * H, n); },
-                       [&](int b, int n, float s) { if (b < B) hc_stc(w.dT + (size_t)b * H + n, s + w.dlo[b] * p.Wc2[n]); });
+                       [&](int b, int n, float s) {
+                           if (b < B) {
+                               if constexpr (CLS) {
+                                   const int C = p.ncls;
+                                   float u = 0.f;
+                                   for (int q = 0; q < C; ++q) u += w.dlo[(size_t)b * C + q] * p.Wc2[(size_t)q * H + n];     // class order
+                                   hc_stc(w.dT + (size_t)b * H + n, s + u);
+                               } else hc_stc(w.dT + (size_t)b * H + n, s + w.dlo[b] * p.Wc2[n]);
+                           } });
         }
         for (int t = rwave; t < 3 * tH * tH; t += 2 * nwave) {             // gWq_m[n][k] += d sum_b dXP_m[b][n] T[b][k]   (rows n' = m H + n of one 3H x H job)
             hc_wave_tile_pair(t, t + nwave, t + nwave < 3 * tH * tH, tH, B,
@@ -489,11 +540,21 @@ __global__ __launch_bounds__(HC_THREADS) void heads_bwd_level_kernel(const mmber
                                              return v; },
                          [&](int n, int k, float s) { p.gWc1[(size_t)n * 3 * H + k] += d * s; });
         }
+        if constexpr (CLS) {                                                // gWc2[q][k] += d sum_b dlo[b][q] T[b][k];  gbc2[q] += d sum_b dlo[b][q]
+            const int C = p.ncls;
+            for (int i = rthread; i < H + C * H + C; i += nthread) {
+                float s = 0.f;
+                if (i < H) { for (int b = 0; b < B; ++b) s += hc_ldc(w.dT + (size_t)b * H + i); p.gbc1[i] += d * s; }
+                else if (i < H + C * H) { const int q = (i - H) / H, k = i - H - q * H; for (int b = 0; b < B; ++b) s += w.dlo[(size_t)b * C + q] * w.T[(size_t)b * H + k]; p.gWc2[(size_t)q * H + k] += d * s; }
+                else { const int q = i - H - C * H; for (int b = 0; b < B; ++b) s += w.dlo[(size_t)b * C + q]; p.gbc2[q] += d * s; }
+            }
+        } else {
         for (int i = rthread; i < 2 * H + 1; i += nthread) {
             float s = 0.f;
             if (i < H) { for (int b = 0; b < B; ++b) s += hc_ldc(w.dT + (size_t)b * H + i); p.gbc1[i] += d * s; }
             else if (i < 2 * H) { const int k = i - H; for (int b = 0; b < B; ++b) s += w.dlo[b] * w.T[(size_t)b * H + k]; p.gWc2[k] += d * s; }
             else { for (int b = 0; b < B; ++b) s += w.dlo[b]; p.gbc2[0] += d * s; }
+        }
         }
     }
     }
@@ -583,6 +644,7 @@ size_t mmbert_heads_step_workspace(int B, int H) {
 static int hc_check(const mmbert_heads_step* p, int* cus) {
     if (!p || p->B <= 0) return -1;
     if (p->B > 128 || p->H < 16 || (p->H & 15) || p->nmlm < 0 || p->nmlm > 256 || !p->ws || !p->sync || (!p->first && (!p->y || !p->first_rows || (p->ldy & 3)))) return -1;
+    if (p->ncls < 0 || p->ncls == 1 || p->ncls > 16 || (p->ncls > 0 && (!p->sent_cls || !p->pred))) return -1;
     *cus = mmb_device_cus();
     return 0;
 }
@@ -597,7 +659,10 @@ static inline int hc_grid(int wg_tiles, int wave_jobs, int cus, int floor_) {
     if (g < floor_) g = floor_;
     return g > cus ? cus : (g < 1 ? 1 : g);
 }
-#define HC_LAUNCH(K, L, GRID, LDS) do { hipLaunchKernelGGL((K<L>), dim3(GRID), dim3(HC_THREADS), (LDS), stream, *p); MMB_CHECK_LAUNCH(); } while (0)
+#define HC_LAUNCH(K, L, GRID, LDS) do { hipLaunchKernelGGL((K<L, false>), dim3(GRID), dim3(HC_THREADS), (LDS), stream, *p); MMB_CHECK_LAUNCH(); } while (0)
+// ... a level whose class-head instantiation differs (forward 5 and 7, backward 2 and 3)
+#define HC_LAUNCH_CLS(K, L, GRID, LDS) do { if (p->ncls > 0) { hipLaunchKernelGGL((K<L, true>), dim3(GRID), dim3(HC_THREADS), (LDS), stream, *p); MMB_CHECK_LAUNCH(); } \
+                                            else HC_LAUNCH(K, L, GRID, LDS); } while (0)
 
 // levels lo .. hi of the forward (1 .. 7) / backward (1 .. 6): the model runs the heads beside the MLM head's launches on a side stream and
 // only the loss level (which reads the MLM losses) behind both
@@ -605,16 +670,16 @@ int mmbert_heads_step_fwd_levels(hipStream_t stream, const mmbert_heads_step* p,
     int cus;
     if (hc_check(p, &cus)) return -1;
     if (lo < 1 || hi > 7 || lo > hi) return -1;
-    if (!p->loss || !p->aux || !p->out5 || !p->logits || !p->t_rel || !p->rel || !p->ap || !p->sent || (hi == 7 && p->nmlm > 0 && !p->mlm)) return -1;
+    if (!p->loss || !p->aux || !p->out5 || !p->logits || !p->t_rel || !p->rel || !p->ap || (p->ncls == 0 && !p->sent) || (hi == 7 && p->nmlm > 0 && !p->mlm)) return -1;
     const int B = p->B, H = p->H, R = 3 * B, tH = H >> 4, tB = (B + 15) >> 4, tR = (R + 15) >> 4, t2B = (2 * B + 15) >> 4;
     const int red = HC_WAVES * 256 * (int)sizeof(float);
     if (lo <= 1 && 1 <= hi) HC_LAUNCH(heads_fwd_level_kernel, 1, hc_grid(tR * tH + t2B, p->first ? 0 : R, cus, 1), red);
     if (lo <= 2 && 2 <= hi) HC_LAUNCH(heads_fwd_level_kernel, 2, hc_grid(tR * tH + tB, 0, cus, 1), red);
     if (lo <= 3 && 3 <= hi) HC_LAUNCH(heads_fwd_level_kernel, 3, hc_grid(0, R, cus, 1), red);
     if (lo <= 4 && 4 <= hi) HC_LAUNCH(heads_fwd_level_kernel, 4, hc_grid(tB * tH, 0, cus, 1), red);
-    if (lo <= 5 && 5 <= hi) HC_LAUNCH(heads_fwd_level_kernel, 5, hc_grid(tB * 3 * tH + tB, 0, cus, 1), red);
+    if (lo <= 5 && 5 <= hi) HC_LAUNCH_CLS(heads_fwd_level_kernel, 5, hc_grid(tB * 3 * tH + tB, 0, cus, 1), red + (p->ncls > 0 ? 256 * (int)sizeof(float) : 0));
     if (lo <= 6 && 6 <= hi) HC_LAUNCH(heads_fwd_level_kernel, 6, hc_grid(3 * tB * tB, R, cus, 1), red);
-    if (lo <= 7 && 7 <= hi) HC_LAUNCH(heads_fwd_level_kernel, 7, 4, red + (int)((HC_WAVES * (size_t)B + 2 * HC_WAVES) * sizeof(float)));
+    if (lo <= 7 && 7 <= hi) HC_LAUNCH_CLS(heads_fwd_level_kernel, 7, 4, red + (int)((HC_WAVES * (size_t)B + 2 * HC_WAVES) * sizeof(float)));
     return 0;
 }
 
@@ -625,6 +690,7 @@ int mmbert_heads_step_fwd(hipStream_t stream, const mmbert_heads_step* p) { retu
 int mmbert_heads_predict(hipStream_t stream, const mmbert_heads_step* p) {
     if (!p || p->B <= 0 || p->B > 128 || p->H < 16 || (p->H & 15) || !p->ws || (!p->first && (!p->y || !p->first_rows || (p->ldy & 3)))) return -1;
     if (!p->logits || !p->t_rel || !p->rel) return -1;
+    if (p->ncls < 0 || p->ncls == 1 || p->ncls > 16 || (p->ncls > 0 && !p->pred)) return -1;
     if (!p->Wp || !p->bp || !p->Wal || !p->bal || !p->Wsr || !p->bsr || !p->Wat || !p->bat || !p->Wc1 || !p->bc1 || !p->Wc2 || !p->bc2) return -1;
     for (int m = 0; m < 3; ++m) if (!p->vw[m] || !p->vb[m] || !p->Wq[m] || !p->bq[m]) return -1;
     const int cus = mmb_device_cus();
@@ -634,7 +700,7 @@ int mmbert_heads_predict(hipStream_t stream, const mmbert_heads_step* p) {
     HC_LAUNCH(heads_fwd_level_kernel, 2, hc_grid(tR * tH + tB, 0, cus, 1), red);
     HC_LAUNCH(heads_fwd_level_kernel, 3, hc_grid(0, R, cus, 1), red);
     HC_LAUNCH(heads_fwd_level_kernel, 4, hc_grid(tB * tH, 0, cus, 1), red);
-    HC_LAUNCH(heads_fwd_level_kernel, 5, hc_grid(tB * 3 * tH + tB, 0, cus, 1), red);
+    HC_LAUNCH_CLS(heads_fwd_level_kernel, 5, hc_grid(tB * 3 * tH + tB, 0, cus, 1), red + (p->ncls > 0 ? 256 * (int)sizeof(float) : 0));
     return 0;
 }
 
@@ -654,9 +720,10 @@ int mmbert_heads_step_bwd_levels(hipStream_t stream, const mmbert_heads_step* p,
     const int B = p->B, H = p->H, R = 3 * B, tH = H >> 4, tB = (B + 15) >> 4, tR = (R + 15) >> 4;
     const int red = HC_WAVES * 256 * (int)sizeof(float);
     const int cols = (4 * H + 3 + HC_THREADS - 1) / HC_THREADS;         // workgroups that cover the widest column-sum job with one thread per column
+    const int cols3 = p->ncls > 0 ? (H + p->ncls * H + p->ncls + HC_THREADS - 1) / HC_THREADS : cols;      // (level 3 of a class head: H + C H + C columns)
     if (lo <= 1 && 1 <= hi) HC_LAUNCH(heads_bwd_level_kernel, 1, hc_grid(0, 6 * tB * tH, cus, 1), red);
-    if (lo <= 2 && 2 <= hi) HC_LAUNCH(heads_bwd_level_kernel, 2, hc_grid(tB * tH, 3 * tH * tH, cus, cols), red);
-    if (lo <= 3 && 3 <= hi) HC_LAUNCH(heads_bwd_level_kernel, 3, hc_grid(tB * 3 * tH, tH * 3 * tH, cus, cols), red);
+    if (lo <= 2 && 2 <= hi) HC_LAUNCH_CLS(heads_bwd_level_kernel, 2, hc_grid(tB * tH, 3 * tH * tH, cus, cols), red);
+    if (lo <= 3 && 3 <= hi) HC_LAUNCH_CLS(heads_bwd_level_kernel, 3, hc_grid(tB * 3 * tH, tH * 3 * tH, cus, cols3 > cols ? cols3 : cols), red);
     if (lo <= 4 && 4 <= hi) HC_LAUNCH(heads_bwd_level_kernel, 4, hc_grid(0, R, cus, 1), red);
     if (lo <= 5 && 5 <= hi) HC_LAUNCH(heads_bwd_level_kernel, 5, hc_grid(tR * tH, tH * tH, cus, cols), red);
     if (lo <= 6 && 6 <= hi) HC_LAUNCH(heads_bwd_level_kernel, 6, hc_grid(tR * tH, tH * tH, cus, cols), red);
@@ -674,6 +741,7 @@ int mmbert_heads_step_dmlm(hipStream_t stream, const mmbert_heads_step* p) {
     MMB_CHECK_LAUNCH();
     return 0;
 }
+#undef HC_LAUNCH_CLS
 #undef HC_LAUNCH
 
 }  // extern "C"

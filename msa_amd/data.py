@@ -44,10 +44,12 @@ def _mask_tokens(rng, ids, p_mlm, pad_selectable=True):
 
 
 def synthetic_batch(batch: int, text_len: int, visual_len: int, speech_len: int, *, dataset="mosei",
-                    vocab=30522, seed=1, mlm_probability=0.15, full_length=False, pad_selectable=True):
+                    vocab=30522, seed=1, mlm_probability=0.15, full_length=False, pad_selectable=True, num_labels=None):
     """Returns the six keyword arguments of ``MMBertForPretraining.forward`` as CPU tensors:
     ``dict(input_ids=..., token_type_ids=..., attention_mask=..., masked_labels=..., ap_label=...,
-    sentiment=...)``."""
+    sentiment=...)``.  ``num_labels`` = C: ``sentiment`` holds class labels for a C-class head, int64 [B] uniform in [0, C), from the
+    batch's seeded generator (the last draw: everything else is the batch of the same seed without the keyword); None: regression
+    targets, fp32 [B] uniform in (-3, 3)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     vd, sd = MODALITY_DIMS[dataset]
     B, T = batch, text_len
@@ -92,7 +94,10 @@ def synthetic_batch(batch: int, text_len: int, visual_len: int, speech_len: int,
     )
     masked_labels = (tt(t_lab), tt(pair_labels(v_lab, visual_len)), tt(pair_labels(s_lab, speech_len)))
     ap_label = (tt(rng.integers(0, 2, B).astype(np.int64)), tt(rng.integers(0, 2, B).astype(np.int64)))
-    sentiment = tt(rng.uniform(-3, 3, B).astype(np.float32))
+    if num_labels is None:
+        sentiment = tt(rng.uniform(-3, 3, B).astype(np.float32))
+    else:
+        sentiment = tt(rng.integers(0, int(num_labels), B).astype(np.int64))
     return dict(input_ids=input_ids, token_type_ids=token_type_ids, attention_mask=attention_mask,
                 masked_labels=masked_labels, ap_label=ap_label, sentiment=sentiment)
 

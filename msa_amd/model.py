@@ -1759,6 +1759,13 @@ class MMBertPreTrainingHeads(nn.Module):
         return scores, self.seq_relationship(pooled_output)
 
 
+def _class_head(top) -> int:
+    """C when ``top`` carries a C-class label head -- ``num_labels`` = C outside (1, 7) AND a C-wide ``classifier1_2`` (the constructor's
+    ``num_labels=`` / ``set_num_labels``) --, else 0: the regression head, or a bare ``model.num_labels = C`` on a one-output layer."""
+    n = int(top.num_labels)
+    return n if n not in (1, 7) and 2 <= n <= 16 and top.classifier1_2.out_features == n else 0
+
+
 class _HeadsStepFn(torch.autograd.Function):
     """The heads, one launch per dependency level (csrc/heads_coop.hip, round 6): ``mmbert_heads_step_fwd`` (ONE C call, seven launches) evaluates
     everything downstream of the [CLS] rows -- pooler, align / seq_relationship scores, gates, gated concatenation, classifier1_1 / 1_2, the
@@ -1775,7 +1782,9 @@ class _HeadsStepFn(torch.autograd.Function):
         vs3 = (top.vt, top.vv, top.vs)
         c1, c2 = top.classifier1_1, top.classifier1_2
         qs = (top.cpc_zt.net, top.cpc_zv.net, top.cpc_za.net)
-        assert c2.weight.shape[0] == 1 and at.weight.is_contiguous()
+        ncls = _class_head(top)
+        assert c2.weight.shape[0] == (ncls or 1) and c2.weight.is_contiguous() and at.weight.is_contiguous()
+        a.ncls = ncls
         a.Wp, a.bp, a.Wal, a.bal, a.Wsr, a.bsr = (t.data_ptr() for t in (pool.weight, pool.bias, al.weight, al.bias, sr.weight, sr.bias))
         a.Wat, a.bat, a.Wc1, a.bc1, a.Wc2, a.bc2 = (t.data_ptr() for t in (at.weight, at.bias, c1.weight, c1.bias, c2.weight, c2.bias))
         for m in range(3):
@@ -1785,9 +1794,11 @@ class _HeadsStepFn(torch.autograd.Function):
     def predict(top, y, B):
         """The heads of a label-free prediction on the compact [3B, H] bf16 [CLS] rows ``y`` (text, visual, speech): forward levels 1 - 5
         (mmbert_heads_predict: no labels, no losses), in chunks of <= 128 samples -- without the loss level nothing couples the samples of
-        a batch, so any B goes through the level-launch kernels.  Returns (logits [B,1], t_rel, v_rel, s_rel [B,2], pooled [3,B,H], fused [B,H])."""
+        a batch, so any B goes through the level-launch kernels.  Returns (logits [B,1], t_rel, v_rel, s_rel [B,2], pooled [3,B,H], fused [B,H]);
+        with a C-class head ``logits`` is the raw [B, C] and a seventh value follows: the predicted classes, int64 [B]."""
         H, dev, f32 = y.shape[1], y.device, torch.float32
         assert y.dtype == torch.bfloat16 and y.is_contiguous() and y.shape[0] == 3 * B
+        ncls = _class_head(top)
         parts = []
         for b0 in range(0, B, 128):
             n = min(128, B - b0)
@@ -1796,15 +1807,19 @@ class _HeadsStepFn(torch.autograd.Function):
             rows = (torch.arange(b0, b0 + n, device=dev, dtype=torch.int64)[None, :] + torch.arange(3, device=dev, dtype=torch.int64)[:, None] * B).reshape(-1)
             a.first, a.y, a.first_rows, a.ldy = None, y.data_ptr(), rows.data_ptr(), y.stride(0)
             _HeadsStepFn._set_params(top, a)
-            logits, t_rel, rel = torch.empty((n, 1), device=dev, dtype=f32), torch.empty((n, 2), device=dev, dtype=f32), torch.empty((2 * n, 2), device=dev, dtype=f32)
+            logits, t_rel, rel = torch.empty((n, ncls or 1), device=dev, dtype=f32), torch.empty((n, 2), device=dev, dtype=f32), torch.empty((2 * n, 2), device=dev, dtype=f32)
             ws = ops.heads_step_workspace(n, H, dev)
             a.logits, a.t_rel, a.rel, a.ws = logits.data_ptr(), t_rel.data_ptr(), rel.data_ptr(), ws.data_ptr()
+            pred = ()
+            if ncls:
+                pred = (torch.empty(n, device=dev, dtype=torch.int64),)
+                a.pred = pred[0].data_ptr()
             ops.heads_predict(a)
             P, T = ops.heads_step_outputs(ws, n, H)
-            parts.append((logits, t_rel, rel[:n], rel[n:], P, T))
+            parts.append((logits, t_rel, rel[:n], rel[n:], P, T) + pred)
         if len(parts) == 1:
             return parts[0]
-        return tuple(torch.cat([q[i] for q in parts], dim=1 if i == 4 else 0) for i in range(6))
+        return tuple(torch.cat([q[i] for q in parts], dim=1 if i == 4 else 0) for i in range(len(parts[0])))
 
     @staticmethod
     def _setup(top, B, H, dev, ap, sent, first=None, src=None):
@@ -1829,15 +1844,21 @@ class _HeadsStepFn(torch.autograd.Function):
             assert ap.dtype == torch.int64 and ap.numel() == 2 * B
             a.ap = ap.data_ptr()
         sent = sent.contiguous()
-        assert sent.dtype == torch.float32 and sent.numel() == B
+        ncls = a.ncls
+        assert sent.dtype == (torch.int64 if ncls else torch.float32) and sent.numel() == B
         f32 = torch.float32
         loss, aux, out5 = torch.empty((), device=dev, dtype=f32), torch.empty(3, device=dev, dtype=f32), torch.empty(5, device=dev, dtype=f32)
-        logits, t_rel, rel = torch.empty((B, 1), device=dev, dtype=f32), torch.empty((B, 2), device=dev, dtype=f32), torch.empty((2 * B, 2), device=dev, dtype=f32)
+        logits, t_rel, rel = torch.empty((B, ncls or 1), device=dev, dtype=f32), torch.empty((B, 2), device=dev, dtype=f32), torch.empty((2 * B, 2), device=dev, dtype=f32)
         ws = ops.heads_step_workspace(B, H, dev)
-        a.sent = sent.data_ptr()
+        pred = None
+        if ncls:                                               # class labels int64 [B]; the predicted classes come back in ``pred``
+            pred = torch.empty(B, device=dev, dtype=torch.int64)
+            a.sent_cls, a.pred = sent.data_ptr(), pred.data_ptr()
+        else:
+            a.sent = sent.data_ptr()
         a.loss, a.aux, a.out5, a.logits, a.t_rel, a.rel, a.ws = (t.data_ptr() for t in (loss, aux, out5, logits, t_rel, rel, ws))
         a.sync = ops.heads_step_sync(dev).data_ptr()
-        return a, (loss, aux, logits, t_rel, rel), (ap, sent, ws, out5)
+        return a, (loss, aux, logits, t_rel, rel), (ap, sent, ws, pred, out5)
 
     @staticmethod
     def prelaunch(top, y, rows, ap, sent):
@@ -1877,6 +1898,8 @@ class _HeadsStepFn(torch.autograd.Function):
         ops.heads_step_fwd(a, lo, 7)
         loss, aux, logits, t_rel, rel = outs
         ctx.top, ctx.a, ctx.B, ctx.H, ctx.keep = top, a, B, H, (keep,) + tuple(keep3)
+        if a.ncls:
+            top.__dict__["_heads_pred"] = keep3[3]             # (the predicted classes, int64 [B]: _run_heads hands them on in place of the logits)
         ctx.side = src is not None          # (the gradient of the [CLS] rows then goes to _MLMHeadFn.backward and nowhere else: it joins the side stream)
         ctx.save_for_backward(*([] if src is not None else [first]))
         ctx.mark_non_differentiable(aux, logits, t_rel, rel)
@@ -1902,7 +1925,7 @@ class _HeadsStepFn(torch.autograd.Function):
         for m in range(3):
             a.gvw[m], a.gvb[m], a.gWq[m], a.gbq[m] = (vs3[m].weight.grad.data_ptr(), vs3[m].bias.grad.data_ptr(), qs[m].weight.grad.data_ptr(),
                                                       qs[m].bias.grad.data_ptr())
-        assert at.weight.grad.is_contiguous()
+        assert at.weight.grad.is_contiguous() and c2.weight.grad.is_contiguous() and c2.weight.grad.shape == c2.weight.shape
         a.sync = ops.heads_step_sync(dev).data_ptr()
         if ctx.side and dmlm is not None and getattr(top, "heads_side_stream", True):
             # round 6: the six levels on a side stream, beside the MLM head's sparse backward (which needs nothing of the heads' but the
@@ -2029,7 +2052,10 @@ class _HeadsFn(torch.autograd.Function):
 class MMBertForPretraining(_GpuModelBase):
     """REF:MMBertForPretraining.py:304-449."""
 
-    def __init__(self, config, _bert=None):
+    def __init__(self, config, num_labels=None, _bert=None):
+        """``num_labels`` -- DECLARED EXTENSION (the reference fixes 7 before it builds ``classifier1_2``, REF :309-314, and sets the attribute
+        only afterwards, REF:train.py:71): None = the reference's model (``num_labels = 7``, one output); 1 or 7: regression, one output;
+        C in 2 .. 16 otherwise: a C-class head, ``classifier1_2 = Linear(H, C)`` with the C-way cross-entropy (REF :314, :438-442)."""
         super().__init__()
         import weakref
         self.config = config
@@ -2038,9 +2064,9 @@ class MMBertForPretraining(_GpuModelBase):
         self.bert = _bert if _bert is not None else MMBertModel(config, _owner=weakref.ref(self))
         self.cls = MMBertPreTrainingHeads(config)
         self.cls._owner = weakref.ref(self)
-        self.num_labels = 7
+        self.num_labels = 7 if num_labels is None else self._check_num_labels(num_labels)
         self.classifier1_1 = nn.Linear(H * 3, H)
-        self.classifier1_2 = nn.Linear(H, 1) if self.num_labels == 7 else nn.Linear(H, self.num_labels)
+        self.classifier1_2 = nn.Linear(H, 1 if self.num_labels in (1, 7) else self.num_labels)
         self.attn = nn.Linear(H * 2, H)
         self.relu = nn.ReLU()
         self.vt, self.vs, self.vv = nn.Linear(H, 1), nn.Linear(H, 1), nn.Linear(H, 1)
@@ -2116,7 +2142,7 @@ class MMBertForPretraining(_GpuModelBase):
         return out
 
     @classmethod
-    def from_pretrained(cls, name_or_path, ignore_unexpected=True, **kw):
+    def from_pretrained(cls, name_or_path, ignore_unexpected=True, num_labels=None, **kw):
         """Loads ``config.json`` + ``pytorch_model.bin`` / ``model.safetensors`` from a LOCAL directory (there is no network on the
         target boxes): ``BertForPreTraining`` / ``BertForMaskedLM`` / ``BertModel`` key names, current or legacy (``_checkpoint_keys``).
         LOUD about what did not arrive: a missing ``bert.embeddings.*`` / ``bert.encoder.*`` tensor raises (a silently fresh encoder
@@ -2125,13 +2151,14 @@ class MMBertForPretraining(_GpuModelBase):
         checkpoint with extra heads or buffers that loaded under the reference loads here too; ``ignore_unexpected=False`` makes it an
         error, round 3's default); heads the file does not have (``cls.*``, ``bert.pooler.*``) and the reference's own additions
         (jointEmbeddings, fusion head, CPC) keep their fresh initialisation, with a warning that names them -- HF's
-        "newly initialized" message.  ``model.load_report`` = dict(missing=[...], unexpected=[...])."""
+        "newly initialized" message.  ``model.load_report`` = dict(missing=[...], unexpected=[...]).  ``num_labels``: the constructor's (a
+        checkpoint whose ``classifier1_2`` has another width fails with torch's size-mismatch error)."""
         import warnings
         if not os.path.isdir(name_or_path):
             raise OSError(f"{name_or_path}: from_pretrained needs a local checkpoint directory (no network access)")
         with open(os.path.join(name_or_path, "config.json")) as fh:
             cfg = MMBertConfig(**json.load(fh))
-        model = cls(cfg)
+        model = cls(cfg, num_labels=num_labels)
         st = os.path.join(name_or_path, "model.safetensors")
         if os.path.exists(st):
             from safetensors.torch import load_file
@@ -2164,6 +2191,29 @@ class MMBertForPretraining(_GpuModelBase):
 
     def set_alpha_beta(self, alpha, beta):
         self.alpha, self.beta = alpha, beta
+
+    @staticmethod
+    def _check_num_labels(n) -> int:
+        if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= 16:
+            raise ValueError(f"num_labels = {n!r}: 1 or 7 (regression, one output) or a class count from 2 to 16 (one 16-wide tile of the heads kernels)")
+        return int(n)
+
+    def set_num_labels(self, n):
+        """DECLARED EXTENSION: the constructor's ``num_labels`` on an existing model, where the reference flow sets the attribute
+        (REF:train.py:70-72, after ``from_pretrained``): ``classifier1_2`` is re-created (HF initialisation, ``config.initializer_range``)
+        when its width has to change -- one output for 1 / 7, C outputs for a class count C in 2 .. 16 --, on the device and in the dtype
+        of the old layer, and the flat parameter / gradient buffers are dropped (rebuilt on the next use).  Call it BEFORE the optimizer is
+        built: an optimizer holds the old layer's parameters and the old flat buffers.  State-dict key names do not change."""
+        n = self._check_num_labels(n)
+        width = 1 if n in (1, 7) else n
+        old = self.classifier1_2
+        if old.out_features != width:
+            new = nn.Linear(old.in_features, width)
+            _hf_init(new, self.config.initializer_range)
+            self.classifier1_2 = new.to(device=old.weight.device, dtype=old.weight.dtype)
+            self._flat = None
+        self.num_labels = n
+        return self
 
     def _apply(self, fn, *a, **k):
         self._flat = None                       # .cuda()/.to() re-creates parameter storage: re-flatten lazily
@@ -2221,15 +2271,22 @@ class MMBertForPretraining(_GpuModelBase):
                     logits_out = self.tanh(logits_out)
                 label_loss = F.mse_loss(logits_out.view(-1), sentiment.view(-1).float())
             else:
-                label_loss = F.cross_entropy(logits_out, sentiment)
+                label_loss = F.cross_entropy(logits_out, sentiment.view(-1).long() if _class_head(self) else sentiment)
                 logits_out = torch.argmax(self.sigmoid(logits_out), dim=1)
         heads_loss = ap_loss + label_loss - self.beta * nce
         return heads_loss, ap_loss, label_loss, nce, logits_out, t_rel, v_rel, s_rel
 
+    def _check_class_labels(self, sentiment) -> int:
+        """The class count of a C-class head (0: regression); its labels are integers -- checked before anything is launched."""
+        ncls = _class_head(self)
+        if ncls and sentiment is not None and (sentiment.is_floating_point() or sentiment.dtype == torch.bool):
+            raise TypeError(f"a {ncls}-class head takes integer class labels in [0, {ncls}), one per sample: sentiment is {sentiment.dtype}")
+        return ncls
+
     def _coop_heads_apply(self, sentiment, B) -> bool:
         """Whether the level-launch heads (_HeadsStepFn) will run this step: then the MLM head leaves the [CLS] rows in the encoder output for
         that kernel to read (no gather / cast launch)."""
-        return bool(self.fused_heads and getattr(self, "coop_heads", True) and sentiment is not None and self.num_labels in (1, 7) and B <= 128
+        return bool(self.fused_heads and getattr(self, "coop_heads", True) and sentiment is not None and (self.num_labels in (1, 7) or _class_head(self)) and B <= 128
                     and self.config.hidden_size % 16 == 0
                     and all(q.grad is not None for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight)))
 
@@ -2241,7 +2298,8 @@ class MMBertForPretraining(_GpuModelBase):
         measured in round 1: no gain; the device time of the tiny kernels, not their dispatch, is the cost.)"""
         src = self.__dict__.pop("_heads_src", None)
         grads_ok = all(q.grad is not None for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight))
-        fused = coop or (self.fused_heads and sentiment is not None and first.is_cuda and self.num_labels in (1, 7) and grads_ok)
+        ncls = _class_head(self)
+        fused = coop or (self.fused_heads and sentiment is not None and first.is_cuda and (self.num_labels in (1, 7) or ncls) and grads_ok)
         if src is not None and not (coop and src[2] == first.data_ptr()):
             # the rows were left to the level-launch heads, which do not run on this placeholder after all: gathered into it now, in place --
             # ``first`` is what carries the heads' gradient back to the [CLS] rows (a fresh gather would have no autograd edge to the trunk)
@@ -2250,18 +2308,26 @@ class MMBertForPretraining(_GpuModelBase):
             with torch.no_grad():
                 first.copy_(src[0].index_select(0, src[1]))
             src = None
-        if fused and not coop and B > 32:
+        if fused and not coop and (B > 32 or ncls):              # (a class head never takes the 19-launch form: eager beyond 128 samples)
             fused = False
-            if not self.__dict__.get("_warned_heads_batch"):
+            if ncls and B <= 128:
+                if not self.__dict__.get("_warned_heads_cls"):
+                    import warnings
+                    self.__dict__["_warned_heads_cls"] = True
+                    warnings.warn(f"msa_amd: a {ncls}-class head has kernels in the level-launch heads only (model.coop_heads, hidden_size % 16 == 0, "
+                                  "gradient buffers in place): the heads run in eager PyTorch (~250 small launches per step)")
+            elif not self.__dict__.get("_warned_heads_batch"):
                 import warnings
                 self.__dict__["_warned_heads_batch"] = True
                 warnings.warn(f"msa_amd: per-GPU batch {B} is beyond the fused heads' limit (128 samples on the level-launch path, 32 on "
                               "the 19-launch path): the heads run in eager PyTorch (~250 small launches per step)")
         if fused:
-            sent = sentiment.to(dev).view(-1).float()
+            sent = sentiment.to(dev).view(-1).long() if ncls else sentiment.to(dev).view(-1).float()
             if coop:
                 ap = (ap_v.to(dev).view(-1).long(), ap_s.to(dev).view(-1).long())
                 loss, aux, logits_out, t_rel, rel = _HeadsStepFn.apply(first, self, ap, sent, mlm, None if src is None else (src[0], src[1]))
+                if ncls:                                          # the second return value of forward: the predicted classes (REF :442)
+                    logits_out = self.__dict__.pop("_heads_pred")
             else:
                 ap = torch.cat((ap_v.to(dev).view(-1), ap_s.to(dev).view(-1))).long()
                 loss, aux, logits_out, t_rel, rel = _HeadsFn.apply(first, self, ap, sent, mlm)
@@ -2280,6 +2346,7 @@ class MMBertForPretraining(_GpuModelBase):
           output is outputs[0], which is what trainer.py differentiates (REF:trainer.py:83); ``model.fused_heads = False``
           (the eager heads) keeps them in the autograd graph like the reference."""
         self.outputs = ()
+        ncls = self._check_class_labels(sentiment)
         text_ids, visual, speech, twv, tws = input_ids
         tt_t = token_type_ids[0]
         am_t, am_v, am_s = attention_mask
@@ -2311,7 +2378,7 @@ class MMBertForPretraining(_GpuModelBase):
         if coop and getattr(self, "heads_side_stream", True) and y.is_cuda and y.is_contiguous():
             # the heads' forward levels below the losses go out NOW, on the side stream, beside the MLM head's launches (_HeadsStepFn.prelaunch)
             _HeadsStepFn.prelaunch(self, y, plan["first"], (ap_v.to(dev).view(-1).long(), ap_s.to(dev).view(-1).long()),
-                                   sentiment.to(dev).view(-1).float())
+                                   sentiment.to(dev).view(-1).long() if ncls else sentiment.to(dev).view(-1).float())
         # first = [3B, H]: the [CLS] rows of every sequence; joint_loss = alpha * (mlm_t + mlm_v + mlm_s) / 3 + heads_loss  (:427, :443)
         mlm, logits, first = _MLMHeadFn.apply(y, self.cls.predictions.transform.LayerNorm.weight, self, labels, plan["bounds"], plan["bounds_dev"],
                                               self.return_scores, rows, plan["first"], trunk)
@@ -2339,10 +2406,16 @@ class MMBertForPretraining(_GpuModelBase):
         seed sequence, prologue buffers, pending gradients), so it can sit between two train steps.  What it does not run: the MLM
         transform, the vocabulary GEMM (no [tokens, vocab] buffer), any cross-entropy, and the top encoder layer on any row but the 3 B
         [CLS] rows -- only those are read by the pooler (REF :297, :406-415; HF pooler): one-query attention (ops.attn_fwd_first), then
-        out-projection / LayerNorm / FFN / LayerNorm on 3 B rows, then the heads' forward levels 1 - 5 (any B: chunks of 128)."""
-        if self.num_labels not in (1, 7):
-            raise NotImplementedError(f"predict(): num_labels = {self.num_labels} -- only the regression head (num_labels 1 or 7) is implemented; "
-                                      "classifier1_2 has one output whatever num_labels says (REF:MMBertForPretraining.py:369)")
+        out-projection / LayerNorm / FFN / LayerNorm on 3 B rows, then the heads' forward levels 1 - 5 (any B: chunks of 128).
+
+        With a C-class head (``num_labels=C`` / ``set_num_labels``): returns the predicted classes, int64 [B] -- the index of the largest
+        raw logit, the lowest index on an exact tie (the reference's ``argmax(sigmoid(logits))``, REF :442, differs only where two fp32
+        sigmoids coincide) --, and ``return_pooled`` adds ``class_logits`` fp32 [B, C] (raw) to the dict."""
+        ncls = _class_head(self)
+        if self.num_labels not in (1, 7) and not ncls:
+            raise NotImplementedError(f"predict(): num_labels = {self.num_labels} on a classifier1_2 with {self.classifier1_2.out_features} output(s) -- setting the "
+                                      "attribute alone does not widen the layer (REF:MMBertForPretraining.py:309-314); build the class head with "
+                                      "MMBertForPretraining(config, num_labels=C) or model.set_num_labels(C), 2 <= C <= 16")
         text_ids, visual, speech, twv, tws = input_ids
         tt_t = token_type_ids[0]
         am_t, am_v, am_s = attention_mask
@@ -2356,7 +2429,11 @@ class MMBertForPretraining(_GpuModelBase):
                       dict(ids=twv, tt=None, mask=am_v[0].to(dev), pair=visual, pair_mask=am_v[1].to(dev)),
                       dict(ids=tws, tt=None, mask=am_s[0].to(dev), pair=speech, pair_mask=am_s[1].to(dev))]
             y, _plan, _lens, _ = self._encode(passes, None, False, predict=True)
-            logits, t_rel, v_rel, s_rel, pooled, fused = _HeadsStepFn.predict(self, y, B)
+            logits, t_rel, v_rel, s_rel, pooled, fused, *pred = _HeadsStepFn.predict(self, y, B)
+        if ncls:                                                  # the classes (what forward returns second); the raw logits on request
+            if return_pooled:
+                return pred[0], dict(pooled=pooled, fused=fused, t_rel=t_rel, v_rel=v_rel, s_rel=s_rel, class_logits=logits)
+            return pred[0]
         if return_pooled:
             return logits, dict(pooled=pooled, fused=fused, t_rel=t_rel, v_rel=v_rel, s_rel=s_rel)
         return logits
@@ -2373,6 +2450,7 @@ class MMBertForPretraining(_GpuModelBase):
         attention_mask=(text_mask[B,T], visual_mask[B,V,Dv], speech_mask[B,A,Ds]); masked_labels [B, T+V+A] (-100 = ignore).
         Returns ((joint_loss, None, None, None, ap_loss, label_loss, nce, scores[B,S,V] | None, rel[B,2]), logits[B,1]).
         Checked against oracle.fused_forward (the same extension of the CPU restatement)."""
+        self._check_class_labels(sentiment)
         text_ids, visual, speech = input_ids
         am_t, am_v, am_s = attention_mask
         ap_v, ap_s = ap_label

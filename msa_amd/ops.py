@@ -1183,12 +1183,12 @@ _VP, _VP3 = ctypes.c_void_p, ctypes.c_void_p * 3
 class _HeadsStep(ctypes.Structure):
     """Mirror of ``mmbert_heads_step`` (include/mmbert_hip.h), field for field."""
     _fields_ = ([("B", ctypes.c_int), ("H", ctypes.c_int), ("tanh_lo", ctypes.c_int), ("nmlm", ctypes.c_int), ("alpha", ctypes.c_float), ("beta", ctypes.c_float),
-                 ("first", _VP), ("y", _VP), ("first_rows", _VP), ("ldy", ctypes.c_int), ("pad0_", ctypes.c_int), ("ap", _VP), ("ap2", _VP), ("sent", _VP), ("mlm", _VP)]
+                 ("first", _VP), ("y", _VP), ("first_rows", _VP), ("ldy", ctypes.c_int), ("ncls", ctypes.c_int), ("ap", _VP), ("ap2", _VP), ("sent", _VP), ("mlm", _VP)]
                 + [(n, _VP) for n in ("Wp", "bp", "Wal", "bal", "Wsr", "bsr", "Wat", "bat")] + [("vw", _VP3), ("vb", _VP3)]
                 + [(n, _VP) for n in ("Wc1", "bc1", "Wc2", "bc2")] + [("Wq", _VP3), ("bq", _VP3)]
                 + [(n, _VP) for n in ("loss", "aux", "out5", "logits", "t_rel", "rel", "ws", "dloss", "dfirst", "dmlm")]
                 + [(n, _VP) for n in ("gWp", "gbp", "gWal", "gbal", "gWat", "gbat")] + [("gvw", _VP3), ("gvb", _VP3)]
-                + [(n, _VP) for n in ("gWc1", "gbc1", "gWc2", "gbc2")] + [("gWq", _VP3), ("gbq", _VP3)] + [("sync", _VP)])
+                + [(n, _VP) for n in ("gWc1", "gbc1", "gWc2", "gbc2")] + [("gWq", _VP3), ("gbq", _VP3)] + [("sync", _VP), ("sent_cls", _VP), ("pred", _VP)])
 
 
 _heads_sync = {}

@@ -288,7 +288,7 @@ def eval_epoch(args, model, valdata, tokenizer=None, *, device="cuda", generator
             dev_loss += outputs[0].mean()
             label_loss += outputs[5].mean()
             ap_loss = outputs[4]
-            preds.append(logits.detach().float())
+            preds.append(logits.detach().float() if logits.is_floating_point() else logits.detach())     # (a class head: int64 class ids)
             labels.append(kwargs["sentiment"].detach())
             n += 1
     if n == 0:
@@ -316,7 +316,8 @@ def predict_epoch(args, model, data, *, device="cuda", batches=None):
     utterances as they are (no MLM masking: ``eval_epoch`` masks because the reference's evaluation does; a prediction does not).
     ``data``: a Dataset of the reference's 16-tuples (collated here, ``args.test_batch_size``, else ``args.val_batch_size``), or pass
     ``batches`` = an iterable of model-kwargs dicts (keys other than ``input_ids`` / ``token_type_ids`` / ``attention_mask``, such as
-    labels, are ignored).  Returns the predictions as one float32 array [N, 1]: one device->host transfer at the end.  Leaves
+    labels, are ignored).  Returns the predictions as one float32 array [N, 1] -- from a model with a C-class head (``num_labels=C``
+    / ``set_num_labels``) the predicted classes, one int64 array [N] --: one device->host transfer at the end.  Leaves
     ``model.training`` as it found it."""
     import numpy as np
     if batches is None:
@@ -326,8 +327,10 @@ def predict_epoch(args, model, data, *, device="cuda", batches=None):
         batches = (pack_predict_inputs(b, device) for b in loader)
     preds = [model.predict(kw["input_ids"], kw["token_type_ids"], kw["attention_mask"]) for kw in batches]
     if not preds:
-        return np.zeros((0, 1), dtype=np.float32)
-    return torch.cat(preds).float().cpu().numpy()
+        from .model import _class_head
+        return np.zeros((0,), dtype=np.int64) if _class_head(model) else np.zeros((0, 1), dtype=np.float32)
+    preds = torch.cat(preds)
+    return (preds.float() if preds.is_floating_point() else preds).cpu().numpy()
 
 
 def _weighted_f1(y_true, y_pred):

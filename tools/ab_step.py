@@ -22,15 +22,16 @@ for a in sys.argv[1:]:
 # variants that differ in power draw read +-1-2 % wrong that way (round 4: three "+-0" results turned into -0.7 ... -2.5 % with longer
 # windows and with alternating 600-step processes)
 steps, rounds = int(os.environ.get("STEPS", 40)), int(os.environ.get("ROUNDS", 4))
+num_labels = int(os.environ["NUM_LABELS"]) if os.environ.get("NUM_LABELS") else None      # NUM_LABELS=C: a C-class label head and class labels
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
-model = MMBertForPretraining(MMBertConfig())
+model = MMBertForPretraining(MMBertConfig(), num_labels=num_labels)
 model.bert.set_joint_embeddings("mosei")
 model.to(dev).train()
 model.manual_seed(1234)
 model.async_prologue = os.environ.get("ASYNC_PROLOGUE", "1") != "0"     # (the pool below is resident; attr.async_prologue=False for the A/B)
 opt, sched = build_optimizer(model, default_args(train_batch_size=16, learning_rate=5e-5), 1000)
-pool = [batch_to(synthetic_batch(16, 50, 500, 500, seed=1 + i), dev) for i in range(4)]
+pool = [batch_to(synthetic_batch(16, 50, 500, 500, seed=1 + i, num_labels=None if num_labels in (None, 1, 7) else num_labels), dev) for i in range(4)]
 all_keys = {k for _, env in variants for k in env}
 
 
