@@ -1026,11 +1026,13 @@ class _MLMHeadFn(torch.autograd.Function):
     their sum."""
 
     @staticmethod
-    def forward(ctx, y, anchor, top, labels, seg_bounds_host, seg_bounds, want_scores, rows=None, first_rows=None, trunk=None):
+    def forward(ctx, y, anchor, top, labels, seg_bounds_host, seg_bounds, want_scores, rows=None, first_rows=None, trunk=None, leave_rows=False):
         """``trunk``: the _Trunk record of the _TrunkFn call that produced y (forward() / forward_fused() pass it): when the top encoder
         layer's sparse backward applies, backward hands it the gradient of y in COMPACT form -- the labelled rows and the [CLS] rows,
         the only ones with a gradient -- through ``trunk.compact`` and returns a stride-0 dummy for y (round 2: a zero-filled [tokens, H]
-        tensor, an index_copy, an index_add, and a row gather to pick the rows out again)."""
+        tensor, an index_copy, an index_add, and a row gather to pick the rows out again).
+        ``leave_rows``: the level-launch heads (_HeadsStepFn) read rows first_rows of y themselves, handed (y, first_rows) by the caller beside
+        the graph like the trunk's compact gradient: ``first`` only carries the autograd edge (an uninitialised buffer: no gather, no cast)."""
         cfg, w = top.config, top._w
         ctx.trunk = trunk
         M, H = y.shape
@@ -1041,11 +1043,8 @@ class _MLMHeadFn(torch.autograd.Function):
         ctx.first_rows = first_rows
         first = None
         if first_rows is not None:
-            if getattr(top, "_heads_read_rows", False):
-                # the level-launch heads (_HeadsStepFn) read rows first_rows of y themselves: `first` only carries the autograd edge (an
-                # uninitialised buffer: no gather, no cast); the real operand travels beside the graph, like the trunk's compact gradient
+            if leave_rows:
                 first = torch.empty((first_rows.numel(), H), device=y.device, dtype=torch.float32)
-                top.__dict__["_heads_src"] = (y, first_rows, first.data_ptr())
             else:
                 first = y.index_select(0, first_rows).float()
         if (not want_scores) and keep and rows is not None and getattr(top, "sparse_mlm_backward", True):
@@ -1100,7 +1099,7 @@ class _MLMHeadFn(torch.autograd.Function):
         nf = t.top_rows[1].numel() if (t is not None and t.top_rows is not None and dfirst is not None) else 0
         res = _MLMHeadFn._backward(ctx, dloss, extra_rows=nf)
         _join_heads(ctx.top)                                  # (the heads' backward may still run on its side stream: dfirst is read from here on)
-        nones = (None,) * 9
+        nones = (None,) * 10
         if isinstance(res, tuple):                            # (labelled rows int32 or int64, their gradients [n (+ nf), H] bf16): the sparse paths
             sel, dy_all = res
             n = sel.numel()
@@ -1133,6 +1132,21 @@ class _MLMHeadFn(torch.autograd.Function):
         return 4 * (n + first.numel()) <= ra and int(host[1]) == 0 and n == _active_row_count(t.top_rows[0])
 
     @staticmethod
+    def _few_rows_backward(top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows):
+        """The head's backward over the n labelled rows alone (the sparse paths of _backward), from their dlogits ``dl`` [n, Vpad]: returns
+        [n + extra_rows, H] bf16 with the rows' gradient wrt y in its first n rows."""
+        w = top._w
+        n = dl.shape[0]
+        _late_wgrad(top, (dl, t_c, w["g_word_pad"], w["g_pred_bias"]), late)
+        dt = ops.gemm_nt_splitk(dl, w["wordT"])                     # K = vocabulary, a few hundred rows: split-K
+        dt0 = ops.ln_bwd(dt, t0_c, mean_c, rstd_c, w["mlm_ln_g"], w["g_mlm_ln_g"], w["g_mlm_ln_b"], deferred=lnd)
+        dpre = ops.gelu_bwd(dt0, pre_c)
+        _late_wgrad(top, (dpre, y_c, w["g_Wt"], w["g_bt"]), late)
+        dy_all = torch.empty((n + extra_rows, y_c.shape[1]), device=y_c.device, dtype=torch.bfloat16)
+        ops.gemm_nt(dpre, w["WtT"], out=dy_all[:n])
+        return dy_all
+
+    @staticmethod
     def _backward(ctx, dloss, extra_rows=0):
         w = ctx.top._w
         V = ctx.top.config.vocab_size
@@ -1155,14 +1169,7 @@ class _MLMHeadFn(torch.autograd.Function):
         if ctx.compact:
             y_c, pre_c, t0_c, mean_c, rstd_c, t_c, logits_c, labels_c, bounds_c, inv, lse, sel = ctx.saved_tensors
             dl = ops.ce_bwd(logits_c, V, labels_c, bounds_c, ctx.nseg, inv, gs, lse, logits_c)       # in place: the scores go nowhere
-            _late_wgrad(ctx.top, (dl, t_c, w["g_word_pad"], w["g_pred_bias"]), late)
-            dt = ops.gemm_nt_splitk(dl, w["wordT"])
-            dt0 = ops.ln_bwd(dt, t0_c, mean_c, rstd_c, w["mlm_ln_g"], w["g_mlm_ln_g"], w["g_mlm_ln_b"], deferred=lnd)
-            dpre = ops.gelu_bwd(dt0, pre_c)
-            _late_wgrad(ctx.top, (dpre, y_c, w["g_Wt"], w["g_bt"]), late)
-            dy_all = torch.empty((sel.numel() + extra_rows, y_c.shape[1]), device=y_c.device, dtype=torch.bfloat16)
-            ops.gemm_nt(dpre, w["WtT"], out=dy_all[:sel.numel()])
-            return sel, dy_all
+            return sel, _MLMHeadFn._few_rows_backward(ctx.top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows)
         y, pre, t0, mean, rstd, t, logits, labels, seg_bounds, inv, lse = ctx.saved_tensors
         M = y.shape[0]
         if ctx.rows is not None:
@@ -1175,14 +1182,7 @@ class _MLMHeadFn(torch.autograd.Function):
                 dl = torch.empty((n, logits.shape[1]), device=y.device, dtype=torch.bfloat16)
                 ops.ce_bwd(logits, V, labels, seg_bounds, ctx.nseg, inv, gs, lse, dl, rows=idx)
                 t_c, t0_c, pre_c, y_c, mean_c, rstd_c = ops.gather_rows([t, t0, pre, y, mean, rstd], idx)      # one launch
-                _late_wgrad(ctx.top, (dl, t_c, w["g_word_pad"], w["g_pred_bias"]), late)
-                dt = ops.gemm_nt_splitk(dl, w["wordT"])                     # K = vocabulary, a few hundred rows: split-K
-                dt0 = ops.ln_bwd(dt, t0_c, mean_c, rstd_c, w["mlm_ln_g"], w["g_mlm_ln_g"], w["g_mlm_ln_b"], deferred=lnd)
-                dpre = ops.gelu_bwd(dt0, pre_c)
-                _late_wgrad(ctx.top, (dpre, y_c, w["g_Wt"], w["g_bt"]), late)
-                dy_all = torch.empty((n + extra_rows, y.shape[1]), device=y.device, dtype=torch.bfloat16)
-                ops.gemm_nt(dpre, w["WtT"], out=dy_all[:n])
-                return idx, dy_all
+                return idx, _MLMHeadFn._few_rows_backward(ctx.top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows)
         # dense path: dlogits with the per-pass upstream gradients folded in; in place unless the scores were handed to the caller
         dl = torch.empty(logits.shape, device=logits.device, dtype=torch.bfloat16) if (ctx.keep_logits or logits.dtype != torch.bfloat16) else logits
         ops.ce_bwd(logits, V, labels, seg_bounds, ctx.nseg, inv, gs, lse, dl)
@@ -1264,13 +1264,10 @@ class _GpuModelBase(nn.Module):
 
     def _drop_leftovers(self):
         """At a forward pass, no backward pass is in flight: what one that raised half-way left behind goes -- side-stream launches are
-        joined, the few-row weight-gradient problems it had queued and the [CLS]-row records of a forward pass that stopped before the
-        heads are dropped (the LayerNorm' collector: see _encode)."""
+        joined and the few-row weight-gradient problems it had queued are dropped (the LayerNorm' collector: see _encode).  A forward pass
+        leaves nothing behind: its hand-overs are arguments and return values."""
         self._join_side_writers()
-        d = self.__dict__
-        d.pop("_late_wgrads", None)
-        d.pop("_heads_src", None)
-        d.pop("_heads_pre", None)
+        self.__dict__.pop("_late_wgrads", None)
 
     def _layer_grads_done(self, i: int):
         if self.grad_hook is not None:
@@ -1404,9 +1401,26 @@ class _GpuModelBase(nn.Module):
         n = len(passes) * B * T
         return packed[:n], packed[n:2 * n], (packed[2 * n:] if label_parts else None)
 
+    def _stage_labels(self, passes, label_parts):
+        """(labels [tokens] int64 on the device in the order of the token matrix, packed (ids, token types) for _encode or None): through
+        _pack_inputs where it applies, else concatenated / cast by torch -- on the input stream when the prologue runs there."""
+        pk = self._pack_inputs(passes, label_parts)
+        if pk is not None:
+            return pk[2], pk[:2]
+        ids = passes[0]["ids"]
+        side = self._prologue_stream(ids) if label_parts[0].is_cuda else None
+        # (async_prologue: the prologue's inputs must not queue behind the current stream)
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            labels = torch.cat([l.reshape(-1) for l in label_parts]) if len(label_parts) > 1 else label_parts[0].reshape(-1)
+            labels = labels.to(device=ids.device, dtype=torch.long)
+        if side is not None:
+            labels.record_stream(torch.cuda.current_stream())
+        return labels, None
+
     def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None, predict=False):
         """passes: list of dict(ids[B,T], tt[B,T]|None, mask, pair[B,P,D]|None, pair_mask|None).
-        Returns (Y [tokens,H] bf16, plan, lens_per_pass, rows) -- ``rows`` = (labelled-row list, host words, event) when asked for.
+        Returns (Y [tokens,H] bf16, plan, lens_per_pass, rows, trunk) -- ``rows`` = (labelled-row list, host words, event) when asked for;
+        ``trunk`` = the _Trunk record of the call (forward() hands it to the MLM head: compact output gradient), None for ``predict``.
         ``rowset``: the valid-first packing over a row SET instead of a prefix per sequence (the prologue's row-set mode): for
         sequences whose masked-out rows do not sit at the end -- the fused text | visual | speech sequence has its visual padding in
         the middle.  Every sequence is then run in its own valid-first order (active rows = unmasked keys and labelled rows, first):
@@ -1575,15 +1589,14 @@ class _GpuModelBase(nn.Module):
         y = _TrunkFn.apply(bert.embeddings.LayerNorm.weight, self, t)
         split = t.split
         if predict:
-            return y, plan, lens, rows
-        self._last_trunk = t                                       # (forward() hands it to the MLM head: compact output gradient)
+            return y, plan, lens, rows, None
         if self.debug_hidden is not None:
             packed = self.debug_hidden.pop("_layers_packed", [])
             if split is not None:                   # back to the original row order (left-out rows of the drop form read as zeros)
                 pad = getattr(split, "dropped", False)
                 packed = [None if q is None else (torch.cat((q, q.new_zeros((1, q.shape[1])))) if pad else q).index_select(0, split.inv) for q in packed]
             self.debug_hidden["layers"] = [y.detach() if q is None else q for q in packed]
-        return y, plan, lens, rows
+        return y, plan, lens, rows, t
 
     def _request_lengths(self, plan, kv_len, labels, infer=False, pairs=None):
         """Inference only (training takes the prologue's ``valid`` words): starts the device -> host copy of the per-sequence count
@@ -1720,7 +1733,7 @@ class MMBertModel(_GpuModelBase):
             text = input_ids
             tmask = attention_mask if attention_mask is not None else torch.ones(text.shape, device=text.device)
             p = dict(ids=text, tt=token_type_ids, mask=tmask)
-        y, plan, lens, _ = top._encode([p])
+        y, plan, lens, _, _ = top._encode([p])
         B = text.shape[0]
         seq = y.view(B, lens[0], -1).float()
         pooled = torch.tanh(F.linear(seq[:, 0], self.pooler.dense.weight, self.pooler.dense.bias))     # HF:457-463
@@ -1864,7 +1877,8 @@ class _HeadsStepFn(torch.autograd.Function):
     def prelaunch(top, y, rows, ap, sent):
         """Round 6: forward levels 1 - 6 (everything but the losses) on the heads' side stream, queued BEFORE the MLM head's forward: they
         need the encoder output's [CLS] rows and nothing of the MLM head, whose launches (transform, the vocabulary GEMM, cross-entropy)
-        then run beside them instead of in front of them.  ``forward`` picks the record up, joins, and runs level 7."""
+        then run beside them instead of in front of them.  Returns the record (a, outs, keep, event) for ``forward`` (``pre``), which joins and runs
+        level 7; whoever drops it unused lets the current stream wait for the event first (the side stream writes buffers of that stream's pool)."""
         B, H, dev = rows.numel() // 3, y.shape[1], y.device
         a, outs, keep = _HeadsStepFn._setup(top, B, H, dev, ap, sent, src=(y, rows))
         s = ops.side_stream("heads", dev)
@@ -1872,34 +1886,29 @@ class _HeadsStepFn(torch.autograd.Function):
         with torch.cuda.stream(s):
             ops.heads_step_fwd(a, 1, 6)
             ev = s.record_event()
-        top.__dict__["_heads_pre"] = (y.data_ptr(), rows.data_ptr(), a, outs, keep, ev)
+        return a, outs, keep, ev
 
     @staticmethod
-    def forward(ctx, first, top, ap, sent, mlm=None, src=None):
+    def forward(ctx, first, top, ap, sent, mlm=None, src=None, pre=None):
+        """``pre``: the record (a, outs, keep, event) of this call's _setup, made by the caller from the same operands -- by prelaunch(), which
+        has queued levels 1 - 6 behind ``event``, or with no event and nothing launched; None: made here."""
         B, H = first.shape[0] // 3, first.shape[1]
         dev = first.device
-        pre = top.__dict__.pop("_heads_pre", None)
-        if pre is not None and not (src is not None and pre[0] == src[0].data_ptr() and pre[1] == src[1].data_ptr() and pre[2].B == B):
-            pre = None                                          # (a record some other forward pass left behind)
-        if pre is not None:
-            _, _, a, outs, keep3, ev = pre
-            torch.cuda.current_stream().wait_event(ev)
-            lo = 7
-        else:
+        if pre is None:
             if src is None:
                 first = first.contiguous()
-            a, outs, keep3 = _HeadsStepFn._setup(top, B, H, dev, ap, sent, first=first, src=src)
-            lo = 1
+            pre = _HeadsStepFn._setup(top, B, H, dev, ap, sent, first=first, src=src) + (None,)
+        a, outs, keep3, ev = pre
+        if ev is not None:
+            torch.cuda.current_stream().wait_event(ev)
         keep = []
         if mlm is not None:
             mlm = mlm.detach().float().contiguous()
             a.mlm, a.nmlm = mlm.data_ptr(), mlm.numel()
             keep.append(mlm)
-        ops.heads_step_fwd(a, lo, 7)
+        ops.heads_step_fwd(a, 1 if ev is None else 7, 7)
         loss, aux, logits, t_rel, rel = outs
         ctx.top, ctx.a, ctx.B, ctx.H, ctx.keep = top, a, B, H, (keep,) + tuple(keep3)
-        if a.ncls:
-            top.__dict__["_heads_pred"] = keep3[3]             # (the predicted classes, int64 [B]: _run_heads hands them on in place of the logits)
         ctx.side = src is not None          # (the gradient of the [CLS] rows then goes to _MLMHeadFn.backward and nowhere else: it joins the side stream)
         ctx.save_for_backward(*([] if src is not None else [first]))
         ctx.mark_non_differentiable(aux, logits, t_rel, rel)
@@ -1909,7 +1918,7 @@ class _HeadsStepFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d, *_unused):
         if d is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         top, a, B, H = ctx.top, ctx.a, ctx.B, ctx.H
         dev = d.device
         d1 = d.reshape(1).float().contiguous()
@@ -1943,9 +1952,9 @@ class _HeadsStepFn(torch.autograd.Function):
                 # LAST event covers all of them; every record keeps its operands alive until then)
                 top.__dict__.setdefault("_heads_join", []).append((s.record_event(), scratch, d1, ctx.keep))
             a.dmlm = dmlm.data_ptr()
-            return dfirst, None, None, None, dmlm, None
+            return dfirst, None, None, None, dmlm, None, None
         ops.heads_step_bwd(a)
-        return dfirst, None, None, None, dmlm, None
+        return dfirst, None, None, None, dmlm, None, None
 
 
 class _HeadsFn(torch.autograd.Function):
@@ -2290,21 +2299,19 @@ class MMBertForPretraining(_GpuModelBase):
                     and self.config.hidden_size % 16 == 0
                     and all(q.grad is not None for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight)))
 
-    def _run_heads(self, first, ap_v, ap_s, sentiment, dev, B, mlm=None, coop=False):
+    def _run_heads(self, first, ap_v, ap_s, sentiment, dev, B, mlm=None, coop=False, src=None, pre=None):
         """The heads on the [3B, H] [CLS] rows: the fused kernels (csrc/heads.hip) where they apply, else the eager form.
         ``coop``: the forward pass's _coop_heads_apply() -- the ONE decision the MLM head acted on too (it then left the rows in the encoder
         output and ``first`` is a placeholder): not evaluated a second time here.
+        ``src``: (y, first_rows) when the rows were left there, else None; ``pre``: the record of _HeadsStepFn.prelaunch, if that ran.
         (A captured hipGraph of the eager [B,H]-sized glue -- forward and backward, ~200 dependent launches -- was built and
         measured in round 1: no gain; the device time of the tiny kernels, not their dispatch, is the cost.)"""
-        src = self.__dict__.pop("_heads_src", None)
         grads_ok = all(q.grad is not None for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight))
         ncls = _class_head(self)
         fused = coop or (self.fused_heads and sentiment is not None and first.is_cuda and (self.num_labels in (1, 7) or ncls) and grads_ok)
-        if src is not None and not (coop and src[2] == first.data_ptr()):
+        if src is not None and not coop:
             # the rows were left to the level-launch heads, which do not run on this placeholder after all: gathered into it now, in place --
             # ``first`` is what carries the heads' gradient back to the [CLS] rows (a fresh gather would have no autograd edge to the trunk)
-            if src[2] != first.data_ptr():
-                raise RuntimeError("msa_amd: the [CLS] rows left for the heads belong to another forward pass")
             with torch.no_grad():
                 first.copy_(src[0].index_select(0, src[1]))
             src = None
@@ -2325,9 +2332,11 @@ class MMBertForPretraining(_GpuModelBase):
             sent = sentiment.to(dev).view(-1).long() if ncls else sentiment.to(dev).view(-1).float()
             if coop:
                 ap = (ap_v.to(dev).view(-1).long(), ap_s.to(dev).view(-1).long())
-                loss, aux, logits_out, t_rel, rel = _HeadsStepFn.apply(first, self, ap, sent, mlm, None if src is None else (src[0], src[1]))
+                if pre is None:                                   # (nothing was prelaunched: the record is made here, with no event)
+                    pre = _HeadsStepFn._setup(self, B, first.shape[1], dev, ap, sent, first=first, src=src) + (None,)
+                loss, aux, logits_out, t_rel, rel = _HeadsStepFn.apply(first, self, ap, sent, mlm, src, pre)
                 if ncls:                                          # the second return value of forward: the predicted classes (REF :442)
-                    logits_out = self.__dict__.pop("_heads_pred")
+                    logits_out = pre[2][3]
             else:
                 ap = torch.cat((ap_v.to(dev).view(-1), ap_s.to(dev).view(-1))).long()
                 loss, aux, logits_out, t_rel, rel = _HeadsFn.apply(first, self, ap, sent, mlm)
@@ -2336,6 +2345,21 @@ class MMBertForPretraining(_GpuModelBase):
         if mlm is not None:                                   # joint loss, eager form   (:427, :443)
             out = (self.alpha * mlm.mean() + out[0],) + tuple(out[1:])
         return out
+
+    @staticmethod
+    def _three_passes(input_ids, token_type_ids, attention_mask):
+        """forward()'s and predict()'s passes for _encode: text, text | visual, text | speech."""
+        text_ids, visual, speech, twv, tws = input_ids
+        am_t, am_v, am_s = attention_mask
+        dev = text_ids.device
+        return [dict(ids=text_ids, tt=token_type_ids[0], mask=am_t),
+                dict(ids=twv, tt=None, mask=am_v[0].to(dev), pair=visual, pair_mask=am_v[1].to(dev)),
+                dict(ids=tws, tt=None, mask=am_s[0].to(dev), pair=speech, pair_mask=am_s[1].to(dev))]
+
+    def _scores_view(self, logits, B, S):
+        """Prediction scores [B, S, vocab] in ``self.scores_dtype``: a zero-copy view of the logits' rows [B * S, Vpad] unless the dtype differs."""
+        scores = logits.view(B, S, -1)[:, :, :self.config.vocab_size]
+        return scores if self.scores_dtype == scores.dtype else scores.to(self.scores_dtype)
 
     def forward(self, input_ids, token_type_ids, attention_mask, masked_labels, ap_label, sentiment):
         """REF:MMBertForPretraining.py:392-449, same arguments and the same 13-tuple + logits.  Deviations, all switchable:
@@ -2347,48 +2371,38 @@ class MMBertForPretraining(_GpuModelBase):
           (the eager heads) keeps them in the autograd graph like the reference."""
         self.outputs = ()
         ncls = self._check_class_labels(sentiment)
-        text_ids, visual, speech, twv, tws = input_ids
-        tt_t = token_type_ids[0]
-        am_t, am_v, am_s = attention_mask
-        lab_t, lab_v, lab_s = masked_labels
+        text_ids, visual, speech = input_ids[:3]
         ap_v, ap_s = ap_label
         dev = text_ids.device
         B, T = text_ids.shape
-        passes = [dict(ids=text_ids, tt=tt_t, mask=am_t),
-                  dict(ids=twv, tt=None, mask=am_v[0].to(dev), pair=visual, pair_mask=am_v[1].to(dev)),
-                  dict(ids=tws, tt=None, mask=am_s[0].to(dev), pair=speech, pair_mask=am_s[1].to(dev))]
-        H, V = self.config.hidden_size, self.config.vocab_size
-        pk = self._pack_inputs(passes, (lab_t, lab_v, lab_s))
-        if pk is not None:
-            labels, pk = pk[2], pk[:2]
-        else:
-            side = self._prologue_stream(text_ids) if lab_t.is_cuda else None
-            if side is None:
-                labels = torch.cat((lab_t.reshape(-1), lab_v.reshape(-1), lab_s.reshape(-1))).to(device=dev, dtype=torch.long)
-            else:                                   # async_prologue: the prologue's inputs must not queue behind the current stream
-                with torch.cuda.stream(side):
-                    labels = torch.cat((lab_t.reshape(-1), lab_v.reshape(-1), lab_s.reshape(-1))).to(device=dev, dtype=torch.long)
-                labels.record_stream(torch.cuda.current_stream())
+        passes = self._three_passes(input_ids, token_type_ids, attention_mask)
+        labels, pk = self._stage_labels(passes, tuple(masked_labels))
         if labels.numel() != B * (T + (T + visual.shape[1]) + (T + speech.shape[1])):
             raise ValueError("masked_labels must cover text (+ pair) positions of every pass")
         want_rows = torch.is_grad_enabled() and getattr(self, "sparse_mlm_backward", True) and labels.is_cuda
-        y, plan, lens, rows = self._encode(passes, labels, want_rows, packed=pk)
-        trunk, self._last_trunk = self._last_trunk, None
-        coop = self._heads_read_rows = self._coop_heads_apply(sentiment, B)
-        if coop and getattr(self, "heads_side_stream", True) and y.is_cuda and y.is_contiguous():
+        y, plan, lens, rows, trunk = self._encode(passes, labels, want_rows, packed=pk)
+        y = y.contiguous()
+        coop = self._heads_read_rows = self._coop_heads_apply(sentiment, B)     # (a record of the decision; nothing reads it back)
+        src = (y, plan["first"]) if coop else None          # the [CLS] rows stay in y for the level-launch heads
+        pre = None
+        if coop and getattr(self, "heads_side_stream", True) and y.is_cuda:
             # the heads' forward levels below the losses go out NOW, on the side stream, beside the MLM head's launches (_HeadsStepFn.prelaunch)
-            _HeadsStepFn.prelaunch(self, y, plan["first"], (ap_v.to(dev).view(-1).long(), ap_s.to(dev).view(-1).long()),
-                                   sentiment.to(dev).view(-1).long() if ncls else sentiment.to(dev).view(-1).float())
-        # first = [3B, H]: the [CLS] rows of every sequence; joint_loss = alpha * (mlm_t + mlm_v + mlm_s) / 3 + heads_loss  (:427, :443)
-        mlm, logits, first = _MLMHeadFn.apply(y, self.cls.predictions.transform.LayerNorm.weight, self, labels, plan["bounds"], plan["bounds_dev"],
-                                              self.return_scores, rows, plan["first"], trunk)
-        joint_loss, ap_loss, label_loss, nce, logits_out, t_rel, v_rel, s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=mlm, coop=coop)
+            pre = _HeadsStepFn.prelaunch(self, y, plan["first"], (ap_v.to(dev).view(-1).long(), ap_s.to(dev).view(-1).long()),
+                                         sentiment.to(dev).view(-1).long() if ncls else sentiment.to(dev).view(-1).float())
+        try:
+            # first = [3B, H]: the [CLS] rows of every sequence; joint_loss = alpha * (mlm_t + mlm_v + mlm_s) / 3 + heads_loss  (:427, :443)
+            mlm, logits, first = _MLMHeadFn.apply(y, self.cls.predictions.transform.LayerNorm.weight, self, labels, plan["bounds"], plan["bounds_dev"],
+                                                  self.return_scores, rows, plan["first"], trunk, coop)
+            joint_loss, ap_loss, label_loss, nce, logits_out, t_rel, v_rel, s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=mlm, coop=coop,
+                                                                                                     src=src, pre=pre)
+        except BaseException:
+            if pre is not None:             # the side stream may still write the record's buffers: joined before the record goes with this frame
+                torch.cuda.current_stream().wait_event(pre[3])
+            raise
         scores = (None, None, None)
         if logits is not None:
             b = plan["bounds"]
-            scores = tuple(logits[b[k]:b[k + 1]].view(B, lens[k], -1)[:, :, :V] for k in range(3))
-            if self.scores_dtype != logits.dtype:
-                scores = tuple(sc.to(self.scores_dtype) for sc in scores)
+            scores = tuple(self._scores_view(logits[b[k]:b[k + 1]], B, lens[k]) for k in range(3))
         self.outputs = (_scalar_loss(joint_loss), None, None, None, ap_loss, label_loss, nce,
                         scores[0], t_rel, scores[1], v_rel, scores[2], s_rel)
         return self.outputs, logits_out
@@ -2416,19 +2430,14 @@ class MMBertForPretraining(_GpuModelBase):
             raise NotImplementedError(f"predict(): num_labels = {self.num_labels} on a classifier1_2 with {self.classifier1_2.out_features} output(s) -- setting the "
                                       "attribute alone does not widen the layer (REF:MMBertForPretraining.py:309-314); build the class head with "
                                       "MMBertForPretraining(config, num_labels=C) or model.set_num_labels(C), 2 <= C <= 16")
-        text_ids, visual, speech, twv, tws = input_ids
-        tt_t = token_type_ids[0]
-        am_t, am_v, am_s = attention_mask
+        text_ids = input_ids[0]
         dev = text_ids.device
         if self.config.hidden_size % 16 != 0:
             raise RuntimeError(f"predict(): hidden_size {self.config.hidden_size} is not a multiple of 16 (the level-launch heads)")
         with torch.no_grad():
             self._ensure_ready(dev)                               # (CPU tensors: the "no CPU path" error, before anything is moved)
             B = text_ids.shape[0]
-            passes = [dict(ids=text_ids, tt=tt_t, mask=am_t),
-                      dict(ids=twv, tt=None, mask=am_v[0].to(dev), pair=visual, pair_mask=am_v[1].to(dev)),
-                      dict(ids=tws, tt=None, mask=am_s[0].to(dev), pair=speech, pair_mask=am_s[1].to(dev))]
-            y, _plan, _lens, _ = self._encode(passes, None, False, predict=True)
+            y = self._encode(self._three_passes(input_ids, token_type_ids, attention_mask), None, False, predict=True)[0]
             logits, t_rel, v_rel, s_rel, pooled, fused, *pred = _HeadsStepFn.predict(self, y, B)
         if ncls:                                                  # the classes (what forward returns second); the raw logits on request
             if return_pooled:
@@ -2457,30 +2466,19 @@ class MMBertForPretraining(_GpuModelBase):
         dev = text_ids.device
         B, T = text_ids.shape
         passes = [dict(ids=text_ids, tt=token_type_ids, mask=am_t, pair=(visual, speech), pair_mask=(am_v, am_s))]
-        V = self.config.vocab_size
-        pk = self._pack_inputs(passes, (masked_labels,))
-        if pk is not None:
-            labels, pk = pk[2], pk[:2]
-        else:
-            side = self._prologue_stream(text_ids) if masked_labels.is_cuda else None
-            if side is None:
-                labels = masked_labels.reshape(-1).to(device=dev, dtype=torch.long)
-            else:                                   # async_prologue: see forward()
-                with torch.cuda.stream(side):
-                    labels = masked_labels.reshape(-1).to(device=dev, dtype=torch.long)
-                labels.record_stream(torch.cuda.current_stream())
+        labels, pk = self._stage_labels(passes, (masked_labels,))
         if labels.numel() != B * (T + visual.shape[1] + speech.shape[1]):
             raise ValueError("masked_labels must cover the text and both pair blocks")
         want_rows = torch.is_grad_enabled() and getattr(self, "sparse_mlm_backward", True) and labels.is_cuda
         # the visual padding sits in the MIDDLE of the fused sequence: valid-first packing over the row set, not over a prefix
-        y, plan, lens, rows = self._encode(passes, labels, want_rows, rowset=getattr(self, "fused_rowset_packing", True), packed=pk)
-        trunk, self._last_trunk = self._last_trunk, None
-        coop = self._heads_read_rows = self._coop_heads_apply(sentiment, B)
+        y, plan, lens, rows, trunk = self._encode(passes, labels, want_rows, rowset=getattr(self, "fused_rowset_packing", True), packed=pk)
+        y = y.contiguous()
+        coop = self._heads_read_rows = self._coop_heads_apply(sentiment, B)     # (a record of the decision; nothing reads it back)
+        first_rows = plan["first"].repeat(3)                                    # the one [CLS] row in the t / v / s slots
         mlm, logits, first = _MLMHeadFn.apply(y, self.cls.predictions.transform.LayerNorm.weight, self, labels, plan["bounds"], plan["bounds_dev"],
-                                              self.return_scores, rows, plan["first"].repeat(3), trunk)   # the one [CLS] row in the t / v / s slots
-        joint_loss, ap_loss, label_loss, nce, logits_out, _t_rel, v_rel, _s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=mlm, coop=coop)
-        scores = None if logits is None else logits.view(B, lens[0], -1)[:, :, :V]
-        if scores is not None and self.scores_dtype != scores.dtype:
-            scores = scores.to(self.scores_dtype)
+                                              self.return_scores, rows, first_rows, trunk, coop)
+        joint_loss, ap_loss, label_loss, nce, logits_out, _t_rel, v_rel, _s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=mlm, coop=coop,
+                                                                                                   src=(y, first_rows) if coop else None)
+        scores = None if logits is None else self._scores_view(logits, B, lens[0])
         self.outputs = (_scalar_loss(joint_loss), None, None, None, ap_loss, label_loss, nce, scores, v_rel)
         return self.outputs, logits_out

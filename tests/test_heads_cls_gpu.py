@@ -97,7 +97,7 @@ def _run(c, model_form=False):
         else:
             f = c.first.to(DEV).requires_grad_(True)
             loss, aux, logits, t_rel, rel = MM._HeadsStepFn.apply(f, m, torch.cat((ap_v, ap_s)), y, mlm)
-        pred = m.__dict__.pop("_heads_pred")
+        pred = loss.grad_fn.keep[-2]
         out5 = loss.grad_fn.keep[-1]
         loss.backward(torch.tensor(c.d, device=DEV))
         MM._join_heads(m)

@@ -1062,3 +1062,82 @@ def test_a_backward_that_raised_leaks_nothing_into_the_next_step(where, size, ze
     if zero_grad:
         assert not [k for k in a["after_zero_grad"] if k != "_late_wgrads"], a["after_zero_grad"]
     assert not a["after_forward"] and not b["after_forward"], (a["after_forward"], b["after_forward"])
+
+
+@pytest.mark.parametrize("num_labels", [7, 3])
+def test_a_forward_that_raised_after_the_heads_prelaunch_leaks_nothing_into_the_next_step(num_labels):
+    """A forward pass hands its pieces on as arguments and return values: one that raises half-way leaves nothing on the model.  Twins
+    with the same weights and seeds: A runs forward on batch 1 with an ordinary Python exception injected at the entry of
+    _MLMHeadFn.forward -- behind _HeadsStepFn.prelaunch, which has queued the heads' levels 1 - 6 on the side stream into buffers that only
+    the forward pass's frame holds --, then a full step on batch 2; B runs the same batch-1 forward to the end, discards it, and takes the
+    same batch-2 step.  Deterministic mode: the loss, the flat gradient buffer before the update and the parameters after it are compared
+    BIT for bit.  The regression head and a 3-class head (integer labels; its predicted classes travel in the prelaunched record too).
+    ``_heads_read_rows``, the plain record of the pass's one heads decision, is the only ``_heads_*`` attribute a forward pass may write."""
+    from msa_amd import model as M
+    from msa_amd import ops as _ops
+    from msa_amd import trainer as T_
+    cfg = dict(hidden=256, layers=2, heads=4, intermediate=1024, vocab=4096, dataset="mosei", alpha=1.0, beta=1.0)
+    b1 = batch_to(synthetic_batch(4, 24, 90, 70, dataset="mosei", vocab=cfg["vocab"], seed=81), DEV)
+    b2 = batch_to(synthetic_batch(4, 24, 90, 70, dataset="mosei", vocab=cfg["vocab"], seed=82), DEV)
+    if num_labels == 3:
+        b1 = dict(b1, sentiment=torch.tensor([0, 2, 1, 2], device=DEV))
+        b2 = dict(b2, sentiment=torch.tensor([1, 1, 0, 2], device=DEV))
+    orig_fwd, orig_pre = M._MLMHeadFn.__dict__["forward"], M._HeadsStepFn.__dict__["prelaunch"]
+    prelaunched, at_raise = [], {}
+
+    def counting_prelaunch(*a, **k):
+        prelaunched.append(1)
+        return orig_pre.__func__(*a, **k)
+
+    def failing_forward(*a, **k):
+        at_raise["prelaunched"] = len(prelaunched)
+        raise RuntimeError("injected failure")
+
+    runs = {}
+    was = _ops.deterministic()
+    try:
+        _ops.set_deterministic(True)
+        M._HeadsStepFn.prelaunch = staticmethod(counting_prelaunch)
+        for twin in ("warm-up", "failed", "clean"):             # (warm-up: process-wide workspaces that grow on demand take their size first)
+            m = build(cfg, dropout=0.1)
+            if num_labels == 3:
+                torch.manual_seed(5)                            # (the new classifier1_2 is drawn from torch's generator: the same for every twin)
+                m.set_num_labels(3)
+            m.train()
+            m.manual_seed(17)
+            m.coop_heads = m.heads_side_stream = True
+            opt, sched = T_.build_optimizer(m, T_.default_args(train_batch_size=4, learning_rate=1e-3), 10, mode="hf")
+            sched.step()
+            del prelaunched[:]
+            if twin == "failed":
+                M._MLMHeadFn.forward = staticmethod(failing_forward)
+                try:
+                    with pytest.raises(RuntimeError, match="injected failure"):
+                        m(**b1)
+                finally:
+                    M._MLMHeadFn.forward = orig_fwd
+                left = sorted(k for k in m.__dict__ if (k.startswith("_heads_") and k != "_heads_read_rows") or k == "_last_trunk")
+            else:
+                o1, _ = m(**b1)
+                if twin == "warm-up":
+                    o1[0].mean().backward()
+                del o1
+                left = []
+            assert m._heads_read_rows and len(prelaunched) == 1  # the level-launch heads were to run, their lower levels on the side stream
+            o2, _ = m(**b2)
+            o2[0].mean().backward()
+            torch.cuda.synchronize()
+            flat_grads = m._flat.grads.clone()
+            opt.step()
+            torch.cuda.synchronize()
+            runs[twin] = dict(loss=o2[0].detach().clone(), flat_grads=flat_grads, params=m._flat.params.clone(), left=left)
+    finally:
+        _ops.set_deterministic(was)
+        M._MLMHeadFn.forward, M._HeadsStepFn.prelaunch = orig_fwd, orig_pre
+    assert at_raise == dict(prelaunched=1), at_raise            # the injection came behind a prelaunch
+    a, b = runs["failed"], runs["clean"]
+    assert not a["left"], a["left"]
+    assert torch.equal(a["loss"], b["loss"])
+    assert torch.equal(a["flat_grads"], b["flat_grads"])
+    assert torch.equal(a["params"], b["params"])
+    assert bool(b["flat_grads"].any()) and bool(torch.isfinite(b["params"]).all())
