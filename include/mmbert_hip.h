@@ -190,6 +190,16 @@ int mmbert_attn_fwd(mmbert_stream_t stream, const void* qkv, void* ctx, float* l
  * is a softmax over equally biased keys.  One workgroup per (sequence, head), no atomics: bitwise reproducible.  nseq <= 65535. */
 int mmbert_attn_fwd_first(mmbert_stream_t stream, const void* qkv, void* ctx, const float* key_bias, const int* bias_start, int H, int heads,
                           const int* seq_start, const int* seq_len, const int* q_row, int nseq, const int* kv_len);
+/* The attention PROBABILITIES of the same one query row per sequence, for every head: probs [nseq, heads, ld] fp32,
+ *   probs[s][h][k] = exp(s_k - m) / sum_j exp(s_j - m),  s_k = (q / 8) . k_k + key_bias[k],  over the keys k < Skv = min(seq_len[s], kv_len[s])
+ * -- what the model attends with at that row (no dropout), in the arithmetic of mmbert_attn_fwd_first (fp32 scores and softmax).  All
+ * other arguments as there; V is not read.  EVERY element of probs[s][h][0 .. ld) is written (the buffer may be uninitialised): exact
+ * 0.0f for k in [Skv, ld), a zero row for an empty sequence; a sequence whose keys are all masked keeps its full length and comes out
+ * as the softmax over its equally biased keys.  ld >= the longest sequence is the caller's business; stores are clamped at ld either
+ * way.  The score row of a workgroup lives in LDS (4 bytes per key, no opt-in): ld <= 16376, beyond it the call returns -1.
+ * No allocation, no synchronisation, no atomics: bitwise reproducible.  nseq <= 65535, ld >= 1. */
+int mmbert_attn_probs_first(mmbert_stream_t stream, const void* qkv, float* probs, int ld, const float* key_bias, const int* bias_start, int H, int heads,
+                            const int* seq_start, const int* seq_len, const int* q_row, int nseq, const int* kv_len /* may be null */);
 int mmbert_attn_bwd(mmbert_stream_t stream, const void* qkv, const void* ctx, const void* dctx, void* dqkv, const float* lse, float* delta,
                     const float* key_bias, const int* bias_start, int H, int heads, const int* seq_start, const int* seq_len, const unsigned* elem_base,
                     const int* qtile_seq, const int* qtile_r0, int nqtiles,      /* query tiles: mmbert_attn_tile_rows(0) rows */

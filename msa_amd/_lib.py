@@ -48,6 +48,7 @@ SIGNATURES = {
     "mmbert_attn_kv_len": (I, [P, P, P, P, I, P]),
     "mmbert_attn_fwd": (I, [P, P, P, P, P, P, I, I, P, P, P, P, P, I, U32, U32, F, P, P, P]),
     "mmbert_attn_fwd_first": (I, [P, P, P, P, P, I, I, P, P, P, I, P]),
+    "mmbert_attn_probs_first": (I, [P, P, P, I, P, P, I, I, P, P, P, I, P]),
     "mmbert_attn_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, I, P, P, I, U32, U32, F, P, P, P, I, P]),
     "mmbert_attn_q_limit": (I, [P, P, I, P, I, P]),
     "mmbert_attn_dropout_mask": (I, [P, P, I, C.c_uint, I, U32, U32]),

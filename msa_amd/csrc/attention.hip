@@ -886,6 +886,110 @@ __global__ __launch_bounds__(256) void attn_fwd_first_kernel(const AttnFirstArgs
     }
 }
 
+// =============================================================================================
+// the attention PROBABILITIES of ONE query row per sequence (inference: the [CLS] attention maps that predict(return_attention=...)
+// hands out).  Same work item, lane / key mapping and score arithmetic as attn_fwd_first_kernel -- workgroup = one (sequence, head),
+// 8 lanes per key, the query times 1/8 in fp32, an 8-term fma chain per lane, three shuffles, + key_bias -- but no V: without the
+// V registers a group keeps EIGHT keys in flight (keys g + 32 u, u < 8; stride 256 per round).  A group carries its running
+// (maximum m, denominator l) and parks the raw fp32 scores in dynamic LDS (4 bytes per key: the row never leaves the CU); the 32
+// groups' (m, l) are merged in a fixed order (shuffles over the 8 groups of a wave, then the 4 waves through LDS, every thread folding
+// them in the same order), and behind ONE barrier all 256 threads rescale p[k] = exp2((s_k - m) * log2e) * (1 / l) and store the row
+// coalesced, exact zeros from Skv up to ld.  fp32 throughout, no atomics: the same bits every run.  Bound by the K read.
+// Dynamic LDS: ld_pad = ld rounded up to 4 floats | 4 x (m, l); APF_LDS_BYTES(ld) <= 64 KiB is checked by the launcher.
+// =============================================================================================
+struct AttnProbsArgs {
+    const bf16_t* qkv; int ld_qkv;
+    float* probs; int ld;    // [nseq, heads, ld]
+    const float* key_bias; const int* bias_start; const int* kv_len;
+    const int* seq_start; const int* seq_len; const int* q_row;
+    int H, heads; float scale;
+};
+#define APF_PAD(ld) (((ld) + 3) & ~3)
+#define APF_LDS_BYTES(ld) ((size_t)APF_PAD(ld) * 4 + 32)
+#define APF_LDS_MAX 65536
+
+struct ApState { float m, l; };
+__device__ __forceinline__ void ap_merge(ApState& a, const ApState& b) {
+    const float M = fmaxf(a.m, b.m);
+    const float wa = a.m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f((a.m - M) * LOG2E);
+    const float wb = b.m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f((b.m - M) * LOG2E);
+    a.m = M; a.l = a.l * wa + b.l * wb;
+}
+
+__global__ __launch_bounds__(256) void attn_probs_first_kernel(const AttnProbsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float apf_lds[];
+    float* sc = apf_lds;                                                  // raw scores, key k at sc[k], k < min(Skv, ld)
+    float* part = apf_lds + APF_PAD(a.ld);                                // [4 waves][m, l]
+    const int head = blockIdx.x, seq = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 7, grp = wave * 8 + (lane >> 3);
+    const int start = a.seq_start[seq], S = a.seq_len[seq];
+    const int Skv = a.kv_len ? min(S, a.kv_len[seq]) : S;               // keys at and past Skv are all masked out (probability exactly 0)
+    float* prow = a.probs + ((size_t)seq * a.heads + head) * a.ld;
+    if (Skv <= 0) {                                                       // an empty sequence has no keys: a zero row
+        for (int k = threadIdx.x; k < a.ld; k += 256) prow[k] = 0.f;
+        return;
+    }
+    const bf16_t* kbase = a.qkv + (size_t)start * a.ld_qkv + a.H + head * 64 + 8 * c;
+    const float* bbase = a.key_bias + a.bias_start[seq];
+    float q[8];
+    {
+        const bf16x8 qv = *(const bf16x8*)(a.qkv + (size_t)a.q_row[seq] * a.ld_qkv + head * 64 + 8 * c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q[j] = bf2f(qv[j]) * a.scale;
+    }
+    ApState st;
+    st.m = -INFINITY; st.l = 0.f;
+
+    for (int k0 = grp; k0 < Skv; k0 += 256) {                            // (k0 < Skv: at least one key of the eight is real, the maximum stays finite)
+        bf16x8 kf[8];
+        float b[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int k = min(k0 + 32 * u, Skv - 1);                     // clamped address; the score of a key past the end is set to -inf below
+            kf[u] = *(const bf16x8*)(kbase + (size_t)k * a.ld_qkv);
+            b[u] = bbase[k];
+        }
+        float s[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            float d = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], bf2f(kf[u][j]), d);
+            d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64); d += __shfl_xor(d, 4, 64);
+            const int k = k0 + 32 * u;
+            s[u] = k < Skv ? d + b[u] : -INFINITY;
+            if (c == 0 && k < Skv && k < a.ld) sc[k] = s[u];             // (k < ld: a violated ld >= S cannot write past the score array)
+        }
+        const float mnew = fmaxf(fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), fmaxf(fmaxf(s[4], s[5]), fmaxf(s[6], s[7]))), st.m);
+        st.l *= __builtin_amdgcn_exp2f((st.m - mnew) * LOG2E);           // first batch: exp2(-inf) = 0
+        st.m = mnew;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) st.l += __builtin_amdgcn_exp2f((s[u] - mnew) * LOG2E);
+    }
+    // the 8 key groups of a wave, then the 4 waves (every thread folds them in the same order: all hold the same m, l)
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+        ApState o2;
+        o2.m = __shfl_xor(st.m, off, 64); o2.l = __shfl_xor(st.l, off, 64);
+        ap_merge(st, o2);
+    }
+    if (lane == 0) { part[2 * wave] = st.m; part[2 * wave + 1] = st.l; }
+    __syncthreads();
+    ApState tot;
+    tot.m = part[0]; tot.l = part[1];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        ApState o2;
+        o2.m = part[2 * w]; o2.l = part[2 * w + 1];
+        ap_merge(tot, o2);
+    }
+    const float inv = 1.0f / tot.l;
+    const int nk = min(Skv, a.ld);
+    for (int k = threadIdx.x; k < a.ld; k += 256)
+        prow[k] = k < nk ? __builtin_amdgcn_exp2f((sc[k] - tot.m) * LOG2E) * inv : 0.f;
+}
+
 // test/debug: the keep mask of one (sequence, head) as bytes [S, S]
 __global__ void attn_mask_kernel(uint8_t* out, int S, unsigned elem_base, int head, uint32_t stream, uint32_t thr) {
     const int Spad = (S + 3) & ~3;
@@ -985,6 +1089,19 @@ int mmbert_attn_fwd_first(hipStream_t stream, const void* qkv, void* ctx, const 
     a.qkv = (const bf16_t*)qkv; a.ld_qkv = 3 * H; a.ctx = (bf16_t*)ctx; a.key_bias = key_bias; a.bias_start = bias_start; a.kv_len = kv_len;
     a.seq_start = seq_start; a.seq_len = seq_len; a.q_row = q_row; a.H = H; a.scale = 0.125f;
     hipLaunchKernelGGL(attn_fwd_first_kernel, dim3(heads, nseq), dim3(256), 0, stream, a);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+int mmbert_attn_probs_first(hipStream_t stream, const void* qkv, float* probs, int ld, const float* key_bias, const int* bias_start, int H, int heads,
+                            const int* seq_start, const int* seq_len, const int* q_row, int nseq, const int* kv_len) {
+    if (nseq <= 0) return 0;
+    if (heads <= 0 || H != heads * 64 || nseq > 65535 || ld < 1 || !qkv || !probs || !key_bias || !bias_start || !seq_start || !seq_len || !q_row) return -1;
+    if (APF_LDS_BYTES(ld) > APF_LDS_MAX) return -1;    // the score row lives in LDS without an opt-in: ld <= 16376 keys
+    AttnProbsArgs a;
+    a.qkv = (const bf16_t*)qkv; a.ld_qkv = 3 * H; a.probs = probs; a.ld = ld; a.key_bias = key_bias; a.bias_start = bias_start; a.kv_len = kv_len;
+    a.seq_start = seq_start; a.seq_len = seq_len; a.q_row = q_row; a.H = H; a.heads = heads; a.scale = 0.125f;
+    hipLaunchKernelGGL(attn_probs_first_kernel, dim3(heads, nseq), dim3(256), APF_LDS_BYTES(ld), stream, a);
     MMB_CHECK_LAUNCH();
     return 0;
 }

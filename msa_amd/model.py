@@ -385,10 +385,11 @@ class _EncoderFn:
     autograd between its stages)."""
 
     @staticmethod
-    def run_forward(top, x, layout, key_bias, seed, kv_len, keep, y_out=None, y_rows=None, stop=None, train=None):
+    def run_forward(top, x, layout, key_bias, seed, kv_len, keep, y_out=None, y_rows=None, stop=None, train=None, probe=None):
         """Returns (y, saved).  ``y_out`` / ``y_rows``: the LAST layer's LayerNorm writes row i of its output to y_out[y_rows[i]] --
         the un-packing of the valid-first layout (ops.SplitLayout.perm32) rides on that store instead of a [tokens, H] gather.
-        ``stop``: run layers 0 .. stop - 1 only; ``train``: the dropout decision, when it is not the module's mode (both: predict())."""
+        ``stop``: run layers 0 .. stop - 1 only; ``train``: the dropout decision, when it is not the module's mode (both: predict()).
+        ``probe`` (predict(return_attention="all")): called as probe(layer index, qkv) once a layer's QKV matrix is final; it only reads."""
         cfg = top.config
         H, L = cfg.hidden_size, cfg.num_hidden_layers
         nl = L if stop is None else stop
@@ -435,6 +436,8 @@ class _EncoderFn:
                 a.tile_queue = tq
                 ops._set_drop(a.att, d_att); ops._set_drop(a.h1, d_h1); ops._set_drop(a.h2, d_h2)
                 ops.layer_fwd(AL, a)
+                if probe is not None:
+                    probe(i, qkv)
                 if keep:
                     saved.append((x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2))
                 x = y2
@@ -444,6 +447,8 @@ class _EncoderFn:
             d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
             qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
             actx, lse = ops.attn_fwd(qkv, key_bias, layout, H, drop=d_att, kv_len=kv_len)
+            if probe is not None:
+                probe(i, qkv)
             z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=x, drop=d_h1)
             y1, m1, r1 = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=keep)
             u = torch.empty((x.shape[0], cfg.intermediate_size), device=x.device, dtype=torch.bfloat16) if keep else None
@@ -460,18 +465,21 @@ class _EncoderFn:
         return x, saved
 
     @staticmethod
-    def run_top_first(top, x, layout, key_bias, kv_len, q_rows):
+    def run_top_first(top, x, layout, key_bias, kv_len, q_rows, probe=None):
         """The TOP layer for a label-free prediction (inference arithmetic, no dropout): its output is read at one row per sequence only
         (``q_rows`` int32: the packed row of each sequence's [CLS] query), so only that query attends (ops.attn_fwd_first) and everything
         behind the attention runs on the gathered [sequences, H] rows.  The QKV projection stays the existing full launch: K and V are
         needed for every row, and leaving the Q third out (N = 2H plus a Q product on the gathered rows) cannot win -- at the headline shape
         the full launch takes 58 us, so a third is 19 us, and a 48-row product on the small-shape kernel takes 19 - 36 us (the three behind
-        the attention, profiles/predict_ab.txt); the split form itself was not built.  Returns [sequences, H] bf16."""
+        the attention, profiles/predict_ab.txt); the split form itself was not built.  ``probe``: as in run_forward, called for the top
+        layer.  Returns [sequences, H] bf16."""
         cfg = top.config
         H = cfg.hidden_size
         lw = top._lw[cfg.num_hidden_layers - 1]
         qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
         actx = ops.attn_fwd_first(qkv, key_bias, layout, H, q_rows, kv_len=kv_len)
+        if probe is not None:
+            probe(cfg.num_hidden_layers - 1, qkv)
         del qkv
         xr = ops.gather_rows([x], q_rows)[0]
         z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=xr)
@@ -743,7 +751,7 @@ def _trunk_static(plan, B, T, lens, joff, dev):
 class _Trunk:
     """What one _TrunkFn call works on (plain attributes; built by _encode)."""
     __slots__ = ("ids", "tts", "B", "T", "lens", "pair_info", "feats", "feat_versions", "plan", "layout", "split", "key_bias", "kv_len", "seed", "top_rows",
-                 "d_emb", "d_joint", "infer", "late_split", "compact", "J_pre", "predict")
+                 "d_emb", "d_joint", "infer", "late_split", "compact", "J_pre", "predict", "attention")
 
 
 class _TrunkFn(torch.autograd.Function):
@@ -844,12 +852,19 @@ class _TrunkFn(torch.autograd.Function):
             # label-free prediction: layers 0 .. L - 2 as always, the top layer for the [CLS] query of every sequence only; no [tokens, H]
             # un-packing -- the output is the compact [sequences, H] matrix of those rows, in the caller's sequence order
             kvl = None if split is not None else t.kv_len
-            y, _ = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, kvl, False, stop=cfg.num_hidden_layers - 1, train=False)
             first32 = plan.get("first32")
             if first32 is None:
                 first32 = plan["first32"] = plan["first"].to(torch.int32)
             q_rows = split.inv32.index_select(0, plan["first"]) if split is not None else first32
-            return _EncoderFn.run_top_first(top, y, layout, t.key_bias, kvl, q_rows)
+            probe = below = None
+            if t.attention is not None:
+                # predict(return_attention=...): the [CLS] query's attention row of a layer, from that layer's QKV matrix with the very
+                # layout / key bias / kv_len / query rows the top layer attends with -- one more launch per probed layer, which only reads
+                mode, maps = t.attention
+                probe = lambda i, qkv: maps.append((i, ops.attn_probs_first(qkv, t.key_bias, layout, H, q_rows, kv_len=kvl)))
+                below = probe if mode == "all" else None        # ("top": the top layer alone)
+            y, _ = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, kvl, False, stop=cfg.num_hidden_layers - 1, train=False, probe=below)
+            return _EncoderFn.run_top_first(top, y, layout, t.key_bias, kvl, q_rows, probe=probe)
         y, saved = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, None if split is not None else t.kv_len, keep, y_out, y_rows)
         if split is not None and t.infer:
             y = y.index_select(0, split.inv)                      # every masked-out row reads its sequence's representative
@@ -1417,7 +1432,7 @@ class _GpuModelBase(nn.Module):
             labels.record_stream(torch.cuda.current_stream())
         return labels, None
 
-    def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None, predict=False):
+    def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None, predict=False, attention=None):
         """passes: list of dict(ids[B,T], tt[B,T]|None, mask, pair[B,P,D]|None, pair_mask|None).
         Returns (Y [tokens,H] bf16, plan, lens_per_pass, rows, trunk) -- ``rows`` = (labelled-row list, host words, event) when asked for;
         ``trunk`` = the _Trunk record of the call (forward() hands it to the MLM head: compact output gradient), None for ``predict``.
@@ -1430,7 +1445,9 @@ class _GpuModelBase(nn.Module):
         inference packing -- with the top layer run for the [CLS] rows only; Y is then the compact [sequences, H] matrix of those rows.
         Such a call takes nothing from and leaves nothing in the model's per-step state: no dropout seed is drawn, the prologue runs
         on the current stream into buffers of its own (the alternating sets of ``async_prologue`` stay as they are), the leftovers of
-        a train step are not touched and no trunk record is kept."""
+        a train step are not touched and no trunk record is kept.  ``attention`` (with ``predict`` only) = (``"top"`` | ``"all"``, list):
+        the list receives (layer index, fp32 [sequences, heads, longest sequence]) per probed layer -- the [CLS] queries' attention rows
+        (ops.attn_probs_first)."""
         bert = self._bert()
         dev = passes[0]["ids"].device
         self._ensure_ready(dev)
@@ -1538,6 +1555,7 @@ class _GpuModelBase(nn.Module):
         t = _Trunk()
         t.compact = None
         t.predict = bool(predict)
+        t.attention = attention if predict else None
         t.ids, t.tts, t.B, t.T, t.lens, t.pair_info, t.plan = ids, tts, B, T, lens, pair_info, plan
         t.feats = [None if info is None else tuple(_pair_features(f, dev) for f in info[0]) for info in pair_info]
         t.feat_versions = [None if fs is None else tuple(f._version for f in fs) for fs in t.feats]
@@ -1770,6 +1788,15 @@ class MMBertPreTrainingHeads(nn.Module):
         if joint:
             return scores, self.align(sequence_output[:, 0])
         return scores, self.seq_relationship(pooled_output)
+
+
+def attention_modality_mass(att, T):
+    """[..., S] attention rows of a joint pass (text positions first, then the pair positions) -> [..., 2]: the share of each row on its
+    ``T`` text keys and on its pair keys.  Plain torch, on whatever device ``att`` lives (CPU tensors included); the two shares add up to
+    the row sum."""
+    if not 0 <= int(T) <= att.shape[-1]:
+        raise ValueError(f"attention_modality_mass: T = {T} outside a row of {att.shape[-1]} keys")
+    return torch.stack((att[..., :T].sum(-1), att[..., T:].sum(-1)), dim=-1)
 
 
 def _class_head(top) -> int:
@@ -2407,7 +2434,7 @@ class MMBertForPretraining(_GpuModelBase):
                         scores[0], t_rel, scores[1], v_rel, scores[2], s_rel)
         return self.outputs, logits_out
 
-    def predict(self, input_ids, token_type_ids, attention_mask, return_pooled=False):
+    def predict(self, input_ids, token_type_ids, attention_mask, return_pooled=False, return_attention=None):
         """DECLARED EXTENSION, not in the reference (its ``sampling.py`` does not run against its own model's signature): the sentiment
         prediction WITHOUT labels.  The first three arguments are ``forward``'s.  Returns ``logits`` [B, 1] fp32 -- what ``forward``
         returns as its second value in eval mode, classifier1_2(classifier1_1(gated concat)), through tanh when ``num_labels == 1``
@@ -2424,7 +2451,28 @@ class MMBertForPretraining(_GpuModelBase):
 
         With a C-class head (``num_labels=C`` / ``set_num_labels``): returns the predicted classes, int64 [B] -- the index of the largest
         raw logit, the lowest index on an exact tie (the reference's ``argmax(sigmoid(logits))``, REF :442, differs only where two fp32
-        sigmoids coincide) --, and ``return_pooled`` adds ``class_logits`` fp32 [B, C] (raw) to the dict."""
+        sigmoids coincide) --, and ``return_pooled`` adds ``class_logits`` fp32 [B, C] (raw) to the dict.
+
+        ``return_attention`` = ``"top"`` | ``"all"`` (``None`` / ``False``: off; anything else raises ``ValueError``): also returns a dict
+        (ONE dict when ``return_pooled`` is set as well) with the attention rows of every sequence's [CLS] query -- the only rows the pooler
+        and the fusion head read -- of the top layer or of every layer:
+          ``attention``         {"text": [Lsel, B, heads, T], "visual": [Lsel, B, heads, T + V], "speech": [Lsel, B, heads, T + A]} fp32 on the
+                                device; the key axis in the caller's order, text positions first, then the pair positions;
+          ``attention_layers``  the layer indices behind axis 0: [L - 1] or 0 .. L - 1;
+          ``attention_mass``    {"visual", "speech": [Lsel, B, heads, 2]}: the share of a row on the T text keys and on the pair keys
+                                (``attention_modality_mass``).
+        The values are exactly what the model attends with (fp32 softmax of the bf16 Q / K the layer computed, no dropout), the
+        reference's quirks preserved here included: a pair position is masked by feature 0 of its mask alone
+        (REF:MMBertForPretraining.py:76), and the text padding of the joint passes is masked only if the caller's text-with-pair mask
+        says so -- the reference's collate hands over all ones there (REF:model_utils.py:128,136), so [PAD] text keys carry weight in
+        the "visual" and "speech" maps.  One read-only launch per returned layer (ops.attn_probs_first): the prediction and the
+        pooled outputs keep their bits."""
+        if return_attention is None or return_attention is False:
+            att = None
+        elif isinstance(return_attention, str) and return_attention in ("top", "all"):
+            att = (return_attention, [])
+        else:
+            raise ValueError(f"predict(): return_attention = {return_attention!r}; expected None, False, 'top' or 'all'")
         ncls = _class_head(self)
         if self.num_labels not in (1, 7) and not ncls:
             raise NotImplementedError(f"predict(): num_labels = {self.num_labels} on a classifier1_2 with {self.classifier1_2.out_features} output(s) -- setting the "
@@ -2437,15 +2485,22 @@ class MMBertForPretraining(_GpuModelBase):
         with torch.no_grad():
             self._ensure_ready(dev)                               # (CPU tensors: the "no CPU path" error, before anything is moved)
             B = text_ids.shape[0]
-            y = self._encode(self._three_passes(input_ids, token_type_ids, attention_mask), None, False, predict=True)[0]
+            y, _, lens = self._encode(self._three_passes(input_ids, token_type_ids, attention_mask), None, False, predict=True, attention=att)[:3]
             logits, t_rel, v_rel, s_rel, pooled, fused, *pred = _HeadsStepFn.predict(self, y, B)
-        if ncls:                                                  # the classes (what forward returns second); the raw logits on request
+            extra = {}
             if return_pooled:
-                return pred[0], dict(pooled=pooled, fused=fused, t_rel=t_rel, v_rel=v_rel, s_rel=s_rel, class_logits=logits)
-            return pred[0]
-        if return_pooled:
-            return logits, dict(pooled=pooled, fused=fused, t_rel=t_rel, v_rel=v_rel, s_rel=s_rel)
-        return logits
+                extra.update(pooled=pooled, fused=fused, t_rel=t_rel, v_rel=v_rel, s_rel=s_rel)
+                if ncls:
+                    extra.update(class_logits=logits)
+            if att is not None:
+                # per probed layer [3B, heads, longest sequence], sequences pass by pass: text, text | visual, text | speech
+                maps = sorted(att[1], key=lambda e: e[0])
+                names = ("text", "visual", "speech")
+                extra["attention"] = {n: torch.stack([p[k * B:(k + 1) * B, :, :lens[k]] for _, p in maps]) for k, n in enumerate(names)}
+                extra["attention_layers"] = [i for i, _ in maps]
+                extra["attention_mass"] = {n: attention_modality_mass(extra["attention"][n], lens[0]) for n in names[1:]}
+        out = pred[0] if ncls else logits                         # the classes (what forward returns second); the raw logits on request
+        return (out, extra) if (return_pooled or att is not None) else out
 
     def forward_fused(self, input_ids, token_type_ids, attention_mask, masked_labels, ap_label, sentiment):
         """DECLARED EXTENSION, not in the reference (SURVEY S8(d) mode ``fused1050``; BASELINE.json quotes its metric on a "fused

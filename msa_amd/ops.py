@@ -844,6 +844,32 @@ def attn_fwd_first(qkv, key_bias, layout: SeqLayout, H, q_rows, *, kv_len=None):
     return ctx
 
 
+def attn_probs_first(qkv, key_bias, layout: SeqLayout, H, q_rows, *, kv_len=None, out=None):
+    """The attention probabilities of ONE query row per sequence, every head (mmbert_attn_probs_first; inference arithmetic: no dropout):
+    same arguments as ``attn_fwd_first``.  Returns fp32 [sequences, heads, max(layout.lens)]: entry k of a row is the weight of the key at
+    position k of the caller's sequence whatever the packing (under a split layout the keys of a sequence are its region-A rows, its
+    leading positions); exact zeros behind the sequence's keys.  ``out``: a contiguous fp32 buffer of that shape to write into (every
+    element is written).  Reads nothing but ``qkv`` and the layout."""
+    lib = _lib.load()
+    M = qkv.shape[0]
+    if key_bias.numel() != layout.bias_len or layout.bias_len == M:
+        key_bias = pad_key_bias(key_bias, layout) if key_bias.numel() == M else key_bias
+    assert qkv.shape[1] == 3 * H and qkv.is_contiguous() and qkv.dtype == torch.bfloat16
+    if getattr(layout, "split", False):
+        kv_len = layout.kv_len                           # keys of a sequence = its region-A rows
+    ns = layout.seq_len.numel()
+    assert q_rows.dtype == torch.int32 and q_rows.is_contiguous() and q_rows.numel() == ns and key_bias.dtype == torch.float32
+    ld = max(max(layout.lens, default=1), 1)
+    if out is None:
+        out = torch.empty((ns, layout.heads, ld), device=qkv.device, dtype=torch.float32)
+    assert out.shape == (ns, layout.heads, ld) and out.dtype == torch.float32 and out.is_contiguous() and out.device == qkv.device
+    probs = out
+    _lib.check(lib.mmbert_attn_probs_first(_stream(), qkv.data_ptr(), probs.data_ptr(), ld, key_bias.data_ptr(), layout.bias_start.data_ptr(), H,
+                                           layout.heads, layout.seq_start.data_ptr(), layout.seq_len.data_ptr(), q_rows.data_ptr(), ns, _ptr(kv_len)),
+               "mmbert_attn_probs_first")
+    return probs
+
+
 def attn_q_limit(rows32, layout):
     """Per sequence of ``layout``: 1 + the largest query index among the packed rows ``rows32`` (int32) -- what ``attn_bwd(q_limit=...)``
     takes when only those rows have a non-zero output gradient (mmbert_attn_q_limit)."""
@@ -1381,7 +1407,7 @@ def layer_bwd(L: _AttnLayout, a: _LayerBwd):
 
 # the per-launch wrappers as defined here: model.py takes the composite path only while nobody has wrapped them (bench.py's per-launch
 # event timing, tests that spy on launches)
-_UNWRAPPED = dict(gemm_nt=gemm_nt, attn_fwd=attn_fwd, attn_fwd_first=attn_fwd_first, attn_bwd=attn_bwd, ln_fwd=ln_fwd, ln_bwd=ln_bwd)
+_UNWRAPPED = dict(gemm_nt=gemm_nt, attn_fwd=attn_fwd, attn_fwd_first=attn_fwd_first, attn_probs_first=attn_probs_first, attn_bwd=attn_bwd, ln_fwd=ln_fwd, ln_bwd=ln_bwd)
 
 
 def launches_unwrapped() -> bool:

@@ -310,7 +310,7 @@ def pack_predict_inputs(batch, device):
     )
 
 
-def predict_epoch(args, model, data, *, device="cuda", batches=None):
+def predict_epoch(args, model, data, *, device="cuda", batches=None, return_attention=None):
     """The label-free counterpart of ``eval_epoch`` (what the reference's ``sampling.py`` is for; that script does not run against its
     own model's signature): ``model.predict`` over ``data`` in SEQUENTIAL order -- row i of the result is item i of the dataset -- on the
     utterances as they are (no MLM masking: ``eval_epoch`` masks because the reference's evaluation does; a prediction does not).
@@ -318,8 +318,16 @@ def predict_epoch(args, model, data, *, device="cuda", batches=None):
     ``batches`` = an iterable of model-kwargs dicts (keys other than ``input_ids`` / ``token_type_ids`` / ``attention_mask``, such as
     labels, are ignored).  Returns the predictions as one float32 array [N, 1] -- from a model with a C-class head (``num_labels=C``
     / ``set_num_labels``) the predicted classes, one int64 array [N] --: one device->host transfer at the end.  Leaves
-    ``model.training`` as it found it."""
+    ``model.training`` as it found it.
+
+    ``return_attention`` = ``"top"`` | ``"all"`` (``model.predict``'s argument): returns ``(preds, dict)`` with ``attention`` and
+    ``attention_mass`` as numpy arrays per pass, concatenated over the dataset on the sample axis (axis 1) in dataset order, and
+    ``attention_layers``.  The maps go to the host batch by batch; every batch must have the same key widths (T, T + V, T + A), else
+    ``ValueError``.  Host memory of ``"all"``: L * N * heads * S * 4 bytes per pass (12 layers, 12 heads, S = 550: 317 KB per sample and
+    pass); ``"top"`` is 1 / L of it."""
     import numpy as np
+    if return_attention is not None and return_attention is not False:
+        return _predict_epoch_attention(args, model, data, device, batches, return_attention)
     if batches is None:
         from torch.utils.data import DataLoader, SequentialSampler
         bs = getattr(args, "test_batch_size", None) or args.val_batch_size
@@ -331,6 +339,36 @@ def predict_epoch(args, model, data, *, device="cuda", batches=None):
         return np.zeros((0,), dtype=np.int64) if _class_head(model) else np.zeros((0, 1), dtype=np.float32)
     preds = torch.cat(preds)
     return (preds.float() if preds.is_floating_point() else preds).cpu().numpy()
+
+
+def _predict_epoch_attention(args, model, data, device, batches, return_attention):
+    """``predict_epoch`` with the [CLS] attention maps (see there)."""
+    import numpy as np
+    if batches is None:
+        from torch.utils.data import DataLoader, SequentialSampler
+        bs = getattr(args, "test_batch_size", None) or args.val_batch_size
+        loader = DataLoader(data, sampler=SequentialSampler(data), batch_size=bs, collate_fn=collate)
+        batches = (pack_predict_inputs(b, device) for b in loader)
+    preds, att, mass, layers = [], {}, {}, None
+    for kw in batches:
+        p, ex = model.predict(kw["input_ids"], kw["token_type_ids"], kw["attention_mask"], return_attention=return_attention)
+        preds.append(p)
+        layers = ex["attention_layers"]
+        for store, key in ((att, "attention"), (mass, "attention_mass")):
+            for n, v in ex[key].items():
+                have = store.setdefault(n, [])
+                if have and have[0].shape[-1] != v.shape[-1]:
+                    raise ValueError(f"predict_epoch(return_attention=...): the {n} maps of two batches differ in their key width "
+                                     f"({have[0].shape[-1]} and {v.shape[-1]}); pad the batches to one length")
+                have.append(v.cpu().numpy())
+    if not preds:
+        from .model import _class_head
+        empty = np.zeros((0,), dtype=np.int64) if _class_head(model) else np.zeros((0, 1), dtype=np.float32)
+        return empty, dict(attention={}, attention_mass={}, attention_layers=[])
+    preds = torch.cat(preds)
+    preds = (preds.float() if preds.is_floating_point() else preds).cpu().numpy()
+    cat = lambda d: {n: np.concatenate(v, axis=1) for n, v in d.items()}
+    return preds, dict(attention=cat(att), attention_mass=cat(mass), attention_layers=list(layers))
 
 
 def _weighted_f1(y_true, y_pred):

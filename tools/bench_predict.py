@@ -9,10 +9,13 @@ up first, ``--rounds`` alternating rounds: median, and the spread max - min over
   (a) model.eval() + no_grad + forward with dummy labels          -- the only way to predictions without predict()
   (b) the same with return_scores = False                         -- expected equal to (a): the dense MLM head runs under no_grad anyway
   (c) model.predict                                               -- no labels, [CLS]-only top layer, no MLM head
+  (d) model.predict(return_attention="top")                       -- (c) + one ops.attn_probs_first launch and the slicing of its result
+  (e) model.predict(return_attention="all")                       -- (c) + one such launch per layer
 plus the peak allocation of each above the level before the call (torch.cuda.max_memory_allocated).
 ``--kernel``: the stand-alone time of ops.attn_fwd_first at the headline layout (16 x 50 + 32 x 550 rows, 12 heads; device events
 around 200 launches) and the bytes it reads (K and V of every row once, one query row and the key bias per (sequence, head)) over
-that time, as a share of the 6.3 TB/s a long copy reaches (a bandwidth share: the kernel has no MFMA work).
+that time, as a share of the 6.3 TB/s a long copy reaches (a bandwidth share: the kernel has no MFMA work); and the same for
+ops.attn_probs_first, whose counted bytes are the K read, the fp32 [sequences, heads, 550] store, the query rows and the key bias.
 The last line of the output is one JSON object with every number."""
 import argparse
 import json
@@ -72,7 +75,9 @@ def bench_shape(name, s, calls, rounds, dev):
             with torch.no_grad():
                 return model(**batch)[1]
         return f
-    legs = [("a_forward", forward(True)), ("b_forward_no_scores", forward(False)), ("c_predict", lambda: model.predict(*args3))]
+    legs = [("a_forward", forward(True)), ("b_forward_no_scores", forward(False)), ("c_predict", lambda: model.predict(*args3)),
+            ("d_predict_attn_top", lambda: model.predict(*args3, return_attention="top")),
+            ("e_predict_attn_all", lambda: model.predict(*args3, return_attention="all"))]
     for _, fn in legs:                                        # warm-up of every leg at this shape
         for _ in range(3):
             fn()
@@ -92,6 +97,9 @@ def bench_shape(name, s, calls, rounds, dev):
     for n, _ in legs:
         print(f"{name:10s} {n:22s} {res[n]['ms']:9.3f} ms/call  spread {res[n]['spread_ms']:.3f} ms  peak {res[n]['peak_bytes'] / 2 ** 20:9.1f} MiB")
     print(f"{name:10s} predict / min(a, b) = {res['predict_over_forward']:.4f}")
+    for n in ("d_predict_attn_top", "e_predict_attn_all"):
+        res[n]["over_predict_ms"] = res[n]["ms"] - res["c_predict"]["ms"]
+        print(f"{name:10s} {n} - c_predict = {res[n]['over_predict_ms'] * 1e3:+.1f} us")
     del model
     torch.cuda.empty_cache()
     return res
@@ -119,6 +127,32 @@ def bench_kernel(dev):
     return res
 
 
+def bench_probs_kernel(dev):
+    from msa_amd import ops
+    heads, H = 12, 768
+    lens = [50] * 16 + [550] * 32
+    M = sum(lens)
+    layout = ops.SeqLayout(lens, heads, dev)
+    g = torch.Generator().manual_seed(1)
+    qkv = torch.randn(M, 3 * H, generator=g).to(torch.bfloat16).to(dev)
+    kb = ops.pad_key_bias(torch.zeros(M, device=dev), layout)
+    q_rows = layout.seq_start.to(torch.int32).contiguous()
+    out = torch.empty((len(lens), heads, max(lens)), device=dev, dtype=torch.float32)
+    fn = lambda: ops.attn_probs_first(qkv, kb, layout, H, q_rows, out=out)
+    for _ in range(10):
+        fn()
+    ts = sorted(timed(fn, 200) for _ in range(3))
+    ms = ts[1]
+    k_bytes, store = M * H * 2, out.numel() * 4
+    nbytes = k_bytes + store + len(lens) * H * 2 + M * 4 * heads              # K | probabilities | query rows | key bias per head
+    res = dict(ms=ms, spread_ms=ts[-1] - ts[0], bytes=nbytes, k_bytes=k_bytes, store_bytes=store, bytes_per_s=nbytes / (ms * 1e-3),
+               share_of_copy_bandwidth=nbytes / (ms * 1e-3) / COPY_BW)
+    print(f"attn_probs_first headline layout: {ms * 1e3:.1f} us (spread {res['spread_ms'] * 1e3:.1f} us), {k_bytes / 1e6:.1f} MB K read + "
+          f"{store / 1e6:.1f} MB store, {nbytes / 1e6:.1f} MB in all -> {res['bytes_per_s'] / 1e12:.2f} TB/s = "
+          f"{100 * res['share_of_copy_bandwidth']:.1f} % of the 6.3 TB/s of a long copy (bandwidth share)")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
@@ -134,6 +168,7 @@ def main():
         out["shapes"][name] = bench_shape(name, SHAPES[name], a.calls, a.rounds, dev)
     if a.kernel:
         out["attn_fwd_first"] = bench_kernel(dev)
+        out["attn_probs_first"] = bench_probs_kernel(dev)
     print(json.dumps(out))
 
 
