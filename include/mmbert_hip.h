@@ -226,6 +226,21 @@ int mmbert_ce_bwd(mmbert_stream_t stream, const void* logits, int ldv, int V, co
                   const int* seg_bounds, int nseg, const float* inv_count, const float* gscale, const float* row_lse, void* dlogits, int ldd,
                   const int* rows /* NULL: all M rows; else a row list: dlogits row j = gradient of row rows[j] */, int nrows,
                   int logits_f32 /* logits are fp32; dlogits stays bf16 */);
+/* ---- vocabulary top-k (masked-token prediction; a declared extension) ----
+ * For each of the M rows of logits [M, ldv] (bf16, or fp32 rounded to bf16 as loaded: identical outputs), over columns 0 .. V-1 only:
+ *   top_ids[i, j]     the j-th column in the total order "larger value first, on equal values the lower column first" (j < k);
+ *   top_logprob[i, j] = x[i, top_ids[i, j]] - row_lse[i];
+ *   row_lse[i]        = logsumexp(x[i, 0..V-1]) in mmbert_ce_fwd's arithmetic and order (bit-equal to its row_lse on a labelled row);
+ *   with labels (int64 [M]): for 0 <= label < V  label_logprob[i] = x[i, label] - row_lse[i] and
+ *   label_rank[i] = #{c < V : x_c > x_label} + #{c < label : x_c == x_label}  (0 <=> top_ids[i, 0] == label; < k <=> in the top k);
+ *   for any other label (-100, out of range) label_logprob = 0 and label_rank = -1 -- the row's top-k and row_lse are written all the same.
+ * One launch, one workgroup per row, one pass over the logits; no atomics, every output element written on every call, two calls give
+ * equal bits.  1 <= k <= min(8, V), V <= 32768, ldv % 8 == 0, ldv >= V, label_logprob / label_rank given iff labels: anything else
+ * returns -1 before a launch; M == 0 is a no-op.  NaN logits are out of contract (outputs then unspecified, accesses stay in bounds). */
+int mmbert_vocab_topk(mmbert_stream_t stream, const void* logits, int ldv, int V, int M, int logits_f32, int k,
+                      const int64_t* labels /* M, may be NULL */,
+                      int32_t* top_ids /* [M, k] */, float* top_logprob /* [M, k] */, float* row_lse /* [M] */,
+                      float* label_logprob /* [M], NULL iff labels NULL */, int32_t* label_rank /* [M], same */);
 /* Row maps of the valid-first packing (msa_amd/ops.py SplitLayout): inv[original row] = packed row, perm = the
  * inverse, from the per-sequence unmasked lengths.  mode 0: masked-out rows behind all others, in order; 1: ONE shared row per
  * sequence (inference); 2: left out (inv = rows_a).  rank (optional, from mmbert_prologue's row-set mode): the position of every

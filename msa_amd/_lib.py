@@ -54,6 +54,7 @@ SIGNATURES = {
     "mmbert_attn_dropout_mask": (I, [P, P, I, C.c_uint, I, U32, U32]),
     "mmbert_ce_fwd": (I, [P, P, I, I, P, I, P, I, P, P, P, I, P]),
     "mmbert_ce_bwd": (I, [P, P, I, I, P, I, P, I, P, P, P, P, I, P, I, I]),
+    "mmbert_vocab_topk": (I, [P, P, I, I, I, I, I, P, P, P, P, P, P]),
     "mmbert_active_rows": (I, [P, P, I, I, P, P]),
     "mmbert_prologue": (I, [P, I, P, P, P, P, P, P, P, I, P, I, P, I, P, P, P, P, P, P, P, P]),
     "mmbert_split_rows": (I, [P, P, P, P, P, P, I, I, I, P, P, P, P, P]),

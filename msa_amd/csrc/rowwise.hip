@@ -1334,6 +1334,192 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const void* __restrict__ lo
 }
 
 // --------------------------------------------------------------------------------------------
+// Vocabulary top-k (mmbert_vocab_topk): the k first columns of a logits row in the TOTAL order "larger value first, on equal values
+// the lower column first", their log-probabilities, the row's logsumexp and, with a label, its log-probability and its rank in that
+// order.  One workgroup per row, the row in registers as in ce_row_kernel; one pass over memory.
+//
+// The order as ONE unsigned compare: an element is the 32-bit word  key(value) << 16 | (0xFFFF - column)  with key() the usual
+// monotone map of the bf16 bits (positive: sign bit set; negative: value bits inverted; -0 is read as +0, which it equals).  A larger
+// word comes EARLIER, and no two columns share a word.  Pad columns (and register chunks past the row) carry the bits 0xFFFF, whose
+// key is 0: below every real value (-inf has key 0x007F), so they are never chosen and never counted -- the scans need no bounds test.
+// Round j takes the workgroup-wide largest word strictly below round j - 1's winner: no "taken" mask.  Every lane keeps its own best
+// candidate; after a round only the winner's lane has lost its candidate, so only that lane scans its 128 values again (every lane
+// scans once, for round 0 and the label's rank).  Lanes merge by xor shuffles, the four waves through LDS; no atomics.
+// The logsumexp is ce_row_kernel<0>'s arithmetic statement for statement (max, per-lane __expf sum over c then r, wave_sum, the four
+// waves in order): on a labelled row row_lse has the bits mmbert_ce_fwd writes.
+// --------------------------------------------------------------------------------------------
+typedef uint32_t vt_u32x4 __attribute__((ext_vector_type(4)));
+
+// bf16 bits in the HIGH half of h (low half zero) -> sortable key in the high half, low half zero
+__device__ __forceinline__ uint32_t vt_key(uint32_t h) {
+    const uint32_t neg = (uint32_t)((int32_t)h >> 31);
+    return h ^ ((neg & 0x7FFF0000u) | 0x80000000u);
+}
+__device__ __forceinline__ float vt_value(uint32_t word) {      // the value behind an order word
+    const uint32_t kk = word & 0xFFFF0000u;
+    return __builtin_bit_cast(float, (kk & 0x80000000u) ? (kk ^ 0x80000000u) : (kk ^ 0xFFFF0000u));
+}
+__device__ __forceinline__ uint32_t vt_wave_max(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    return v;
+}
+// a lane's largest order word strictly below `prev` (0: none); COUNT: also how many of its words lie above `lab_word`.
+// e - prev in unsigned arithmetic puts every word below prev above every word at or past it, the closest one highest: one subtraction
+// and one max per element.
+template <bool COUNT>
+__device__ __forceinline__ uint32_t vt_scan(const uint32_t (&e)[CE_MAXC * 8], uint32_t prev, uint32_t lab_word, int& above) {
+    uint32_t best = 0u;
+#pragma unroll
+    for (int n = 0; n < CE_MAXC * 8; ++n) {
+        best = max(best, e[n] - prev);
+        if (COUNT) above += e[n] > lab_word ? 1 : 0;
+    }
+    const uint32_t word = best + prev;
+    return word < prev ? word : 0u;
+}
+
+template <bool F32>
+__global__ __launch_bounds__(256) void vocab_topk_kernel(const void* __restrict__ logits_, int ldv, int V, int k, const int64_t* __restrict__ labels,
+                                                         int32_t* __restrict__ top_ids, float* __restrict__ top_logprob, float* __restrict__ row_lse,
+                                                         float* __restrict__ label_logprob, int32_t* __restrict__ label_rank) {
+    __shared__ float red[4];
+    __shared__ float lab_logit;
+    __shared__ int red_above[4];
+    __shared__ uint32_t red_word[2][4];
+    const int i = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int nchunk = (V + 7) >> 3;                           // <= CE_MAXC * 256; pad columns past the last of these are never loaded
+    const int64_t lab = labels ? labels[i] : -1;
+    const bool has_lab = lab >= 0 && lab < V;                  // workgroup-uniform
+    const int lab_chunk = has_lab ? (int)(lab >> 3) : -1;
+    bf16x8 v[CE_MAXC];
+    if constexpr (F32) {
+        const float* row = (const float*)logits_ + (size_t)i * ldv;
+#pragma unroll
+        for (int c = 0; c < CE_MAXC; ++c) {
+            const int ch = c * 256 + tid;
+            if (ch < nchunk) {
+                const float4 lo = *(const float4*)(row + ch * 8), hi = *(const float4*)(row + ch * 8 + 4);
+                v[c] = (bf16x8){f2bf(lo.x), f2bf(lo.y), f2bf(lo.z), f2bf(lo.w), f2bf(hi.x), f2bf(hi.y), f2bf(hi.z), f2bf(hi.w)};
+            }
+        }
+    } else {
+        const bf16_t* row = (const bf16_t*)logits_ + (size_t)i * ldv;
+#pragma unroll
+        for (int c = 0; c < CE_MAXC; ++c) {
+            const int ch = c * 256 + tid;
+            if (ch < nchunk) v[c] = *(const bf16x8*)(row + ch * 8);
+        }
+    }
+    // ---- logsumexp: ce_row_kernel<0>
+    float mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < CE_MAXC; ++c) {
+        const int ch = c * 256 + tid;
+        if (ch < nchunk) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) if (ch * 8 + r < V) mx = fmaxf(mx, bf2f(v[c][r]));
+        }
+    }
+    mx = wave_max(mx);
+    if (lane == 0) red[w] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float se = 0.f;
+    {
+        // the per-lane sum in ascending (c, r) order, as ce_row_kernel's is emitted: pinned, so that -ffast-math cannot re-associate it here
+#pragma clang fp reassociate(off)
+#pragma unroll
+        for (int c = 0; c < CE_MAXC; ++c) {
+            const int ch = c * 256 + tid;
+            if (ch < nchunk) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) if (ch * 8 + r < V) se += __expf(bf2f(v[c][r]) - mx);
+            }
+        }
+    }
+    if (lab_chunk >= 0) {                                       // (outside the sum's loop: nothing but the sum in the pinned block)
+#pragma unroll
+        for (int c = 0; c < CE_MAXC; ++c)
+            if (lab_chunk == c * 256 + tid) lab_logit = bf2f(v[c][lab & 7]);
+    }
+    se = wave_sum(se);
+    if (lane == 0) red[w] = se;
+    __syncthreads();
+    float lse = 0.f;
+    if (tid == 0) {
+        float tot;
+        {
+            // the four waves in ce_row_kernel's order: the library is built with -ffast-math, and left free the compiler pairs them here
+            // ((0 + 2) + (1 + 3) through one packed add), which moves the last bit of the lse on some rows
+#pragma clang fp reassociate(off)
+            tot = ((red[0] + red[1]) + red[2]) + red[3];
+        }
+        lse = mx + __logf(tot);
+        row_lse[i] = lse;
+    }
+    // ---- the row as order words: -0 -> +0, pad columns and absent chunks -> key 0
+    uint32_t e[CE_MAXC * 8];
+#pragma unroll
+    for (int c = 0; c < CE_MAXC; ++c) {
+        const int ch = c * 256 + tid;
+        const vt_u32x4 t = __builtin_bit_cast(vt_u32x4, v[c]);
+        const uint32_t low = 0xFFFFu - (uint32_t)(ch * 8);     // 0xFFFF - column of the chunk's first element (ch * 8 + 7 <= 32767 where ch < nchunk)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            uint32_t h0 = t[d] << 16, h1 = t[d] & 0xFFFF0000u;
+            const int col = ch * 8 + 2 * d;
+            if (h0 == 0x80000000u) h0 = 0u;
+            if (h1 == 0x80000000u) h1 = 0u;
+            if (ch >= nchunk || col >= V) h0 = 0xFFFF0000u;
+            if (ch >= nchunk || col + 1 >= V) h1 = 0xFFFF0000u;
+            e[c * 8 + 2 * d] = vt_key(h0) | ((low - (uint32_t)(2 * d)) & 0xFFFFu);
+            e[c * 8 + 2 * d + 1] = vt_key(h1) | ((low - (uint32_t)(2 * d + 1)) & 0xFFFFu);
+        }
+    }
+    // ---- every lane's first candidate, and the label's rank = the number of words above the label's own
+    uint32_t lab_word = 0u;
+    float lab_x = 0.f;
+    int above = 0;
+    uint32_t mine;
+    if (has_lab) {
+        lab_x = lab_logit;                                     // (written before the barrier above)
+        uint32_t hb = __builtin_bit_cast(uint32_t, lab_x);
+        if (hb == 0x80000000u) hb = 0u;
+        lab_word = vt_key(hb) | (0xFFFFu - (uint32_t)lab);
+        mine = vt_scan<true>(e, 0xFFFFFFFFu, lab_word, above);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o, 64);
+        if (lane == 0) red_above[w] = above;
+    } else {
+        mine = vt_scan<false>(e, 0xFFFFFFFFu, 0u, above);
+    }
+    // ---- k rounds
+    for (int j = 0; j < k; ++j) {
+        const uint32_t wm = vt_wave_max(mine);
+        if (lane == 0) red_word[j & 1][w] = wm;
+        __syncthreads();                                       // (round j + 2 rewrites this slot behind round j + 1's barrier)
+        const uint32_t win = max(max(red_word[j & 1][0], red_word[j & 1][1]), max(red_word[j & 1][2], red_word[j & 1][3]));
+        if (tid == 0) {
+            top_ids[(size_t)i * k + j] = (int32_t)(0xFFFFu - (win & 0xFFFFu));
+            top_logprob[(size_t)i * k + j] = vt_value(win) - lse;
+        }
+        if (j + 1 < k && mine == win) mine = vt_scan<false>(e, win, 0u, above);
+    }
+    if (tid == 0 && label_logprob) {
+        if (has_lab) {
+            label_logprob[i] = lab_x - lse;
+            label_rank[i] = red_above[0] + red_above[1] + red_above[2] + red_above[3];
+        } else {
+            label_logprob[i] = 0.f;
+            label_rank[i] = -1;
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------------------
 // Flat AdamW over the model's contiguous fp32 parameter / gradient / moment buffers.
 // flags[block of 256 elements]: 0 = no weight decay, 1 = weight decay, 2 = frozen (the
 // reference's never-differentiated parameters keep grad None and are skipped by the optimizer);
@@ -2225,6 +2411,22 @@ int mmbert_ce_fwd(hipStream_t stream, const void* logits, int ldv, int V, const 
         hipLaunchKernelGGL(ce_loss_sum_ordered_kernel, dim3(1), dim3(1024), 0, stream, (const float*)row_loss, M, seg_bounds, nseg, loss_sum);
         MMB_CHECK_LAUNCH();
     }
+    return 0;
+}
+
+int mmbert_vocab_topk(hipStream_t stream, const void* logits, int ldv, int V, int M, int logits_f32, int k, const int64_t* labels,
+                      int32_t* top_ids, float* top_logprob, float* row_lse, float* label_logprob, int32_t* label_rank) {
+    if (M < 0 || V < 1 || V > CE_MAXC * 256 * 8 || k < 1 || k > 8 || k > V || (ldv & 7) || ldv < V) return -1;
+    if (M == 0) return 0;                                          // (an empty tensor has no address)
+    if (!logits || !top_ids || !top_logprob || !row_lse) return -1;
+    if (labels ? (!label_logprob || !label_rank) : (label_logprob || label_rank)) return -1;
+    if (logits_f32)
+        hipLaunchKernelGGL(vocab_topk_kernel<true>, dim3(M), dim3(256), 0, stream, logits, ldv, V, k, labels, top_ids, top_logprob, row_lse,
+                           label_logprob, label_rank);
+    else
+        hipLaunchKernelGGL(vocab_topk_kernel<false>, dim3(M), dim3(256), 0, stream, logits, ldv, V, k, labels, top_ids, top_logprob, row_lse,
+                           label_logprob, label_rank);
+    MMB_CHECK_LAUNCH();
     return 0;
 }
 

@@ -751,7 +751,7 @@ def _trunk_static(plan, B, T, lens, joff, dev):
 class _Trunk:
     """What one _TrunkFn call works on (plain attributes; built by _encode)."""
     __slots__ = ("ids", "tts", "B", "T", "lens", "pair_info", "feats", "feat_versions", "plan", "layout", "split", "key_bias", "kv_len", "seed", "top_rows",
-                 "d_emb", "d_joint", "infer", "late_split", "compact", "J_pre", "predict", "attention")
+                 "d_emb", "d_joint", "infer", "late_split", "compact", "J_pre", "predict", "attention", "dense")
 
 
 class _TrunkFn(torch.autograd.Function):
@@ -774,7 +774,9 @@ class _TrunkFn(torch.autograd.Function):
         B, T, lens, plan, split = t.B, t.T, t.lens, t.plan, t.split
         bounds, tokens = plan["bounds"], plan["layout"].tokens
         dev = t.ids.device
-        keep = ctx.needs_input_grad[0]
+        # (a stateless inference call saves nothing for a backward pass: needs_input_grad stays set under no_grad, and the saved
+        # operands of every layer -- 5 GB at the headline shape -- would otherwise live to the end of the encoder)
+        keep = ctx.needs_input_grad[0] and not t.predict
         late = t.layout                                           # callable: the packing is decided after the embedding launches
         npass = len(lens)
         joint = [k for k in range(npass) if t.pair_info[k] is not None]
@@ -848,7 +850,7 @@ class _TrunkFn(torch.autograd.Function):
         if split is not None and not t.infer:
             y_out = (torch.zeros if dropped else torch.empty)((tokens, H), device=dev, dtype=torch.bfloat16)
             y_rows = split.perm32
-        if t.predict:
+        if t.predict and not t.dense:
             # label-free prediction: layers 0 .. L - 2 as always, the top layer for the [CLS] query of every sequence only; no [tokens, H]
             # un-packing -- the output is the compact [sequences, H] matrix of those rows, in the caller's sequence order
             kvl = None if split is not None else t.kv_len
@@ -865,7 +867,9 @@ class _TrunkFn(torch.autograd.Function):
                 below = probe if mode == "all" else None        # ("top": the top layer alone)
             y, _ = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, kvl, False, stop=cfg.num_hidden_layers - 1, train=False, probe=below)
             return _EncoderFn.run_top_first(top, y, layout, t.key_bias, kvl, q_rows, probe=probe)
-        y, saved = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, None if split is not None else t.kv_len, keep, y_out, y_rows)
+        # (predict_tokens(): every layer dense, in inference arithmetic whatever the module's mode is)
+        y, saved = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, None if split is not None else t.kv_len, keep, y_out, y_rows,
+                                          train=False if t.predict else None)
         if split is not None and t.infer:
             y = y.index_select(0, split.inv)                      # every masked-out row reads its sequence's representative
         ctx.top, ctx.t, ctx.saved, ctx.joff, ctx.early = top, t, saved, joff, early
@@ -1447,7 +1451,8 @@ class _GpuModelBase(nn.Module):
         on the current stream into buffers of its own (the alternating sets of ``async_prologue`` stay as they are), the leftovers of
         a train step are not touched and no trunk record is kept.  ``attention`` (with ``predict`` only) = (``"top"`` | ``"all"``, list):
         the list receives (layer index, fp32 [sequences, heads, longest sequence]) per probed layer -- the [CLS] queries' attention rows
-        (ops.attn_probs_first)."""
+        (ops.attn_probs_first).  ``predict="dense"`` (predict_tokens()): the same stateless inference call with EVERY layer run on every
+        row; Y is the [tokens, H] matrix in the caller's row order."""
         bert = self._bert()
         dev = passes[0]["ids"].device
         self._ensure_ready(dev)
@@ -1555,6 +1560,7 @@ class _GpuModelBase(nn.Module):
         t = _Trunk()
         t.compact = None
         t.predict = bool(predict)
+        t.dense = predict == "dense"
         t.attention = attention if predict else None
         t.ids, t.tts, t.B, t.T, t.lens, t.pair_info, t.plan = ids, tts, B, T, lens, pair_info, plan
         t.feats = [None if info is None else tuple(_pair_features(f, dev) for f in info[0]) for info in pair_info]
@@ -2120,6 +2126,9 @@ class MMBertForPretraining(_GpuModelBase):
         # and gradients are bit-identical either way (the CE kernels round fp32 logits to bf16 as they load them).  trainer.py
         # never reads the scores (``return_scores = False`` drops them altogether).
         self.scores_dtype = torch.bfloat16
+        # predict_tokens(): the selected rows go through the MLM head in chunks of at most this many rows, so that the [rows, Vpad] bf16
+        # logits never take more than token_chunk_rows * Vpad * 2 bytes (250 MB at the default and the 30 522-word vocabulary)
+        self.token_chunk_rows = 4096
         # heads through _HeadsFn (hand-written backward, csrc/heads.hip); False = the eager autograd form (_heads), in which
         # ap_loss / label_loss / nce and the relationship scores stay differentiable outputs
         self.fused_heads = os.environ.get("MMBERT_FUSED_HEADS", "1") != "0"
@@ -2501,6 +2510,106 @@ class MMBertForPretraining(_GpuModelBase):
                 extra["attention_mass"] = {n: attention_modality_mass(extra["attention"][n], lens[0]) for n in names[1:]}
         out = pred[0] if ncls else logits                         # the classes (what forward returns second); the raw logits on request
         return (out, extra) if (return_pooled or att is not None) else out
+
+    def predict_tokens(self, input_ids, token_type_ids, attention_mask, masked_labels=None, positions=None, top_k=5):
+        """DECLARED EXTENSION, not in the reference: what the masked-token (MLM) head predicts at chosen positions, WITHOUT the
+        [tokens, vocab] prediction scores.  The first three arguments are ``forward``'s.  Exactly one of (else ``ValueError``):
+          ``masked_labels``  ``forward``'s 3-tuple (text, text | visual, text | speech; -100 = no label).  The rows scored are exactly the
+                             rows ``forward``'s cross-entropy counts for these labels (a label in [0, vocab_size)), in the order of the
+                             token matrix (pass, sample, position: ``_stage_labels``' order); a label that is neither -100 nor a
+                             vocabulary index raises ``IndexError`` as in ``forward``;
+          ``positions``      a 3-tuple of bool masks [B, T], [B, T + V], [B, T + A]: those rows, unscored.
+        ``top_k``: 1 .. min(8, vocab_size).
+
+        Returns a dict: ``"text"`` / ``"visual"`` / ``"speech"`` -> dict(``index`` int64 [n_p, 2]: (sample, position) in the caller's order,
+        ascending by sample then position; ``top_ids`` int64 [n_p, k]: the k most probable tokens, most probable first, the lower id
+        first on equal scores; ``top_logprob`` fp32 [n_p, k]: their log-probabilities; with labels also ``label`` int64 [n_p],
+        ``label_logprob`` fp32 [n_p], ``label_rank`` int64 [n_p]: the number of tokens ranked before the label, 0 = predicted), and
+        ``"loss"`` fp32 [3] on the device: the per-pass mean of -label_logprob -- the three MLM losses ``forward`` computes and drops (0 for a
+        pass without labelled rows and in ``positions`` mode).
+
+        Inference arithmetic as in ``predict()``: no dropout, no autograd graph, ``self.training`` untouched, on the current stream;
+        nothing is taken from or left in the per-step state (dropout seed sequence, prologue buffers, pending gradients,
+        ``self.outputs``), so it can sit between two train steps.  The encoder runs in full, every layer dense (``_encode`` in its
+        inference form; a row-list attention for the top layer is not built).  Behind it, the n selected rows ONLY go through the
+        launches of the compact MLM head (``_MLMHeadFn.forward``): gather, transform GEMM + GELU, LayerNorm, the vocabulary GEMM to
+        [rows, Vpad] bf16, then ``ops.vocab_topk`` -- in chunks of at most ``self.token_chunk_rows`` rows, so the logits never exceed
+        chunk x Vpad x 2 bytes however many rows are selected.  n = 0: none of the head's launches, empty tensors of the same dtypes."""
+        if (masked_labels is None) == (positions is None):
+            raise ValueError("predict_tokens(): give exactly one of masked_labels and positions")
+        cfg = self.config
+        V = cfg.vocab_size
+        k = int(top_k)
+        if not 1 <= k <= min(8, V):
+            raise ValueError(f"predict_tokens(): top_k = {top_k!r}; expected 1 .. {min(8, V)}")
+        text_ids, visual, speech = input_ids[:3]
+        dev = text_ids.device
+        names = ("text", "visual", "speech")
+        with torch.no_grad():
+            self._ensure_ready(dev)
+            B, T = text_ids.shape
+            want = [T, T + visual.shape[1], T + speech.shape[1]]
+            parts = tuple(masked_labels if masked_labels is not None else positions)
+            if len(parts) != 3 or any(tuple(q.shape) != (B, S) for q, S in zip(parts, want)):
+                raise ValueError("predict_tokens(): masked_labels / positions must cover the text (+ pair) positions of every pass: "
+                                 f"[{B}, {want[0]}], [{B}, {want[1]}], [{B}, {want[2]}]")
+            # the order of the token matrix (pass, sample, position), staged on the current stream
+            flat = torch.cat([q.reshape(-1).to(dev) for q in parts])
+            if masked_labels is not None:
+                labels = flat.to(torch.long)
+                marks = labels
+            else:
+                labels = None
+                marks = torch.where(flat != 0, 0, -100).to(torch.long)             # a chosen row reads as "labelled" for the row list alone
+            rows = mlm_active_rows(marks, V)                            # the row list; its count travels while the encoder is queued
+            # ... and so do the three per-pass counts (the cuts of the row list): no device -> host read behind the head's launches
+            edges = [0, B * want[0], B * (want[0] + want[1]), B * sum(want)]
+            per_pass = torch.stack([((marks[edges[p]:edges[p + 1]] >= 0) & (marks[edges[p]:edges[p + 1]] < V)).sum() for p in range(3)])
+            cnt_host = torch.empty(3, dtype=torch.int64, pin_memory=True)
+            cnt_host.copy_(per_pass, non_blocking=True)
+            cnt_ev = torch.cuda.Event()
+            cnt_ev.record()
+            y, plan, lens = self._encode(self._three_passes(input_ids, token_type_ids, attention_mask), None, False, predict="dense")[:3]
+            n = _active_row_count(rows)                                 # (raises on a label outside the vocabulary)
+            sel32 = rows[0][:n]
+            sel = sel32.long()
+            w = self._w
+            chunk = max(1, int(self.token_chunk_rows))
+            outs = []
+            for a in range(0, n, chunk):
+                s_c = sel[a:a + chunk]
+                y_c = y.index_select(0, s_c)
+                t0_c = ops.gemm_nt(y_c, w["Wt"], bias=w["bt"], gelu=True)
+                t_c = ops.ln_fwd(t0_c, w["mlm_ln_g"], w["mlm_ln_b"], cfg.layer_norm_eps, stats=False)[0]
+                logits_c = ops.gemm_nt(t_c, w["word_h"], bias=w["pred_bias"])              # [rows, Vpad] bf16
+                outs.append(ops.vocab_topk(logits_c, V, k, None if labels is None else labels.index_select(0, s_c)))
+                del logits_c
+            nout = 3 if labels is None else 5
+            if len(outs) == 1:
+                cols = list(outs[0])
+            elif outs:
+                cols = [torch.cat([o[j] for o in outs]) for j in range(nout)]
+            else:
+                cols = [torch.empty((0, k), device=dev, dtype=torch.int32), torch.empty((0, k), device=dev, dtype=torch.float32),
+                        torch.empty(0, device=dev, dtype=torch.float32), torch.empty(0, device=dev, dtype=torch.float32),
+                        torch.empty(0, device=dev, dtype=torch.int32)][:nout]
+            cnt_ev.synchronize()                                        # (recorded in front of the encoder: long complete)
+            c = [int(x) for x in cnt_host]
+            cut = [0, c[0], c[0] + c[1], c[0] + c[1] + c[2]]           # the row list is in row order: pass by pass
+            res = {}
+            loss = torch.zeros(3, device=dev, dtype=torch.float32)
+            for p, name in enumerate(names):
+                lo, hi = cut[p], cut[p + 1]
+                r = sel[lo:hi] - plan["bounds"][p]
+                e = dict(index=torch.stack((torch.div(r, lens[p], rounding_mode="floor"), r % lens[p]), 1),
+                         top_ids=cols[0][lo:hi].long(), top_logprob=cols[1][lo:hi])
+                if labels is not None:
+                    e.update(label=labels.index_select(0, sel[lo:hi]), label_logprob=cols[3][lo:hi], label_rank=cols[4][lo:hi].long())
+                    if hi > lo:
+                        loss[p] = -cols[3][lo:hi].sum() / (hi - lo)
+                res[name] = e
+            res["loss"] = loss
+        return res
 
     def forward_fused(self, input_ids, token_type_ids, attention_mask, masked_labels, ap_label, sentiment):
         """DECLARED EXTENSION, not in the reference (SURVEY S8(d) mode ``fused1050``; BASELINE.json quotes its metric on a "fused

@@ -938,6 +938,32 @@ def ce_bwd(logits, V, labels, seg_bounds, nseg, inv, gscale, lse, dlogits, rows=
     return dlogits
 
 
+def vocab_topk(logits, V, k, labels=None):
+    """(top_ids int32 [M, k], top_logprob fp32 [M, k], row_lse fp32 [M][, label_logprob fp32 [M], label_rank int32 [M]]) of the rows
+    of ``logits`` [M, ldv] (bf16 or fp32) over columns 0 .. V-1, in the order "larger value first, lower column first on a tie"
+    (see mmbert_vocab_topk).  ``labels`` int64 [M]: rows with a label outside [0, V) get log-prob 0 and rank -1."""
+    lib = _lib.load()
+    assert logits.dim() == 2 and logits.dtype in (torch.bfloat16, torch.float32) and logits.stride(1) in (0, 1)
+    M, dev = logits.shape[0], logits.device
+    k = int(k)
+    # the kernel reads columns 0 .. V-1 of every row in 16-byte pieces: they must lie inside the tensor, and its first element on a 16-byte boundary
+    assert int(V) <= logits.shape[1], f"vocab_topk: V = {V} columns asked of a [{M}, {logits.shape[1]}] tensor"
+    assert M == 0 or logits.data_ptr() % 16 == 0, "vocab_topk: the logits must start on a 16-byte boundary (a column-offset view does not)"
+    top_ids = torch.empty((M, max(k, 0)), device=dev, dtype=torch.int32)
+    top_lp = torch.empty((M, max(k, 0)), device=dev, dtype=torch.float32)
+    lse = torch.empty(M, device=dev, dtype=torch.float32)
+    lab_lp = lab_rank = None
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.numel() == M and labels.is_contiguous()
+        lab_lp = torch.empty(M, device=dev, dtype=torch.float32)
+        lab_rank = torch.empty(M, device=dev, dtype=torch.int32)
+    ldv = logits.stride(0) if (M > 1 or logits.stride(0) >= logits.shape[1]) else logits.shape[1]     # (a one-row view may report any stride)
+    _lib.check(lib.mmbert_vocab_topk(_stream(), logits.data_ptr(), ldv, int(V), M,
+                                     1 if logits.dtype == torch.float32 else 0, k, _ptr(labels), top_ids.data_ptr(), top_lp.data_ptr(),
+                                     lse.data_ptr(), _ptr(lab_lp), _ptr(lab_rank)), "mmbert_vocab_topk")
+    return (top_ids, top_lp, lse) if labels is None else (top_ids, top_lp, lse, lab_lp, lab_rank)
+
+
 def active_rows(labels, V):
     """(idx int32 [M], count int32 [1]) on the device: rows with a label in [0, V), ascending (see mmbert_active_rows)."""
     lib = _lib.load()

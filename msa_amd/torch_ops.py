@@ -208,6 +208,7 @@ _lib.define("adamw_multi_tensor(Tensor(a!) p, Tensor(b!) g, Tensor(c!) m, Tensor
             "float beta2, float eps, float weight_decay, int step, float grad_scale=1.0, str mode='hf', bool zero_grad=True) -> ()")
 _lib.define("mlm_mask_rng(Tensor(a!) ids, float p, int seed, int[] special_ids, int mask_id=103) -> Tensor")
 _lib.define("grad_norm(Tensor g, Tensor segments, float max_norm, float norm_type=2.0, float grad_scale=1.0) -> Tensor")
+_lib.define("vocab_topk(Tensor logits, int vocab, int k, Tensor? labels=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 
 _DROP_SITE_EMB, _DROP_SITE_JOINT = 78, 79
 
@@ -319,10 +320,22 @@ def _mlm_mask(ids, p, seed, special_ids, mask_id=103):
     return ops.mlm_mask(ids, float(p), int(seed), special_ids=tuple(special_ids), mask_id=int(mask_id))
 
 
+def _vocab_topk(logits, vocab, k, labels=None):
+    """Masked-token prediction over the rows of logits [M, ld >= vocab] (bf16 or fp32, row stride a multiple of 8): (top_ids int32 [M, k],
+    top_logprob [M, k], row_lse [M], label_logprob [M], label_rank int32 [M]) in the order "larger value first, lower column first on a
+    tie"; the last two are empty without ``labels`` (int64 [M]; a label outside [0, vocab) gives log-prob 0 and rank -1)."""
+    lg = logits if logits.dtype in (torch.bfloat16, torch.float32) else _bf(logits)
+    lg = lg if lg.stride(-1) == 1 else lg.contiguous()
+    if labels is None:
+        ids, lp, lse = ops.vocab_topk(lg, int(vocab), int(k))
+        return ids, lp, lse, lse.new_empty(0), ids.new_empty(0)
+    return ops.vocab_topk(lg, int(vocab), int(k), labels.long().contiguous())
+
+
 for _name, _fn in (("embed_ln", _emb), ("embed_ln_fwd", _emb_fwd), ("embed_ln_bwd", _emb_bwd), ("joint_embed", _joint),
                    ("joint_embed_fwd", _joint_fwd), ("joint_embed_bwd", _joint_bwd), ("mlm_head_ce", _ce), ("mlm_head_ce_fwd", _ce_fwd),
                    ("mlm_head_ce_bwd", _ce_bwd), ("adamw_multi_tensor", _adamw), ("mlm_mask_rng", _mlm_mask),
-                   ("grad_norm", _grad_norm)):
+                   ("grad_norm", _grad_norm), ("vocab_topk", _vocab_topk)):
     _lib.impl(_name, _fn, "CUDA")
 
 

@@ -371,6 +371,45 @@ def _predict_epoch_attention(args, model, data, device, batches, return_attentio
     return preds, dict(attention=cat(att), attention_mass=cat(mass), attention_layers=list(layers))
 
 
+def mlm_eval_epoch(args, model, data, tokenizer=None, *, device="cuda", generator=None, batches=None, top_k=5):
+    """Masked-token quality per modality pass -- what ``eval_epoch`` cannot report (``forward`` returns ``None`` for the three MLM
+    losses): ``model.predict_tokens`` over ``data`` in SEQUENTIAL order, the batches from ``pack_step_inputs`` (masked like
+    ``eval_epoch``'s when ``args.mlm``; every position labelled with its own id when not, as the reference packs them), or pass
+    ``batches`` = an iterable of model-kwargs dicts (``input_ids`` / ``token_type_ids`` / ``attention_mask`` / ``masked_labels``).
+    Returns {"text" | "visual" | "speech": dict(count = labelled positions, loss = token-weighted mean negative log-likelihood over the
+    epoch, perplexity = exp(loss), top1 / topk = share of positions whose label is the first / among the first ``top_k`` predictions,
+    mrr = mean of 1 / (rank + 1))}; a pass without labelled positions (an empty dataset: every pass) gives zeros and count = 0.  The
+    sums stay on the device: one device->host transfer at the end.  Leaves ``model.training`` as it found it."""
+    import math
+    names = ("text", "visual", "speech")
+    if batches is None:
+        from torch.utils.data import DataLoader, SequentialSampler
+        loader = DataLoader(data, sampler=SequentialSampler(data), batch_size=args.val_batch_size, collate_fn=collate)
+        batches = (pack_step_inputs(b, args, device, generator) for b in loader)
+    k = int(top_k)
+    acc = None                                                     # [3, 5] float64: count, sum of -log p, rank = 0, rank < k, sum of 1 / (rank + 1)
+    for kw in batches:
+        res = model.predict_tokens(kw["input_ids"], kw["token_type_ids"], kw["attention_mask"], masked_labels=kw["masked_labels"], top_k=k)
+        rows = []
+        for n in names:
+            rank = res[n]["label_rank"].to(torch.float64)
+            nll = -res[n]["label_logprob"].to(torch.float64)
+            rows.append(torch.stack((rank.new_tensor(float(rank.numel())), nll.sum(), (rank == 0).sum().to(torch.float64),
+                                     (rank < k).sum().to(torch.float64), (1.0 / (rank + 1.0)).sum())))
+        rows = torch.stack(rows)
+        acc = rows if acc is None else acc + rows
+    out = {}
+    host = None if acc is None else acc.cpu().tolist()
+    for p, n in enumerate(names):
+        cnt, nll, top1, topk, mrr = host[p] if host is not None else (0.0,) * 5
+        if cnt == 0:
+            out[n] = dict(count=0, loss=0.0, perplexity=0.0, top1=0.0, topk=0.0, mrr=0.0)
+            continue
+        loss = nll / cnt
+        out[n] = dict(count=int(cnt), loss=loss, perplexity=math.exp(min(loss, 700.0)), top1=top1 / cnt, topk=topk / cnt, mrr=mrr / cnt)
+    return out
+
+
 def _weighted_f1(y_true, y_pred):
     """F1 per class weighted by the class's support in ``y_true`` (sklearn ``f1_score(average="weighted")``)."""
     import numpy as np

@@ -16,6 +16,12 @@ plus the peak allocation of each above the level before the call (torch.cuda.max
 around 200 launches) and the bytes it reads (K and V of every row once, one query row and the key bias per (sequence, head)) over
 that time, as a share of the 6.3 TB/s a long copy reaches (a bandwidth share: the kernel has no MFMA work); and the same for
 ops.attn_probs_first, whose counted bytes are the K read, the fp32 [sequences, heads, 550] store, the query rows and the key bias.
+``--tokens``: masked-token prediction at ``headline`` and ``refdef32`` (15 % masking, the batch's own labels), same timing rules:
+  (ta) the route without predict_tokens: (a) with return_scores = True, then log_softmax + torch.topk(5) + the labels' log-probabilities on
+       the labelled rows of the three score tensors
+  (tb) model.predict_tokens on the same labels
+``--topk-kernel``: ops.vocab_topk (k = 1, 5, 8, with labels) against ops.ce_fwd on the same [n, Vpad] bf16 logits (V = 30 522), n = the
+headline batch's labelled rows and n = 4096 (one full chunk of predict_tokens); device events around 200 launches, median of 3.
 The last line of the output is one JSON object with every number."""
 import argparse
 import json
@@ -153,12 +159,85 @@ def bench_probs_kernel(dev):
     return res
 
 
+def bench_tokens(name, s, calls, rounds, dev):
+    torch.manual_seed(0)
+    model = MMBertForPretraining(MMBertConfig(vocab_size=s["V"], hidden_size=s["H"], num_hidden_layers=s["L"], num_attention_heads=s["heads"],
+                                              intermediate_size=s["I"]))
+    model.bert.set_joint_embeddings("mosei")
+    model.set_alpha_beta(1.0, 1.0)
+    model.to(dev).eval()
+    batch = batch_to(synthetic_batch(s["B"], s["T"], s["Pv"], s["Pa"], vocab=s["V"], seed=50), dev)
+    args3 = (batch["input_ids"], batch["token_type_ids"], batch["attention_mask"])
+    labels = batch["masked_labels"]
+    masks = [(l >= 0) & (l < s["V"]) for l in labels]
+    n = int(sum(int(m.sum()) for m in masks))
+    tokens = sum(l.numel() for l in labels)
+
+    def today():
+        model.return_scores = True
+        with torch.no_grad():
+            out = model(**batch)[0]
+            res = []
+            for p, k in enumerate((7, 9, 11)):
+                lp = torch.log_softmax(out[k][masks[p]].float(), -1)
+                res.append((torch.topk(lp, 5, dim=-1), lp.gather(1, labels[p][masks[p]][:, None])))
+        return res
+    legs = [("ta_forward_scores_topk", today), ("tb_predict_tokens", lambda: model.predict_tokens(*args3, masked_labels=labels, top_k=5))]
+    for _, fn in legs:
+        for _ in range(3):
+            fn()
+    times = {k: [] for k, _ in legs}
+    for r in range(rounds):
+        for k, fn in (legs if r % 2 == 0 else legs[::-1]):
+            fn()
+            times[k].append(timed(fn, calls))
+    res = dict(labelled_rows=n, tokens=tokens)
+    for k, fn in legs:
+        t = sorted(times[k])
+        res[k] = dict(ms=t[len(t) // 2], spread_ms=t[-1] - t[0], peak_bytes=peak_of(fn))
+        print(f"{name:10s} {k:24s} {res[k]['ms']:9.3f} ms/call  spread {res[k]['spread_ms']:.3f} ms  peak {res[k]['peak_bytes'] / 2 ** 20:9.1f} MiB")
+    res["tb_over_ta"] = res["tb_predict_tokens"]["ms"] / res["ta_forward_scores_topk"]["ms"]
+    print(f"{name:10s} {n} labelled rows of {tokens}: predict_tokens / (forward + topk) = {res['tb_over_ta']:.4f} in time, "
+          f"{res['tb_predict_tokens']['peak_bytes'] / max(1, res['ta_forward_scores_topk']['peak_bytes']):.4f} in peak memory")
+    del model
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_topk_kernel(dev, rows):
+    from msa_amd import ops
+    V, Vp = 30522, 30528
+    out = {}
+    for n in rows:
+        g = torch.Generator().manual_seed(n)
+        logits = (3.0 * torch.randn(n, Vp, generator=g)).to(torch.bfloat16).to(dev)
+        labels = torch.randint(0, V, (n,), generator=g).to(dev)
+        bounds = torch.tensor([0, n], dtype=torch.int32, device=dev)
+        legs = [("ce_fwd", lambda: ops.ce_fwd(logits, V, labels, bounds, 1))] + \
+               [(f"vocab_topk_k{k}", (lambda k=k: ops.vocab_topk(logits, V, k, labels))) for k in (1, 5, 8)]
+        r = {}
+        for name, fn in legs:
+            for _ in range(10):
+                fn()
+            ts = sorted(timed(fn, 200) for _ in range(3))
+            r[name] = dict(us=ts[1] * 1e3, spread_us=(ts[-1] - ts[0]) * 1e3, tb_per_s=n * Vp * 2 / (ts[1] * 1e-3) / 1e12)
+        for k in (1, 5, 8):
+            r[f"vocab_topk_k{k}"]["over_ce_fwd"] = r[f"vocab_topk_k{k}"]["us"] / r["ce_fwd"]["us"]
+        for name, _ in legs:
+            print(f"n = {n:5d}  {name:16s} {r[name]['us']:8.1f} us (spread {r[name]['spread_us']:.1f})  {r[name]['tb_per_s']:.2f} TB/s of logits read"
+                  + (f"  x{r[name]['over_ce_fwd']:.2f} of ce_fwd" if "over_ce_fwd" in r[name] else ""))
+        out[str(n)] = r
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--shapes", default="headline,refdef32,refdef256")
     ap.add_argument("--kernel", action="store_true")
+    ap.add_argument("--tokens", action="store_true")
+    ap.add_argument("--topk-kernel", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_predict.py needs the GPU: there is no CPU path and no number to report without one")
@@ -169,6 +248,11 @@ def main():
     if a.kernel:
         out["attn_fwd_first"] = bench_kernel(dev)
         out["attn_probs_first"] = bench_probs_kernel(dev)
+    if a.tokens:
+        out["tokens"] = {name: bench_tokens(name, SHAPES[name], a.calls, a.rounds, dev) for name in ("headline", "refdef32")}
+    if a.topk_kernel:
+        rows = [out["tokens"]["headline"]["labelled_rows"]] if a.tokens else [360]
+        out["vocab_topk"] = bench_topk_kernel(dev, rows + [4096])
     print(json.dumps(out))
 
 
