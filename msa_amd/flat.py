@@ -12,6 +12,11 @@ have pre-transposed bf16 copies (``halfT``) so that input gradients are NT GEMMs
 
 ``nn.Parameter.data`` / ``.grad`` are views into these buffers, so ``state_dict()``,
 ``load_state_dict()``, ``named_parameters()`` keep the reference's names and shapes.
+What torch code may do to them and still be seen (tests/test_flat_semantics_gpu.py): in-place edits that bump a parameter's version
+counter (``load_state_dict``, ``nn.init.*``, ``with torch.no_grad(): p.mul_()``, ``p.detach().add_()``, a foreign optimizer) are picked up
+by the next forward; writes through ``p.data`` and re-pointed parameters after ``model.parameters_changed()``; a ``.grad`` set to None
+(``zero_grad(set_to_none=True)``, any subset) is a dropped gradient (reconcile_grads).  Not covered: a ``.grad`` replaced by a tensor of
+the caller's, ``requires_grad_(False)``.  The storage is never copied or pickled: a copy of the model re-flattens on its first use.
 The layout order follows the order in which backward finishes gradients (heads, layer L-1..0,
 embeddings; the tied word embedding last) so buckets can be reduced while backward still runs.
 """
@@ -50,7 +55,15 @@ def grad_segments(offset: Dict[str, int], numel: Dict[str, int], names, exclude=
     return segs
 
 
+def _no_storage():
+    return None
+
+
 class FlatParams:
+    def __reduce__(self):
+        """Never copied or pickled (``p._mmb_flat`` travels with a pickled Parameter): the copy reads None and the model re-flattens."""
+        return (_no_storage, ())
+
     def __init__(self, model: torch.nn.Module, cfg, device):
         self.device = device
         H, L, I, V = cfg.hidden_size, cfg.num_hidden_layers, cfg.intermediate_size, cfg.vocab_size
@@ -173,6 +186,8 @@ class FlatParams:
         self.lazy: Dict[int, Tuple[torch.Tensor, List[str]]] = {}
         self.stale: set = set()
         self.lazy_detached = False
+        self._detached: frozenset = frozenset()     # the names detach_lazy() set to None (reconcile_grads: not a caller's drop)
+        self._reconciled_task = -1                  # the backward pass (autograd graph task) reconcile_in_backward() last ran in
         # the factor the optimizer applies to ``grads`` (1 / world under parallel.DataParallel, which sets it): the torch-semantics
         # clip (optim.clip_grad_norm_) measures the gradient the step will apply, the mean over ranks
         self.grad_scale = 1.0
@@ -234,6 +249,7 @@ class FlatParams:
         for i in self.stale:
             for n in self.lazy[i][1]:
                 self.named[n].grad = None
+        self._detached = frozenset(n for i in self.stale for n in self.lazy[i][1])
         self.lazy_detached = True
 
     def attach_lazy(self):
@@ -336,22 +352,60 @@ class FlatParams:
         if self._param_versions() != self._version:
             self.refresh()
 
+    def owns_all(self) -> bool:
+        """Every parameter's ``.data`` is still the view into ``params`` (owns() looks at three)."""
+        base = self.params.data_ptr()
+        return all(p.data_ptr() == base + 4 * self.offset[n] for n, p in self.named.items())
+
     def owns(self, model: torch.nn.Module) -> bool:
-        """Cheap per-forward check (three sentinel parameters) that the module's parameters still
-        alias this storage; re-attaches ``.grad`` views dropped by ``zero_grad(set_to_none=True)``."""
+        """Cheap per-forward check (three sentinel parameters) that the module's parameters still alias this storage; gradients the
+        caller dropped since the last look are settled (reconcile_grads)."""
         if not hasattr(self, "_sentinels"):
-            lazy_names = {n for _, names in self.lazy.values() for n in names}          # (their .grad is None between zero_grad and backward)
+            lazy_names = {n for _, names in self.lazy.values() for n in names}
             cand = [n for n in self.order if n not in lazy_names]
             self._sentinels = (cand[0], cand[len(cand) // 2], cand[-1])
-        sentinels = self._sentinels
-        for n in sentinels:
+        for n in self._sentinels:
             p = self.named[n]
             if p.data_ptr() != self.params.data_ptr() + 4 * self.offset[n]:
                 return False
-        if any(self.named[n].grad is None for n in sentinels):
-            for n, p in self.named.items():
-                o = self.offset[n]
-                if p.grad is None or p.grad.data_ptr() != self.grads.data_ptr() + 4 * o:
-                    p.grad = self.grads[o:o + self.numel[n]].view(p.shape)
-            self.lazy_detached = False
+        self.reconcile_grads()
         return True
+
+    def _attach(self, n: str):
+        p, o = self.named[n], self.offset[n]
+        p.grad = self.grads[o:o + self.numel[n]].view(p.shape)
+
+    def reconcile_in_backward(self):
+        """reconcile_grads() once per backward pass, from whichever of the model's gradient stages runs first (before its launches)."""
+        task = torch._C._current_graph_task_id()
+        if task != self._reconciled_task:
+            self._reconciled_task = task
+            self.reconcile_grads()
+
+    def reconcile_grads(self):
+        """A ``.grad`` the caller set to None (``zero_grad(set_to_none=True)`` of the module or of a foreign optimizer, ``p.grad = None``;
+        any subset of the parameters) is a DROPPED gradient: its part of ``grads`` is zero-filled and the view attached again, so the next
+        backward, clip or optimizer step starts from zero there, while the gradients left alone keep accumulating.  The names
+        detach_lazy() itself set to None are not a caller's drop (their buffer is stale: the next backward overwrites it).  Runs at every
+        forward (owns), at the first gradient stage of every backward pass (a drop between forward and backward) and at every optimizer
+        call: one scan of ``p.grad is None`` on the host; everything dropped = one fill of the buffer."""
+        named = self.named
+        none = [n for n, p in named.items() if p.grad is None]
+        if not none:
+            return
+        ours = self._detached if self.lazy_detached else ()
+        dropped = [n for n in none if n not in ours]
+        if not dropped:
+            return
+        self.join_side_writers()             # (a backward that raised may still have launches adding into the gradients filled here)
+        if len(none) == len(named):
+            self.grads.zero_()
+            self.stale.clear()
+            self.grads_dirty = False
+            dropped, self.lazy_detached = none, False
+        else:
+            for n in dropped:
+                o = self.offset[n]
+                self.grads[o:o + self.numel[n]].zero_()
+        for n in dropped:
+            self._attach(n)

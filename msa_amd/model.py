@@ -96,6 +96,24 @@ def _make_bert_holder(cfg) -> nn.Module:
     return bert
 
 
+# What a module holds for the step at hand or as a cache over the flat storage -- streams, events, side-stream joins, workspaces, views,
+# the storage itself, the last outputs (autograd graph included) -- and the weak reference to the model around it: none of it goes into a
+# copy.deepcopy() / pickle of the module (``__getstate__``).  The copy re-flattens on its first use; MMBertForPretraining.__setstate__
+# points the ``_owner`` references of its parts at the copy.
+_RUNTIME_STATE = ("_flat", "_lw", "_w", "_plans", "_lnd", "_input_stream", "_input_stream_batch", "_wgrad_join", "_heads_join",
+                  "_late_wgrads", "_row_inverse", "_pro_calls", "_pro_marks", "_pro_bufs", "_last_valid_dev", "_deferred_embed_rows",
+                  "_private_top", "outputs")
+
+
+def _copyable_state(module: nn.Module) -> dict:
+    state = module.__dict__.copy()
+    for k in _RUNTIME_STATE:
+        state.pop(k, None)
+    if "_owner" in state:
+        state["_owner"] = None
+    return state
+
+
 def _hf_init(module: nn.Module, std: float, skip: Optional[nn.Module] = None):
     """HF ``_init_weights``: N(0, std) Linear/Embedding weights, zero biases, LayerNorm (1, 0),
     zero padding row -- what ``init_weights()`` does at REF:MMBertForPretraining.py:22,347.  ``skip``: a submodule whose
@@ -157,6 +175,9 @@ class JointEmbeddings(nn.Module):
         self.dropout = nn.Dropout(dropout_prob)
         self._owner = None
 
+    def __getstate__(self):
+        return _copyable_state(self)
+
     def which(self, pair_ids) -> str:
         d = pair_ids.size()[-1]
         if d == self.VISUALDIM:
@@ -206,6 +227,7 @@ class _JointFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx):
+        ctx.top._flat.reconcile_in_backward()
         j0, mean, rstd, *feats = ctx.saved_tensors
         w, B, T = ctx.top._w, ctx.B, ctx.T
         H = j0.shape[1]
@@ -497,6 +519,7 @@ class _EncoderFn:
         over by the MLM head (no dense [tokens, H] gradient exists then; ``dy`` is ignored).  Returns dx for the leading rows_a rows."""
         H = top.config.hidden_size
         L = top.config.num_hidden_layers
+        top._flat.reconcile_in_backward()
         top._flat.grads_dirty = True
         top._flat.attach_lazy()
         top._flat.wait_transposes()                               # (the optimizer's transposed-copy launch runs on a side stream)
@@ -880,6 +903,7 @@ class _TrunkFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         top, t = ctx.top, ctx.t
+        top._flat.reconcile_in_backward()
         cfg, w = top.config, top._w
         H = cfg.hidden_size
         e0, mean0, rstd0, J, *js = ctx.saved_tensors
@@ -1171,6 +1195,7 @@ class _MLMHeadFn(torch.autograd.Function):
         V = ctx.top.config.vocab_size
         if dloss is None:
             return None
+        ctx.top._flat.reconcile_in_backward()                     # (gradients the caller set to None since the forward pass: dropped)
         ctx.top._flat.grads_dirty = True
         ctx.top._flat.attach_lazy()
         ctx.top._flat.wait_transposes()                           # (the optimizer's transposed-copy launch runs on a side stream)
@@ -1233,6 +1258,11 @@ class _GpuModelBase(nn.Module):
         # tests only: a dict here collects, per _encode() call, "emb" (text embeddings of all passes), "x" (encoder input) and
         # "layers" (every encoder layer's output), all [tokens, H] bf16 in the ORIGINAL packed row order (pass, sample, position)
         self.debug_hidden = None
+
+    def __getstate__(self):
+        state = _copyable_state(self)
+        state["_flat"], state["_plans"] = None, {}
+        return state
 
     def _shared_lnd(self):
         """The one ``ops.LnDeferred`` collector of a backward pass (MLM head -> trunk: see ``_TrunkFn.backward``)."""
@@ -1782,6 +1812,9 @@ class MMBertPreTrainingHeads(nn.Module):
         self.align = nn.Linear(H, 2)
         self._owner = None
 
+    def __getstate__(self):
+        return _copyable_state(self)
+
     def forward(self, sequence_output, pooled_output, joint=False):
         top = self._owner()
         B, S, H = sequence_output.shape
@@ -1953,6 +1986,7 @@ class _HeadsStepFn(torch.autograd.Function):
         if d is None:
             return None, None, None, None, None, None, None
         top, a, B, H = ctx.top, ctx.a, ctx.B, ctx.H
+        top._flat.reconcile_in_backward()                         # (the first gradient stage of the pass: .grad set to None since the forward pass)
         dev = d.device
         d1 = d.reshape(1).float().contiguous()
         dfirst = torch.empty((3 * B, H), device=dev, dtype=torch.float32)
@@ -2045,6 +2079,7 @@ class _HeadsFn(torch.autograd.Function):
             return None, None, None, None, None
         first, P, Apre, g, Cc, T, seeds = ctx.saved_tensors
         top, B = ctx.top, ctx.B
+        top._flat.reconcile_in_backward()
         H = P.shape[1]
         pool, al, at = top.bert.pooler.dense, top.cls.align, top.attn
         vs3 = (top.vt, top.vv, top.vs)
@@ -2248,7 +2283,8 @@ class MMBertForPretraining(_GpuModelBase):
         (REF:train.py:70-72, after ``from_pretrained``): ``classifier1_2`` is re-created (HF initialisation, ``config.initializer_range``)
         when its width has to change -- one output for 1 / 7, C outputs for a class count C in 2 .. 16 --, on the device and in the dtype
         of the old layer, and the flat parameter / gradient buffers are dropped (rebuilt on the next use).  Call it BEFORE the optimizer is
-        built: an optimizer holds the old layer's parameters and the old flat buffers.  State-dict key names do not change."""
+        built: an optimizer holds the old layer's parameters and the old flat buffers, and raises at its next call once they are rebuilt
+        (optim.AdamW._check_current).  State-dict key names do not change."""
         n = self._check_num_labels(n)
         width = 1 if n in (1, 7) else n
         old = self.classifier1_2
@@ -2261,8 +2297,35 @@ class MMBertForPretraining(_GpuModelBase):
         return self
 
     def _apply(self, fn, *a, **k):
-        self._flat = None                       # .cuda()/.to() re-creates parameter storage: re-flatten lazily
+        # .cuda()/.to() re-creates parameter storage: re-flatten lazily.  (Also when nothing moves: the next use then builds a NEW storage,
+        # and an optimizer bound to the old one raises at its next call -- optim.AdamW._check_current.)
+        self._flat = None
         return super()._apply(fn, *a, **k)
+
+    def __setstate__(self, state):
+        """A copy (copy.deepcopy, torch.load of the whole module) arrives without runtime state (_RUNTIME_STATE): its parts point at it."""
+        import weakref
+        super().__setstate__(state)
+        ref = weakref.ref(self)
+        self.bert._owner = self.cls._owner = ref
+        if hasattr(self.bert, "jointEmbeddings"):
+            self.bert.jointEmbeddings._owner = ref
+
+    def parameters_changed(self):
+        """Tell the model that parameter VALUES were written in a way torch does not report.  In-place tensor operations on a parameter
+        (``load_state_dict``, ``nn.init.*``, ``with torch.no_grad(): p.copy_() / p.mul_()``, ``p.detach().add_()``, a torch optimizer)
+        bump its version counter and are picked up by the next forward on their own; writes through ``p.data`` (``p.data.copy_(w)``,
+        ``p.data.normal_()``: HF-style ``_init_weights``, EMA / SWA weight swaps) and a re-pointed ``p.data = w`` are not -- call this after
+        them.  While every parameter still views the flat storage, the bf16 working copy and the transposed copies are refreshed from
+        the fp32 masters (also right after an optimizer step); otherwise the storage is dropped and the next use builds a new one from the
+        parameters as they are -- an optimizer bound to the old storage then raises at its next call: build it again."""
+        f = self._flat
+        if f is None:
+            return
+        if f.owns_all():
+            f.refresh()
+        else:
+            self._flat = None
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         sd = {k: v for k, v in state_dict.items() if not k.endswith("embeddings.position_ids")}   # transformers-4.x buffer

@@ -112,15 +112,14 @@ class AdamW:
         for g in self.param_groups:
             for p in g["params"]:
                 ref = getattr(p, "_mmb_flat", None)
-                if ref is None:
+                if ref is None or ref[0] is None:
                     raise RuntimeError("AdamW: parameter is not backed by msa_amd flat storage -- run one forward "
                                        "pass (or model._ensure_ready) on the GPU before the first optimizer step")
                 if flat is None:
                     flat = ref[0]
                 elif ref[0] is not flat:
                     raise RuntimeError("AdamW: parameters belong to different flat storages")
-        if not flat.owns_any():
-            raise RuntimeError("AdamW: the model was re-materialised (e.g. moved) after this storage was created")
+        self._check_current(flat)
         if len(self.param_groups) > ops.ADAMW_MAX_GROUPS:
             raise NotImplementedError(f"AdamW: {len(self.param_groups)} param groups, the fused step takes at most {ops.ADAMW_MAX_GROUPS}: "
                                       "merge the groups that share lr, betas, eps and weight_decay")
@@ -130,6 +129,15 @@ class AdamW:
         self._flat = flat
         self._names = [flat.name_at(p._mmb_flat[1]) for g in self.param_groups for p in g["params"]]
         self._build_flags()
+
+    @staticmethod
+    def _check_current(flat):
+        """Raises when the model's parameters no longer view ``flat`` -- the model built a new storage since (``.to()`` / ``.cuda()`` /
+        ``.float()``, ``set_num_labels``, ``parameters_changed()`` after a re-pointed parameter): a step would update buffers that nothing
+        reads any more.  One pointer comparison, at every optimizer call, before anything is launched: build a new optimizer then."""
+        if not flat.owns_any():
+            raise RuntimeError("AdamW: the model was re-materialised (e.g. moved) after this storage was created: its parameters "
+                               "live in a new flat storage -- build the optimizer again")
 
     def _build_maps(self, flat):
         """The kernel's per-block maps: flags (decay bit from each group's weight_decay > 0; blocks this optimizer does not step are
@@ -179,7 +187,9 @@ class AdamW:
         if self._flat is None:
             self._bind()
         flat = self._flat
+        self._check_current(flat)
         flat.join_side_writers()             # (see step(): nothing may still add into the gradients read here)
+        flat.reconcile_grads()               # a .grad the caller set to None counts as zero
         flat.settle()                        # a dropped lazy gradient counts as zero
         segs, nseg = flat.segments(self._names, FROZEN)
         out = ops.grad_norm(flat.grads, segs, nseg, max_norm=max_norm, norm_type=norm_type, gscale=self.grad_scale,
@@ -191,6 +201,7 @@ class AdamW:
         hyper = self._hyper()
         if self._flat is None:
             self._bind()
+        self._check_current(self._flat)
         if tuple(h[4] > 0 for h in hyper) != self._decay:
             self._build_maps(self._flat)     # a group's weight_decay turned on or off since the flags were built
             self._build_flags()
@@ -205,6 +216,7 @@ class AdamW:
         self._steps += 1
         flat.join_side_writers()             # (left by a backward that raised: nothing may still add into the gradients the kernel reads and zeroes)
         flat.wait_transposes()               # (a step without a backward in between: the last step's transposed copies still read the bf16 copy)
+        flat.reconcile_grads()               # a .grad the caller set to None counts as zero
         flat.settle()                        # a lazy gradient no backward has written since the last step counts as zero
         flat.attach_lazy()
         clip, self._clip = self._clip, None
@@ -238,6 +250,7 @@ class AdamW:
                     if p.grad is not None:
                         p.grad.zero_()
             return
+        self._check_current(flat)
         flat.join_side_writers()             # (left by a backward that raised: see step())
         if flat.grads_dirty:                 # step() already zeroed the buffer in the same kernel
             flat.grads.zero_()
@@ -308,7 +321,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     flat, names = None, []
     for p in params:
         ref = getattr(p, "_mmb_flat", None)
-        if ref is None or (flat is not None and ref[0] is not flat):
+        if ref is None or ref[0] is None or (flat is not None and ref[0] is not flat):
             flat = None
             break
         flat = ref[0]

@@ -54,7 +54,7 @@ def _load(m, c):
         for n, t in c.params.items():
             assert params[n].shape == t.shape, n
             params[n].copy_(t.to(DEV))
-    m._flat.maybe_refresh()
+    m.parameters_changed()
     g = m._flat.grads
     g.copy_(torch.randn(g.numel(), generator=torch.Generator().manual_seed(c.B * 7 + c.H)).to(DEV))
     outside = torch.ones(g.numel(), dtype=torch.bool, device=DEV)
@@ -175,7 +175,7 @@ def _scaled_head(m, seed):
         for n, q in m.named_parameters():
             if n in HR.PARAMS or n in HR.FWD_ONLY:
                 q.copy_((torch.randn(q.shape, generator=g) * ((1.0 if q.dim() > 1 else 0.1) / (q.shape[-1] ** 0.5 if q.dim() > 1 else 1.0))).to(DEV))
-    m._flat.maybe_refresh()
+    m.parameters_changed()
 
 
 @pytest.mark.parametrize("C,H", [(2, 64), (6, 256), (16, 80)])

@@ -51,7 +51,7 @@ def _load(m, c):
     with torch.no_grad():
         for n, t in c.params.items():
             params[n].copy_(t.to(DEV))
-    m._flat.maybe_refresh()
+    m.parameters_changed()
     g = m._flat.grads
     g.copy_(torch.randn(g.numel(), generator=torch.Generator().manual_seed(c.B * 7 + c.H)).to(DEV))
     outside = torch.ones(g.numel(), dtype=torch.bool, device=DEV)
