@@ -488,6 +488,20 @@ int mmbert_adamw_grouped(mmbert_stream_t stream, float* p, float* g, float* m, f
                          const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale,
                          const float* coef, int mode, int zero_grad);
 
+/* ---- exponential moving average of the weights, fused into the AdamW step ----
+ * mmbert_adamw_grouped's update (per-block groups, coef == NULL for the host gscale or the device scalar, both modes, every flag, bf16
+ * refresh, fused zero_grad) that also folds the new p into ema: for every block with (flags & 3) != 2, ema += omd * (p_new - ema),
+ * omd = 1 - ema_decay formed in double and rounded to fp32 once.  Frozen blocks leave ema alone.  group_of_block == NULL: every block
+ * is group 0.  The writes to p, m, v, g and the bf16 copy are bit-identical to the kernel that would run without the average
+ * (mmbert_adamw / _devscale / _grouped).  +8 B/parameter, no extra launch, no sync.  Returns -1 under mmbert_adamw_grouped's
+ * conditions, for ema == NULL and for an ema_decay outside [0, 1). */
+int mmbert_adamw_ema(mmbert_stream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags,
+                     const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale,
+                     const float* coef, int mode, int zero_grad, float* ema, double ema_decay);
+/* p[i] <-> ema[i] for i < n, and p_bf16[i] = bf16 of the new p[i] (mmbert_cast_f32_bf16's rounding; p_bf16 may be NULL).  One launch, no
+ * temporary; twice restores everything bitwise.  n % 256 == 0. */
+int mmbert_ema_swap(mmbert_stream_t stream, float* p, float* ema, void* p_bf16, size_t n);
+
 /* ---- global gradient-norm clipping (torch.nn.utils.clip_grad_norm_) ----
  * segs: device int64 array of nseg pairs (offset, length) in elements of g[0..n): the elements the norm covers, any offsets and lengths
  * (0 <= offset, offset + length <= n; parameters pack inside 256-element blocks).  g 16-byte aligned.  Two launches, no float atomics:

@@ -1660,6 +1660,65 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ 
     if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
 }
 
+// adamw_grouped_kernel plus an exponential moving average of the weights: once a live block's new p is formed (it is in registers),
+// ema += omd * (p - ema) with omd = 1 - decay (mmbert_adamw_ema forms it in double and rounds once; the form e + omd (p - e) keeps
+// updates that are small against e at decay 0.9999).  Frozen blocks (flag 2) leave ema alone.  group_of_block == NULL: every block is
+// group 0 (one hyper-parameter set: the table then holds mmbert_adamw's coefficients in slot 0).  The update of p, m, v, g and the bf16
+// copy is adamw_kernel's line for line -- a kernel of its own for the reason given above adamw_devscale_kernel -- so that turning the
+// average on moves no bit of a training trajectory.  New traffic: one float4 load and one store of ema per lane (36 B/parameter).
+template <bool DEVSCALE>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                        float* __restrict__ ema, bf16_t* __restrict__ pb, const uint8_t* __restrict__ flags,
+                                                        const uint8_t* __restrict__ group_of_block, size_t n, const AdamWSlots a,
+                                                        float host_gscale, const float* __restrict__ coef, float omd, int mode, int zero_grad) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float gscale = DEVSCALE ? *coef : host_gscale;
+    const uint8_t fb = flags[i >> 8];
+    const uint8_t f = fb & 3;
+    const int grp = group_of_block ? __builtin_amdgcn_readfirstlane((int)group_of_block[i >> 8]) : 0;
+    float4 P = *(float4*)(p + i);
+    if (f != 2) {
+        const float* c = a.c[(a.slot4[grp >> 2] >> ((grp & 3) * 8)) & 255u];
+        const float beta1 = c[0], beta2 = c[1], omb1 = c[2], omb2 = c[3], eps = c[4], step_size = c[5], rsbc2 = c[6], lrwd = c[7];
+        float4 G = *(float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i);
+        const float4 E = *(float4*)(ema + i);
+        float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w}, ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
+        const float decay = (f == 1) ? lrwd : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float gr = ga[r] * gscale;
+            if (mode == 1) pa[r] *= (1.0f - decay);
+            ma[r] = beta1 * ma[r] + omb1 * gr;
+            va[r] = beta2 * va[r] + omb2 * gr * gr;
+            if (mode == 0) {
+                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) + eps);
+                pa[r] -= decay * pa[r];
+            } else {
+                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) * rsbc2 + eps);
+            }
+        }
+        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
+        *(float4*)(p + i) = P;
+        *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
+        *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
+        *(float4*)(ema + i) = make_float4(E.x + omd * (P.x - E.x), E.y + omd * (P.y - E.y), E.z + omd * (P.z - E.z), E.w + omd * (P.w - E.w));
+    }
+    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+}
+
+// p <-> ema, and the bf16 working copy of the new p (mmbert_cast_f32_bf16's rounding), in one pass: 16 B/parameter + 2 for the copy, no
+// temporary.  Indexed like the AdamW kernels (n % 256 == 0: whole float4s).
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ ema, bf16_t* __restrict__ pb, size_t n) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float4 P = *(float4*)(p + i), E = *(float4*)(ema + i);
+    *(float4*)(p + i) = E;
+    *(float4*)(ema + i) = P;
+    if (pb) { bf16x4 o = {f2bf(E.x), f2bf(E.y), f2bf(E.z), f2bf(E.w)}; *(bf16x4*)(pb + i) = o; }
+}
+
 // --------------------------------------------------------------------------------------------
 // Global gradient norm over a list of element segments of a flat fp32 buffer (torch.nn.utils.clip_grad_norm_: the reference
 // never clips; BERT's recipe and HF Trainer clip at 1.0).  segs[2 s], segs[2 s + 1] = offset, length of
@@ -2574,6 +2633,57 @@ int mmbert_adamw_grouped(hipStream_t stream, float* p, float* g, float* m, float
     else
         hipLaunchKernelGGL(adamw_grouped_kernel<false>, grid, dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, group_of_block, n, a,
                            (float)gscale, (const float*)nullptr, mode, zero_grad);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+// mmbert_adamw_grouped with the weight EMA fused in.  The slot table is built exactly as there (that entry point stays as it is: the
+// tests hold the two to bit-identity); 1 - ema_decay in double, rounded to fp32 once like the other coefficients.
+int mmbert_adamw_ema(hipStream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags,
+                     const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale, const float* coef,
+                     int mode, int zero_grad, float* ema, double ema_decay) {
+    if (n == 0) return 0;
+    if ((n & 255) || !hyper || ngroups < 1 || ngroups > ADAMW_MAX_GROUPS) return -1;
+    if (!ema || !(ema_decay >= 0.0 && ema_decay < 1.0)) return -1;
+    AdamWSlots a;
+    memset(&a, 0, sizeof(a));
+    double key[ADAMW_MAX_SLOTS][5];
+    int nslot = 0;
+    for (int k = 0; k < ngroups; ++k) {
+        const double* h = hyper + 5 * k;
+        int s = 0;
+        while (s < nslot && !(key[s][0] == h[0] && key[s][1] == h[1] && key[s][2] == h[2] && key[s][3] == h[3] && key[s][4] == h[4])) ++s;
+        if (s == nslot) {
+            if (nslot == ADAMW_MAX_SLOTS) return -1;
+            for (int j = 0; j < 5; ++j) key[s][j] = h[j];
+            ++nslot;
+        }
+        a.slot4[k >> 2] |= (uint32_t)s << ((k & 3) * 8);
+    }
+    for (int s = 0; s < nslot; ++s) {
+        const double lr = key[s][0], beta1 = key[s][1], beta2 = key[s][2], eps = key[s][3], wd = key[s][4];
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        const double step_size = mode == 0 ? lr * sqrt(bc2) / bc1 : lr / bc1;
+        const float c[8] = {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size,
+                            (float)(1.0 / sqrt(bc2)), (float)(lr * wd)};
+        for (int j = 0; j < 8; ++j) a.c[s][j] = c[j];
+    }
+    const float omd = (float)(1.0 - ema_decay);
+    const dim3 grid((unsigned)((n / 4 + 255) / 256));
+    if (coef)
+        hipLaunchKernelGGL(adamw_ema_kernel<true>, grid, dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)p_bf16, flags, group_of_block, n, a,
+                           1.0f, coef, omd, mode, zero_grad);
+    else
+        hipLaunchKernelGGL(adamw_ema_kernel<false>, grid, dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)p_bf16, flags, group_of_block, n, a,
+                           (float)gscale, (const float*)nullptr, omd, mode, zero_grad);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+int mmbert_ema_swap(hipStream_t stream, float* p, float* ema, void* p_bf16, size_t n) {
+    if (n == 0) return 0;
+    if ((n & 255) || !p || !ema) return -1;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, p, ema, (bf16_t*)p_bf16, n);
     MMB_CHECK_LAUNCH();
     return 0;
 }

@@ -1004,7 +1004,28 @@ def adamw_grouped(p, g, m, v, p_bf16, flags, group_of_block, hyper, *, step=1, g
                                                 1 if zero_grad else 0), "mmbert_adamw_grouped")
 
 
-GRAD_NORM_WORKSPACE = 8192          # MMBERT_GRAD_NORM_WORKSPACE (include/mmbert_hip.h), bytes
+def adamw_ema(p, g, m, v, p_bf16, flags, group_of_block, hyper, ema, *, ema_decay, step=1, gscale=1.0, coef=None, mode=0, zero_grad=True):
+    """ops.adamw_grouped that also folds the new ``p`` of every live block into the fp32 ``ema``: ema += (1 - ema_decay) (p - ema)
+    (mmbert_adamw_ema).  ``group_of_block`` None: every block is group 0 (``hyper`` then holds one tuple)."""
+    hyper = [tuple(float(x) for x in h) for h in hyper]
+    assert all(len(h) == 5 for h in hyper)
+    assert group_of_block is None or (group_of_block.dtype == torch.uint8 and group_of_block.numel() * 256 >= p.numel())
+    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == p.numel())
+    arr = (ctypes.c_double * (5 * max(1, len(hyper))))(*[x for h in hyper for x in h])
+    _lib.check(_lib.load().mmbert_adamw_ema(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16),
+                                            flags.data_ptr(), _ptr(group_of_block), p.numel(), arr, len(hyper), int(step), float(gscale),
+                                            None if coef is None else coef.data_ptr(), int(mode), 1 if zero_grad else 0, _ptr(ema),
+                                            float(ema_decay)), "mmbert_adamw_ema")
+
+
+def ema_swap(p, ema, p_bf16=None):
+    """p <-> ema in place, ``p_bf16`` (may be None) = bf16 of the new ``p`` (mmbert_ema_swap): one launch, no temporary."""
+    assert p.dtype == torch.float32 and ema.dtype == torch.float32 and p.is_contiguous() and ema.is_contiguous() and p.numel() == ema.numel()
+    assert p_bf16 is None or (p_bf16.dtype == torch.bfloat16 and p_bf16.is_contiguous() and p_bf16.numel() == p.numel())
+    _lib.check(_lib.load().mmbert_ema_swap(_stream(), p.data_ptr(), ema.data_ptr(), _ptr(p_bf16), p.numel()), "mmbert_ema_swap")
+
+
+GRAD_NORM_WORKSPACE = 8192         # MMBERT_GRAD_NORM_WORKSPACE (include/mmbert_hip.h), bytes
 
 
 def grad_norm(g, segs, nseg, *, max_norm, norm_type=2.0, gscale=1.0, workspace=None, out=None):

@@ -8,6 +8,7 @@ imports (eps 1e-6, bias correction, decay applied after the update); ``mode="tor
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Iterable, List, Union
 
@@ -43,6 +44,14 @@ def adamw_slots(hyper):
     return slots, list(index)
 
 
+def ema_decay_at(decay, updates, warmup=False):
+    """The decay of EMA update number ``updates`` (0 for the first ``step()`` after the copy that enabling makes): ``decay``, or with
+    ``warmup`` ``min(decay, (1 + updates) / (10 + updates))`` -- early averages follow the weights, late ones use ``decay``.  A pure
+    host function in double: the kernel only ever sees its value."""
+    decay = float(decay)
+    return min(decay, (1.0 + updates) / (10.0 + updates)) if warmup else decay
+
+
 class AdamW:
     def __init__(self, params: Union[Iterable[torch.nn.Parameter], List[dict]], lr=1e-3, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, correct_bias=True, mode="hf"):
@@ -65,6 +74,9 @@ class AdamW:
         self._flat = None
         self._steps = 0
         self._clip = None                   # clip_grad_norm_'s device scalars until the next step() applies them (or zero_grad() drops them)
+        self._ema = None                    # fp32 average of flat.params (ema(): +4 B/parameter), updated inside the step's kernel
+        self._ema_decay, self._ema_warmup, self.ema_updates = None, False, 0
+        self._swapped = False               # swap_ema(): flat.params holds the averages, _ema the trained weights
 
     # The dense weights' gradients (3/4 of the parameters) are not zero-filled between steps: the next backward's weight-gradient
     # launches overwrite them (flat.FlatParams lazy zero; torch's zero_grad(set_to_none=True) semantics).  False: fill with zeros.
@@ -129,6 +141,8 @@ class AdamW:
         self._flat = flat
         self._names = [flat.name_at(p._mmb_flat[1]) for g in self.param_groups for p in g["params"]]
         self._build_flags()
+        if self._ema_decay is not None:
+            self._ema = flat.params.clone()
 
     @staticmethod
     def _check_current(flat):
@@ -184,6 +198,7 @@ class AdamW:
         applies it (one reduction pass, no host sync, no write pass).  A second call before ``step()`` replaces the coefficient;
         ``zero_grad()`` without a step drops it.  norm_type: 2 or inf."""
         max_norm, norm_type = _clip_args(max_norm, norm_type)
+        self._refuse_swapped("clip_grad_norm_()")
         if self._flat is None:
             self._bind()
         flat = self._flat
@@ -197,7 +212,86 @@ class AdamW:
         self._clip = out
         return out[0]
 
+    # ---- exponential moving average of the weights ----
+    def ema(self, decay=0.999, warmup=False):
+        """Keeps an fp32 exponential moving average of the flat parameters, updated inside every ``step()``'s kernel (mmbert_adamw_ema:
+        +8 B/parameter of traffic, no launch, no sync; p, m, v and the bf16 copy keep the bits they have without it).  The average starts
+        as a copy of the parameters -- at once when the optimizer is bound, else at its first use -- which is
+        ``torch.optim.swa_utils.AveragedModel``'s first ``update_parameters``; every step then does ``ema += (1 - d) (p - ema)`` with
+        ``d = ema_decay_at(decay, ema_updates, warmup)``.  Called again it changes ``decay`` / ``warmup`` and keeps the average.
+        Frozen parameters and those this optimizer does not own keep their copy.  Under parallel.DataParallel nothing is exchanged: equal
+        parameters on every rank give equal averages.  Returns self."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"AdamW.ema: decay must be in [0, 1), got {decay}")
+        self._ema_decay, self._ema_warmup = decay, bool(warmup)
+        if self._flat is not None and self._ema is None:
+            self._ema = self._flat.params.clone()
+        return self
+
+    def ema_reset(self):
+        """Starts the average again from the current parameters (after a ``load_state_dict`` into the model)."""
+        self._refuse_swapped("ema_reset()")
+        self.ema_updates = 0
+        if self._ema is not None:
+            self._ema.copy_(self._flat.params)
+
+    def _refuse_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError(f"AdamW.{what} while the EMA weights are swapped in (swap_ema() / ema_weights()): the averages are not "
+                               "trained -- swap back first")
+
+    def _need_ema(self, what):
+        if self._ema_decay is None:
+            raise RuntimeError(f"AdamW.{what}: no EMA -- call ema(decay) first")
+        if self._flat is None:
+            self._bind()
+        self._check_current(self._flat)
+
+    def swap_ema(self):
+        """Exchanges the parameters with their averages in place (one launch that also rewrites the bf16 working copy; the transposed
+        copies follow): every path of the model -- forward, predict, predict_tokens, state_dict() -- then sees the averaged weights,
+        until the next call swaps back, bit for bit.  Version counters, m / v, the gradients and the lazy-zero state are untouched.
+        While swapped, step(), clip_grad_norm_() and state_dict() raise."""
+        self._need_ema("swap_ema()")
+        flat = self._flat
+        flat.join_side_writers()
+        flat.wait_transposes()               # (a side-stream transposed-copy launch may still read the bf16 copy rewritten here)
+        ops.ema_swap(flat.params, self._ema, flat.half)
+        flat.refresh_transposes()
+        flat.mark_synced()
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with opt.ema_weights():`` -- the model runs on the averaged weights inside, on the trained ones again after (swap_ema twice)."""
+        self._refuse_swapped("ema_weights()")
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_state_dict(self):
+        """The averaged weights under the model's ``state_dict()`` keys, as clones (buffers and anything outside the flat storage as the
+        model holds them); nothing is swapped."""
+        self._need_ema("ema_state_dict()")
+        flat = self._flat
+        model = flat._owner()
+        if model is None:
+            raise RuntimeError("AdamW.ema_state_dict(): the model of this storage is gone")
+        src = flat.params if self._swapped else self._ema
+        base, out = flat.params.data_ptr(), {}
+        for k, t in model.state_dict().items():
+            o = t.data_ptr() - base
+            if t.dtype == torch.float32 and t.is_contiguous() and t.numel() > 0 and 0 <= o and o + 4 * t.numel() <= 4 * flat.total:
+                out[k] = src[o // 4:o // 4 + t.numel()].view(t.shape).clone()
+            else:
+                out[k] = t.clone()
+        return out
+
     def step(self):
+        self._refuse_swapped("step()")
         hyper = self._hyper()
         if self._flat is None:
             self._bind()
@@ -220,7 +314,13 @@ class AdamW:
         flat.settle()                        # a lazy gradient no backward has written since the last step counts as zero
         flat.attach_lazy()
         clip, self._clip = self._clip, None
-        if grouped:                          # per-group hyper-parameters: each block reads its own group's coefficients
+        if self._ema is not None:            # the same update with the weight average folded in: one kernel for the three routes below
+            ops.adamw_ema(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, self._group_of_block if grouped else None,
+                          hyper if grouped else [(lr, beta1, beta2, eps, wd)], self._ema,
+                          ema_decay=ema_decay_at(self._ema_decay, self.ema_updates, self._ema_warmup), step=self._steps,
+                          gscale=self.grad_scale, coef=None if clip is None else clip[2:3], mode=self.mode, zero_grad=True)
+            self.ema_updates += 1
+        elif grouped:                        # per-group hyper-parameters: each block reads its own group's coefficients
             ops.adamw_grouped(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, self._group_of_block, hyper,
                               step=self._steps, gscale=self.grad_scale, coef=None if clip is None else clip[2:3], mode=self.mode,
                               zero_grad=True)
@@ -261,12 +361,20 @@ class AdamW:
             flat.detach_lazy()               # the dropped gradients read None (torch: set_to_none) until the next backward writes them
 
     def state_dict(self):
+        self._refuse_swapped("state_dict()")
         return dict(steps=self._steps, m=None if self._flat is None else self._m, v=None if self._flat is None else self._v,
-                    lrs=[g["lr"] for g in self.param_groups])
+                    lrs=[g["lr"] for g in self.param_groups], ema=self._ema, ema_decay=self._ema_decay, ema_warmup=self._ema_warmup,
+                    ema_updates=self.ema_updates)
 
     def load_state_dict(self, sd):
+        self._refuse_swapped("load_state_dict()")
         if self._flat is None:
             self._bind()
+        if sd.get("ema_decay") is not None:  # (a dict without the ema keys, or saved with the EMA off, leaves the EMA as it is)
+            self.ema(sd["ema_decay"], sd.get("ema_warmup", False))
+            self.ema_updates = int(sd.get("ema_updates", 0))
+            if sd.get("ema") is not None:
+                self._ema.copy_(sd["ema"])
         self._steps = sd["steps"]
         if sd["m"] is not None:
             self._m.copy_(sd["m"])

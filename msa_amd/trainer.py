@@ -246,7 +246,9 @@ def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
     """REF:train.py:76-97: two parameter groups by NAME substring, AdamW, linear warm-up with
     warmup = N and total = warmup_proportion * N.
     ``args.layer_lr_decay`` / ``args.head_learning_rate`` (optional; not reference arguments, ``default_args()`` leaves them out): the
-    groups of optim.layerwise_param_groups (layer-wise lr decay, a learning rate of its own for the parts a BERT checkpoint lacks)."""
+    groups of optim.layerwise_param_groups (layer-wise lr decay, a learning rate of its own for the parts a BERT checkpoint lacks).
+    ``args.ema_decay`` / ``args.ema_warmup`` (optional, likewise): an exponential moving average of the weights, kept inside the
+    optimizer step (``AdamW.ema``); ``train`` then validates, tests and saves under the averaged weights."""
     from .optim import AdamW, get_linear_schedule_with_warmup, layerwise_param_groups
     layer_decay, head_lr = getattr(args, "layer_lr_decay", None), getattr(args, "head_learning_rate", None)
     if layer_decay is not None or head_lr is not None:
@@ -257,6 +259,8 @@ def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
         groups = [{"params": [p for n, p in named if not any(nd in n for nd in no_decay)], "weight_decay": 0.01},
                   {"params": [p for n, p in named if any(nd in n for nd in no_decay)], "weight_decay": 0.0}]
     opt = AdamW(groups, lr=args.learning_rate, mode=mode)
+    if getattr(args, "ema_decay", None) is not None:
+        opt.ema(args.ema_decay, warmup=bool(getattr(args, "ema_warmup", False)))
     sched = get_linear_schedule_with_warmup(opt, num_warmup_steps=num_train_optimization_steps,
                                             num_training_steps=args.warmup_proportion * num_train_optimization_steps)
     return opt, sched
@@ -470,6 +474,8 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
     without improvement the best predictions / targets go to ``predict.npy`` / ``target.npy`` and the loop stops.
     ``epoch_batches``: optional callable ``(split, epoch) -> iterable of model kwargs`` replacing the datasets (synthetic data).
     ``args.max_grad_norm``, when present, reaches every epoch's train_epoch (global-norm clipping).
+    An optimizer with a weight EMA (``AdamW.ema``; ``args.ema_decay`` through build_optimizer): each epoch's validation, test and saved
+    state dict use the averaged weights (``optimizer.ema_weights()``); training goes on from the trained ones.
     Returns a dict with the best epoch's numbers and the per-epoch history."""
     import os
     import numpy as np
@@ -486,25 +492,28 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
         tb = epoch_batches("train", epoch) if epoch_batches else None
         tr = train_epoch(args, model, train_dataset, optimizer, scheduler, tokenizer, device=device, dp=dp, batches=tb)
         log("[Train Epoch {}] Joint Loss : {} AP Loss : {} Label Loss : {}".format(epoch + 1, tr[0], tr[4], tr[5]))
-        va = eval_epoch(args, model, val_dataset, tokenizer, device=device, batches=epoch_batches("val", epoch) if epoch_batches else None)
-        log("[Val Epoch {}] Joint Loss : {} AP Loss : {} Label Loss : {}".format(epoch + 1, va[0], va[4], va[5]))
-        te = eval_epoch(args, model, test_dataset, tokenizer, device=device, batches=epoch_batches("test", epoch) if epoch_batches else None)
-        acc, mae, f_score = score(te[6], te[7])
-        if dp is not None and torch.distributed.get_world_size() > 1:
-            # ranks evaluate with their own sampler order and MLM draws, so their metrics can differ in the last digits: rank 0's
-            # numbers decide the save rule and the patience stop on EVERY rank (a rank that stopped alone would leave the
-            # others waiting in the next epoch's gradient all-reduce)
-            t = torch.tensor([acc, mae, f_score], dtype=torch.float64, device=device)
-            torch.distributed.broadcast(t, src=0)
-            acc, mae, f_score = (float(x) for x in t.tolist())
-        log("[Epoch {}] Test_ACC : {}, Test_MAE : {}, Test_F_Score: {}".format(epoch + 1, acc, mae, f_score))
-        history.append(dict(epoch=epoch + 1, train_loss=tr[0], valid_loss=va[0], test_acc=acc, test_mae=mae, test_f_score=f_score))
-        if acc > best["acc"]:
-            path = os.path.join(save_dir, "model_" + str(epoch + 1) + ".pt")
-            if rank0:
-                torch.save(model.state_dict(), path)
-            best.update(epoch=epoch, acc=acc, loss=va[0], mae=mae, f_score=f_score, preds=te[6], labels=te[7], path=path if rank0 else None)
-            patience = 0
+        # (an optimizer with a weight EMA: the epoch is judged and saved under the averaged weights, swapped out again before the next epoch)
+        averaged = optimizer.ema_weights() if getattr(optimizer, "_ema_decay", None) is not None else _null()
+        with averaged:
+            va = eval_epoch(args, model, val_dataset, tokenizer, device=device, batches=epoch_batches("val", epoch) if epoch_batches else None)
+            log("[Val Epoch {}] Joint Loss : {} AP Loss : {} Label Loss : {}".format(epoch + 1, va[0], va[4], va[5]))
+            te = eval_epoch(args, model, test_dataset, tokenizer, device=device, batches=epoch_batches("test", epoch) if epoch_batches else None)
+            acc, mae, f_score = score(te[6], te[7])
+            if dp is not None and torch.distributed.get_world_size() > 1:
+                # ranks evaluate with their own sampler order and MLM draws, so their metrics can differ in the last digits: rank 0's
+                # numbers decide the save rule and the patience stop on EVERY rank (a rank that stopped alone would leave the
+                # others waiting in the next epoch's gradient all-reduce)
+                t = torch.tensor([acc, mae, f_score], dtype=torch.float64, device=device)
+                torch.distributed.broadcast(t, src=0)
+                acc, mae, f_score = (float(x) for x in t.tolist())
+            log("[Epoch {}] Test_ACC : {}, Test_MAE : {}, Test_F_Score: {}".format(epoch + 1, acc, mae, f_score))
+            history.append(dict(epoch=epoch + 1, train_loss=tr[0], valid_loss=va[0], test_acc=acc, test_mae=mae, test_f_score=f_score))
+            if acc > best["acc"]:
+                path = os.path.join(save_dir, "model_" + str(epoch + 1) + ".pt")
+                if rank0:
+                    torch.save(model.state_dict(), path)
+                best.update(epoch=epoch, acc=acc, loss=va[0], mae=mae, f_score=f_score, preds=te[6], labels=te[7], path=path if rank0 else None)
+                patience = 0
         if patience == patience_limit:
             if rank0 and best["preds"] is not None:
                 out = _dated_dir(numpy_root)
