@@ -226,6 +226,18 @@ int mmbert_ce_bwd(mmbert_stream_t stream, const void* logits, int ldv, int V, co
                   const int* seg_bounds, int nseg, const float* inv_count, const float* gscale, const float* row_lse, void* dlogits, int ldd,
                   const int* rows /* NULL: all M rows; else a row list: dlogits row j = gradient of row rows[j] */, int nrows,
                   int logits_f32 /* logits are fp32; dlogits stays bf16 */);
+/* The same with label smoothing (a declared extension): torch.nn.functional.cross_entropy(label_smoothing = smoothing,
+ * ignore_index = -100) per segment.  On a labelled row
+ *   loss_i        = lse_i - (1 - smoothing) x[i, label] - (smoothing / V) sum_{c < V} x[i, c]
+ *   dlogits[i, c] = (exp(x[i, c] - lse_i) - (1 - smoothing) [c = label] - smoothing / V) inv_count[s] gscale[s]   for c < V,
+ * exactly 0 on the pad columns V .. ldv and on unlabelled rows; row_lse keeps its meaning.  smoothing outside [0, 1) or not finite: -1,
+ * nothing launched.  smoothing == 0 runs the kernels of the two calls above (the same bits). */
+int mmbert_ce_fwd_smooth(mmbert_stream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M,
+                         const int* seg_bounds, int nseg, float* inv_count, float* loss_sum, float* row_lse, int logits_f32, float* row_loss,
+                         float smoothing);
+int mmbert_ce_bwd_smooth(mmbert_stream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M,
+                         const int* seg_bounds, int nseg, const float* inv_count, const float* gscale, const float* row_lse, void* dlogits,
+                         int ldd, const int* rows, int nrows, int logits_f32, float smoothing);
 /* ---- vocabulary top-k (masked-token prediction; a declared extension) ----
  * For each of the M rows of logits [M, ldv] (bf16, or fp32 rounded to bf16 as loaded: identical outputs), over columns 0 .. V-1 only:
  *   top_ids[i, j]     the j-th column in the total order "larger value first, on equal values the lower column first" (j < k);
@@ -381,6 +393,23 @@ int mmbert_heads_step_bwd_levels(mmbert_stream_t stream, const mmbert_heads_step
 int mmbert_heads_predict(mmbert_stream_t stream, const mmbert_heads_step* p);
 int mmbert_heads_step_outputs(int B, int H, size_t* pooled_offset, size_t* fused_offset);
 /* dmlm[i] = dloss * alpha / nmlm alone (backward level 6 writes the same): the MLM head's backward needs nothing else of the heads' to start */
+/* ---- the label loss's options (a declared extension) ----
+ * mmbert_heads_step_opt = the record above with the options BEHIND it: the offsets of every field of mmbert_heads_step, its size and the
+ * entry points above are untouched, and a pointer to a mmbert_heads_step_opt is a pointer to its mmbert_heads_step.  All zero / NULL: the
+ * losses above, the same bits.
+ *   loss_kind        regression head (ncls == 0): 0 MSE, 1 L1 (mean |d|, seed sign(d) / B with sign(0) = 0), 2 Huber (torch's huber_loss:
+ *                    0.5 d^2 where |d| <= huber_delta, else huber_delta (|d| - 0.5 huber_delta)); d = logit (through tanh when tanh_lo) - sent
+ *   label_smoothing, cls_weight (fp32 [ncls], every entry finite and > 0, or NULL = all ones)
+ *                    class head: torch's cross_entropy(weight = w, label_smoothing = eps), with W = sum_b w[sent_cls[b]]
+ *                    loss = (1 - eps) sum_b w[y_b] (lse_b - l[b, y_b]) / W + eps / (C W) sum_b sum_c w_c (lse_b - l[b, c])
+ * Only forward level 7 reads them.  Refused (-1 from both _opt entry points, nothing launched or written): loss_kind outside 0 .. 2;
+ * loss_kind != 0 with ncls > 0; loss_kind 2 with huber_delta not finite or <= 0; label_smoothing outside [0, 1) or not finite;
+ * label_smoothing != 0 or cls_weight != NULL with ncls == 0. */
+typedef struct { int loss_kind; float huber_delta; float label_smoothing; const float* cls_weight; } mmbert_heads_loss;
+typedef struct { mmbert_heads_step step; mmbert_heads_loss opt; } mmbert_heads_step_opt;
+int mmbert_heads_step_opt_struct_size(void);      /* sizeof(mmbert_heads_step_opt) */
+int mmbert_heads_step_fwd_levels_opt(mmbert_stream_t stream, const mmbert_heads_step_opt* p, int lo, int hi);
+int mmbert_heads_step_bwd_levels_opt(mmbert_stream_t stream, const mmbert_heads_step_opt* p, int lo, int hi);
 int mmbert_heads_step_dmlm(mmbert_stream_t stream, const mmbert_heads_step* p);
 
 /* ---- the heads' dense layers: lists of fp32 products with at most 64 rows, one launch per dependency level ----

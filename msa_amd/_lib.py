@@ -54,6 +54,8 @@ SIGNATURES = {
     "mmbert_attn_dropout_mask": (I, [P, P, I, C.c_uint, I, U32, U32]),
     "mmbert_ce_fwd": (I, [P, P, I, I, P, I, P, I, P, P, P, I, P]),
     "mmbert_ce_bwd": (I, [P, P, I, I, P, I, P, I, P, P, P, P, I, P, I, I]),
+    "mmbert_ce_fwd_smooth": (I, [P, P, I, I, P, I, P, I, P, P, P, I, P, F]),
+    "mmbert_ce_bwd_smooth": (I, [P, P, I, I, P, I, P, I, P, P, P, P, I, P, I, I, F]),
     "mmbert_vocab_topk": (I, [P, P, I, I, I, I, I, P, P, P, P, P, P]),
     "mmbert_active_rows": (I, [P, P, I, I, P, P]),
     "mmbert_prologue": (I, [P, I, P, P, P, P, P, P, P, I, P, I, P, I, P, P, P, P, P, P, P, P]),
@@ -75,6 +77,9 @@ SIGNATURES = {
     "mmbert_heads_step_bwd": (I, [P, P]),
     "mmbert_heads_step_fwd_levels": (I, [P, P, I, I]),
     "mmbert_heads_step_bwd_levels": (I, [P, P, I, I]),
+    "mmbert_heads_step_opt_struct_size": (I, []),
+    "mmbert_heads_step_fwd_levels_opt": (I, [P, P, I, I]),
+    "mmbert_heads_step_bwd_levels_opt": (I, [P, P, I, I]),
     "mmbert_heads_step_dmlm": (I, [P, P]),
     "mmbert_heads_predict": (I, [P, P]),
     "mmbert_heads_step_outputs": (I, [I, I, P, P]),

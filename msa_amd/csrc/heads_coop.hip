@@ -31,6 +31,7 @@
 // Two findings from that form are kept under tools/ubench: HIP's __syncthreads() does not wait for outstanding global stores (a workgroup-scope
 // release on one CU needs no vmcnt wait), and hipcc 22 turns __builtin_amdgcn_raw_buffer_load_b128 with the sc1 cache-policy bit into a ONE-dword
 // load when its lanes are extracted (tools/ubench/exchange_check.py).
+#include <cfloat>
 #include "common.h"
 #include "../../include/mmbert_hip.h"
 
@@ -190,7 +191,7 @@ struct HcFirst {
 // forward
 // =====================================================================================================================================
 template <int LEVEL, bool CLS>
-__global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmbert_heads_step p) {
+__global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmbert_heads_step p, const mmbert_heads_loss lopt) {   // (lopt: level 7 only)
 #if defined(__gfx950__)
     extern __shared__ __attribute__((aligned(16))) float hc_sm[];
     HcCtx c; c.nwg = gridDim.x; c.red = hc_sm; c.wg = blockIdx.x;
@@ -385,6 +386,7 @@ __global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmber
             // mean C-way cross-entropy (REF :438-441) and its seed dlo[b][c] = (softmax_c - [c == y_b]) / B; `se` carries the label loss.
             // A label outside [0, C) is clamped (nothing out of bounds; the loss is then unspecified)
             const int C = p.ncls;
+            if (lopt.label_smoothing == 0.f && !lopt.cls_weight) {
             for (int b = tid; b < B; b += HC_THREADS) {
                 const float* l = w.lo + (size_t)b * C;
                 const long long yl = p.sent_cls[b];
@@ -396,6 +398,58 @@ __global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmber
                 const float lse = mx + logf(sx);
                 se += (lse - hc_ldc(l + y)) / (float)B;
                 for (int q = 0; q < C; ++q) w.dlo[(size_t)b * C + q] = (expf(hc_ldc(l + q) - lse) - (q == y ? 1.f : 0.f)) / (float)B;
+            }
+            } else {
+                // torch's cross_entropy(weight = w, label_smoothing = eps), mean: with W = sum_b w[y_b] (w = 1, W = B without weights)
+                //   loss      = (1 - eps) sum_b w[y_b] (lse_b - l[b, y_b]) / W + eps / (C W) sum_b sum_c w_c (lse_b - l[b, c])
+                //   dlo[b, k] = (1 - eps) w[y_b] (p[b, k] - [k == y_b]) / W + eps / (C W) ((sum_c w_c) p[b, k] - w_k)
+                // This workgroup sees all B <= 128 samples: W first, every thread adding the B weights in sample order (no atomics)
+                const float eps = lopt.label_smoothing;
+                const float* cw = lopt.cls_weight;
+                float* wy = lds2 + 2 * HC_WAVES;                                     // [B] behind this workgroup's two rows of wave partials
+                for (int b = tid; b < B; b += HC_THREADS) {
+                    const long long yl = p.sent_cls[b];
+                    const int y = (int)(yl < 0 ? 0 : (yl > C - 1 ? C - 1 : yl));
+                    wy[b] = cw ? cw[y] : 1.f;
+                }
+                __syncthreads();
+                float W = 0.f, SW = 0.f;
+                for (int b = 0; b < B; ++b) W += wy[b];
+                for (int q = 0; q < C; ++q) SW += cw ? cw[q] : 1.f;
+                const float k1 = (1.f - eps) / W, k2 = eps / ((float)C * W);
+                for (int b = tid; b < B; b += HC_THREADS) {
+                    const float* l = w.lo + (size_t)b * C;
+                    const long long yl = p.sent_cls[b];
+                    const int y = (int)(yl < 0 ? 0 : (yl > C - 1 ? C - 1 : yl));
+                    float mx = hc_ldc(l);
+                    for (int q = 1; q < C; ++q) mx = fmaxf(mx, hc_ldc(l + q));
+                    float sx = 0.f;
+                    for (int q = 0; q < C; ++q) sx += expf(hc_ldc(l + q) - mx);
+                    const float lse = mx + logf(sx);
+                    const float a1 = k1 * wy[b];
+                    float sm = 0.f;
+                    for (int q = 0; q < C; ++q) sm += (cw ? cw[q] : 1.f) * (lse - hc_ldc(l + q));
+                    se += a1 * (lse - hc_ldc(l + y)) + k2 * sm;
+                    for (int q = 0; q < C; ++q) {
+                        const float pq = expf(hc_ldc(l + q) - lse);
+                        w.dlo[(size_t)b * C + q] = a1 * (pq - (q == y ? 1.f : 0.f)) + k2 * (SW * pq - (cw ? cw[q] : 1.f));
+                    }
+                }
+            }
+        } else if (lopt.loss_kind != 0) {
+            // L1 (loss_kind 1): mean |d|, seed sign(d) / B, sign(0) = 0 as torch; Huber (2, torch's huber_loss): 0.5 d^2 inside |d| <= delta,
+            // delta (|d| - 0.5 delta) outside, seed d / B or delta sign(d) / B -- each times tanh' when the logit went through tanh
+            const float delta = lopt.huber_delta;
+            for (int b = tid; b < B; b += HC_THREADS) {
+                const float lo = hc_ldc(w.lo + b);
+                const float v = p.tanh_lo ? tanhf(lo) : lo;
+                const float d = v - p.sent[b];
+                const float ad = fabsf(d), sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+                float g;
+                if (lopt.loss_kind == 1) { se += ad / (float)B; g = sg; }
+                else if (ad <= delta) { se += 0.5f * d * d / (float)B; g = d; }
+                else { se += delta * (ad - 0.5f * delta) / (float)B; g = delta * sg; }
+                w.dlo[b] = g / (float)B * (p.tanh_lo ? 1.f - v * v : 1.f);
             }
         } else {
         for (int b = tid; b < B; b += HC_THREADS) {
@@ -648,6 +702,14 @@ static int hc_check(const mmbert_heads_step* p, int* cus) {
     *cus = mmb_device_cus();
     return 0;
 }
+// the label loss's options (mmbert_heads_step_opt.opt): a kind the head has, a usable delta, a smoothing in [0, 1) (a NaN fails every comparison)
+static int hc_check_loss(const mmbert_heads_step* p, const mmbert_heads_loss* o) {
+    if (o->loss_kind < 0 || o->loss_kind > 2 || (o->loss_kind != 0 && p->ncls > 0)) return -1;
+    if (o->loss_kind == 2 && !(o->huber_delta > 0.f && o->huber_delta <= FLT_MAX)) return -1;
+    if (!(o->label_smoothing >= 0.f && o->label_smoothing < 1.f)) return -1;
+    if (p->ncls == 0 && (o->label_smoothing != 0.f || o->cls_weight)) return -1;
+    return 0;
+}
 __global__ void heads_dmlm_kernel(const float* __restrict__ dloss, float* __restrict__ dmlm, int nmlm, float alpha) {
     const float d = *dloss;
     for (int i = threadIdx.x; i < nmlm; i += blockDim.x) dmlm[i] = d * (alpha / (float)nmlm);      // (the expression of backward level 6)
@@ -659,16 +721,17 @@ static inline int hc_grid(int wg_tiles, int wave_jobs, int cus, int floor_) {
     if (g < floor_) g = floor_;
     return g > cus ? cus : (g < 1 ? 1 : g);
 }
-#define HC_LAUNCH(K, L, GRID, LDS) do { hipLaunchKernelGGL((K<L, false>), dim3(GRID), dim3(HC_THREADS), (LDS), stream, *p); MMB_CHECK_LAUNCH(); } while (0)
+#define HC_LAUNCH(K, L, GRID, LDS) do { hipLaunchKernelGGL((K<L, false>), dim3(GRID), dim3(HC_THREADS), (LDS), stream, HC_KARGS); MMB_CHECK_LAUNCH(); } while (0)
 // ... a level whose class-head instantiation differs (forward 5 and 7, backward 2 and 3)
-#define HC_LAUNCH_CLS(K, L, GRID, LDS) do { if (p->ncls > 0) { hipLaunchKernelGGL((K<L, true>), dim3(GRID), dim3(HC_THREADS), (LDS), stream, *p); MMB_CHECK_LAUNCH(); } \
+#define HC_LAUNCH_CLS(K, L, GRID, LDS) do { if (p->ncls > 0) { hipLaunchKernelGGL((K<L, true>), dim3(GRID), dim3(HC_THREADS), (LDS), stream, HC_KARGS); MMB_CHECK_LAUNCH(); } \
                                             else HC_LAUNCH(K, L, GRID, LDS); } while (0)
 
 // levels lo .. hi of the forward (1 .. 7) / backward (1 .. 6): the model runs the heads beside the MLM head's launches on a side stream and
 // only the loss level (which reads the MLM losses) behind both
-int mmbert_heads_step_fwd_levels(hipStream_t stream, const mmbert_heads_step* p, int lo, int hi) {
+#define HC_KARGS *p, *lopt
+static int hc_fwd_levels(hipStream_t stream, const mmbert_heads_step* p, const mmbert_heads_loss* lopt, int lo, int hi) {
     int cus;
-    if (hc_check(p, &cus)) return -1;
+    if (hc_check(p, &cus) || hc_check_loss(p, lopt)) return -1;
     if (lo < 1 || hi > 7 || lo > hi) return -1;
     if (!p->loss || !p->aux || !p->out5 || !p->logits || !p->t_rel || !p->rel || !p->ap || (p->ncls == 0 && !p->sent) || (hi == 7 && p->nmlm > 0 && !p->mlm)) return -1;
     const int B = p->B, H = p->H, R = 3 * B, tH = H >> 4, tB = (B + 15) >> 4, tR = (R + 15) >> 4, t2B = (2 * B + 15) >> 4;
@@ -683,13 +746,26 @@ int mmbert_heads_step_fwd_levels(hipStream_t stream, const mmbert_heads_step* p,
     return 0;
 }
 
+static const mmbert_heads_loss hc_plain_loss = {};              // all zero / NULL: the MSE, the plain mean cross-entropy
+
+int mmbert_heads_step_fwd_levels(hipStream_t stream, const mmbert_heads_step* p, int lo, int hi) { return hc_fwd_levels(stream, p, &hc_plain_loss, lo, hi); }
+
 int mmbert_heads_step_fwd(hipStream_t stream, const mmbert_heads_step* p) { return mmbert_heads_step_fwd_levels(stream, p, 1, 7); }
+
+// the same with the label loss's options behind the record (mmbert_heads_step_opt): refusals before any launch, from forward and backward alike
+int mmbert_heads_step_opt_struct_size(void) { return (int)sizeof(mmbert_heads_step_opt); }
+
+int mmbert_heads_step_fwd_levels_opt(hipStream_t stream, const mmbert_heads_step_opt* q, int lo, int hi) {
+    if (!q) return -1;
+    return hc_fwd_levels(stream, &q->step, &q->opt, lo, hi);
+}
 
 // prediction without labels: levels 1 .. 5 read the [CLS] rows, the parameters and the workspace -- labels, losses and the loss level's counter
 // are level 7's (so they are not asked for here); same kernels, grids and bits as mmbert_heads_step_fwd_levels(p, 1, 5)
 int mmbert_heads_predict(hipStream_t stream, const mmbert_heads_step* p) {
     if (!p || p->B <= 0 || p->B > 128 || p->H < 16 || (p->H & 15) || !p->ws || (!p->first && (!p->y || !p->first_rows || (p->ldy & 3)))) return -1;
     if (!p->logits || !p->t_rel || !p->rel) return -1;
+    const mmbert_heads_loss* lopt = &hc_plain_loss;              // (levels 1 - 5 read no option)
     if (p->ncls < 0 || p->ncls == 1 || p->ncls > 16 || (p->ncls > 0 && !p->pred)) return -1;
     if (!p->Wp || !p->bp || !p->Wal || !p->bal || !p->Wsr || !p->bsr || !p->Wat || !p->bat || !p->Wc1 || !p->bc1 || !p->Wc2 || !p->bc2) return -1;
     for (int m = 0; m < 3; ++m) if (!p->vw[m] || !p->vb[m] || !p->Wq[m] || !p->bq[m]) return -1;
@@ -712,6 +788,8 @@ int mmbert_heads_step_outputs(int B, int H, size_t* pooled_offset, size_t* fused
     return 0;
 }
 
+#undef HC_KARGS
+#define HC_KARGS *p
 int mmbert_heads_step_bwd_levels(hipStream_t stream, const mmbert_heads_step* p, int lo, int hi) {
     int cus;
     if (hc_check(p, &cus)) return -1;
@@ -732,6 +810,12 @@ int mmbert_heads_step_bwd_levels(hipStream_t stream, const mmbert_heads_step* p,
 
 int mmbert_heads_step_bwd(hipStream_t stream, const mmbert_heads_step* p) { return mmbert_heads_step_bwd_levels(stream, p, 1, 6); }
 
+// (the backward reads no option -- forward left the seed dlo -- but refuses what forward refuses)
+int mmbert_heads_step_bwd_levels_opt(hipStream_t stream, const mmbert_heads_step_opt* q, int lo, int hi) {
+    if (!q || hc_check_loss(&q->step, &q->opt)) return -1;
+    return mmbert_heads_step_bwd_levels(stream, &q->step, lo, hi);
+}
+
 // the gradient of the per-pass MLM losses alone (what backward level 6 also writes): d(joint) / d(mlm[i]) = alpha / nmlm, times the upstream
 // gradient -- one tiny launch, so that the MLM head's backward can start on the current stream while the six levels run on another
 int mmbert_heads_step_dmlm(hipStream_t stream, const mmbert_heads_step* p) {
@@ -742,6 +826,7 @@ int mmbert_heads_step_dmlm(hipStream_t stream, const mmbert_heads_step* p) {
     return 0;
 }
 #undef HC_LAUNCH_CLS
+#undef HC_KARGS
 #undef HC_LAUNCH
 
 }  // extern "C"

@@ -1236,11 +1236,18 @@ __global__ void embed_type_fold_kernel(const float* __restrict__ slab, int T, in
 // Ignored rows (label -100) are never read.
 // F32: the logits are fp32 (the vocabulary GEMM's EPI_OUT_F32 output, handed to the caller as the reference's fp32 prediction scores);
 // they are rounded to bf16 as they are loaded, so losses and gradients are bit-identical to the bf16-logits path.
-template <int MODE, bool F32>
+//
+// SMOOTH (label smoothing eps in (0, 1), torch's cross_entropy(label_smoothing=eps); one_minus = 1 - eps, eps_over_v = eps / V, both formed
+// on the host): a compile-time form, so that the eps = 0 instantiations are the code they were.
+//   forward:  loss term = lse - (1 - eps) logit[label] - (eps / V) sum_{c < V} logit[c]; the row sum of the bf16-rounded logits is taken as
+//             the exp sum is (per lane in ascending (c, r), wave_sum, the four waves in order); row_lse keeps its meaning
+//   backward: dlogits = (exp(logit - row_lse) - (1 - eps) onehot - eps / V) * inv_count[seg] * gscale[seg] on the columns c < V
+template <int MODE, bool F32, bool SMOOTH = false>
 __global__ __launch_bounds__(256) void ce_row_kernel(const void* __restrict__ logits_, int ldv, int V, const int64_t* __restrict__ labels,
                                                      const int* __restrict__ seg_bounds, int nseg, const float* __restrict__ inv_count,
                                                      float* __restrict__ loss_sum, float* __restrict__ row_lse, const float* __restrict__ gscale,
-                                                     bf16_t* __restrict__ dlogits, int ldd, const int* __restrict__ rows, float* __restrict__ row_loss) {
+                                                     bf16_t* __restrict__ dlogits, int ldd, const int* __restrict__ rows, float* __restrict__ row_loss,
+                                                     float one_minus, float eps_over_v) {
     __shared__ float red[4];
     __shared__ float lab_logit;
     const int i = rows ? rows[blockIdx.x] : blockIdx.x;        // backward over a compact row list: output row = blockIdx.x
@@ -1293,17 +1300,36 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const void* __restrict__ lo
         mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         __syncthreads();
         float se = 0.f;
+        float sx = 0.f;                                        // SMOOTH: the row sum of the logits over the V valid columns, never a pad column
 #pragma unroll
         for (int c = 0; c < CE_MAXC; ++c) {
             const int ch = c * 256 + tid;
             if (ch < nchunk) {
 #pragma unroll
-                for (int r = 0; r < 8; ++r) if (ch * 8 + r < V) se += __expf(bf2f(v[c][r]) - mx);
+                for (int r = 0; r < 8; ++r) if (ch * 8 + r < V) {
+                    se += __expf(bf2f(v[c][r]) - mx);
+                    if constexpr (SMOOTH) sx += bf2f(v[c][r]); // (beside the exp sum: the element is converted once)
+                }
                 if ((int)(lab >> 3) == ch) lab_logit = bf2f(v[c][lab & 7]);
             }
         }
         se = wave_sum(se);
         if (lane == 0) red[w] = se;
+        if constexpr (SMOOTH) {
+            __shared__ float red_x[4];
+            sx = wave_sum(sx);
+            if (lane == 0) red_x[w] = sx;
+            __syncthreads();
+            if (tid == 0) {
+                const float lse = mx + __logf(red[0] + red[1] + red[2] + red[3]);
+                const float sum_x = ((red_x[0] + red_x[1]) + red_x[2]) + red_x[3];
+                row_lse[i] = lse;
+                const float term = __fmaf_rn(-eps_over_v, sum_x, __fmaf_rn(-one_minus, lab_logit, lse)) * inv_count[s];
+                if (row_loss) row_loss[i] = term;
+                else atomicAdd(loss_sum + s, term);
+            }
+            return;
+        }
         __syncthreads();
         if (tid == 0) {
             const float lse = mx + __logf(red[0] + red[1] + red[2] + red[3]);
@@ -1324,7 +1350,12 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const void* __restrict__ lo
                 for (int r = 0; r < 8; ++r) {
                     const int col = ch * 8 + r;
                     float pr = col < V ? __expf(bf2f(v[c][r]) - lse) : 0.f;
-                    if (col == (int)lab) pr -= 1.0f;
+                    if constexpr (SMOOTH) {
+                        if (col == (int)lab) pr -= one_minus;
+                        if (col < V) pr -= eps_over_v;         // (a pad column stays exactly 0)
+                    } else {
+                        if (col == (int)lab) pr -= 1.0f;
+                    }
                     o[r] = f2bf(pr * scale);
                 }
                 *(bf16x8*)(drow + ch * 8) = o;
@@ -2450,27 +2481,50 @@ int mmbert_pair_proj_bwd(hipStream_t stream, const void* feat, int feat_f64, int
     return 0;
 }
 
-int mmbert_ce_fwd(hipStream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M,
-                  const int* seg_bounds, int nseg, float* inv_count, float* loss_sum, float* row_lse, int logits_f32, float* row_loss) {
+// label smoothing of the _smooth entry points: inside [0, 1) and finite, or nothing is launched
+static bool ce_smoothing_ok(float smoothing) { return smoothing >= 0.f && smoothing < 1.f; }      // (false for a NaN)
+
+static int ce_fwd_launch(hipStream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M, const int* seg_bounds, int nseg,
+                         float* inv_count, float* loss_sum, float* row_lse, int logits_f32, float* row_loss, float smoothing) {
     if (M <= 0) return 0;
     if (nseg < 1 || nseg > 4 || (ldv & 7) || ldv > CE_MAXC * 256 * 8 || V > ldv) return -1;
+    if (smoothing != 0.f && V < 1) return -1;                     // (eps / V)
     const bool det = mmb_deterministic();
     if (det && !row_loss) return -4;                              // deterministic mode needs the per-row loss buffer (M floats)
     if (!det) row_loss = nullptr;
     hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(1024), 0, stream, labels, M, V, seg_bounds, nseg, inv_count, loss_sum);
     MMB_CHECK_LAUNCH();
-    if (logits_f32)
+    if (smoothing != 0.f) {
+        const float one_minus = 1.f - smoothing, eps_over_v = smoothing / (float)V;
+        if (logits_f32)
+            hipLaunchKernelGGL((ce_row_kernel<0, true, true>), dim3(M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg, inv_count,
+                               loss_sum, row_lse, (const float*)nullptr, (bf16_t*)nullptr, 0, (const int*)nullptr, row_loss, one_minus, eps_over_v);
+        else
+            hipLaunchKernelGGL((ce_row_kernel<0, false, true>), dim3(M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg, inv_count,
+                               loss_sum, row_lse, (const float*)nullptr, (bf16_t*)nullptr, 0, (const int*)nullptr, row_loss, one_minus, eps_over_v);
+    } else if (logits_f32)
         hipLaunchKernelGGL((ce_row_kernel<0, true>), dim3(M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg, inv_count, loss_sum,
-                           row_lse, (const float*)nullptr, (bf16_t*)nullptr, 0, (const int*)nullptr, row_loss);
+                           row_lse, (const float*)nullptr, (bf16_t*)nullptr, 0, (const int*)nullptr, row_loss, 1.f, 0.f);
     else
         hipLaunchKernelGGL((ce_row_kernel<0, false>), dim3(M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg, inv_count, loss_sum,
-                           row_lse, (const float*)nullptr, (bf16_t*)nullptr, 0, (const int*)nullptr, row_loss);
+                           row_lse, (const float*)nullptr, (bf16_t*)nullptr, 0, (const int*)nullptr, row_loss, 1.f, 0.f);
     MMB_CHECK_LAUNCH();
     if (det) {
         hipLaunchKernelGGL(ce_loss_sum_ordered_kernel, dim3(1), dim3(1024), 0, stream, (const float*)row_loss, M, seg_bounds, nseg, loss_sum);
         MMB_CHECK_LAUNCH();
     }
     return 0;
+}
+
+int mmbert_ce_fwd(hipStream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M,
+                  const int* seg_bounds, int nseg, float* inv_count, float* loss_sum, float* row_lse, int logits_f32, float* row_loss) {
+    return ce_fwd_launch(stream, logits, ldv, V, labels, M, seg_bounds, nseg, inv_count, loss_sum, row_lse, logits_f32, row_loss, 0.f);
+}
+
+int mmbert_ce_fwd_smooth(hipStream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M, const int* seg_bounds, int nseg,
+                         float* inv_count, float* loss_sum, float* row_lse, int logits_f32, float* row_loss, float smoothing) {
+    if (!ce_smoothing_ok(smoothing)) return -1;
+    return ce_fwd_launch(stream, logits, ldv, V, labels, M, seg_bounds, nseg, inv_count, loss_sum, row_lse, logits_f32, row_loss, smoothing);
 }
 
 int mmbert_vocab_topk(hipStream_t stream, const void* logits, int ldv, int V, int M, int logits_f32, int k, const int64_t* labels,
@@ -2504,19 +2558,42 @@ int mmbert_id_runs_sum_rows(hipStream_t stream, const void* src, int src_bf16, i
     return 0;
 }
 
+static int ce_bwd_launch(hipStream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M, const int* seg_bounds, int nseg,
+                         const float* inv_count, const float* gscale, const float* row_lse, void* dlogits, int ldd, const int* rows, int nrows,
+                         int logits_f32, float smoothing) {
+    if (M <= 0 || (rows && nrows <= 0)) return 0;
+    if (nseg < 1 || nseg > 4 || (ldv & 7) || (ldd & 7) || ldv > CE_MAXC * 256 * 8 || V > ldv) return -1;
+    if (smoothing != 0.f && V < 1) return -1;
+    if (smoothing != 0.f) {
+        const float one_minus = 1.f - smoothing, eps_over_v = smoothing / (float)V;
+        if (logits_f32)
+            hipLaunchKernelGGL((ce_row_kernel<1, true, true>), dim3(rows ? nrows : M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg,
+                               inv_count, (float*)nullptr, (float*)row_lse, gscale, (bf16_t*)dlogits, ldd, rows, (float*)nullptr, one_minus, eps_over_v);
+        else
+            hipLaunchKernelGGL((ce_row_kernel<1, false, true>), dim3(rows ? nrows : M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg,
+                               inv_count, (float*)nullptr, (float*)row_lse, gscale, (bf16_t*)dlogits, ldd, rows, (float*)nullptr, one_minus, eps_over_v);
+    } else if (logits_f32)
+        hipLaunchKernelGGL((ce_row_kernel<1, true>), dim3(rows ? nrows : M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg, inv_count,
+                           (float*)nullptr, (float*)row_lse, gscale, (bf16_t*)dlogits, ldd, rows, (float*)nullptr, 1.f, 0.f);
+    else
+        hipLaunchKernelGGL((ce_row_kernel<1, false>), dim3(rows ? nrows : M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg, inv_count,
+                           (float*)nullptr, (float*)row_lse, gscale, (bf16_t*)dlogits, ldd, rows, (float*)nullptr, 1.f, 0.f);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
 int mmbert_ce_bwd(hipStream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M,
                   const int* seg_bounds, int nseg, const float* inv_count, const float* gscale, const float* row_lse, void* dlogits, int ldd,
                   const int* rows, int nrows, int logits_f32) {
-    if (M <= 0 || (rows && nrows <= 0)) return 0;
-    if (nseg < 1 || nseg > 4 || (ldv & 7) || (ldd & 7) || ldv > CE_MAXC * 256 * 8 || V > ldv) return -1;
-    if (logits_f32)
-        hipLaunchKernelGGL((ce_row_kernel<1, true>), dim3(rows ? nrows : M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg, inv_count,
-                           (float*)nullptr, (float*)row_lse, gscale, (bf16_t*)dlogits, ldd, rows, (float*)nullptr);
-    else
-        hipLaunchKernelGGL((ce_row_kernel<1, false>), dim3(rows ? nrows : M), dim3(256), 0, stream, logits, ldv, V, labels, seg_bounds, nseg, inv_count,
-                           (float*)nullptr, (float*)row_lse, gscale, (bf16_t*)dlogits, ldd, rows, (float*)nullptr);
-    MMB_CHECK_LAUNCH();
-    return 0;
+    return ce_bwd_launch(stream, logits, ldv, V, labels, M, seg_bounds, nseg, inv_count, gscale, row_lse, dlogits, ldd, rows, nrows, logits_f32, 0.f);
+}
+
+int mmbert_ce_bwd_smooth(hipStream_t stream, const void* logits, int ldv, int V, const int64_t* labels, int M, const int* seg_bounds, int nseg,
+                         const float* inv_count, const float* gscale, const float* row_lse, void* dlogits, int ldd, const int* rows, int nrows,
+                         int logits_f32, float smoothing) {
+    if (!ce_smoothing_ok(smoothing)) return -1;
+    return ce_bwd_launch(stream, logits, ldv, V, labels, M, seg_bounds, nseg, inv_count, gscale, row_lse, dlogits, ldd, rows, nrows, logits_f32,
+                         smoothing);
 }
 
 int mmbert_split_rows(hipStream_t stream, const int64_t* row_seq, const int64_t* row_pos, const int* start_a, const int* start_b, const int* valid,

@@ -1083,6 +1083,8 @@ class _MLMHeadFn(torch.autograd.Function):
         keep = ctx.needs_input_grad[0]
         y = y.contiguous()
         ctx.compact = False
+        # label smoothing of the three MLM losses (set_loss_options): 0.0 runs the calls and kernels it always did
+        eps = ctx.smoothing = float(getattr(top, "mlm_label_smoothing", 0.0))
         ctx.first_rows = first_rows
         first = None
         if first_rows is not None:
@@ -1106,7 +1108,7 @@ class _MLMHeadFn(torch.autograd.Function):
                 labels_c = labels.index_select(0, sel)
                 nseg = len(seg_bounds_host) - 1
                 bounds_c = torch.searchsorted(sel32, seg_bounds.to(sel32.dtype)).to(torch.int32)   # labelled rows are in row order
-                loss, inv, lse = ops.ce_fwd(logits_c, V, labels_c, bounds_c, nseg)
+                loss, inv, lse = ops.ce_fwd(logits_c, V, labels_c, bounds_c, nseg, smoothing=eps)
                 ctx.top, ctx.nseg, ctx.compact, ctx.M = top, nseg, True, M
                 ctx.set_materialize_grads(False)
                 ctx.save_for_backward(y_c, pre_c, t0_c, mean_c, rstd_c, t_c, logits_c, labels_c, bounds_c, inv, lse, sel)
@@ -1118,7 +1120,7 @@ class _MLMHeadFn(torch.autograd.Function):
         f32_scores = want_scores and getattr(top, "scores_dtype", torch.bfloat16) == torch.float32
         logits = ops.gemm_nt(t, w["word_h"], bias=w["pred_bias"], out_f32=f32_scores)
         nseg = len(seg_bounds_host) - 1
-        loss, inv, lse = ops.ce_fwd(logits, V, labels, seg_bounds, nseg)
+        loss, inv, lse = ops.ce_fwd(logits, V, labels, seg_bounds, nseg, smoothing=eps)
         ctx.top, ctx.nseg, ctx.keep_logits, ctx.M = top, nseg, want_scores, M
         ctx.set_materialize_grads(False)      # or autograd zero-fills a [tokens, vocab] gradient for the returned scores
         # Rows without a label have an exactly-zero CE gradient (ignore_index): backward needs the labelled rows only (~2 % of
@@ -1212,7 +1214,7 @@ class _MLMHeadFn(torch.autograd.Function):
             _flush_late_wgrads(ctx.top)
         if ctx.compact:
             y_c, pre_c, t0_c, mean_c, rstd_c, t_c, logits_c, labels_c, bounds_c, inv, lse, sel = ctx.saved_tensors
-            dl = ops.ce_bwd(logits_c, V, labels_c, bounds_c, ctx.nseg, inv, gs, lse, logits_c)       # in place: the scores go nowhere
+            dl = ops.ce_bwd(logits_c, V, labels_c, bounds_c, ctx.nseg, inv, gs, lse, logits_c, smoothing=ctx.smoothing)       # in place: the scores go nowhere
             return sel, _MLMHeadFn._few_rows_backward(ctx.top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows)
         y, pre, t0, mean, rstd, t, logits, labels, seg_bounds, inv, lse = ctx.saved_tensors
         M = y.shape[0]
@@ -1224,12 +1226,12 @@ class _MLMHeadFn(torch.autograd.Function):
                     return idx_all[:0], y.new_zeros((extra_rows, y.shape[1]))
                 idx = idx_all[:n]
                 dl = torch.empty((n, logits.shape[1]), device=y.device, dtype=torch.bfloat16)
-                ops.ce_bwd(logits, V, labels, seg_bounds, ctx.nseg, inv, gs, lse, dl, rows=idx)
+                ops.ce_bwd(logits, V, labels, seg_bounds, ctx.nseg, inv, gs, lse, dl, rows=idx, smoothing=ctx.smoothing)
                 t_c, t0_c, pre_c, y_c, mean_c, rstd_c = ops.gather_rows([t, t0, pre, y, mean, rstd], idx)      # one launch
                 return idx, _MLMHeadFn._few_rows_backward(ctx.top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows)
         # dense path: dlogits with the per-pass upstream gradients folded in; in place unless the scores were handed to the caller
         dl = torch.empty(logits.shape, device=logits.device, dtype=torch.bfloat16) if (ctx.keep_logits or logits.dtype != torch.bfloat16) else logits
-        ops.ce_bwd(logits, V, labels, seg_bounds, ctx.nseg, inv, gs, lse, dl)
+        ops.ce_bwd(logits, V, labels, seg_bounds, ctx.nseg, inv, gs, lse, dl, smoothing=ctx.smoothing)
         ops.gemm_tn(dl, t, w["g_word_pad"], bias_out=w["g_pred_bias"], accumulate=ctx.top._flat.take_accumulate([w["g_word_pad"]]))   # tied decoder weight + prediction bias gradient
         dt = ops.gemm_nt(dl, w["wordT"])
         dt0 = ops.ln_bwd(dt, t0, mean, rstd, w["mlm_ln_g"], w["g_mlm_ln_g"], w["g_mlm_ln_b"], deferred=lnd)
@@ -1935,9 +1937,17 @@ class _HeadsStepFn(torch.autograd.Function):
             a.sent_cls, a.pred = sent.data_ptr(), pred.data_ptr()
         else:
             a.sent = sent.data_ptr()
+        # the label loss's options (set_loss_options): zero / NULL unless one is on
+        cw = getattr(top, "class_weights", None)
+        a.loss_kind = MMBertForPretraining._LOSS_KINDS.index(getattr(top, "label_loss_kind", "mse"))
+        a.huber_delta = float(getattr(top, "huber_delta", 1.0)) if a.loss_kind == 2 else 0.0
+        a.label_smoothing = float(getattr(top, "label_smoothing", 0.0))
+        if cw is not None:
+            assert cw.dtype == torch.float32 and cw.device == dev and cw.numel() == ncls and cw.is_contiguous()
+            a.cls_weight = cw.data_ptr()
         a.loss, a.aux, a.out5, a.logits, a.t_rel, a.rel, a.ws = (t.data_ptr() for t in (loss, aux, out5, logits, t_rel, rel, ws))
         a.sync = ops.heads_step_sync(dev).data_ptr()
-        return a, (loss, aux, logits, t_rel, rel), (ap, sent, ws, pred, out5)
+        return a, (loss, aux, logits, t_rel, rel), (ap, sent, ws, pred, out5)     # (the class weights are the model's buffer; only level 7 reads them)
 
     @staticmethod
     def prelaunch(top, y, rows, ap, sent):
@@ -2164,6 +2174,9 @@ class MMBertForPretraining(_GpuModelBase):
         # predict_tokens(): the selected rows go through the MLM head in chunks of at most this many rows, so that the [rows, Vpad] bf16
         # logits never take more than token_chunk_rows * Vpad * 2 bytes (250 MB at the default and the 30 522-word vocabulary)
         self.token_chunk_rows = 4096
+        # the losses' options (set_loss_options; DECLARED EXTENSION): all off = the reference's losses, the same launches and bits
+        self.label_loss_kind, self.huber_delta, self.label_smoothing, self.mlm_label_smoothing = "mse", 1.0, 0.0, 0.0
+        self.register_buffer("class_weights", None, persistent=False)      # fp32 [C] or None: follows .to() / deepcopy / pickling, not in state_dict()
         # heads through _HeadsFn (hand-written backward, csrc/heads.hip); False = the eager autograd form (_heads), in which
         # ap_loss / label_loss / nce and the relationship scores stay differentiable outputs
         self.fused_heads = os.environ.get("MMBERT_FUSED_HEADS", "1") != "0"
@@ -2272,6 +2285,50 @@ class MMBertForPretraining(_GpuModelBase):
     def set_alpha_beta(self, alpha, beta):
         self.alpha, self.beta = alpha, beta
 
+    _LOSS_KINDS = ("mse", "l1", "huber")
+
+    def set_loss_options(self, *, regression="mse", huber_delta=1.0, class_weights=None, label_smoothing=0.0, mlm_label_smoothing=0.0):
+        """DECLARED EXTENSION: what the reference gets by swapping its loss objects (REF:MMBertForPretraining.py:381, :433, :438), inside the
+        fused step.  Keywords only; every call sets all five (the defaults switch an option off again).
+        * ``regression`` -- the regression head's label loss (``num_labels`` 1 / 7): "mse" (the reference's), "l1" (``F.l1_loss``) or
+          "huber" (``F.huber_loss(delta=huber_delta)``);
+        * ``class_weights`` (C finite values > 0) and ``label_smoothing`` -- a C-class head's ``F.cross_entropy(weight=, label_smoothing=)``;
+        * ``mlm_label_smoothing`` -- ``label_smoothing=`` of the three vocabulary cross-entropies (ignore_index -100, per pass).
+        Smoothings in [0, 1).  Raises ValueError, before anything is stored, for an option the model's head does not have.  The options are
+        no parameters: ``class_weights`` is a non-persistent fp32 buffer, ``state_dict()`` keeps the reference's keys.  outputs[5] is the
+        loss as configured, in train and eval mode alike; ``predict_tokens`` / ``mlm_eval_epoch`` report the plain negative log-likelihood."""
+        import math
+        kind = regression
+        if kind not in self._LOSS_KINDS:
+            raise ValueError(f"regression = {kind!r}: one of {self._LOSS_KINDS}")
+        ncls = _class_head(self)
+        if ncls and kind != "mse":
+            raise ValueError(f"regression = {kind!r} on a {ncls}-class head (its label loss is the cross-entropy)")
+
+        def smoothing(x, name):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= float(x) < 1.0:
+                raise ValueError(f"{name} = {x!r}: a number in [0, 1)")
+            return float(x)
+        eps, meps = smoothing(label_smoothing, "label_smoothing"), smoothing(mlm_label_smoothing, "mlm_label_smoothing")
+        if isinstance(huber_delta, bool) or not isinstance(huber_delta, (int, float)) or not (0.0 < float(huber_delta) < math.inf):
+            raise ValueError(f"huber_delta = {huber_delta!r}: a finite number > 0")
+        cw = None
+        if class_weights is not None:
+            if not ncls:
+                raise ValueError("class_weights on a regression head (num_labels 1 / 7): build the model with a class count first")
+            cw = torch.as_tensor(class_weights, dtype=torch.float32).detach().reshape(-1).clone()
+            if cw.numel() != ncls or not bool(torch.isfinite(cw).all()) or not bool((cw > 0).all()):
+                raise ValueError(f"class_weights: {ncls} finite values > 0 (one per class), got {class_weights!r}")
+        if eps != 0.0 and not ncls:
+            raise ValueError("label_smoothing on a regression head (num_labels 1 / 7); mlm_label_smoothing smooths the vocabulary losses")
+        self.label_loss_kind, self.huber_delta, self.label_smoothing, self.mlm_label_smoothing = kind, float(huber_delta), eps, meps
+        self.class_weights = None if cw is None else cw.to(self.classifier1_2.weight.device)
+        return self
+
+    def _heads_options(self) -> bool:
+        """Whether any option of the label loss is on (the vocabulary losses' smoothing is the MLM head's, not the heads')."""
+        return self.label_loss_kind != "mse" or self.label_smoothing != 0.0 or self.class_weights is not None
+
     @staticmethod
     def _check_num_labels(n) -> int:
         if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= 16:
@@ -2287,6 +2344,8 @@ class MMBertForPretraining(_GpuModelBase):
         (optim.AdamW._check_current).  State-dict key names do not change."""
         n = self._check_num_labels(n)
         width = 1 if n in (1, 7) else n
+        if self.class_weights is not None and self.class_weights.numel() != (0 if n in (1, 7) else n):
+            raise ValueError(f"set_num_labels({n}): class weights for {self.class_weights.numel()} classes are set -- clear them first (set_loss_options())")
         old = self.classifier1_2
         if old.out_features != width:
             new = nn.Linear(old.in_features, width)
@@ -2300,7 +2359,11 @@ class MMBertForPretraining(_GpuModelBase):
         # .cuda()/.to() re-creates parameter storage: re-flatten lazily.  (Also when nothing moves: the next use then builds a NEW storage,
         # and an optimizer bound to the old one raises at its next call -- optim.AdamW._check_current.)
         self._flat = None
-        return super()._apply(fn, *a, **k)
+        out = super()._apply(fn, *a, **k)
+        cw = self.__dict__.get("_buffers", {}).get("class_weights")
+        if cw is not None and cw.dtype != torch.float32:        # .double() / .half() cast buffers: the kernels read the class weights as fp32
+            self.class_weights = cw.float()
+        return out
 
     def __setstate__(self, state):
         """A copy (copy.deepcopy, torch.load of the whole module) arrives without runtime state (_RUNTIME_STATE): its parts point at it."""
@@ -2377,7 +2440,18 @@ class MMBertForPretraining(_GpuModelBase):
             if self.num_labels == 1 or self.num_labels == 7:
                 if self.num_labels == 1:
                     logits_out = self.tanh(logits_out)
-                label_loss = F.mse_loss(logits_out.view(-1), sentiment.view(-1).float())
+                target = sentiment.view(-1).float()
+                if self.label_loss_kind == "l1":
+                    label_loss = F.l1_loss(logits_out.view(-1), target)
+                elif self.label_loss_kind == "huber":
+                    label_loss = F.huber_loss(logits_out.view(-1), target, delta=self.huber_delta)
+                else:
+                    label_loss = F.mse_loss(logits_out.view(-1), target)
+            elif _class_head(self) and (self.class_weights is not None or self.label_smoothing != 0.0):
+                cw = self.class_weights
+                label_loss = F.cross_entropy(logits_out, sentiment.view(-1).long(), weight=None if cw is None else cw.to(logits_out.dtype),
+                                             label_smoothing=self.label_smoothing)
+                logits_out = torch.argmax(self.sigmoid(logits_out), dim=1)             # the predicted classes, as below (REF :442)
             else:
                 label_loss = F.cross_entropy(logits_out, sentiment.view(-1).long() if _class_head(self) else sentiment)
                 logits_out = torch.argmax(self.sigmoid(logits_out), dim=1)
@@ -2414,9 +2488,16 @@ class MMBertForPretraining(_GpuModelBase):
             with torch.no_grad():
                 first.copy_(src[0].index_select(0, src[1]))
             src = None
-        if fused and not coop and (B > 32 or ncls):              # (a class head never takes the 19-launch form: eager beyond 128 samples)
+        opts = self._heads_options()                             # (an option of the label loss: the level-launch heads or eager, like a class head)
+        if fused and not coop and (B > 32 or ncls or opts):      # (a class head never takes the 19-launch form: eager beyond 128 samples)
             fused = False
-            if ncls and B <= 128:
+            if opts and not ncls and B <= 128:
+                if not self.__dict__.get("_warned_heads_options"):
+                    import warnings
+                    self.__dict__["_warned_heads_options"] = True
+                    warnings.warn(f"msa_amd: the {self.label_loss_kind} label loss has kernels in the level-launch heads only (model.coop_heads, "
+                                  "hidden_size % 16 == 0, gradient buffers in place): the heads run in eager PyTorch (~250 small launches per step)")
+            elif ncls and B <= 128:
                 if not self.__dict__.get("_warned_heads_cls"):
                     import warnings
                     self.__dict__["_warned_heads_cls"] = True
@@ -2589,7 +2670,8 @@ class MMBertForPretraining(_GpuModelBase):
         first on equal scores; ``top_logprob`` fp32 [n_p, k]: their log-probabilities; with labels also ``label`` int64 [n_p],
         ``label_logprob`` fp32 [n_p], ``label_rank`` int64 [n_p]: the number of tokens ranked before the label, 0 = predicted), and
         ``"loss"`` fp32 [3] on the device: the per-pass mean of -label_logprob -- the three MLM losses ``forward`` computes and drops (0 for a
-        pass without labelled rows and in ``positions`` mode).
+        pass without labelled rows and in ``positions`` mode).  That loss is the PLAIN negative log-likelihood: ``mlm_label_smoothing``
+        (set_loss_options) shapes the training objective and is not applied here.
 
         Inference arithmetic as in ``predict()``: no dropout, no autograd graph, ``self.training`` untouched, on the current stream;
         nothing is taken from or left in the per-step state (dropout seed sequence, prologue buffers, pending gradients,

@@ -912,29 +912,48 @@ def attn_dropout_mask(S, elem_base, head, drop, device):
     return out
 
 
-def ce_fwd(logits, V, labels, seg_bounds, nseg):
-    """Returns (loss_mean_per_segment[nseg], inv_count[4], row_lse[M])  (see mmbert_ce_fwd)."""
+def _ce_smoothing(smoothing) -> float:
+    """The label smoothing of ce_fwd / ce_bwd as a float in [0, 1) (torch's range, without its 1.0: W stays positive); raises otherwise."""
+    eps = float(smoothing)
+    if not (0.0 <= eps < 1.0):
+        raise ValueError(f"label smoothing must be in [0, 1), got {smoothing!r}")
+    return eps
+
+
+def ce_fwd(logits, V, labels, seg_bounds, nseg, smoothing=0.0):
+    """Returns (loss_mean_per_segment[nseg], inv_count[4], row_lse[M])  (see mmbert_ce_fwd).
+    ``smoothing``: torch's cross_entropy(label_smoothing=) (mmbert_ce_fwd_smooth); at 0.0 the call is mmbert_ce_fwd's, as before."""
     lib = _lib.load()
+    eps = _ce_smoothing(smoothing)
     M = logits.shape[0]
     inv = torch.empty(4, device=logits.device, dtype=torch.float32)
     loss = torch.empty(nseg, device=logits.device, dtype=torch.float32)   # exactly nseg (<= 4) entries are written: returned as it is, not as a view
     lse = torch.empty(M, device=logits.device, dtype=torch.float32)
     assert logits.dtype in (torch.bfloat16, torch.float32)
     row_loss = _ws_f32(M, logits.device) if deterministic() else None      # (deterministic mode: the rows' loss terms, summed in a fixed order)
-    _lib.check(lib.mmbert_ce_fwd(_stream(), logits.data_ptr(), logits.stride(0), V, labels.data_ptr(), M, seg_bounds.data_ptr(), nseg,
-                                 inv.data_ptr(), loss.data_ptr(), lse.data_ptr(), 1 if logits.dtype == torch.float32 else 0, _ptr(row_loss)),
-               "mmbert_ce_fwd")
+    args = (_stream(), logits.data_ptr(), logits.stride(0), V, labels.data_ptr(), M, seg_bounds.data_ptr(), nseg,
+            inv.data_ptr(), loss.data_ptr(), lse.data_ptr(), 1 if logits.dtype == torch.float32 else 0, _ptr(row_loss))
+    if eps == 0.0:
+        _lib.check(lib.mmbert_ce_fwd(*args), "mmbert_ce_fwd")
+    else:
+        _lib.check(lib.mmbert_ce_fwd_smooth(*args, eps), "mmbert_ce_fwd_smooth")
     return loss, inv, lse
 
 
-def ce_bwd(logits, V, labels, seg_bounds, nseg, inv, gscale, lse, dlogits, rows=None):
+def ce_bwd(logits, V, labels, seg_bounds, nseg, inv, gscale, lse, dlogits, rows=None, smoothing=0.0):
     """dlogits (may be ``logits`` itself) = d(sum_s gscale[s] * loss_s) / d(logits)  (see mmbert_ce_bwd).
-    ``rows`` (int32 row list): compact output, dlogits[j] = gradient of row rows[j]."""
+    ``rows`` (int32 row list): compact output, dlogits[j] = gradient of row rows[j].
+    ``smoothing``: the forward's label smoothing (mmbert_ce_bwd_smooth); at 0.0 the call is mmbert_ce_bwd's, as before."""
     lib = _lib.load()
+    eps = _ce_smoothing(smoothing)
     M = logits.shape[0]
-    _lib.check(lib.mmbert_ce_bwd(_stream(), logits.data_ptr(), logits.stride(0), V, labels.data_ptr(), M, seg_bounds.data_ptr(), nseg,
-                                 inv.data_ptr(), gscale.data_ptr(), lse.data_ptr(), dlogits.data_ptr(), dlogits.stride(0),
-                                 _ptr(rows), 0 if rows is None else rows.numel(), 1 if logits.dtype == torch.float32 else 0), "mmbert_ce_bwd")
+    args = (_stream(), logits.data_ptr(), logits.stride(0), V, labels.data_ptr(), M, seg_bounds.data_ptr(), nseg,
+            inv.data_ptr(), gscale.data_ptr(), lse.data_ptr(), dlogits.data_ptr(), dlogits.stride(0),
+            _ptr(rows), 0 if rows is None else rows.numel(), 1 if logits.dtype == torch.float32 else 0)
+    if eps == 0.0:
+        _lib.check(lib.mmbert_ce_bwd(*args), "mmbert_ce_bwd")
+    else:
+        _lib.check(lib.mmbert_ce_bwd_smooth(*args, eps), "mmbert_ce_bwd_smooth")
     return dlogits
 
 
@@ -1264,18 +1283,33 @@ class _HeadsStep(ctypes.Structure):
                 + [(n, _VP) for n in ("gWc1", "gbc1", "gWc2", "gbc2")] + [("gWq", _VP3), ("gbq", _VP3)] + [("sync", _VP), ("sent_cls", _VP), ("pred", _VP)])
 
 
+class _HeadsLoss(ctypes.Structure):
+    """Mirror of ``mmbert_heads_loss``: the label loss's options (all zero / NULL = the MSE, the plain mean cross-entropy)."""
+    _fields_ = [("loss_kind", ctypes.c_int), ("huber_delta", ctypes.c_float), ("label_smoothing", ctypes.c_float), ("cls_weight", _VP)]
+
+
+class _HeadsStepOpt(ctypes.Structure):
+    """Mirror of ``mmbert_heads_step_opt``: the record with the options behind it.  Both parts are anonymous -- ``a.B``, ``a.loss_kind`` --
+    and its address is its record's, so every entry point that takes a ``mmbert_heads_step`` takes it too."""
+    _anonymous_ = ("step", "opt")
+    _fields_ = [("step", _HeadsStep), ("opt", _HeadsLoss)]
+
+
 _heads_sync = {}
 _heads_struct_checked = False
 
 
-def heads_step_struct() -> "_HeadsStep":
+def heads_step_struct() -> "_HeadsStepOpt":
+    """A zeroed argument record with the label loss's options behind it (zero: off)."""
     global _heads_struct_checked
     if not _heads_struct_checked:
-        n = _lib.load().mmbert_heads_step_struct_size()
-        if n != ctypes.sizeof(_HeadsStep):
-            raise RuntimeError(f"mmbert_heads_step: the library's struct has {n} bytes, the binding's {ctypes.sizeof(_HeadsStep)}")
+        lib = _lib.load()
+        for what, n, mirror in (("mmbert_heads_step", lib.mmbert_heads_step_struct_size(), _HeadsStep),
+                                ("mmbert_heads_step_opt", lib.mmbert_heads_step_opt_struct_size(), _HeadsStepOpt)):
+            if n != ctypes.sizeof(mirror):
+                raise RuntimeError(f"{what}: the library's struct has {n} bytes, the binding's {ctypes.sizeof(mirror)}")
         _heads_struct_checked = True
-    return _HeadsStep()
+    return _HeadsStepOpt()
 
 
 def heads_step_sync(device) -> torch.Tensor:
@@ -1291,8 +1325,16 @@ def heads_step_workspace(B: int, H: int, device) -> torch.Tensor:
     return torch.empty(_lib.load().mmbert_heads_step_workspace(int(B), int(H)) // 4, device=device, dtype=torch.float32)
 
 
-def heads_step_fwd(a: "_HeadsStep", lo: int = 1, hi: int = 7):
-    _lib.check(_lib.load().mmbert_heads_step_fwd_levels(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_fwd_levels")
+def _heads_opt_on(a) -> bool:
+    return isinstance(a, _HeadsStepOpt) and bool(a.loss_kind or a.label_smoothing != 0.0 or a.cls_weight)
+
+
+def heads_step_fwd(a: "_HeadsStepOpt", lo: int = 1, hi: int = 7):
+    """Forward levels lo .. hi.  With every option of the label loss off the call is mmbert_heads_step_fwd_levels's, as before."""
+    if _heads_opt_on(a):
+        _lib.check(_lib.load().mmbert_heads_step_fwd_levels_opt(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_fwd_levels_opt")
+    else:
+        _lib.check(_lib.load().mmbert_heads_step_fwd_levels(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_fwd_levels")
 
 
 def heads_predict(a: "_HeadsStep"):

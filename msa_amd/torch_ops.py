@@ -201,9 +201,9 @@ _lib.define("joint_embed_fwd(Tensor text_emb, Tensor pair, Tensor weight, Tensor
             "float dropout_p=0.0, int seed=0) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("joint_embed_bwd(Tensor dy, Tensor pair, Tensor j0, Tensor mean, Tensor rstd, Tensor gamma, int text_len, float dropout_p=0.0, "
             "int seed=0) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
-_lib.define("mlm_head_ce(Tensor logits, Tensor labels, int vocab) -> Tensor")
-_lib.define("mlm_head_ce_fwd(Tensor logits, Tensor labels, int vocab) -> (Tensor, Tensor, Tensor)")
-_lib.define("mlm_head_ce_bwd(Tensor dloss, Tensor logits, Tensor labels, int vocab, Tensor inv_count, Tensor row_lse) -> Tensor")
+_lib.define("mlm_head_ce(Tensor logits, Tensor labels, int vocab, float label_smoothing=0.0) -> Tensor")
+_lib.define("mlm_head_ce_fwd(Tensor logits, Tensor labels, int vocab, float label_smoothing=0.0) -> (Tensor, Tensor, Tensor)")
+_lib.define("mlm_head_ce_bwd(Tensor dloss, Tensor logits, Tensor labels, int vocab, Tensor inv_count, Tensor row_lse, float label_smoothing=0.0) -> Tensor")
 _lib.define("adamw_multi_tensor(Tensor(a!) p, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!)? p_bf16, Tensor flags, float lr, float beta1, "
             "float beta2, float eps, float weight_decay, int step, float grad_scale=1.0, str mode='hf', bool zero_grad=True) -> ()")
 _lib.define("mlm_mask_rng(Tensor(a!) ids, float p, int seed, int[] special_ids, int mask_id=103) -> Tensor")
@@ -282,22 +282,24 @@ def _ce_bounds(M, device):
     return torch.tensor([0, M], dtype=torch.int32, device=device)
 
 
-def _ce_fwd(logits, labels, vocab):
+def _ce_fwd(logits, labels, vocab, label_smoothing=0.0):
     """Mean cross-entropy over the rows whose label is a vocabulary index (-100 = ignored): HF:466-496 head output -> loss.
-    logits [M, ld >= vocab] bf16 (row stride a multiple of 8), labels int64 [M] -> (loss [], inv_count, row_lse)."""
+    logits [M, ld >= vocab] bf16 (row stride a multiple of 8), labels int64 [M] -> (loss [], inv_count, row_lse).
+    ``label_smoothing``: torch's cross_entropy(label_smoothing=), in [0, 1)."""
     lg = _bf(logits)
-    loss, inv, lse = ops.ce_fwd(lg, int(vocab), labels.long().contiguous(), _ce_bounds(lg.shape[0], lg.device), 1)
+    loss, inv, lse = ops.ce_fwd(lg, int(vocab), labels.long().contiguous(), _ce_bounds(lg.shape[0], lg.device), 1, smoothing=label_smoothing)
     return loss[0].clone(), inv, lse
 
 
-def _ce(logits, labels, vocab):
-    return _ce_fwd(logits, labels, vocab)[0]
+def _ce(logits, labels, vocab, label_smoothing=0.0):
+    return _ce_fwd(logits, labels, vocab, label_smoothing)[0]
 
 
-def _ce_bwd(dloss, logits, labels, vocab, inv_count, row_lse):
+def _ce_bwd(dloss, logits, labels, vocab, inv_count, row_lse, label_smoothing=0.0):
     lg = _bf(logits)
     dl = torch.empty_like(lg)
-    ops.ce_bwd(lg, int(vocab), labels.long().contiguous(), _ce_bounds(lg.shape[0], lg.device), 1, inv_count, dloss.reshape(1).float().contiguous(), row_lse, dl)
+    ops.ce_bwd(lg, int(vocab), labels.long().contiguous(), _ce_bounds(lg.shape[0], lg.device), 1, inv_count, dloss.reshape(1).float().contiguous(), row_lse, dl,
+               smoothing=label_smoothing)
     return dl
 
 
@@ -375,18 +377,18 @@ class _JointOpFn(torch.autograd.Function):
 
 class _CEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, vocab):
-        loss, inv, lse = torch.ops.mmbert.mlm_head_ce_fwd(logits, labels, vocab)
-        ctx.vocab = vocab
+    def forward(ctx, logits, labels, vocab, label_smoothing=0.0):
+        loss, inv, lse = torch.ops.mmbert.mlm_head_ce_fwd(logits, labels, vocab, label_smoothing)
+        ctx.vocab, ctx.smoothing = vocab, label_smoothing
         ctx.save_for_backward(logits, labels, inv, lse)
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
         logits, labels, inv, lse = ctx.saved_tensors
-        return torch.ops.mmbert.mlm_head_ce_bwd(dloss, logits, labels, ctx.vocab, inv, lse).to(logits.dtype), None, None
+        return torch.ops.mmbert.mlm_head_ce_bwd(dloss, logits, labels, ctx.vocab, inv, lse, ctx.smoothing).to(logits.dtype), None, None, None
 
 
 _lib.impl("embed_ln", lambda ids, tt, w, t, p_, g, b, eps, p=0.0, seed=0: _EmbFn.apply(ids, tt, w, t, p_, g, b, eps, p, seed), "AutogradCUDA")
 _lib.impl("joint_embed", lambda te, pr, w, b, g, be, eps=1e-5, p=0.0, seed=0: _JointOpFn.apply(te, pr, w, b, g, be, eps, p, seed), "AutogradCUDA")
-_lib.impl("mlm_head_ce", lambda lg, lab, vocab: _CEFn.apply(lg, lab, vocab), "AutogradCUDA")
+_lib.impl("mlm_head_ce", lambda lg, lab, vocab, label_smoothing=0.0: _CEFn.apply(lg, lab, vocab, label_smoothing), "AutogradCUDA")

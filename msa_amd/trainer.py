@@ -242,6 +242,37 @@ def default_args(**kw):
     return types.SimpleNamespace(**d)
 
 
+def balanced_class_weights(labels, C):
+    """Class weights that undo the imbalance of ``labels`` (integer classes in [0, C)): N / (C * max(count_c, 1)), float32 [C] -- sklearn's
+    ``class_weight="balanced"``, with an absent class counted once so that every weight stays finite."""
+    y = torch.as_tensor(labels).reshape(-1).long()
+    if y.numel() and (int(y.min()) < 0 or int(y.max()) >= int(C)):
+        raise ValueError(f"balanced_class_weights: labels outside [0, {C})")
+    count = torch.bincount(y, minlength=int(C)).clamp(min=1).to(torch.float64)
+    return (float(y.numel()) / (float(C) * count)).to(torch.float32)
+
+
+def apply_loss_options(model, args, train_dataset=None):
+    """``model.set_loss_options`` from the optional ``args.label_loss`` ("mse" | "l1" | "huber"), ``args.huber_delta``, ``args.class_weights``
+    (a sequence of C values, or "balanced": ``balanced_class_weights`` of ``train_dataset``'s labels), ``args.label_smoothing`` and
+    ``args.mlm_label_smoothing``.  ``default_args()`` has none of them: a model is then left exactly as it is (options set by hand stay).
+    Returns whether anything was set."""
+    names = ("label_loss", "huber_delta", "class_weights", "label_smoothing", "mlm_label_smoothing")
+    if not any(hasattr(args, n) for n in names):
+        return False
+    cw = getattr(args, "class_weights", None)
+    if isinstance(cw, str):
+        if cw != "balanced":
+            raise ValueError(f"args.class_weights = {cw!r}: a sequence of weights or \"balanced\"")
+        if train_dataset is None:
+            raise ValueError("args.class_weights = \"balanced\" needs the training set's labels (train_dataset)")
+        C = int(model.num_labels)
+        cw = balanced_class_weights([int(train_dataset[i][3]) for i in range(len(train_dataset))], C)     # (an example's 4th field: its label)
+    model.set_loss_options(regression=getattr(args, "label_loss", "mse"), huber_delta=getattr(args, "huber_delta", 1.0), class_weights=cw,
+                           label_smoothing=getattr(args, "label_smoothing", 0.0), mlm_label_smoothing=getattr(args, "mlm_label_smoothing", 0.0))
+    return True
+
+
 def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
     """REF:train.py:76-97: two parameter groups by NAME substring, AdamW, linear warm-up with
     warmup = N and total = warmup_proportion * N.
@@ -382,7 +413,8 @@ def mlm_eval_epoch(args, model, data, tokenizer=None, *, device="cuda", generato
     ``batches`` = an iterable of model-kwargs dicts (``input_ids`` / ``token_type_ids`` / ``attention_mask`` / ``masked_labels``).
     Returns {"text" | "visual" | "speech": dict(count = labelled positions, loss = token-weighted mean negative log-likelihood over the
     epoch, perplexity = exp(loss), top1 / topk = share of positions whose label is the first / among the first ``top_k`` predictions,
-    mrr = mean of 1 / (rank + 1))}; a pass without labelled positions (an empty dataset: every pass) gives zeros and count = 0.  The
+    mrr = mean of 1 / (rank + 1))} -- ``loss`` is the PLAIN negative log-likelihood whatever ``model.mlm_label_smoothing`` is (smoothing shapes
+    the training objective, not the reported likelihood); a pass without labelled positions (an empty dataset: every pass) gives zeros and count = 0.  The
     sums stay on the device: one device->host transfer at the end.  Leaves ``model.training`` as it found it."""
     import math
     names = ("text", "visual", "speech")
@@ -474,12 +506,15 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
     without improvement the best predictions / targets go to ``predict.npy`` / ``target.npy`` and the loop stops.
     ``epoch_batches``: optional callable ``(split, epoch) -> iterable of model kwargs`` replacing the datasets (synthetic data).
     ``args.max_grad_norm``, when present, reaches every epoch's train_epoch (global-norm clipping).
+    ``args.label_loss`` / ``huber_delta`` / ``class_weights`` / ``label_smoothing`` / ``mlm_label_smoothing``, when present, are set on the
+    model first (apply_loss_options).
     An optimizer with a weight EMA (``AdamW.ema``; ``args.ema_decay`` through build_optimizer): each epoch's validation, test and saved
     state dict use the averaged weights (``optimizer.ema_weights()``); training goes on from the trained ones.
     Returns a dict with the best epoch's numbers and the per-epoch history."""
     import os
     import numpy as np
     log = logger.info if logger is not None else (lambda *a, **k: None)
+    apply_loss_options(model, args, train_dataset)
     save_dir = _dated_dir(save_root)
     log("Model save path: {}".format(save_dir))
     score = test_MSE_score_model if getattr(args, "num_labels", 7) in (1, 7) else test_CE_score_model
