@@ -1,0 +1,1054 @@
+"""Every launch of a real training step, recorded and recomputed in float64 from its own recorded operands.
+
+Not a test module (pytest does not collect it): ``from tests import step_stages as SS``.  Importing it needs no GPU.
+
+``record(model)`` wraps the ``msa_amd.ops`` entry points a training step goes through (``SPIED``, plus ``LnDeferred.flush``: the deferred
+LayerNorm reduce) and restores them on exit.  While they are wrapped the model takes its per-launch path (``ops.launches_unwrapped()`` is
+false); the composite layer calls are bit-identical to it (tests/test_model_gpu.py::test_composite_layer_calls_are_bit_identical).  For
+every call a ``Call`` keeps: the op name, a clone of every tensor operand taken BEFORE the call on the stream the call is issued on
+(``a``: the bound arguments by name; layouts, row inverses and the deferred collector as small snapshots), every non-tensor keyword, a
+clone AFTER the call of every operand the op writes (``post``: output buffers handed in, accumulated gradients) and clones of what it
+returns (``ret``).  The recorder keeps the original tensors alive until it exits, so an address is never handed out twice while it
+records: a storage address identifies a buffer.  It changes nothing else -- the step's results are bit-identical with and without it.
+
+``recompute(call)`` maps the recorded operands and keywords of one call onto the float64 reference of that op and judges the recorded
+outputs by THAT reference's ``check`` -- no tolerance of its own:
+
+    gemm_nt (bias, gelu + aux, resid, dropout, gelu_bwd_u, fp32 out)   gemm_ref.nt          gemm_nt_splitk          gemm_ref.splitk
+    gemm_tn / gemm_tn_grouped (W0, bias sums, per-problem flags)       gemm_ref.tn / tn_grouped
+    attn_fwd / attn_bwd (packed layouts, kv_len, q_limit, dropout)     attention_ref.reference
+    ln_fwd / ln_bwd (row maps, both dropouts, dx2)                     rowwise_ref.ln_fwd / ln_bwd
+    ln_bwd_reduce (LnDeferred.flush)                                   the float64 sum of its calls' rowwise_ref.ln_bwd sums
+    ce_fwd / ce_bwd                                                    rowwise_ref.ce_fwd / ce_bwd
+    embed_gather / embed_scatter / pair_proj_fwd / pair_proj_bwd       embed_ref.gather / scatter / pair_fwd / pair_bwd
+    gather_rows / scatter_rows_zero / attn_q_limit                     exact (layout_ref.scatter_ref for the stamped inverse)
+    gelu_bwd                                                           ``gelu_bwd_ref`` below
+
+Dropout keep masks are rebuilt from the (stream, thr16, scale) triple recorded IN the call, through ``ops.dropout_mask`` /
+``ops.attn_dropout_mask`` on a GPU and through their exact CPU references (tests/layout_ref.py) without one.  An adapter that cannot
+express a keyword raises: an unrecomputed launch is a failure, never a skip.
+
+``gelu_bwd_ref``: du = bf16(dy * gelu'(u)) on bf16 operands -- gemm_ref's GELU' epilogue with the accumulator replaced by the exact bf16
+``dy``: val = dy * gelu'(u), one fp32 product (acc = |gelu'(u)| |dy|, times C_ACC 2^-24), the erf approximation GELUP_ABS |dy| and the
+bf16 rounding of the output; judged by ``gemm_ref.check``.  Its emulation (fp32 product, bf16 rounding) reaches 0.5 of the bound
+(tests/test_step_stages_reference_cpu.py).
+
+``check_dataflow(calls, model)`` checks the wiring with exact comparisons only:
+
+ 1. the trunk's op sequence is the table below for the flags in force (``FWD_LAYER`` per layer and forward pass; per backward pass and
+    layer, top down, ``BWD_DENSE`` or one of ``BWD_TOP_SPARSE``);
+ 2. every operand a call reads is bit-equal to what the last writer of those addresses left there (a shadow copy of every storage the
+    recorded calls wrote, replayed in issue order): forward chains, every saved activation backward reads, accumulated gradients --
+    in-place reuse, aliasing and a read that overtook its producer on another stream all show here;
+ 3. each backward stage reads the residual, the GELU' operand, the LayerNorm statistics and the attention operands of the SAME layer's
+    forward stage, each forward stage its predecessor's output, each weight-gradient problem its two stages (``_wiring``); the row lists
+    of the sparse top layer agree with each other; ``kv_len`` is the count the recorded key bias implies;
+ 4. every ``W*T`` operand is the transpose of the bf16 working copy the forward read, and that copy is the parameter rounded to bf16;
+ 5. forward and backward of a dropout site carry the same triple, two different sites different streams;
+ 6. every gradient buffer a stage wrote is the view named for that stage, at the address of the parameter's ``.grad``.
+
+Not covered: the fused pretraining / classification heads (``heads_step_*``) and the step prologue.  tests/test_heads_gpu.py and
+tests/test_layout_gpu.py hold them to references at the operands the model passes; the recorder takes their outputs as given inputs.
+"""
+from __future__ import annotations
+
+import contextlib
+import inspect
+import math
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from tests import attention_ref as A
+from tests import embed_ref as E
+from tests import gemm_ref as G
+from tests import layout_ref as LR
+from tests import rowwise_ref as R
+
+SPIED = ("gemm_nt", "gemm_nt_splitk", "gemm_tn", "gemm_tn_grouped", "attn_fwd", "attn_bwd", "attn_q_limit", "ln_fwd", "ln_bwd", "gelu_bwd",
+         "embed_gather", "embed_scatter", "pair_proj_fwd", "pair_proj_bwd", "ce_fwd", "ce_bwd", "gather_rows", "scatter_rows_zero")
+# operands an op writes (cloned again after the call); ACCUMULATES: of those, the ones whose previous value the op reads
+WRITES = {"gemm_nt": ("out", "aux"), "gemm_nt_splitk": ("out",), "gemm_tn": ("W", "bias_out"), "gemm_tn_grouped": ("problems",),
+          "attn_fwd": ("ctx", "lse"), "attn_bwd": ("dqkv",), "ln_fwd": ("out", "stats"), "ln_bwd": ("dx", "dx2", "dgamma", "dbeta", "dbias2"),
+          "gelu_bwd": ("du",), "embed_gather": ("out",), "embed_scatter": ("gword", "gtype", "gpos"), "pair_proj_fwd": ("out",),
+          "pair_proj_bwd": ("dW", "db"), "ce_bwd": ("dlogits",)}
+ACCUMULATES = {"gemm_tn": ("bias_out",), "embed_scatter": ("gword", "gtype", "gpos"), "pair_proj_bwd": ("dW", "db"), "pair_proj_fwd": ("out",),
+               "ln_fwd": ("out",)}          # (the last two write some rows of a larger matrix: the others keep their values)
+
+# ---- the op sequence of the trunk (check 1): stage names, see ``_stage``
+FWD_LAYER = ("qkv", "attn_fwd", "z1", "ln1", "g", "z2", "ln2")                                  # model._EncoderFn.run_forward, per-launch body
+BWD_DENSE = ("ln2_bwd", "du", "dy1", "ln1_bwd", "dctx", "attn_bwd", "dx")                        # ... run_backward, dense body
+BWD_TOP_SPARSE = (                                                                              # ... _last_layer_sparse
+    ("gather_rows8", "ln2_bwd", "du", "dy1", "ln1_bwd", "dctx", "scatter_rows_zero", "attn_q_limit", "attn_bwd", "dx"),    # compact hand-over
+    ("gather_rows1", "gather_rows8", "ln2_bwd", "du", "dy1", "ln1_bwd", "dctx", "attn_q_limit", "attn_bwd", "dx"))         # dense dy, gathered
+# (gather_rows<n>: n tensors gathered in the launch -- 8 saved activations of the top layer, 1 = the output gradient; the MLM head's own
+# gather of 6 is not part of the trunk)
+_NT_STAGE = {"Wqkv": "qkv", "Wo": "z1", "W1": "g", "W2": "z2", "W2T": "du", "W1T": "dy1", "WoT": "dctx", "WqkvT": "dx",
+             "Wt": "mlm_t0", "word_h": "logits", "wordT": "mlm_dt", "WtT": "mlm_dy"}
+_LN_STAGE = {"ln1_g": "ln1", "ln2_g": "ln2", "emb_ln_g": "emb_ln", "joint_ln_g": "joint_ln", "mlm_ln_g": "mlm_ln"}
+_TRANSPOSED = {"W2T": "W2", "W1T": "W1", "WoT": "Wo", "WqkvT": "Wqkv", "WtT": "Wt", "wordT": "word_h"}
+_PARAM_OF = {"Wqkv": "attention.self.query.weight", "Wo": "attention.output.dense.weight", "W1": "intermediate.dense.weight",
+             "W2": "output.dense.weight", "bqkv": "attention.self.query.bias", "bo": "attention.output.dense.bias",
+             "b1": "intermediate.dense.bias", "b2": "output.dense.bias", "ln1_g": "attention.output.LayerNorm.weight",
+             "ln1_b": "attention.output.LayerNorm.bias", "ln2_g": "output.LayerNorm.weight", "ln2_b": "output.LayerNorm.bias"}
+_PARAM_OF_W = {"word_pad": "bert.embeddings.word_embeddings.weight", "word": "bert.embeddings.word_embeddings.weight",
+               "type": "bert.embeddings.token_type_embeddings.weight", "pos": "bert.embeddings.position_embeddings.weight",
+               "emb_ln_g": "bert.embeddings.LayerNorm.weight", "emb_ln_b": "bert.embeddings.LayerNorm.bias",
+               "joint_ln_g": "bert.jointEmbeddings.LayerNorm.weight", "joint_ln_b": "bert.jointEmbeddings.LayerNorm.bias",
+               "Wv_w": "bert.jointEmbeddings.Wv.weight", "Wv_b": "bert.jointEmbeddings.Wv.bias", "Ws_w": "bert.jointEmbeddings.Ws.weight",
+               "Ws_b": "bert.jointEmbeddings.Ws.bias", "pred_bias": "cls.predictions.bias", "bt": "cls.predictions.transform.dense.bias",
+               "mlm_ln_g": "cls.predictions.transform.LayerNorm.weight", "mlm_ln_b": "cls.predictions.transform.LayerNorm.bias",
+               "Wt": "cls.predictions.transform.dense.weight"}
+
+
+# ------------------------------------------------------------------------------------------------ recorded values
+_BITS = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+class Rec:
+    """A recorded tensor: a clone (``t``, on the tensor's device; ``cpu()`` caches the host copy) and where the original lived --
+    storage address and size, offset, shape, strides."""
+    __slots__ = ("t", "_cpu", "live", "sptr", "sbytes", "off", "shape", "stride", "dtype", "ptr")
+
+    def __init__(self, t, hold=True):
+        self.t = t.detach().clone()
+        self._cpu = None
+        self.live = t if hold else None
+        st = t.untyped_storage()
+        self.sptr, self.sbytes, self.off = st.data_ptr(), st.nbytes(), t.storage_offset()
+        self.shape, self.stride, self.dtype, self.ptr = tuple(t.shape), tuple(t.stride()), t.dtype, t.data_ptr()
+
+    def cpu(self):
+        if self._cpu is None:
+            self._cpu = self.t.cpu()
+        return self._cpu
+
+    def region(self):
+        """What identifies the buffer a row-matrix lives in, whatever number of leading rows a view of it has."""
+        return (self.ptr, self.stride, self.shape[1:], self.dtype)
+
+
+@dataclass
+class LayoutSnap:
+    lens: list
+    heads: int
+    split: bool
+    dropped: bool
+    elem_base: list
+    bias_start: object
+    seq_start: object
+    kv_len: object = None
+    inv: object = None
+
+
+@dataclass
+class Call:
+    op: str
+    a: dict
+    post: dict = field(default_factory=dict)
+    ret: object = None
+    meta: dict = field(default_factory=dict)
+    index: int = -1
+
+
+def _c(x):
+    """Host value of a recorded tensor / plain tensor / None."""
+    if x is None:
+        return None
+    return x.cpu() if isinstance(x, Rec) else x.detach().cpu() if torch.is_tensor(x) else x
+
+
+def _snap(v, hold=True):
+    if torch.is_tensor(v):
+        return Rec(v, hold)
+    if isinstance(v, (list, tuple)):
+        return type(v)(_snap(x, hold) for x in v)
+    if hasattr(v, "lens") and hasattr(v, "heads") and hasattr(v, "seq_start"):
+        base = getattr(v, "base", v)
+        split = bool(getattr(v, "split", False))
+        return LayoutSnap(list(v.lens), int(v.heads), split, bool(getattr(v, "dropped", False)), list(base.elem_base_host),
+                          _snap(base.bias_start, False), _snap(v.seq_start, False), _snap(v.kv_len, False) if split else None,
+                          _snap(v.inv, False) if split else None)
+    if hasattr(v, "table") and hasattr(v, "stamp"):
+        return dict(table=_snap(v.table, False), stamp=int(v.stamp), nlist=int(v.nlist))
+    if hasattr(v, "flush") and hasattr(v, "items"):
+        return "deferred"
+    return v
+
+
+def _recs(v):
+    if isinstance(v, Rec):
+        yield v
+    elif isinstance(v, (list, tuple)):
+        for x in v:
+            yield from _recs(x)
+
+
+def synth(op, a, ret=None, post=None, meta=None):
+    """A Call built from live tensors (the CPU chain of tests/test_step_stages_reference_cpu.py): ``a`` as the op was handed it, ``post``
+    / ``ret`` as it left them."""
+    return Call(op, {k: _snap(v) for k, v in a.items()}, {k: _snap(v) for k, v in (post or {}).items()}, _snap(ret), dict(meta or {}))
+
+
+# ------------------------------------------------------------------------------------------------ the recorder
+@contextlib.contextmanager
+def record(model=None):
+    """Wraps the spied ``msa_amd.ops`` entry points; yields the list the calls are appended to (complete when the block exits: it
+    synchronises, indexes the calls and lets go of the original tensors)."""
+    from msa_amd import ops
+    calls, orig, by_ptr, by_ws = [], {}, {}, {}
+
+    def wrap(name, fn):
+        sig = inspect.signature(fn)
+
+        def spy(*args, **kw):
+            b = sig.bind(*args, **kw)
+            b.apply_defaults()
+            call = Call(name, {k: _snap(v) for k, v in b.arguments.items()})
+            call.meta["stream"] = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0
+            call.meta["det"] = bool(ops.deterministic()) if name == "embed_scatter" else None
+            out = fn(*args, **kw)
+            call.ret = _snap(out)
+            for k in WRITES.get(name, ()):
+                if b.arguments.get(k) is not None and not isinstance(b.arguments[k], bool):
+                    call.post[k] = _snap(b.arguments[k])
+            if name == "ln_bwd":
+                for k in ("dgamma", "dbeta"):
+                    by_ptr[b.arguments[k].data_ptr()] = b.arguments[k]
+                d = b.arguments.get("deferred")
+                if d is not None:
+                    by_ws[d.items[-1][0]] = call
+            calls.append(call)
+            return out
+        return spy
+
+    flush0 = ops.LnDeferred.flush
+
+    def flush(self):
+        items = list(self.items)
+        if not items:
+            return flush0(self)
+        targets = [(by_ptr[it[1]], by_ptr[it[2]]) for it in items]
+        call = Call("ln_bwd_reduce", dict(pre=[(_snap(g), _snap(b)) for g, b in targets], H=self.H))
+        call.meta["calls"] = [by_ws[it[0]] for it in items]
+        call.meta["stream"] = torch.cuda.current_stream().cuda_stream
+        out = flush0(self)
+        call.post["grads"] = [(_snap(g), _snap(b)) for g, b in targets]
+        calls.append(call)
+        return out
+
+    for n in SPIED:
+        orig[n] = getattr(ops, n)
+        setattr(ops, n, wrap(n, orig[n]))
+    ops.LnDeferred.flush = flush
+    try:
+        yield calls
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+    finally:
+        for n, f in orig.items():
+            setattr(ops, n, f)
+        ops.LnDeferred.flush = flush0
+        for i, c in enumerate(calls):
+            c.index = i
+            for r in list(_recs(list(c.a.values()))) + list(_recs(list(c.post.values()))) + list(_recs(c.ret)):
+                r.live = None
+
+
+# ------------------------------------------------------------------------------------------------ dropout masks
+def _on_gpu():
+    return torch.cuda.is_available()
+
+
+def flat_mask(n, drop):
+    """The keep mask of elements 0 .. n-1 of a dropout site, from the triple the call carried."""
+    if _on_gpu():
+        from msa_amd import ops
+        return ops.dropout_mask(int(n), tuple(drop), "cuda").cpu()
+    return torch.from_numpy(LR.dropout_mask_ref(int(n), int(drop[0]), int(drop[1])))
+
+
+def attn_masks(lay: LayoutSnap, drop):
+    if not drop or not drop[1]:
+        return None
+    out = []
+    for s, S in enumerate(lay.lens):
+        if _on_gpu():
+            from msa_amd import ops
+            m = torch.stack([ops.attn_dropout_mask(S, lay.elem_base[s], h, tuple(drop), "cuda") for h in range(lay.heads)]).cpu()
+        else:
+            m = torch.from_numpy(np.stack([LR.attn_dropout_mask_ref(S, lay.elem_base[s], h, int(drop[0]), int(drop[1])) for h in range(lay.heads)]))
+        out.append(m)
+    return out
+
+
+def _on(drop):
+    return bool(drop) and bool(drop[1])
+
+
+# ------------------------------------------------------------------------------------------------ adapters
+def gelu_bwd_ref(dy, u, emu=False):
+    """mmbert_gelu_bwd: du = bf16(dy * gelu'(u)), see the module docstring."""
+    d, gp = dy.to(torch.float64).reshape(1, -1), G.gelu_grad64(u.to(torch.float64).reshape(1, -1))
+    if emu:
+        return G._bf(G._f32(d * G._f32(gp))).reshape(dy.shape)
+    return G.Ref(d * gp, gp.abs() * d.abs(), G.GELUP_ABS * d.abs(), G.U_BF16, (1, 4096))
+
+
+def _nt_tile(M, N, K, epi):
+    if _on_gpu():
+        from msa_amd import ops
+        r, c = ops.gemm_nt_describe(M, N, K, epi, with_queue=ops.dynamic_tile_queue)["tile"].split("x")
+        return int(r), int(c)
+    return (128, 128)
+
+
+def _r_gemm_nt(c):
+    a = c.a
+    A_, B_ = _c(a["A"]), _c(a["B"])
+    M, K = A_.shape
+    N = B_.shape[0]
+    drop, keep = a.get("drop"), None
+    if _on(drop):
+        if a["resid"] is None:
+            raise NotImplementedError("gemm_nt: dropout without a residual")
+        keep = flat_mask(M * N, drop).view(M, N)
+    if a.get("gelu") and (a.get("resid") is not None or a.get("gelu_bwd_u") is not None):
+        raise NotImplementedError("gemm_nt: gelu together with resid / gelu_bwd_u")
+    epi = (1 if a["bias"] is not None else 0) | (2 if a["gelu"] else 0) | (4 if a["resid"] is not None else 0) | \
+          (8 if a["gelu_bwd_u"] is not None else 0) | (16 if a["out_f32"] else 0)
+    ad = a.get("alpha_dev")
+    ref = G.nt(A_, B_, bias=_c(a["bias"]), gelu=bool(a["gelu"]), resid=_c(a["resid"]), keep=keep, drop_scale=drop[2] if keep is not None else 1.0,
+               gelu_u=_c(a["gelu_bwd_u"]), alpha=a["alpha"], alpha_dev=None if ad is None else float(_c(ad).reshape(-1)[0]),
+               out_f32=bool(a["out_f32"]), tile=_nt_tile(M, N, K, epi))
+    res = [("out", G.check(_c(c.ret), ref["out"], "gemm_nt out").worst)]
+    if a["aux"] is not None:
+        if not a["gelu"]:
+            raise NotImplementedError("gemm_nt: aux without gelu")
+        res.append(("aux", G.check(_c(c.post["aux"]), ref["aux"], "gemm_nt aux").worst))
+    return res
+
+
+def _r_splitk(c):
+    ref = G.splitk(_c(c.a["A"]), _c(c.a["B"]), resid=_c(c.a["resid"]))
+    return [("out", G.check(_c(c.ret), ref["out"], "gemm_nt_splitk").worst)]
+
+
+def _tn_splits(M, N, K):
+    if _on_gpu():
+        import ctypes
+        from msa_amd import _lib
+        sp = ctypes.c_int(0)
+        _lib.load().mmbert_gemm_tn_workspace(M, N, K, ctypes.byref(sp))
+        return max(1, sp.value)
+    return 1
+
+
+def _r_gemm_tn(c):
+    a = c.a
+    A_, B_ = _c(a["A"]), _c(a["B"])
+    ad = a.get("alpha_dev")
+    ref = G.tn(A_, B_, W0=_c(a["W"]), bias0=_c(a["bias_out"]), with_bias=a["bias_out"] is not None, alpha=a["alpha"],
+               alpha_dev=None if ad is None else float(_c(ad).reshape(-1)[0]), accumulate=bool(a["accumulate"]),
+               splits=_tn_splits(A_.shape[0], A_.shape[1], B_.shape[1]))
+    res = [("W", G.check(_c(c.post["W"]), ref["W"], "gemm_tn W").worst)]
+    if a["bias_out"] is not None:
+        res.append(("bias", G.check(_c(c.post["bias_out"]), ref["bias"], "gemm_tn bias").worst))
+    return res
+
+
+def tn_flags(c):
+    acc, n = c.a["accumulate"], len(c.a["problems"])
+    return [bool(x) for x in acc] if isinstance(acc, (list, tuple)) else [bool(acc)] * n
+
+
+def _r_tn_grouped(c):
+    probs = [tuple(_c(x) for x in p) for p in c.a["problems"]]
+    refs = G.tn_grouped(probs, tn_flags(c), alpha=c.a["alpha"])
+    res = []
+    for i, (r, p) in enumerate(zip(refs, c.post["problems"])):
+        res.append(("W", G.check(_c(p[2]), r["W"], f"gemm_tn_grouped problem {i} W").worst))
+        if p[3] is not None:
+            res.append(("bias", G.check(_c(p[3]), r["bias"], f"gemm_tn_grouped problem {i} bias").worst))
+    return res
+
+
+def _token_bias(c, seq, pos):
+    """The additive key bias per token of the original order: ops.attn_* take it padded per sequence (ops.pad_key_bias) or per token."""
+    kb = _c(c.a["key_bias"]).float()
+    if kb.numel() == seq.numel():
+        return kb
+    return kb[_c(c.a["layout"].bias_start).long()[seq] + pos]
+
+
+def _attn_inputs(c):
+    """The call's operands in the ORIGINAL row order: (layout, qkv, key bias per token with the keys behind kv_len removed, the
+    original row of every packed row or None, bool [tokens]: the rows backward covers)."""
+    lay = c.a["layout"]
+    if lay.dropped:
+        raise NotImplementedError("attention: the region-B-dropped packing")
+    lens, M = lay.lens, sum(lay.lens)
+    seq = torch.repeat_interleave(torch.arange(len(lens)), torch.tensor(lens))
+    pos = torch.cat([torch.arange(n) for n in lens])
+    bias = _token_bias(c, seq, pos).double()
+    kv = _c(lay.kv_len) if lay.split else _c(c.a.get("kv_len"))
+    region_a = torch.ones(M, dtype=torch.bool)
+    if kv is not None:
+        kv = kv.long()
+        bias = torch.where(pos >= kv[seq], torch.full_like(bias, -1.0e30), bias)
+        if lay.split:
+            region_a = pos < kv[seq]
+    return lay, bias, (_c(lay.inv).long() if lay.split else None), region_a, seq, pos
+
+
+def _unpacked(t, inv, M):
+    """Packed rows -> original order; rows the packed matrix does not hold (backward's region B) read as zero."""
+    if inv is None:
+        return t
+    t2 = torch.cat((t, t.new_zeros((1,) + tuple(t.shape[1:]))))
+    return t2[inv.clamp(max=t.shape[0])]
+
+
+def _r_attn_fwd(c):
+    lay, bias, inv, _ra, _s, _p = _attn_inputs(c)
+    M = sum(lay.lens)
+    drop = c.a.get("drop")
+    ref = A.reference(_unpacked(_c(c.a["qkv"]), inv, M), bias, lay.lens, lay.heads, attn_masks(lay, drop), drop[2] if _on(drop) else 1.0)
+    got = {"ctx": _unpacked(_c(c.ret[0]), inv, M).double(), "lse": _unpacked(_c(c.ret[1]), inv, M).double()}
+    return sorted(A.check(got, ref, lay.lens, lay.heads, "attn_fwd").items())
+
+
+def _r_attn_bwd(c):
+    lay, bias, inv, region_a, seq, pos = _attn_inputs(c)
+    M = sum(lay.lens)
+    drop = c.a.get("drop")
+    dctx = _unpacked(_c(c.a["dctx"]), inv, M)
+    ql = _c(c.a.get("q_limit"))
+    if ql is not None:
+        beyond = pos >= ql.long()[seq]
+        assert float(dctx[beyond].float().abs().max()) == 0.0 if bool(beyond.any()) else True, "attn_bwd: a non-zero dctx row at or past q_limit"
+    ref = A.reference(_unpacked(_c(c.a["qkv"]), inv, M), bias, lay.lens, lay.heads, attn_masks(lay, drop), drop[2] if _on(drop) else 1.0, dctx)
+    d = _unpacked(_c(c.ret), inv, M).double()
+    H = d.shape[1] // 3
+    got = {"dq": d[:, :H], "dk": d[:, H:2 * H], "dv": d[:, 2 * H:]}
+    return sorted(A.check(got, ref, lay.lens, lay.heads, "attn_bwd", rows=None if bool(region_a.all()) else region_a).items())
+
+
+def _r_q_limit(c):
+    lay = c.a["layout"]
+    st = _c(lay.seq_start).long()
+    rows = _c(c.a["rows32"]).long()
+    s = torch.searchsorted(st, rows, right=True) - 1
+    want = torch.zeros(len(lay.lens), dtype=torch.long).scatter_reduce_(0, s, rows - st[s] + 1, "amax")
+    assert torch.equal(_c(c.ret).long(), want), "attn_q_limit differs from 1 + the largest listed query index per sequence"
+    return [("out", 0.0)]
+
+
+def _site_keep(drop, rows, H):
+    return flat_mask(rows * H, drop).view(rows, H) if _on(drop) else None
+
+
+def _r_ln_fwd(c):
+    a = c.a
+    x = _c(a["x"])
+    H = x.shape[1]
+    M = a["M"] if a["M"] is not None else (_c(a["in_rows"]).numel() if a["in_rows"] is not None else x.shape[0])
+    drop = a.get("drop")
+    ref = R.ln_fwd(x, _c(a["gamma"]), _c(a["beta"]), a["eps"], M=M, in_rows=_c(a["in_rows"]), out_rows=_c(a["out_rows"]),
+                   keep=_site_keep(drop, M + a["drop_row0"], H), dscale=drop[2] if _on(drop) else 1.0, drop_row0=a["drop_row0"])
+    y, mean, rstd = c.ret
+    res = [("y", R.check(_c(y), ref["y"], "ln_fwd y").worst)]
+    if mean is not None:
+        res += [("mean", R.check(_c(mean), ref["mean"], "ln_fwd mean").worst), ("rstd", R.check(_c(rstd), ref["rstd"], "ln_fwd rstd").worst)]
+    return res
+
+
+def ln_bwd_refs(c, dgamma0=None, dbeta0=None):
+    a = c.a
+    if a.get("dbias2") is not None:
+        raise NotImplementedError("ln_bwd: dbias2")
+    x = _c(a["x"])
+    H = x.shape[1]
+    M = a["M"] if a["M"] is not None else _c(a["mean"]).numel()
+    dr = _c(a["drop_rows"])
+    site = int(dr.max()) + 1 if dr is not None and dr.numel() else M
+    po, pr = a.get("post_drop"), a.get("pre_drop")
+    return R.ln_bwd(_c(a["dy"]), x, _c(a["mean"]), _c(a["rstd"]), _c(a["gamma"]), M=M, dy_rows=_c(a["dy_rows"]), x_rows=_c(a["x_rows"]),
+                    dx_rows=_c(a["dx_rows"]), drop_rows=dr, dy_row_limit=a["dy_row_limit"], post_keep=_site_keep(po, site, H),
+                    post_scale=po[2] if _on(po) else 1.0, pre_keep=_site_keep(pr, site, H), pre_scale=pr[2] if _on(pr) else 1.0,
+                    dx2=a["dx2"] is not None, dgamma0=dgamma0, dbeta0=dbeta0, adds=8)
+
+
+def _r_ln_bwd(c):
+    deferred = c.a.get("deferred") is not None
+    ref = ln_bwd_refs(c) if deferred else ln_bwd_refs(c, _c(c.a["dgamma"]), _c(c.a["dbeta"]))
+    c.meta["refs"] = ref
+    res = [("dx", R.check(_c(c.ret), ref["dx"], "ln_bwd dx").worst)]
+    if c.a["dx2"] is not None:
+        res.append(("dx2", R.check(_c(c.post["dx2"]), ref["dx2"], "ln_bwd dx2").worst))
+    if not deferred:
+        res += [(k, R.check(_c(c.post[k]), ref[k], "ln_bwd " + k).worst) for k in ("dgamma", "dbeta")]
+    return res
+
+
+def _r_ln_reduce(c):
+    """The gamma / beta gradients after the reduce against value before + the float64 sums of every call folded into them."""
+    groups = {}
+    for j in range(len(c.meta["calls"])):
+        groups.setdefault(c.a["pre"][j][0].ptr, []).append(j)
+    res = []
+    for js in groups.values():
+        refs = [c.meta["calls"][j].meta.get("refs") or ln_bwd_refs(c.meta["calls"][j]) for j in js]
+        for q, k in enumerate(("dgamma", "dbeta")):
+            pre = _c(c.a["pre"][js[0]][q]).double()
+            tot = R.Ref(pre + sum(r[k].val for r in refs), sum(r[k].acc for r in refs) + 8.0 * pre.abs(), 0.0, R.U_F32)
+            res.append((k, R.check(_c(c.post["grads"][js[-1]][q]), tot, f"ln_bwd_reduce {k} ({len(js)} calls)").worst))
+    return res
+
+
+def _r_gelu_bwd(c):
+    return [("du", G.check(_c(c.ret).reshape(1, -1), gelu_bwd_ref(_c(c.a["dy"]), _c(c.a["u"])), "gelu_bwd").worst)]
+
+
+def _r_ce_fwd(c):
+    a = c.a
+    if float(a.get("smoothing") or 0.0) != 0.0:
+        raise NotImplementedError("ce_fwd: label smoothing")
+    nseg = a["nseg"]
+    ref = R.ce_fwd(_c(a["logits"]), _c(a["labels"]), a["V"], _c(a["seg_bounds"]), nseg)
+    loss, inv, lse = c.ret
+    cnt = ref["count"].clamp(min=1).double()
+    assert bool(((_c(inv)[:nseg].double() * cnt - 1.0).abs() <= 2.0 ** -23).all()), "ce_fwd: inv_count"
+    return [("loss", R.check(_c(loss), ref["loss"], "ce loss").worst), ("row_lse", R.check(_c(lse), ref["row_lse"], "ce row_lse").worst)]
+
+
+def _r_ce_bwd(c):
+    a = c.a
+    if float(a.get("smoothing") or 0.0) != 0.0:
+        raise NotImplementedError("ce_bwd: label smoothing")
+    lab, rows = _c(a["labels"]), _c(a["rows"])
+    dl = _c(c.ret)
+    worst = 0.0
+    for j, ref in R.ce_bwd(_c(a["logits"]), lab, a["V"], _c(a["seg_bounds"]), a["nseg"], _c(a["gscale"]), _c(a["lse"]), rows=rows):
+        worst = max(worst, R.check(dl[j], ref, "ce dlogits", gathered=True).worst)
+    src = torch.arange(lab.numel()) if rows is None else rows.long()
+    labelled = (lab[src] >= 0) & (lab[src] < a["V"])
+    assert int((dl[:src.numel()][~labelled].view(torch.int16) != 0).sum()) == 0, "ce_bwd: unlabelled rows of dlogits not exactly zero"
+    return [("dlogits", worst)]
+
+
+def _r_embed_gather(c):
+    a = c.a
+    ref = E.gather(_c(a["ids"]).reshape(-1), None if a["tts"] is None else _c(a["tts"]).reshape(-1), _c(a["word"]), _c(a["type_"]), _c(a["pos"]), a["T"])
+    return [("out", E.check(_c(c.ret), ref, "embed_gather").worst)]
+
+
+def _r_embed_scatter(c):
+    a = c.a
+    ref = E.scatter(_c(a["ids"]).reshape(-1), None if a["tts"] is None else _c(a["tts"]).reshape(-1), _c(a["d"]), a["T"], _c(a["gword"]),
+                    _c(a["gtype"]), _c(a["gpos"]), V=a.get("vocab"), det=bool(c.meta.get("det")))
+    return [(k, E.check(_c(c.post[k]), ref[k], "embed_scatter " + k).worst) for k in ("gword", "gtype", "gpos") if k in ref]
+
+
+def _pair(c):
+    feat = _c(c.a["feat"])
+    B, P, _D = feat.shape
+    return feat, E.pair_rows(B, P, c.a["T"], c.a.get("seq_len"), c.a.get("offset"))
+
+
+def _r_pair_fwd(c):
+    feat, rows = _pair(c)
+    ref = E.pair_fwd(feat, _c(c.a["W"]), _c(c.a["bias"]), rows=rows)
+    out0, out1 = _c(c.a["out"]), _c(c.post["out"])
+    other = torch.ones(out0.shape[0], dtype=torch.bool)
+    other[rows] = False
+    assert torch.equal(out0[other].view(torch.int16), out1[other].view(torch.int16)), "pair_proj_fwd wrote a row outside its pair block"
+    return [("out", E.check(out1, ref, "pair_proj_fwd").worst)]
+
+
+def _cus():
+    return int(torch.cuda.get_device_properties(0).multi_processor_count) if _on_gpu() else E.CUS
+
+
+def _r_pair_bwd(c):
+    feat, rows = _pair(c)
+    ref = E.pair_bwd(feat, _c(c.a["J"])[rows], _c(c.a["dJ"])[rows], _c(c.a["dW"]), _c(c.a["db"]), cus=_cus())
+    return [("dW", E.check(_c(c.post["dW"]), ref["dW"], "pair_proj_bwd dW").worst), ("db", E.check(_c(c.post["db"]), ref["db"], "pair_proj_bwd db").worst)]
+
+
+def _bits(t):
+    return t.contiguous().view(_BITS[t.element_size()])
+
+
+def _r_gather_rows(c):
+    idx = _c(c.a["idx32"]).long()
+    for j, (s, o) in enumerate(zip(c.a["srcs"], c.ret)):
+        assert torch.equal(_bits(_c(s)[idx]), _bits(_c(o))), f"gather_rows: output {j} is not its source's listed rows"
+    return [("out", 0.0)]
+
+
+def _r_scatter_rows(c):
+    inv = c.a["inverse"]
+    take = torch.from_numpy(LR.scatter_ref(_c(inv["table"]).numpy(), inv["stamp"], inv["nlist"], c.a["nrows"]))
+    for j, (s, o) in enumerate(zip(c.a["srcs"], c.ret)):
+        s = _c(s)
+        want = torch.where((take >= 0)[:, None], s[take.clamp(min=0)], torch.zeros_like(s[:1]))
+        assert torch.equal(_bits(want), _bits(_c(o))), f"scatter_rows_zero: output {j}"
+    return [("out", 0.0)]
+
+
+ADAPTERS = {"gemm_nt": _r_gemm_nt, "gemm_nt_splitk": _r_splitk, "gemm_tn": _r_gemm_tn, "gemm_tn_grouped": _r_tn_grouped, "attn_fwd": _r_attn_fwd,
+            "attn_bwd": _r_attn_bwd, "attn_q_limit": _r_q_limit, "ln_fwd": _r_ln_fwd, "ln_bwd": _r_ln_bwd, "ln_bwd_reduce": _r_ln_reduce,
+            "gelu_bwd": _r_gelu_bwd, "ce_fwd": _r_ce_fwd, "ce_bwd": _r_ce_bwd, "embed_gather": _r_embed_gather, "embed_scatter": _r_embed_scatter,
+            "pair_proj_fwd": _r_pair_fwd, "pair_proj_bwd": _r_pair_bwd, "gather_rows": _r_gather_rows, "scatter_rows_zero": _r_scatter_rows}
+
+
+def recompute(call):
+    """[(output name, worst ratio to its reference's bound)] of one recorded call; raises where an output misses its bound (the
+    reference's own ``check``) or the adapter cannot express the call."""
+    if call.op not in ADAPTERS:
+        raise NotImplementedError(f"no reference adapter for {call.op}")
+    try:
+        return ADAPTERS[call.op](call)
+    except AssertionError as e:
+        raise AssertionError(f"call {call.index} ({call.op}, stage {call.meta.get('stage')} layer {call.meta.get('layer')}): {e}") from None
+
+
+def recompute_all(calls, model=None):
+    """Every call recomputed: {op kind: [number of calls, worst ratio]}.  ``model``: the calls are given their stage names first (a
+    failure then says which stage of which layer it was)."""
+    if model is not None:
+        annotate(calls, model)
+    out = {}
+    for c in calls:
+        worst = max([float(r) for _, r in recompute(c)] + [0.0])
+        n, w = out.get(c.op, (0, 0.0))
+        out[c.op] = (n + 1, max(w, worst))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ dataflow
+def names_of(model):
+    """{address: [names]} of the model's weight, working-copy, transposed-copy and gradient views ("l3.W1T", "g_word_pad", ...)."""
+    out = {}
+    for i, lw in enumerate(model._lw):
+        for k, v in lw.items():
+            if torch.is_tensor(v):
+                out.setdefault(v.data_ptr(), []).append(f"l{i}.{k}")
+    for k, v in model._w.items():
+        if torch.is_tensor(v):
+            out.setdefault(v.data_ptr(), []).append(k)
+    return out
+
+
+def _name(names, rec, among=None):
+    for n in names.get(rec.ptr, []) if rec is not None else []:
+        base = n.split(".")[-1]
+        if among is None or base in among:
+            return n
+    return None
+
+
+def _stage(c, names, qkv_layer):
+    """(stage name, layer or None) of a call, from the weight / gamma operand it carries."""
+    op = c.op
+    if op in ("gemm_nt", "gemm_nt_splitk"):
+        n = _name(names, c.a["B"], _NT_STAGE)
+        if n is None:
+            return op, None
+        l, _, k = n.rpartition(".")
+        return _NT_STAGE[k], int(l[1:]) if l else None
+    if op in ("ln_fwd", "ln_bwd"):
+        n = _name(names, c.a["gamma"], _LN_STAGE)
+        if n is None:
+            return op, None
+        l, _, k = n.rpartition(".")
+        return _LN_STAGE[k] + ("_bwd" if op == "ln_bwd" else ""), int(l[1:]) if l else None
+    if op in ("attn_fwd", "attn_bwd"):
+        return op, qkv_layer.get(c.a["qkv"].region())
+    if op == "gather_rows":
+        return f"gather_rows{len(c.a['srcs'])}", None
+    return op, None
+
+
+def annotate(calls, model):
+    names = names_of(model)
+    qkv_layer = {}
+    for c in calls:
+        st, layer = _stage(c, names, qkv_layer)
+        c.meta["stage"], c.meta["layer"] = st, layer
+        if st == "qkv":
+            qkv_layer[c.ret.region()] = layer
+    return names
+
+
+def check_sequence(calls, L):
+    """Check 1: the trunk's stages in issue order are, per forward pass, FWD_LAYER for layers 0 .. L-1 and, per backward pass, for
+    layers L-1 .. 0, BWD_DENSE or (top layer only) one of BWD_TOP_SPARSE."""
+    helpers = ("gather_rows8", "gather_rows1", "scatter_rows_zero", "attn_q_limit")
+    trunk = [c for c in calls if c.meta["layer"] is not None or c.meta["stage"] in helpers]
+    seq = [(c.meta["stage"], c.meta["layer"]) for c in trunk]
+    i, passes = 0, {"fwd": 0, "bwd": 0}
+    strip = lambda part: [s for s, _ in part]
+    while i < len(seq):
+        if seq[i] == ("qkv", 0):
+            for l in range(L):
+                part = seq[i:i + 7]
+                assert strip(part) == list(FWD_LAYER) and all(x[1] == l for x in part), f"forward of layer {l}: {part}"
+                i += 7
+            passes["fwd"] += 1
+            continue
+        for l in reversed(range(L)):
+            forms = [BWD_DENSE] + (list(BWD_TOP_SPARSE) if l == L - 1 else [])
+            for f in forms:
+                part = seq[i:i + len(f)]
+                if strip(part) == list(f) and all(x[1] in (l, None) for x in part):
+                    i += len(f)
+                    break
+            else:
+                raise AssertionError(f"backward of layer {l}: {seq[i:i + 10]} is none of {forms}")
+        passes["bwd"] += 1
+    assert passes["fwd"] >= 1 and passes["fwd"] == passes["bwd"], passes
+    return passes
+
+
+class Shadow:
+    """What the recorded calls left in every storage they wrote, element by element (check 2)."""
+
+    def __init__(self):
+        self.mem = {}
+
+    def _views(self, r: Rec):
+        key = (r.sptr, r.dtype)
+        if key not in self.mem:
+            n = r.sbytes // torch.empty(0, dtype=r.dtype).element_size()
+            self.mem[key] = (torch.zeros(n, dtype=_BITS[torch.empty(0, dtype=r.dtype).element_size()]), torch.zeros(n, dtype=torch.bool))
+        v, k = self.mem[key]
+        return torch.as_strided(v, r.shape, r.stride, r.off), torch.as_strided(k, r.shape, r.stride, r.off)
+
+    def read(self, r: Rec, what, allow_rows=None):
+        if (r.sptr, r.dtype) not in self.mem or 0 in r.stride and r.t.numel() > 1:
+            return
+        v, k = self._views(r)
+        got = r.cpu().view(_BITS[r.cpu().element_size()])
+        bad = k & (v != got)
+        if allow_rows is not None:
+            bad[allow_rows] = False
+        assert not bool(bad.any()), f"{what}: {int(bad.sum())} of {bad.numel()} elements differ from what their last writer left (first at {tuple(bad.nonzero()[0].tolist())})"
+
+    def write(self, r: Rec):
+        v, k = self._views(r)
+        v.copy_(r.cpu().view(_BITS[r.cpu().element_size()]))
+        k.fill_(True)
+
+
+def check_producers(calls, cls_rows=None):
+    """Check 2, see the module docstring.  One writer is no recorded launch: torch's ``index_add_`` of the heads' [CLS]-row gradients onto
+    the dense output gradient the MLM head returned (model._MLMHeadFn.backward) -- where the top layer's LayerNorm' reads that matrix
+    (stage mlm_dy -> ln2_bwd operand dy), the rows ``cls_rows`` (the first row of every sequence) may differ, no other."""
+    sh = Shadow()
+    top = max([c.meta["layer"] for c in calls if c.meta.get("layer") is not None] + [0])
+    for c in calls:
+        pure = set(WRITES.get(c.op, ())) - set(ACCUMULATES.get(c.op, ()))
+        for k, v in c.a.items():
+            if c.op == "gemm_tn_grouped" and k == "problems":
+                for j, (p, acc) in enumerate(zip(v, tn_flags(c))):
+                    for q, r in enumerate(p):
+                        if r is not None and (q != 2 or acc):
+                            sh.read(r, f"call {c.index} ({c.op}) problem {j} operand {q}")
+                continue
+            if c.op == "gemm_tn" and k == "W" and not c.a["accumulate"]:
+                continue
+            if k in pure:
+                continue
+            allow = cls_rows if (c.meta.get("stage") == "ln2_bwd" and c.meta.get("layer") == top and k == "dy" and c.a.get("dy_rows") is None
+                                 and cls_rows is not None and c.a["dy"].shape[0] > int(cls_rows.max())) else None
+            for r in _recs(v):
+                sh.read(r, f"call {c.index} ({c.op}, {c.meta.get('stage')}) operand {k}", allow)
+        for r in list(_recs(list(c.post.values()))) + list(_recs(c.ret)):
+            if r.sbytes:
+                sh.write(r)
+
+
+def _same(x: Rec, y: Rec, what):
+    assert x is not None and y is not None and x.region() == y.region(), f"{what}: not the expected buffer"
+
+
+def _wiring(calls, names, L):
+    """Check 3 (and 6 for the weight-gradient problems)."""
+    fwd, bwd = {}, {}
+    gathered, scattered = {}, {}                               # output region -> (source Rec, row list Rec)
+    last_gather = None
+    for c in calls:
+        st, l = c.meta["stage"], c.meta["layer"]
+        if c.op == "gather_rows":
+            for s, o in zip(c.a["srcs"], c.ret):
+                gathered[o.region()] = (s, c.a["idx32"])
+            last_gather = c
+        if c.op == "scatter_rows_zero":
+            for s, o in zip(c.a["srcs"], c.ret):
+                scattered[o.region()] = s
+        if l is None:
+            if c.op == "gemm_tn_grouped":
+                _wgrad_wiring(c, names, fwd, bwd, gathered)
+            continue
+        root = lambda r: gathered[r.region()][0] if r.region() in gathered else r       # noqa: E731
+        w = f"layer {l} {st}"
+        if st in FWD_LAYER:
+            if st == "qkv":
+                fwd[l] = {}
+                bwd.pop(l, None)
+                if l > 0:
+                    _same(c.a["A"], fwd[l - 1]["ln2"].ret[0], w + " input = the layer below's output")
+            f = fwd[l]
+            if st == "attn_fwd":
+                _same(c.a["qkv"], f["qkv"].ret, w + " qkv")
+            elif st == "z1":
+                _same(c.a["A"], f["attn_fwd"].ret[0], w + " A = ctx")
+                _same(c.a["resid"], f["qkv"].a["A"], w + " residual = the layer's input")
+            elif st == "ln1":
+                _same(c.a["x"], f["z1"].ret, w + " x = z1")
+            elif st == "g":
+                _same(c.a["A"], f["ln1"].ret[0], w + " A = y1")
+            elif st == "z2":
+                _same(c.a["A"], f["g"].ret, w + " A = g")
+                _same(c.a["resid"], f["ln1"].ret[0], w + " residual = y1")
+            elif st == "ln2":
+                _same(c.a["x"], f["z2"].ret, w + " x = z2")
+            f[st] = c
+            continue
+        f, b = fwd[l], bwd.setdefault(l, {})
+        dxo = lambda lb: lb.post["dx2"] if "dx2" in lb.post else lb.ret                 # noqa: E731  (the dropped gradient, where there is a dropout)
+        if st in ("ln2_bwd", "ln1_bwd"):
+            ln, z = ("ln2", "z2") if st == "ln2_bwd" else ("ln1", "z1")
+            _same(c.a["x"], f[z].ret, w + f" x = {z}")
+            _same(root(c.a["mean"]), f[ln].ret[1], w + " mean")
+            _same(root(c.a["rstd"]), f[ln].ret[2], w + " rstd")
+            for k in ("mean", "rstd"):
+                if c.a[k].region() in gathered:
+                    idx = gathered[c.a[k].region()][1]
+                    for rk in ("x_rows", "drop_rows"):
+                        assert c.a[rk] is not None and torch.equal(_c(c.a[rk]), _c(idx)), w + f": {rk} is not the row list its statistics were gathered with"
+            want = f["z2" if st == "ln2_bwd" else "z1"].a["drop"]
+            assert tuple(c.a["pre_drop"] or (0, 0, 1.0)) == tuple(want or (0, 0, 1.0)), w + ": pre_drop is not the forward's triple"
+            if st == "ln1_bwd":
+                _same(c.a["dy"], b["dy1"].ret, w + " dy = dy1")
+        elif st == "du":
+            _same(c.a["A"], dxo(b["ln2_bwd"]), w + " A = dz2 (dropped)")
+            _same(root(c.a["gelu_bwd_u"]), f["g"].post["aux"], w + " gelu_bwd_u = the forward's aux u")
+        elif st == "dy1":
+            _same(c.a["A"], b["du"].ret, w + " A = du")
+            _same(c.a["resid"], b["ln2_bwd"].ret, w + " residual = dz2")
+        elif st == "dctx":
+            _same(c.a["A"], dxo(b["ln1_bwd"]), w + " A = dz1 (dropped)")
+        elif st == "attn_bwd":
+            _same(c.a["qkv"], f["qkv"].ret, w + " qkv")
+            _same(c.a["ctx"], f["attn_fwd"].ret[0], w + " ctx")
+            _same(c.a["lse"], f["attn_fwd"].ret[1], w + " lse")
+            d = c.a["dctx"]
+            if d.region() in scattered:
+                _same(scattered[d.region()], b["dctx"].ret, w + " dctx = the scattered rows of dctx")
+            elif d.shape[0] == b["dctx"].ret.shape[0]:           # (few rows put back by torch's index_copy_ are no recorded launch)
+                _same(d, b["dctx"].ret, w + " dctx")
+            assert tuple(c.a["drop"] or (0, 0, 1.0)) == tuple(f["attn_fwd"].a["drop"] or (0, 0, 1.0)), w + ": dropout triple differs from the forward's"
+            assert c.a["layout"].lens == f["attn_fwd"].a["layout"].lens
+        elif st == "dx":
+            _same(c.a["A"], b["attn_bwd"].ret, w + " A = dqkv")
+            r = c.a["resid"]
+            if r.region() in scattered:
+                _same(scattered[r.region()], b["ln1_bwd"].ret, w + " residual = the scattered rows of dz1")
+            elif r.shape[0] == b["ln1_bwd"].ret.shape[0]:
+                _same(r, b["ln1_bwd"].ret, w + " residual = dz1")
+        b[st] = c
+        b["_gather"] = last_gather
+    return fwd, bwd
+
+
+_WG = {"g_W1": ("du", "ret", "ln1", 0, "g_b1"), "g_W2": ("ln2_bwd", "dxo", "g", "ret", "g_b2"), "g_Wqkv": ("attn_bwd", "ret", "qkv", "A", "g_bqkv"),
+       "g_Wo": ("ln1_bwd", "dxo", "attn_fwd", 0, "g_bo")}
+
+
+def _wgrad_wiring(c, names, fwd, bwd, gathered):
+    root = lambda r: gathered[r.region()][0] if r.region() in gathered else r           # noqa: E731
+    for j, (A_, B_, W, bias) in enumerate(c.a["problems"]):
+        n = _name(names, W, set(_WG) | {"g_word_pad", "g_Wt"})
+        assert n is not None, f"weight-gradient problem {j}: W is no gradient view of the model"
+        l, _, k = n.rpartition(".")
+        if k not in _WG:
+            want_b = {"g_word_pad": "g_pred_bias", "g_Wt": "g_bt"}[k]
+            assert bias is not None and want_b in names.get(bias.ptr, []), f"problem {j} ({n}): bias buffer is not {want_b}"
+            continue
+        l = int(l[1:])
+        sa, ka, sb, kb, bn = _WG[k]
+        ca, cb = bwd[l][sa], fwd[l][sb]
+        wantA = (ca.post["dx2"] if "dx2" in ca.post else ca.ret) if ka == "dxo" else ca.ret
+        wantB = cb.a["A"] if kb == "A" else cb.ret if kb == "ret" else cb.ret[kb]
+        _same(A_, wantA, f"problem {j} ({n}) A = layer {l} {sa}")
+        _same(root(B_), wantB, f"problem {j} ({n}) B = layer {l} {sb}")
+        assert bias is not None and f"l{l}.{bn}" in names.get(bias.ptr, []), f"problem {j} ({n}): bias buffer is not l{l}.{bn}"
+
+
+def check_transposes(calls, names, model=None):
+    """Check 4."""
+    seen = {}
+    params = dict(model.named_parameters()) if hasattr(model, "named_parameters") else {}
+    for c in calls:
+        if c.op not in ("gemm_nt", "gemm_nt_splitk"):
+            continue
+        n = _name(names, c.a["B"], set(_TRANSPOSED) | set(_TRANSPOSED.values()))
+        if n is None:
+            continue
+        l, _, k = n.rpartition(".")
+        if k in _TRANSPOSED:
+            src = seen.get((l, _TRANSPOSED[k]))
+            assert src is not None, f"{n}: its forward weight was never read in the recording"
+            Wf, WT = _c(src), _c(c.a["B"])
+            assert torch.equal(_bits(WT[:, :Wf.shape[0]]), _bits(Wf.t()[:WT.shape[0]])), f"call {c.index}: {n} is not the transpose of the bf16 working copy"
+        else:
+            seen[(l, k)] = c.a["B"]
+            pn = (f"bert.encoder.layer.{l[1:]}." + _PARAM_OF[k]) if l else _PARAM_OF_W.get("word" if k == "word_h" else k)
+            if pn in params:
+                p = params[pn].detach()
+                if k == "Wqkv":
+                    pre = pn[:-len("query.weight")]
+                    p = torch.cat([params[pre + x + ".weight"].detach() for x in ("query", "key", "value")])
+                Wc = _c(c.a["B"])
+                assert torch.equal(_bits(Wc[:p.shape[0]]), _bits(p.to(torch.bfloat16).cpu())), f"call {c.index}: {n} is not the parameter {pn} rounded to bf16"
+
+
+def check_dropout_sites(calls):
+    """Check 5: one triple per site (a site = a stage of a layer / an embedding launch group), different streams between sites."""
+    site = {}
+    for c in calls:
+        st, l = c.meta["stage"], c.meta["layer"]
+        for k, key in (("drop", st), ("pre_drop", {"ln2_bwd": "z2", "ln1_bwd": "z1"}.get(st)), ("post_drop", {"emb_ln_bwd": "emb_ln", "joint_ln_bwd": "joint_ln"}.get(st))):
+            d = c.a.get(k)
+            if not _on(d) or key is None:
+                continue
+            if key == "attn_bwd":
+                key = "attn_fwd"
+            ident = (c.meta.get("pass"), l, key) if key != "joint_ln" else (c.meta.get("pass"), l, key, tuple(d))
+            site.setdefault(ident, set()).add(tuple(d))
+    for ident, triples in site.items():
+        assert len(triples) == 1, f"dropout site {ident}: forward and backward carry different triples {triples}"
+    streams = [next(iter(t))[0] for t in site.values()]
+    assert len(set(streams)) == len(streams), "two dropout sites share a stream"
+    return len(site)
+
+
+def check_kv_len(calls):
+    """kv_len of every attention call against the number of leading keys behind which the recorded key bias masks every key."""
+    for c in calls:
+        if c.op not in ("attn_fwd", "attn_bwd"):
+            continue
+        lay = c.a["layout"]
+        kv = _c(lay.kv_len) if lay.split else _c(c.a.get("kv_len"))
+        if kv is None:
+            continue
+        seq = torch.repeat_interleave(torch.arange(len(lay.lens)), torch.tensor(lay.lens))
+        kb = _token_bias(c, seq, torch.cat([torch.arange(n) for n in lay.lens]))
+        for s, S in enumerate(lay.lens):
+            live = (kb[seq == s] > A.MASKED).nonzero()
+            want = int(live.max()) + 1 if live.numel() else 0
+            # (a split layout's region A also holds the masked-out rows that carry a label: its key count may exceed the live keys -- the
+            # bias still masks those --, it must never fall short of them)
+            ok = int(kv[s]) >= want if lay.split else (int(kv[s]) == want or (want == 0 and int(kv[s]) <= 1))
+            assert ok, f"call {c.index} ({c.op}): kv_len[{s}] = {int(kv[s])}, the key bias says {want}"
+
+
+def check_grad_views(calls, names, model):
+    """Check 6 for the gradient buffers the other stages write: the LayerNorm gradients of a stage, the embedding tables, the pair
+    projections -- and every gradient view sits at its parameter's ``.grad``."""
+    for c in calls:
+        st, l = c.meta["stage"], c.meta["layer"]
+        if c.op == "ln_bwd":
+            base = st[:-len("_bwd")] + "_"
+            pre = f"l{l}." if l is not None else ""
+            for k, suffix in (("dgamma", "g"), ("dbeta", "b")):
+                assert pre + "g_" + base + suffix in names.get(c.a[k].ptr, []), f"call {c.index} ({st}): {k} is not {pre}g_{base}{suffix}"
+        elif c.op == "embed_scatter":
+            for k, n in (("gword", "g_word"), ("gtype", "g_type"), ("gpos", "g_pos")):
+                assert c.a[k] is None or n in names.get(c.a[k].ptr, []), f"embed_scatter {k} is not {n}"
+        elif c.op == "pair_proj_bwd":
+            nw = _name(names, c.a["dW"], {"g_Wv_w", "g_Ws_w"})
+            assert nw is not None and nw[:-1] + "b" in names.get(c.a["db"].ptr, []), "pair_proj_bwd: dW / db are not one projection's gradients"
+    if not hasattr(model, "named_parameters"):
+        return
+    params = dict(model.named_parameters())
+    for i, lw in enumerate(model._lw):
+        for k, pn in _PARAM_OF.items():
+            g = params[f"bert.encoder.layer.{i}.{pn}"].grad
+            assert g is not None and g.data_ptr() == lw["g_" + k].data_ptr(), f"l{i}.g_{k} is not the .grad of {pn}"
+    for k, pn in _PARAM_OF_W.items():
+        if "g_" + k in model._w:
+            g = params[pn].grad
+            assert g is not None and g.data_ptr() == model._w["g_" + k].data_ptr(), f"g_{k} is not the .grad of {pn}"
+
+
+def check_dataflow(calls, model):
+    """All six checks of the module docstring; returns (forward / backward passes seen, dropout sites seen)."""
+    names = annotate(calls, model)
+    L = len(model._lw)
+    n = 0
+    for c in calls:                                              # the forward pass a call belongs to (dropout sites are per pass)
+        if c.op == "embed_gather":
+            n += 1
+        c.meta["pass"] = n
+    passes = check_sequence(calls, L)
+    lens = next((c.a["layout"].lens for c in calls if c.op == "attn_fwd"), None)
+    check_producers(calls, None if lens is None else torch.tensor([0] + lens[:-1]).cumsum(0))
+    _wiring(calls, names, L)
+    check_kv_len(calls)
+    check_transposes(calls, names, model)
+    sites = check_dropout_sites(calls)
+    check_grad_views(calls, names, model)
+    return passes, sites
+
+
+def check_accumulation(calls, names):
+    """The weight-gradient launches of the recording: {gradient name: [accumulate flag per write, in issue order]} -- and every write
+    that accumulates starts from what the previous writer left (part of check 2), every write that does not starts a new sum."""
+    out = {}
+    for c in calls:
+        if c.op == "gemm_tn_grouped":
+            for p, acc in zip(c.a["problems"], tn_flags(c)):
+                for n in names.get(p[2].ptr, [None]):
+                    out.setdefault(n, []).append(acc)
+        elif c.op == "gemm_tn":
+            for n in names.get(c.a["W"].ptr, [None]):
+                out.setdefault(n, []).append(bool(c.a["accumulate"]))
+    return out
+
+
+def check_tied_word_gradient(calls):
+    """The gradient with two producers per backward pass -- the tied decoder's weight gradient (a weight-gradient problem of the MLM head)
+    and the embedding lookup's rows added onto it (embed_scatter) -- against the float64 sum over BOTH stages' recorded operands: the
+    scatter's reference started from the EXACT value of the decoder product instead of the fp32 buffer it found, its bound widened by
+    that product's own bound (gemm_ref.tn: accumulation term + the fp32 rounding of its output).  Returns the worst ratio per pass."""
+    out = []
+    for c in calls:
+        if c.op in ("gemm_tn_grouped", "gemm_tn"):
+            probs = c.a["problems"] if c.op == "gemm_tn_grouped" else [(c.a["A"], c.a["B"], c.a["W"], c.a["bias_out"])]
+            flags = tn_flags(c) if c.op == "gemm_tn_grouped" else [bool(c.a["accumulate"])]
+            c.meta["_probs"] = list(zip(probs, flags))
+        elif c.op == "embed_scatter" and c.a["gword"] is not None:
+            gw = c.a["gword"]
+            src = None
+            for q in calls[:c.index][::-1]:
+                for p, acc in q.meta.get("_probs", []):
+                    if p[2].ptr == gw.ptr:
+                        src = (p, acc)
+                        break
+                if src is not None:
+                    break
+            assert src is not None, "embed_scatter: no decoder weight-gradient problem wrote the tied table's gradient before it"
+            (A_, B_, W0, _b), acc = src
+            tn = G.tn(_c(A_), _c(B_), W0=_c(W0), accumulate=acc)["W"]
+            Vr = gw.shape[0]
+            ref = E.scatter(_c(c.a["ids"]).reshape(-1), None if c.a["tts"] is None else _c(c.a["tts"]).reshape(-1), _c(c.a["d"]), c.a["T"],
+                            tn.val[:Vr], _c(c.a["gtype"]), _c(c.a["gpos"]), det=bool(c.meta.get("det")))["gword"]
+            rows = ref.rows
+            more = tn.acc[rows] + G.C_OUT * G.U_F32 * tn.val[rows].abs() / (G.C_ACC * G.EPS24)
+            out.append(E.check(_c(c.post["gword"]), R.Ref(ref.val, ref.acc + more, 0.0, R.U_F32, rows, None), "tied word gradient, both producers").worst)
+    return out
