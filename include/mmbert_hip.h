@@ -410,6 +410,27 @@ typedef struct { mmbert_heads_step step; mmbert_heads_loss opt; } mmbert_heads_s
 int mmbert_heads_step_opt_struct_size(void);      /* sizeof(mmbert_heads_step_opt) */
 int mmbert_heads_step_fwd_levels_opt(mmbert_stream_t stream, const mmbert_heads_step_opt* p, int lo, int hi);
 int mmbert_heads_step_bwd_levels_opt(mmbert_stream_t stream, const mmbert_heads_step_opt* p, int lo, int hi);
+/* ---- the multi-label head (a declared extension) ----
+ * mmbert_heads_step_ml = mmbert_heads_step_opt with one more record BEHIND it (every offset and size above is untouched; a pointer to it is a
+ * pointer to its mmbert_heads_step_opt and to its mmbert_heads_step).  With multi_label = 1 the ncls = C outputs of classifier1_2 are C
+ * independent labels: x = raw logits [B, C]; multi_target fp32 [B, C], an entry < 0 = not annotated (no part in the loss, seed exactly 0),
+ * otherwise in [0, 1] (soft targets allowed), smoothed to t' = t (1 - label_smoothing) + label_smoothing / 2; N = the number of annotated
+ * entries of the whole block;
+ *   label_loss = (1 / N) sum_valid (1 - t') x + (1 + (pos_weight[c] - 1) t') softplus(-x)      (torch's binary_cross_entropy_with_logits, mean)
+ *   seed[b, c] = ((1 - t') - (1 + (pos_weight[c] - 1) t') (1 - sigmoid(x))) / N;  N == 0: loss and seeds exactly 0
+ *   pred int64 [B, C] (B * C values), pred[b, c] = x[b, c] > threshold[c] (strict), written by forward level 5 from its own tile
+ * pos_weight fp32 [C], every entry finite and > 0, or NULL = all ones; threshold fp32 [C] in logit space, or NULL = all zero.
+ * sent_cls is not read and may be NULL; logits are [B, C] raw; the backward is the class head's.  multi_label = 0: the entry points below
+ * are the _opt ones (same bits; multi_target is not read).  Refused (-1, nothing launched or written) from all three: multi_label outside
+ * 0 / 1; multi_label with ncls == 0, loss_kind != 0 or cls_weight != NULL; multi_label with a NULL multi_target from forward levels that
+ * include 7; pos_weight or threshold without multi_label; everything the _opt entry points refuse.
+ * mmbert_heads_predict_opt: mmbert_heads_predict with the record visible (level 5 reads multi_label and threshold). */
+typedef struct { int multi_label; const float* multi_target; const float* pos_weight; const float* threshold; } mmbert_heads_multi;
+typedef struct { mmbert_heads_step step; mmbert_heads_loss opt; mmbert_heads_multi ml; } mmbert_heads_step_ml;
+int mmbert_heads_step_ml_struct_size(void);       /* sizeof(mmbert_heads_step_ml) */
+int mmbert_heads_step_fwd_levels_ml(mmbert_stream_t stream, const mmbert_heads_step_ml* p, int lo, int hi);
+int mmbert_heads_step_bwd_levels_ml(mmbert_stream_t stream, const mmbert_heads_step_ml* p, int lo, int hi);
+int mmbert_heads_predict_opt(mmbert_stream_t stream, const mmbert_heads_step_ml* p);
 int mmbert_heads_step_dmlm(mmbert_stream_t stream, const mmbert_heads_step* p);
 
 /* ---- the heads' dense layers: lists of fp32 products with at most 64 rows, one launch per dependency level ----

@@ -80,6 +80,10 @@ SIGNATURES = {
     "mmbert_heads_step_opt_struct_size": (I, []),
     "mmbert_heads_step_fwd_levels_opt": (I, [P, P, I, I]),
     "mmbert_heads_step_bwd_levels_opt": (I, [P, P, I, I]),
+    "mmbert_heads_step_ml_struct_size": (I, []),
+    "mmbert_heads_step_fwd_levels_ml": (I, [P, P, I, I]),
+    "mmbert_heads_step_bwd_levels_ml": (I, [P, P, I, I]),
+    "mmbert_heads_predict_opt": (I, [P, P]),
     "mmbert_heads_step_dmlm": (I, [P, P]),
     "mmbert_heads_predict": (I, [P, P]),
     "mmbert_heads_step_outputs": (I, [I, I, P, P]),

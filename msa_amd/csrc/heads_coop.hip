@@ -191,7 +191,7 @@ struct HcFirst {
 // forward
 // =====================================================================================================================================
 template <int LEVEL, bool CLS>
-__global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmbert_heads_step p, const mmbert_heads_loss lopt) {   // (lopt: level 7 only)
+__global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmbert_heads_step p, const mmbert_heads_loss lopt, const mmbert_heads_multi ml) {   // (lopt: level 7 only; ml: 5 and 7)
 #if defined(__gfx950__)
     extern __shared__ __attribute__((aligned(16))) float hc_sm[];
     HcCtx c; c.nwg = gridDim.x; c.red = hc_sm; c.wg = blockIdx.x;
@@ -286,7 +286,18 @@ __global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmber
                                if (b < B && n < C) { hc_stc(w.lo + (size_t)b * C + n, v); p.logits[(size_t)b * C + n] = v; }
                            });
                 const int b = tb * 16 + tid;
-                if (tid < 16 && b < B) {
+                if (ml.multi_label) {
+                    // (multi-label head: C independent decisions per row, pred [B, C]; strictly above the threshold -- 0 in logit space without one)
+                    // (the C thresholds are fetched together -- 16 loads in flight, index clamped --, not one per decision)
+                    if (tid < 16 && b < B) {
+                        float th[16];
+#pragma unroll
+                        for (int n = 0; n < 16; ++n) th[n] = ml.threshold ? ml.threshold[min(n, C - 1)] : 0.f;
+#pragma unroll
+                        for (int n = 0; n < 16; ++n)
+                            if (n < C) p.pred[(size_t)b * C + n] = lds2[tid * 16 + n] > th[n] ? 1ll : 0ll;
+                    }
+                } else if (tid < 16 && b < B) {
                     int best = 0; float bv = lds2[tid * 16];
                     for (int n = 1; n < C; ++n) { const float v = lds2[tid * 16 + n]; if (v > bv) { bv = v; best = n; } }
                     p.pred[b] = (long long)best;
@@ -386,7 +397,40 @@ __global__ __launch_bounds__(HC_THREADS) void heads_fwd_level_kernel(const mmber
             // mean C-way cross-entropy (REF :438-441) and its seed dlo[b][c] = (softmax_c - [c == y_b]) / B; `se` carries the label loss.
             // A label outside [0, C) is clamped (nothing out of bounds; the loss is then unspecified)
             const int C = p.ncls;
-            if (lopt.label_smoothing == 0.f && !lopt.cls_weight) {
+            if (ml.multi_label) {
+                // C independent labels: torch's binary_cross_entropy_with_logits(x[valid], t'[valid], pos_weight = pw), mean over
+                // the N valid entries (t >= 0) of the whole block, t' = t (1 - eps) + eps / 2:
+                //   loss      = (1 / N) sum_valid (1 - t') x + (1 + (pw_c - 1) t') softplus(-x),   softplus(-x) = max(-x, 0) + log1p(exp(-|x|))
+                //   dlo[b, c] = ((1 - t') - (1 + (pw_c - 1) t') sigmoid(-x)) / N,   0 on an entry that is not annotated
+                // N as W below: per-sample counts to LDS, then every thread adds the B counts in sample order (small integers: exact)
+                const float eps = lopt.label_smoothing;
+                const float* pw = ml.pos_weight;
+                const float* tg = ml.multi_target;
+                float* cnt = lds2 + 2 * HC_WAVES;                                    // [B] behind this workgroup's two rows of wave partials
+                for (int b = tid; b < B; b += HC_THREADS) {
+                    int k = 0;
+                    for (int q = 0; q < C; ++q) k += tg[(size_t)b * C + q] >= 0.f ? 1 : 0;
+                    cnt[b] = (float)k;
+                }
+                __syncthreads();
+                float N = 0.f;
+                for (int b = 0; b < B; ++b) N += cnt[b];
+                for (int b = tid; b < B; b += HC_THREADS) {
+                    for (int q = 0; q < C; ++q) {
+                        const float t = tg[(size_t)b * C + q];
+                        float g = 0.f;
+                        if (t >= 0.f) {                                              // (N >= 1 here)
+                            const float x = hc_ldc(w.lo + (size_t)b * C + q);
+                            const float tp = t * (1.f - eps) + 0.5f * eps, wp = 1.f + ((pw ? pw[q] : 1.f) - 1.f) * tp;
+                            const float e = expf(-fabsf(x));
+                            const float sp = fmaxf(-x, 0.f) + log1pf(e), sn = (x >= 0.f ? e : 1.f) / (1.f + e);      // softplus(-x), sigmoid(-x)
+                            se += ((1.f - tp) * x + wp * sp) / N;
+                            g = ((1.f - tp) - wp * sn) / N;
+                        }
+                        w.dlo[(size_t)b * C + q] = g;
+                    }
+                }
+            } else if (lopt.label_smoothing == 0.f && !lopt.cls_weight) {
             for (int b = tid; b < B; b += HC_THREADS) {
                 const float* l = w.lo + (size_t)b * C;
                 const long long yl = p.sent_cls[b];
@@ -695,10 +739,10 @@ size_t mmbert_heads_step_workspace(int B, int H) {
     return total * sizeof(float);
 }
 
-static int hc_check(const mmbert_heads_step* p, int* cus) {
+static int hc_check(const mmbert_heads_step* p, int* cus, int multi = 0) {      // (multi: the multi-label head reads no sent_cls)
     if (!p || p->B <= 0) return -1;
     if (p->B > 128 || p->H < 16 || (p->H & 15) || p->nmlm < 0 || p->nmlm > 256 || !p->ws || !p->sync || (!p->first && (!p->y || !p->first_rows || (p->ldy & 3)))) return -1;
-    if (p->ncls < 0 || p->ncls == 1 || p->ncls > 16 || (p->ncls > 0 && (!p->sent_cls || !p->pred))) return -1;
+    if (p->ncls < 0 || p->ncls == 1 || p->ncls > 16 || (p->ncls > 0 && ((!p->sent_cls && !multi) || !p->pred))) return -1;
     *cus = mmb_device_cus();
     return 0;
 }
@@ -708,6 +752,13 @@ static int hc_check_loss(const mmbert_heads_step* p, const mmbert_heads_loss* o)
     if (o->loss_kind == 2 && !(o->huber_delta > 0.f && o->huber_delta <= FLT_MAX)) return -1;
     if (!(o->label_smoothing >= 0.f && o->label_smoothing < 1.f)) return -1;
     if (p->ncls == 0 && (o->label_smoothing != 0.f || o->cls_weight)) return -1;
+    return 0;
+}
+// the multi-label head's record (mmbert_heads_step_ml.ml): only behind the flag, on a class-shaped head with the plain loss record
+static int hc_check_multi(const mmbert_heads_step* p, const mmbert_heads_loss* o, const mmbert_heads_multi* m, int need_target) {
+    if (!m->multi_label) return (m->pos_weight || m->threshold) ? -1 : 0;
+    if (m->multi_label != 1 || p->ncls == 0 || o->loss_kind != 0 || o->cls_weight) return -1;
+    if (need_target && !m->multi_target) return -1;
     return 0;
 }
 __global__ void heads_dmlm_kernel(const float* __restrict__ dloss, float* __restrict__ dmlm, int nmlm, float alpha) {
@@ -728,10 +779,10 @@ static inline int hc_grid(int wg_tiles, int wave_jobs, int cus, int floor_) {
 
 // levels lo .. hi of the forward (1 .. 7) / backward (1 .. 6): the model runs the heads beside the MLM head's launches on a side stream and
 // only the loss level (which reads the MLM losses) behind both
-#define HC_KARGS *p, *lopt
-static int hc_fwd_levels(hipStream_t stream, const mmbert_heads_step* p, const mmbert_heads_loss* lopt, int lo, int hi) {
+#define HC_KARGS *p, *lopt, *ml
+static int hc_fwd_levels(hipStream_t stream, const mmbert_heads_step* p, const mmbert_heads_loss* lopt, const mmbert_heads_multi* ml, int lo, int hi) {
     int cus;
-    if (hc_check(p, &cus) || hc_check_loss(p, lopt)) return -1;
+    if (!p || hc_check_loss(p, lopt) || hc_check_multi(p, lopt, ml, lo <= 7 && 7 <= hi) || hc_check(p, &cus, ml->multi_label)) return -1;
     if (lo < 1 || hi > 7 || lo > hi) return -1;
     if (!p->loss || !p->aux || !p->out5 || !p->logits || !p->t_rel || !p->rel || !p->ap || (p->ncls == 0 && !p->sent) || (hi == 7 && p->nmlm > 0 && !p->mlm)) return -1;
     const int B = p->B, H = p->H, R = 3 * B, tH = H >> 4, tB = (B + 15) >> 4, tR = (R + 15) >> 4, t2B = (2 * B + 15) >> 4;
@@ -747,8 +798,9 @@ static int hc_fwd_levels(hipStream_t stream, const mmbert_heads_step* p, const m
 }
 
 static const mmbert_heads_loss hc_plain_loss = {};              // all zero / NULL: the MSE, the plain mean cross-entropy
+static const mmbert_heads_multi hc_no_multi = {};               // flag clear: the regression / class head
 
-int mmbert_heads_step_fwd_levels(hipStream_t stream, const mmbert_heads_step* p, int lo, int hi) { return hc_fwd_levels(stream, p, &hc_plain_loss, lo, hi); }
+int mmbert_heads_step_fwd_levels(hipStream_t stream, const mmbert_heads_step* p, int lo, int hi) { return hc_fwd_levels(stream, p, &hc_plain_loss, &hc_no_multi, lo, hi); }
 
 int mmbert_heads_step_fwd(hipStream_t stream, const mmbert_heads_step* p) { return mmbert_heads_step_fwd_levels(stream, p, 1, 7); }
 
@@ -757,12 +809,20 @@ int mmbert_heads_step_opt_struct_size(void) { return (int)sizeof(mmbert_heads_st
 
 int mmbert_heads_step_fwd_levels_opt(hipStream_t stream, const mmbert_heads_step_opt* q, int lo, int hi) {
     if (!q) return -1;
-    return hc_fwd_levels(stream, &q->step, &q->opt, lo, hi);
+    return hc_fwd_levels(stream, &q->step, &q->opt, &hc_no_multi, lo, hi);
+}
+
+// ... and with the multi-label head's record behind the options (mmbert_heads_step_ml)
+int mmbert_heads_step_ml_struct_size(void) { return (int)sizeof(mmbert_heads_step_ml); }
+
+int mmbert_heads_step_fwd_levels_ml(hipStream_t stream, const mmbert_heads_step_ml* q, int lo, int hi) {
+    if (!q) return -1;
+    return hc_fwd_levels(stream, &q->step, &q->opt, &q->ml, lo, hi);
 }
 
 // prediction without labels: levels 1 .. 5 read the [CLS] rows, the parameters and the workspace -- labels, losses and the loss level's counter
 // are level 7's (so they are not asked for here); same kernels, grids and bits as mmbert_heads_step_fwd_levels(p, 1, 5)
-int mmbert_heads_predict(hipStream_t stream, const mmbert_heads_step* p) {
+static int hc_predict(hipStream_t stream, const mmbert_heads_step* p, const mmbert_heads_multi* ml) {
     if (!p || p->B <= 0 || p->B > 128 || p->H < 16 || (p->H & 15) || !p->ws || (!p->first && (!p->y || !p->first_rows || (p->ldy & 3)))) return -1;
     if (!p->logits || !p->t_rel || !p->rel) return -1;
     const mmbert_heads_loss* lopt = &hc_plain_loss;              // (levels 1 - 5 read no option)
@@ -780,6 +840,14 @@ int mmbert_heads_predict(hipStream_t stream, const mmbert_heads_step* p) {
     return 0;
 }
 
+int mmbert_heads_predict(hipStream_t stream, const mmbert_heads_step* p) { return hc_predict(stream, p, &hc_no_multi); }
+
+// ... with the options visible: level 5 of a multi-label head reads the thresholds (pred [B, ncls]); refuses what forward refuses
+int mmbert_heads_predict_opt(hipStream_t stream, const mmbert_heads_step_ml* q) {
+    if (!q || hc_check_loss(&q->step, &q->opt) || hc_check_multi(&q->step, &q->opt, &q->ml, 0)) return -1;
+    return hc_predict(stream, &q->step, &q->ml);
+}
+
 int mmbert_heads_step_outputs(int B, int H, size_t* pooled_offset, size_t* fused_offset) {
     if (B <= 0 || H <= 0) return -1;
     const HcWs w = hc_ws(B, H, nullptr, nullptr);
@@ -790,9 +858,9 @@ int mmbert_heads_step_outputs(int B, int H, size_t* pooled_offset, size_t* fused
 
 #undef HC_KARGS
 #define HC_KARGS *p
-int mmbert_heads_step_bwd_levels(hipStream_t stream, const mmbert_heads_step* p, int lo, int hi) {
+static int hc_bwd_levels(hipStream_t stream, const mmbert_heads_step* p, int multi, int lo, int hi) {
     int cus;
-    if (hc_check(p, &cus)) return -1;
+    if (hc_check(p, &cus, multi)) return -1;
     if (lo < 1 || hi > 6 || lo > hi) return -1;
     if (!p->dloss || !p->dfirst || (p->nmlm > 0 && !p->dmlm)) return -1;
     const int B = p->B, H = p->H, R = 3 * B, tH = H >> 4, tB = (B + 15) >> 4, tR = (R + 15) >> 4;
@@ -808,12 +876,20 @@ int mmbert_heads_step_bwd_levels(hipStream_t stream, const mmbert_heads_step* p,
     return 0;
 }
 
+int mmbert_heads_step_bwd_levels(hipStream_t stream, const mmbert_heads_step* p, int lo, int hi) { return hc_bwd_levels(stream, p, 0, lo, hi); }
+
 int mmbert_heads_step_bwd(hipStream_t stream, const mmbert_heads_step* p) { return mmbert_heads_step_bwd_levels(stream, p, 1, 6); }
 
 // (the backward reads no option -- forward left the seed dlo -- but refuses what forward refuses)
 int mmbert_heads_step_bwd_levels_opt(hipStream_t stream, const mmbert_heads_step_opt* q, int lo, int hi) {
     if (!q || hc_check_loss(&q->step, &q->opt)) return -1;
     return mmbert_heads_step_bwd_levels(stream, &q->step, lo, hi);
+}
+
+// (a multi-label head's backward is the class head's: the seed dlo [B, ncls] is all it reads of the label loss)
+int mmbert_heads_step_bwd_levels_ml(hipStream_t stream, const mmbert_heads_step_ml* q, int lo, int hi) {
+    if (!q || hc_check_loss(&q->step, &q->opt) || hc_check_multi(&q->step, &q->opt, &q->ml, 0)) return -1;
+    return hc_bwd_levels(stream, &q->step, q->ml.multi_label, lo, hi);
 }
 
 // the gradient of the per-pass MLM losses alone (what backward level 6 also writes): d(joint) / d(mlm[i]) = alpha / nmlm, times the upstream

@@ -8,7 +8,9 @@ reference's pairing), same quirks:
 * the alignment label is **1 for the matching pair** and 0 for a random other sample (REF:MMBertDataset.py:143-155; the
   docstring there says the opposite), and the last item is always paired with itself (:137-141);
 * token types are float64 (``np.zeros`` / ``np.ones``, :160-166), the text label is always 0 (:176);
-* ``sentiment_selection`` returns ``None`` for (dataset, task, mode) combinations it does not know (:63-99).
+* ``sentiment_selection`` returns ``None`` for (dataset, task, mode) combinations it does not know (:63-99).  One rule beside the
+  reference's table: ``task="emotions"``, ``num_labels=6`` on ``mosei`` yields the float multi-hot vector ``sentiment[1:] != 0`` (a
+  multi-label head's targets).
 
 ``DeviceBatchBuilder`` keeps every item in HBM (ids int64, features converted to fp32 ONCE -- the reference ships float64
 features to the device on every step, REF:trainer.py:49-64) and builds a batch with index gathers on the device: the
@@ -45,6 +47,9 @@ class MMBertDataset(Dataset):
 
     def sentiment_selection(self, sentiment, mode):
         """REF:MMBertDataset.py:62-99."""
+        if self.dataset == "mosei" and self.task == "emotions":
+            # DECLARED EXTENSION (beside the reference's table): all six emotions at once, the multi-hot vector of a multi-label head
+            return (torch.tensor(sentiment[1:]) != 0).to(torch.float32) if mode == "6" else None
         if self.dataset == "mosei":
             if self.task == "sentiment":
                 if mode == "2":
@@ -140,8 +145,12 @@ class DeviceBatchBuilder:
             raise ValueError("sentiment_selection has no rule for this (dataset, task, num_labels)")
         # collate() turns every sentiment into one python number per item: float for floating tensors, int for integer ones
         self.sent_is_int = not torch.as_tensor(sent[0]).is_floating_point()
-        flat = [float(torch.as_tensor(s).reshape(-1)[0]) for s in sent]
-        self.sent = torch.tensor(flat, dtype=torch.int64 if self.sent_is_int else torch.float32, device=self.device)
+        if torch.as_tensor(sent[0]).numel() > 1:                 # a vector label per item (multi-label head): float32 [N, C], as collate() stacks them
+            self.sent_is_int = False
+            self.sent = torch.stack([torch.as_tensor(s, dtype=torch.float32).reshape(-1) for s in sent]).to(self.device)
+        else:
+            flat = [float(torch.as_tensor(s).reshape(-1)[0]) for s in sent]
+            self.sent = torch.tensor(flat, dtype=torch.int64 if self.sent_is_int else torch.float32, device=self.device)
         self.segments = [it[-2] for it in items]
         self.raw = [it[-1] for it in items]
         # constant pieces of every batch

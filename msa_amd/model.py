@@ -1847,6 +1847,12 @@ def _class_head(top) -> int:
     return n if n not in (1, 7) and 2 <= n <= 16 and top.classifier1_2.out_features == n else 0
 
 
+def _multi_head(top) -> int:
+    """C when ``top`` carries a multi-label head (``multi_label=True``: the C outputs of a class-shaped ``classifier1_2`` are C independent
+    labels), else 0."""
+    return _class_head(top) if getattr(top, "multi_label", False) else 0
+
+
 class _HeadsStepFn(torch.autograd.Function):
     """The heads, one launch per dependency level (csrc/heads_coop.hip, round 6): ``mmbert_heads_step_fwd`` (ONE C call, seven launches) evaluates
     everything downstream of the [CLS] rows -- pooler, align / seq_relationship scores, gates, gated concatenation, classifier1_1 / 1_2, the
@@ -1876,10 +1882,13 @@ class _HeadsStepFn(torch.autograd.Function):
         """The heads of a label-free prediction on the compact [3B, H] bf16 [CLS] rows ``y`` (text, visual, speech): forward levels 1 - 5
         (mmbert_heads_predict: no labels, no losses), in chunks of <= 128 samples -- without the loss level nothing couples the samples of
         a batch, so any B goes through the level-launch kernels.  Returns (logits [B,1], t_rel, v_rel, s_rel [B,2], pooled [3,B,H], fused [B,H]);
-        with a C-class head ``logits`` is the raw [B, C] and a seventh value follows: the predicted classes, int64 [B]."""
+        with a C-class head ``logits`` is the raw [B, C] and a seventh value follows: the predicted classes, int64 [B] -- of a multi-label
+        head the decisions, int64 [B, C] (level 5 reads the model's thresholds: no launch of their own)."""
         H, dev, f32 = y.shape[1], y.device, torch.float32
         assert y.dtype == torch.bfloat16 and y.is_contiguous() and y.shape[0] == 3 * B
         ncls = _class_head(top)
+        multi = _multi_head(top)
+        thr = getattr(top, "thresholds", None) if multi else None
         parts = []
         for b0 in range(0, B, 128):
             n = min(128, B - b0)
@@ -1893,8 +1902,13 @@ class _HeadsStepFn(torch.autograd.Function):
             a.logits, a.t_rel, a.rel, a.ws = logits.data_ptr(), t_rel.data_ptr(), rel.data_ptr(), ws.data_ptr()
             pred = ()
             if ncls:
-                pred = (torch.empty(n, device=dev, dtype=torch.int64),)
+                pred = (torch.empty((n, ncls) if multi else n, device=dev, dtype=torch.int64),)
                 a.pred = pred[0].data_ptr()
+            if multi:
+                a.multi_label = 1
+                if thr is not None:
+                    assert thr.dtype == f32 and thr.device == dev and thr.numel() == ncls and thr.is_contiguous()
+                    a.threshold = thr.data_ptr()
             ops.heads_predict(a)
             P, T = ops.heads_step_outputs(ws, n, H)
             parts.append((logits, t_rel, rel[:n], rel[n:], P, T) + pred)
@@ -1926,13 +1940,22 @@ class _HeadsStepFn(torch.autograd.Function):
             a.ap = ap.data_ptr()
         sent = sent.contiguous()
         ncls = a.ncls
-        assert sent.dtype == (torch.int64 if ncls else torch.float32) and sent.numel() == B
+        multi = _multi_head(top)
+        assert sent.dtype == (torch.int64 if ncls and not multi else torch.float32) and sent.numel() == (B * ncls if multi else B)
         f32 = torch.float32
         loss, aux, out5 = torch.empty((), device=dev, dtype=f32), torch.empty(3, device=dev, dtype=f32), torch.empty(5, device=dev, dtype=f32)
         logits, t_rel, rel = torch.empty((B, ncls or 1), device=dev, dtype=f32), torch.empty((B, 2), device=dev, dtype=f32), torch.empty((2 * B, 2), device=dev, dtype=f32)
         ws = ops.heads_step_workspace(B, H, dev)
         pred = None
-        if ncls:                                               # class labels int64 [B]; the predicted classes come back in ``pred``
+        if multi:                                              # fp32 targets [B, C] (< 0: not annotated); the decisions [B, C] come back in ``pred``
+            pred = torch.empty((B, ncls), device=dev, dtype=torch.int64)
+            a.multi_label, a.multi_target, a.pred = 1, sent.data_ptr(), pred.data_ptr()
+            for name, field in (("pos_weight", "pos_weight"), ("thresholds", "threshold")):
+                t = getattr(top, name, None)
+                if t is not None:
+                    assert t.dtype == torch.float32 and t.device == dev and t.numel() == ncls and t.is_contiguous()
+                    setattr(a, field, t.data_ptr())
+        elif ncls:                                             # class labels int64 [B]; the predicted classes come back in ``pred``
             pred = torch.empty(B, device=dev, dtype=torch.int64)
             a.sent_cls, a.pred = sent.data_ptr(), pred.data_ptr()
         else:
@@ -1941,7 +1964,7 @@ class _HeadsStepFn(torch.autograd.Function):
         cw = getattr(top, "class_weights", None)
         a.loss_kind = MMBertForPretraining._LOSS_KINDS.index(getattr(top, "label_loss_kind", "mse"))
         a.huber_delta = float(getattr(top, "huber_delta", 1.0)) if a.loss_kind == 2 else 0.0
-        a.label_smoothing = float(getattr(top, "label_smoothing", 0.0))
+        a.label_smoothing = float(getattr(top, "multilabel_smoothing", 0.0)) if multi else float(getattr(top, "label_smoothing", 0.0))
         if cw is not None:
             assert cw.dtype == torch.float32 and cw.device == dev and cw.numel() == ncls and cw.is_contiguous()
             a.cls_weight = cw.data_ptr()
@@ -2139,10 +2162,12 @@ class _HeadsFn(torch.autograd.Function):
 class MMBertForPretraining(_GpuModelBase):
     """REF:MMBertForPretraining.py:304-449."""
 
-    def __init__(self, config, num_labels=None, _bert=None):
+    def __init__(self, config, num_labels=None, multi_label=False, _bert=None):
         """``num_labels`` -- DECLARED EXTENSION (the reference fixes 7 before it builds ``classifier1_2``, REF :309-314, and sets the attribute
         only afterwards, REF:train.py:71): None = the reference's model (``num_labels = 7``, one output); 1 or 7: regression, one output;
-        C in 2 .. 16 otherwise: a C-class head, ``classifier1_2 = Linear(H, C)`` with the C-way cross-entropy (REF :314, :438-442)."""
+        C in 2 .. 16 otherwise: a C-class head, ``classifier1_2 = Linear(H, C)`` with the C-way cross-entropy (REF :314, :438-442).
+        ``multi_label=True`` (DECLARED EXTENSION; needs such a C): the same layer read as C independent labels -- one sigmoid
+        per output, binary cross-entropy over the annotated entries of float targets [B, C], decisions int64 [B, C]."""
         super().__init__()
         import weakref
         self.config = config
@@ -2152,6 +2177,7 @@ class MMBertForPretraining(_GpuModelBase):
         self.cls = MMBertPreTrainingHeads(config)
         self.cls._owner = weakref.ref(self)
         self.num_labels = 7 if num_labels is None else self._check_num_labels(num_labels)
+        self.multi_label = self._check_multi_label(multi_label, self.num_labels)
         self.classifier1_1 = nn.Linear(H * 3, H)
         self.classifier1_2 = nn.Linear(H, 1 if self.num_labels in (1, 7) else self.num_labels)
         self.attn = nn.Linear(H * 2, H)
@@ -2177,6 +2203,10 @@ class MMBertForPretraining(_GpuModelBase):
         # the losses' options (set_loss_options; DECLARED EXTENSION): all off = the reference's losses, the same launches and bits
         self.label_loss_kind, self.huber_delta, self.label_smoothing, self.mlm_label_smoothing = "mse", 1.0, 0.0, 0.0
         self.register_buffer("class_weights", None, persistent=False)      # fp32 [C] or None: follows .to() / deepcopy / pickling, not in state_dict()
+        # ... of a multi-label head: positive weights, decision thresholds (stored as LOGITS), target smoothing
+        self.multilabel_smoothing = 0.0
+        self.register_buffer("pos_weight", None, persistent=False)
+        self.register_buffer("thresholds", None, persistent=False)
         # heads through _HeadsFn (hand-written backward, csrc/heads.hip); False = the eager autograd form (_heads), in which
         # ap_loss / label_loss / nce and the relationship scores stay differentiable outputs
         self.fused_heads = os.environ.get("MMBERT_FUSED_HEADS", "1") != "0"
@@ -2235,7 +2265,7 @@ class MMBertForPretraining(_GpuModelBase):
         return out
 
     @classmethod
-    def from_pretrained(cls, name_or_path, ignore_unexpected=True, num_labels=None, **kw):
+    def from_pretrained(cls, name_or_path, ignore_unexpected=True, num_labels=None, multi_label=False, **kw):
         """Loads ``config.json`` + ``pytorch_model.bin`` / ``model.safetensors`` from a LOCAL directory (there is no network on the
         target boxes): ``BertForPreTraining`` / ``BertForMaskedLM`` / ``BertModel`` key names, current or legacy (``_checkpoint_keys``).
         LOUD about what did not arrive: a missing ``bert.embeddings.*`` / ``bert.encoder.*`` tensor raises (a silently fresh encoder
@@ -2245,13 +2275,13 @@ class MMBertForPretraining(_GpuModelBase):
         error, round 3's default); heads the file does not have (``cls.*``, ``bert.pooler.*``) and the reference's own additions
         (jointEmbeddings, fusion head, CPC) keep their fresh initialisation, with a warning that names them -- HF's
         "newly initialized" message.  ``model.load_report`` = dict(missing=[...], unexpected=[...]).  ``num_labels``: the constructor's (a
-        checkpoint whose ``classifier1_2`` has another width fails with torch's size-mismatch error)."""
+        checkpoint whose ``classifier1_2`` has another width fails with torch's size-mismatch error); ``multi_label``: the constructor's."""
         import warnings
         if not os.path.isdir(name_or_path):
             raise OSError(f"{name_or_path}: from_pretrained needs a local checkpoint directory (no network access)")
         with open(os.path.join(name_or_path, "config.json")) as fh:
             cfg = MMBertConfig(**json.load(fh))
-        model = cls(cfg, num_labels=num_labels)
+        model = cls(cfg, num_labels=num_labels, multi_label=multi_label)
         st = os.path.join(name_or_path, "model.safetensors")
         if os.path.exists(st):
             from safetensors.torch import load_file
@@ -2287,13 +2317,18 @@ class MMBertForPretraining(_GpuModelBase):
 
     _LOSS_KINDS = ("mse", "l1", "huber")
 
-    def set_loss_options(self, *, regression="mse", huber_delta=1.0, class_weights=None, label_smoothing=0.0, mlm_label_smoothing=0.0):
+    def set_loss_options(self, *, regression="mse", huber_delta=1.0, class_weights=None, label_smoothing=0.0, mlm_label_smoothing=0.0,
+                         pos_weight=None, thresholds=None, multilabel_smoothing=0.0):
         """DECLARED EXTENSION: what the reference gets by swapping its loss objects (REF:MMBertForPretraining.py:381, :433, :438), inside the
-        fused step.  Keywords only; every call sets all five (the defaults switch an option off again).
+        fused step.  Keywords only; every call sets all of them (the defaults switch an option off again).
         * ``regression`` -- the regression head's label loss (``num_labels`` 1 / 7): "mse" (the reference's), "l1" (``F.l1_loss``) or
           "huber" (``F.huber_loss(delta=huber_delta)``);
         * ``class_weights`` (C finite values > 0) and ``label_smoothing`` -- a C-class head's ``F.cross_entropy(weight=, label_smoothing=)``;
-        * ``mlm_label_smoothing`` -- ``label_smoothing=`` of the three vocabulary cross-entropies (ignore_index -100, per pass).
+        * ``mlm_label_smoothing`` -- ``label_smoothing=`` of the three vocabulary cross-entropies (ignore_index -100, per pass);
+        * ``pos_weight`` (C finite values > 0), ``thresholds`` (C probabilities in (0, 1); stored as logits, log(p / (1 - p)) in double, and
+          compared with the raw logits) and ``multilabel_smoothing`` (t' = t (1 - eps) + eps / 2) -- a multi-label head's
+          ``F.binary_cross_entropy_with_logits(pos_weight=)`` and its decisions; ``class_weights``, ``label_smoothing`` and another
+          ``regression`` than "mse" raise there.
         Smoothings in [0, 1).  Raises ValueError, before anything is stored, for an option the model's head does not have.  The options are
         no parameters: ``class_weights`` is a non-persistent fp32 buffer, ``state_dict()`` keeps the reference's keys.  outputs[5] is the
         loss as configured, in train and eval mode alike; ``predict_tokens`` / ``mlm_eval_epoch`` report the plain negative log-likelihood."""
@@ -2302,6 +2337,7 @@ class MMBertForPretraining(_GpuModelBase):
         if kind not in self._LOSS_KINDS:
             raise ValueError(f"regression = {kind!r}: one of {self._LOSS_KINDS}")
         ncls = _class_head(self)
+        multi = _multi_head(self)
         if ncls and kind != "mse":
             raise ValueError(f"regression = {kind!r} on a {ncls}-class head (its label loss is the cross-entropy)")
 
@@ -2310,6 +2346,21 @@ class MMBertForPretraining(_GpuModelBase):
                 raise ValueError(f"{name} = {x!r}: a number in [0, 1)")
             return float(x)
         eps, meps = smoothing(label_smoothing, "label_smoothing"), smoothing(mlm_label_smoothing, "mlm_label_smoothing")
+        mleps = smoothing(multilabel_smoothing, "multilabel_smoothing")
+        if multi and (class_weights is not None or eps != 0.0):
+            raise ValueError("class_weights / label_smoothing on a multi-label head: its options are pos_weight, thresholds and multilabel_smoothing")
+        if not multi and (pos_weight is not None or thresholds is not None or mleps != 0.0):
+            raise ValueError("pos_weight / thresholds / multilabel_smoothing on a head that is not multi-label (multi_label=True)")
+        pw = thr = None
+        if pos_weight is not None:
+            pw = torch.as_tensor(pos_weight, dtype=torch.float32).detach().reshape(-1).clone()
+            if pw.numel() != multi or not bool(torch.isfinite(pw).all()) or not bool((pw > 0).all()):
+                raise ValueError(f"pos_weight: {multi} finite values > 0 (one per label), got {pos_weight!r}")
+        if thresholds is not None:
+            pr = torch.as_tensor(thresholds, dtype=torch.float64).detach().reshape(-1)
+            if pr.numel() != multi or not bool(((pr > 0) & (pr < 1)).all()):
+                raise ValueError(f"thresholds: {multi} probabilities in (0, 1) (one per label), got {thresholds!r}")
+            thr = torch.log(pr / (1.0 - pr)).to(torch.float32)
         if isinstance(huber_delta, bool) or not isinstance(huber_delta, (int, float)) or not (0.0 < float(huber_delta) < math.inf):
             raise ValueError(f"huber_delta = {huber_delta!r}: a finite number > 0")
         cw = None
@@ -2323,6 +2374,9 @@ class MMBertForPretraining(_GpuModelBase):
             raise ValueError("label_smoothing on a regression head (num_labels 1 / 7); mlm_label_smoothing smooths the vocabulary losses")
         self.label_loss_kind, self.huber_delta, self.label_smoothing, self.mlm_label_smoothing = kind, float(huber_delta), eps, meps
         self.class_weights = None if cw is None else cw.to(self.classifier1_2.weight.device)
+        self.multilabel_smoothing = mleps
+        self.pos_weight = None if pw is None else pw.to(self.classifier1_2.weight.device)
+        self.thresholds = None if thr is None else thr.to(self.classifier1_2.weight.device)
         return self
 
     def _heads_options(self) -> bool:
@@ -2335,15 +2389,34 @@ class MMBertForPretraining(_GpuModelBase):
             raise ValueError(f"num_labels = {n!r}: 1 or 7 (regression, one output) or a class count from 2 to 16 (one 16-wide tile of the heads kernels)")
         return int(n)
 
-    def set_num_labels(self, n):
+    @staticmethod
+    def _check_multi_label(multi_label, n) -> bool:
+        if not isinstance(multi_label, bool):
+            raise ValueError(f"multi_label = {multi_label!r}: True or False")
+        if multi_label and (n in (1, 7) or not 2 <= n <= 16):
+            raise ValueError(f"multi_label=True with num_labels = {n}: a multi-label head needs a label count from 2 to 16 other than 7 "
+                             "(1 and 7 are the regression head)")
+        return multi_label
+
+    def set_num_labels(self, n, multi_label=False):
         """DECLARED EXTENSION: the constructor's ``num_labels`` on an existing model, where the reference flow sets the attribute
         (REF:train.py:70-72, after ``from_pretrained``): ``classifier1_2`` is re-created (HF initialisation, ``config.initializer_range``)
         when its width has to change -- one output for 1 / 7, C outputs for a class count C in 2 .. 16 --, on the device and in the dtype
         of the old layer, and the flat parameter / gradient buffers are dropped (rebuilt on the next use).  Call it BEFORE the optimizer is
         built: an optimizer holds the old layer's parameters and the old flat buffers, and raises at its next call once they are rebuilt
-        (optim.AdamW._check_current).  State-dict key names do not change."""
+        (optim.AdamW._check_current).  State-dict key names do not change.  ``multi_label``: the constructor's (the layer is a class
+        head's either way)."""
         n = self._check_num_labels(n)
+        multi_label = self._check_multi_label(multi_label, n)
         width = 1 if n in (1, 7) else n
+        for name in ("pos_weight", "thresholds"):
+            t = getattr(self, name, None)
+            if t is not None and (not multi_label or t.numel() != n):
+                raise ValueError(f"set_num_labels({n}, multi_label={multi_label}): {name} for {t.numel()} labels is set -- clear it first (set_loss_options())")
+        if (self.class_weights is not None or self.label_smoothing != 0.0) and multi_label:
+            raise ValueError(f"set_num_labels({n}, multi_label=True): class_weights / label_smoothing are set -- clear them first (set_loss_options())")
+        if getattr(self, "multilabel_smoothing", 0.0) != 0.0 and not multi_label:
+            raise ValueError(f"set_num_labels({n}): multilabel_smoothing is set -- clear it first (set_loss_options())")
         if self.class_weights is not None and self.class_weights.numel() != (0 if n in (1, 7) else n):
             raise ValueError(f"set_num_labels({n}): class weights for {self.class_weights.numel()} classes are set -- clear them first (set_loss_options())")
         old = self.classifier1_2
@@ -2353,6 +2426,7 @@ class MMBertForPretraining(_GpuModelBase):
             self.classifier1_2 = new.to(device=old.weight.device, dtype=old.weight.dtype)
             self._flat = None
         self.num_labels = n
+        self.multi_label = multi_label
         return self
 
     def _apply(self, fn, *a, **k):
@@ -2363,6 +2437,10 @@ class MMBertForPretraining(_GpuModelBase):
         cw = self.__dict__.get("_buffers", {}).get("class_weights")
         if cw is not None and cw.dtype != torch.float32:        # .double() / .half() cast buffers: the kernels read the class weights as fp32
             self.class_weights = cw.float()
+        for name in ("pos_weight", "thresholds"):               # ... and the multi-label head's buffers
+            t = self.__dict__.get("_buffers", {}).get(name)
+            if t is not None and t.dtype != torch.float32:
+                setattr(self, name, t.float())
         return out
 
     def __setstate__(self, state):
@@ -2447,6 +2525,16 @@ class MMBertForPretraining(_GpuModelBase):
                     label_loss = F.huber_loss(logits_out.view(-1), target, delta=self.huber_delta)
                 else:
                     label_loss = F.mse_loss(logits_out.view(-1), target)
+            elif _multi_head(self):
+                # C independent labels: F.binary_cross_entropy_with_logits over the annotated entries (target >= 0), mean over their count
+                x, t = logits_out, sentiment.to(logits_out.dtype).view(logits_out.shape)
+                valid = t >= 0
+                eps = float(getattr(self, "multilabel_smoothing", 0.0))
+                tp = torch.where(valid, t * (1.0 - eps) + 0.5 * eps, torch.zeros_like(t))
+                pw, thr = getattr(self, "pos_weight", None), getattr(self, "thresholds", None)
+                per = F.binary_cross_entropy_with_logits(x, tp, pos_weight=None if pw is None else pw.to(x.dtype), reduction="none")
+                label_loss = torch.where(valid, per, torch.zeros_like(per)).sum() / valid.sum().clamp(min=1).to(x.dtype)
+                logits_out = (x > (0.0 if thr is None else thr.to(x.dtype))).long()     # the decisions [B, C], strictly above the threshold
             elif _class_head(self) and (self.class_weights is not None or self.label_smoothing != 0.0):
                 cw = self.class_weights
                 label_loss = F.cross_entropy(logits_out, sentiment.view(-1).long(), weight=None if cw is None else cw.to(logits_out.dtype),
@@ -2461,9 +2549,23 @@ class MMBertForPretraining(_GpuModelBase):
     def _check_class_labels(self, sentiment) -> int:
         """The class count of a C-class head (0: regression); its labels are integers -- checked before anything is launched."""
         ncls = _class_head(self)
+        if _multi_head(self):
+            if sentiment is not None:
+                if not torch.is_tensor(sentiment) or not sentiment.is_floating_point():
+                    raise TypeError(f"a multi-label head takes floating targets [B, {ncls}] (< 0: not annotated): sentiment is "
+                                    f"{getattr(sentiment, 'dtype', type(sentiment))}")
+                if sentiment.dim() != 2 or sentiment.shape[1] != ncls:
+                    raise ValueError(f"a multi-label head takes targets [B, {ncls}]: sentiment is {tuple(sentiment.shape)}")
+            return ncls
         if ncls and sentiment is not None and (sentiment.is_floating_point() or sentiment.dtype == torch.bool):
             raise TypeError(f"a {ncls}-class head takes integer class labels in [0, {ncls}), one per sample: sentiment is {sentiment.dtype}")
         return ncls
+
+    def _stage_sentiment(self, sentiment, dev):
+        """The labels as the fused heads read them: int64 [B] (class head), fp32 [B, C] (multi-label head) or fp32 [B]."""
+        if _multi_head(self):
+            return sentiment.to(dev).float().contiguous()
+        return sentiment.to(dev).view(-1).long() if _class_head(self) else sentiment.to(dev).view(-1).float()
 
     def _coop_heads_apply(self, sentiment, B) -> bool:
         """Whether the level-launch heads (_HeadsStepFn) will run this step: then the MLM head leaves the [CLS] rows in the encoder output for
@@ -2501,7 +2603,7 @@ class MMBertForPretraining(_GpuModelBase):
                 if not self.__dict__.get("_warned_heads_cls"):
                     import warnings
                     self.__dict__["_warned_heads_cls"] = True
-                    warnings.warn(f"msa_amd: a {ncls}-class head has kernels in the level-launch heads only (model.coop_heads, hidden_size % 16 == 0, "
+                    warnings.warn(f"msa_amd: a {ncls}-{'label multi-label' if _multi_head(self) else 'class'} head has kernels in the level-launch heads only (model.coop_heads, hidden_size % 16 == 0, "
                                   "gradient buffers in place): the heads run in eager PyTorch (~250 small launches per step)")
             elif not self.__dict__.get("_warned_heads_batch"):
                 import warnings
@@ -2509,7 +2611,7 @@ class MMBertForPretraining(_GpuModelBase):
                 warnings.warn(f"msa_amd: per-GPU batch {B} is beyond the fused heads' limit (128 samples on the level-launch path, 32 on "
                               "the 19-launch path): the heads run in eager PyTorch (~250 small launches per step)")
         if fused:
-            sent = sentiment.to(dev).view(-1).long() if ncls else sentiment.to(dev).view(-1).float()
+            sent = self._stage_sentiment(sentiment, dev)
             if coop:
                 ap = (ap_v.to(dev).view(-1).long(), ap_s.to(dev).view(-1).long())
                 if pre is None:                                   # (nothing was prelaunched: the record is made here, with no event)
@@ -2568,7 +2670,7 @@ class MMBertForPretraining(_GpuModelBase):
         if coop and getattr(self, "heads_side_stream", True) and y.is_cuda:
             # the heads' forward levels below the losses go out NOW, on the side stream, beside the MLM head's launches (_HeadsStepFn.prelaunch)
             pre = _HeadsStepFn.prelaunch(self, y, plan["first"], (ap_v.to(dev).view(-1).long(), ap_s.to(dev).view(-1).long()),
-                                         sentiment.to(dev).view(-1).long() if ncls else sentiment.to(dev).view(-1).float())
+                                         self._stage_sentiment(sentiment, dev))
         try:
             # first = [3B, H]: the [CLS] rows of every sequence; joint_loss = alpha * (mlm_t + mlm_v + mlm_s) / 3 + heads_loss  (:427, :443)
             mlm, logits, first = _MLMHeadFn.apply(y, self.cls.predictions.transform.LayerNorm.weight, self, labels, plan["bounds"], plan["bounds_dev"],
@@ -2587,7 +2689,7 @@ class MMBertForPretraining(_GpuModelBase):
                         scores[0], t_rel, scores[1], v_rel, scores[2], s_rel)
         return self.outputs, logits_out
 
-    def predict(self, input_ids, token_type_ids, attention_mask, return_pooled=False, return_attention=None):
+    def predict(self, input_ids, token_type_ids, attention_mask, return_pooled=False, return_attention=None, return_probabilities=False):
         """DECLARED EXTENSION, not in the reference (its ``sampling.py`` does not run against its own model's signature): the sentiment
         prediction WITHOUT labels.  The first three arguments are ``forward``'s.  Returns ``logits`` [B, 1] fp32 -- what ``forward``
         returns as its second value in eval mode, classifier1_2(classifier1_1(gated concat)), through tanh when ``num_labels == 1``
@@ -2605,6 +2707,12 @@ class MMBertForPretraining(_GpuModelBase):
         With a C-class head (``num_labels=C`` / ``set_num_labels``): returns the predicted classes, int64 [B] -- the index of the largest
         raw logit, the lowest index on an exact tie (the reference's ``argmax(sigmoid(logits))``, REF :442, differs only where two fp32
         sigmoids coincide) --, and ``return_pooled`` adds ``class_logits`` fp32 [B, C] (raw) to the dict.
+
+        With a multi-label head (``multi_label=True``): returns the decisions, int64 [B, C] -- 1 where the raw logit lies strictly above the
+        label's threshold (``set_loss_options(thresholds=)``; 0.5 = logit 0 without one) --, written by the classifier tile's own
+        workgroup: no launch more than a class head's predict.  ``return_probabilities=True`` (multi-label head only, else ``ValueError``)
+        returns ``sigmoid(logits)`` fp32 [B, C] as a second value -- (decisions, probabilities[, dict]) -- at the cost of ONE elementwise
+        launch behind the heads.
 
         ``return_attention`` = ``"top"`` | ``"all"`` (``None`` / ``False``: off; anything else raises ``ValueError``): also returns a dict
         (ONE dict when ``return_pooled`` is set as well) with the attention rows of every sequence's [CLS] query -- the only rows the pooler
@@ -2627,6 +2735,8 @@ class MMBertForPretraining(_GpuModelBase):
         else:
             raise ValueError(f"predict(): return_attention = {return_attention!r}; expected None, False, 'top' or 'all'")
         ncls = _class_head(self)
+        if return_probabilities and not _multi_head(self):
+            raise ValueError("predict(): return_probabilities is the multi-label head's (multi_label=True)")
         if self.num_labels not in (1, 7) and not ncls:
             raise NotImplementedError(f"predict(): num_labels = {self.num_labels} on a classifier1_2 with {self.classifier1_2.out_features} output(s) -- setting the "
                                       "attribute alone does not widen the layer (REF:MMBertForPretraining.py:309-314); build the class head with "
@@ -2652,7 +2762,10 @@ class MMBertForPretraining(_GpuModelBase):
                 extra["attention"] = {n: torch.stack([p[k * B:(k + 1) * B, :, :lens[k]] for _, p in maps]) for k, n in enumerate(names)}
                 extra["attention_layers"] = [i for i, _ in maps]
                 extra["attention_mass"] = {n: attention_modality_mass(extra["attention"][n], lens[0]) for n in names[1:]}
+            probs = (torch.sigmoid(logits),) if return_probabilities else ()       # (one elementwise launch)
         out = pred[0] if ncls else logits                         # the classes (what forward returns second); the raw logits on request
+        if probs:
+            return (out,) + probs + ((extra,) if (return_pooled or att is not None) else ())
         return (out, extra) if (return_pooled or att is not None) else out
 
     def predict_tokens(self, input_ids, token_type_ids, attention_mask, masked_labels=None, positions=None, top_k=5):

@@ -1295,21 +1295,34 @@ class _HeadsStepOpt(ctypes.Structure):
     _fields_ = [("step", _HeadsStep), ("opt", _HeadsLoss)]
 
 
+class _HeadsMulti(ctypes.Structure):
+    """Mirror of ``mmbert_heads_multi``: the multi-label head's record (all zero / NULL = off: the regression / class head)."""
+    _fields_ = [("multi_label", ctypes.c_int), ("multi_target", _VP), ("pos_weight", _VP), ("threshold", _VP)]
+
+
+class _HeadsStepMl(_HeadsStepOpt):
+    """Mirror of ``mmbert_heads_step_ml``: ``mmbert_heads_step_opt`` with the multi-label record behind it (a ctypes subclass appends its
+    fields to its base's), anonymous like the other two parts -- ``a.multi_label``, ``a.threshold``."""
+    _anonymous_ = ("ml",)
+    _fields_ = [("ml", _HeadsMulti)]
+
+
 _heads_sync = {}
 _heads_struct_checked = False
 
 
-def heads_step_struct() -> "_HeadsStepOpt":
-    """A zeroed argument record with the label loss's options behind it (zero: off)."""
+def heads_step_struct() -> "_HeadsStepMl":
+    """A zeroed argument record with the label loss's options and the multi-label record behind it (zero / NULL: off)."""
     global _heads_struct_checked
     if not _heads_struct_checked:
         lib = _lib.load()
         for what, n, mirror in (("mmbert_heads_step", lib.mmbert_heads_step_struct_size(), _HeadsStep),
-                                ("mmbert_heads_step_opt", lib.mmbert_heads_step_opt_struct_size(), _HeadsStepOpt)):
+                                ("mmbert_heads_step_opt", lib.mmbert_heads_step_opt_struct_size(), _HeadsStepOpt),
+                                ("mmbert_heads_step_ml", lib.mmbert_heads_step_ml_struct_size(), _HeadsStepMl)):
             if n != ctypes.sizeof(mirror):
                 raise RuntimeError(f"{what}: the library's struct has {n} bytes, the binding's {ctypes.sizeof(mirror)}")
         _heads_struct_checked = True
-    return _HeadsStepOpt()
+    return _HeadsStepMl()
 
 
 def heads_step_sync(device) -> torch.Tensor:
@@ -1329,9 +1342,16 @@ def _heads_opt_on(a) -> bool:
     return isinstance(a, _HeadsStepOpt) and bool(a.loss_kind or a.label_smoothing != 0.0 or a.cls_weight)
 
 
-def heads_step_fwd(a: "_HeadsStepOpt", lo: int = 1, hi: int = 7):
-    """Forward levels lo .. hi.  With every option of the label loss off the call is mmbert_heads_step_fwd_levels's, as before."""
-    if _heads_opt_on(a):
+def _heads_multi_on(a) -> bool:
+    return isinstance(a, _HeadsStepMl) and bool(a.multi_label or a.pos_weight or a.threshold)
+
+
+def heads_step_fwd(a: "_HeadsStepMl", lo: int = 1, hi: int = 7):
+    """Forward levels lo .. hi.  With every option of the label loss off the call is mmbert_heads_step_fwd_levels's, as before; a
+    multi-label head goes through mmbert_heads_step_fwd_levels_ml."""
+    if _heads_multi_on(a):
+        _lib.check(_lib.load().mmbert_heads_step_fwd_levels_ml(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_fwd_levels_ml")
+    elif _heads_opt_on(a):
         _lib.check(_lib.load().mmbert_heads_step_fwd_levels_opt(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_fwd_levels_opt")
     else:
         _lib.check(_lib.load().mmbert_heads_step_fwd_levels(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_fwd_levels")
@@ -1339,7 +1359,10 @@ def heads_step_fwd(a: "_HeadsStepOpt", lo: int = 1, hi: int = 7):
 
 def heads_predict(a: "_HeadsStep"):
     """Forward levels 1 - 5 without labels (mmbert_heads_predict): logits, t_rel, rel and the workspace's P / T (heads_step_outputs)."""
-    _lib.check(_lib.load().mmbert_heads_predict(_stream(), ctypes.addressof(a)), "mmbert_heads_predict")
+    if _heads_multi_on(a):          # (level 5 of a multi-label head reads the thresholds: the entry point that sees the record)
+        _lib.check(_lib.load().mmbert_heads_predict_opt(_stream(), ctypes.addressof(a)), "mmbert_heads_predict_opt")
+    else:
+        _lib.check(_lib.load().mmbert_heads_predict(_stream(), ctypes.addressof(a)), "mmbert_heads_predict")
 
 
 def heads_step_outputs(ws: torch.Tensor, B: int, H: int):
@@ -1354,6 +1377,9 @@ def heads_step_dmlm(a: "_HeadsStep"):
 
 
 def heads_step_bwd(a: "_HeadsStep", lo: int = 1, hi: int = 6):
+    if _heads_multi_on(a):          # (sent_cls may be NULL there: the entry point that knows)
+        _lib.check(_lib.load().mmbert_heads_step_bwd_levels_ml(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_bwd_levels_ml")
+        return
     _lib.check(_lib.load().mmbert_heads_step_bwd_levels(_stream(), ctypes.addressof(a), lo, hi), "mmbert_heads_step_bwd_levels")
 
 

@@ -86,6 +86,8 @@ def collate(examples):
         assert len(a) == len(b) == len(c) == len(d) == len(e)                # :92
     sent_dtype = torch.long if torch.as_tensor(ts[0]).dtype == torch.int64 else torch.float
     mk_sent = lambda x: torch.tensor([float(v) if sent_dtype == torch.float else int(v) for v in x], dtype=sent_dtype)
+    if torch.as_tensor(ts[0]).numel() > 1:                                   # a vector label per item (multi-label head): float32 [B, C]
+        mk_sent = lambda x: torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(-1) for v in x])
     text = pad_sequence([torch.as_tensor(t) for t in te], batch_first=True, padding_value=0)
     text_mask = torch.ones(text.shape, dtype=torch.float64)
     text_mask[text == 0] = 0
@@ -252,12 +254,26 @@ def balanced_class_weights(labels, C):
     return (float(y.numel()) / (float(C) * count)).to(torch.float32)
 
 
+def balanced_pos_weight(labels):
+    """Positive weights that undo the imbalance of multi-hot ``labels`` [N, C] (< 0: not annotated, left out): per column
+    #negatives / max(#positives, 1) over its annotated entries, float32 [C] -- the usual ``pos_weight`` of a binary cross-entropy."""
+    y = torch.as_tensor(labels).to(torch.float64)
+    if y.dim() != 2:
+        raise ValueError(f"balanced_pos_weight: labels [N, C], got {tuple(y.shape)}")
+    valid = y >= 0
+    pos = ((y > 0.5) & valid).sum(0).to(torch.float64)
+    neg = ((y <= 0.5) & valid).sum(0).to(torch.float64)
+    return (neg / pos.clamp(min=1.0)).to(torch.float32)
+
+
 def apply_loss_options(model, args, train_dataset=None):
     """``model.set_loss_options`` from the optional ``args.label_loss`` ("mse" | "l1" | "huber"), ``args.huber_delta``, ``args.class_weights``
     (a sequence of C values, or "balanced": ``balanced_class_weights`` of ``train_dataset``'s labels), ``args.label_smoothing`` and
-    ``args.mlm_label_smoothing``.  ``default_args()`` has none of them: a model is then left exactly as it is (options set by hand stay).
+    ``args.mlm_label_smoothing``; for a multi-label head ``args.pos_weight`` (a sequence of C values, or "balanced":
+    ``balanced_pos_weight`` of ``train_dataset``'s label vectors), ``args.thresholds`` and ``args.multilabel_smoothing``.
+    ``default_args()`` has none of them: a model is then left exactly as it is (options set by hand stay).
     Returns whether anything was set."""
-    names = ("label_loss", "huber_delta", "class_weights", "label_smoothing", "mlm_label_smoothing")
+    names = ("label_loss", "huber_delta", "class_weights", "label_smoothing", "mlm_label_smoothing", "pos_weight", "thresholds", "multilabel_smoothing")
     if not any(hasattr(args, n) for n in names):
         return False
     cw = getattr(args, "class_weights", None)
@@ -268,8 +284,17 @@ def apply_loss_options(model, args, train_dataset=None):
             raise ValueError("args.class_weights = \"balanced\" needs the training set's labels (train_dataset)")
         C = int(model.num_labels)
         cw = balanced_class_weights([int(train_dataset[i][3]) for i in range(len(train_dataset))], C)     # (an example's 4th field: its label)
+    pw = getattr(args, "pos_weight", None)
+    if isinstance(pw, str):
+        if pw != "balanced":
+            raise ValueError(f"args.pos_weight = {pw!r}: a sequence of weights or \"balanced\"")
+        if train_dataset is None:
+            raise ValueError("args.pos_weight = \"balanced\" needs the training set's labels (train_dataset)")
+        pw = balanced_pos_weight(torch.stack([torch.as_tensor(train_dataset[i][3], dtype=torch.float32).reshape(-1) for i in range(len(train_dataset))]))
+        pw = pw.clamp(min=torch.finfo(torch.float32).tiny)      # (a column without negatives: the smallest weight > 0)
     model.set_loss_options(regression=getattr(args, "label_loss", "mse"), huber_delta=getattr(args, "huber_delta", 1.0), class_weights=cw,
-                           label_smoothing=getattr(args, "label_smoothing", 0.0), mlm_label_smoothing=getattr(args, "mlm_label_smoothing", 0.0))
+                           label_smoothing=getattr(args, "label_smoothing", 0.0), mlm_label_smoothing=getattr(args, "mlm_label_smoothing", 0.0),
+                           pos_weight=pw, thresholds=getattr(args, "thresholds", None), multilabel_smoothing=getattr(args, "multilabel_smoothing", 0.0))
     return True
 
 
@@ -352,7 +377,8 @@ def predict_epoch(args, model, data, *, device="cuda", batches=None, return_atte
     ``data``: a Dataset of the reference's 16-tuples (collated here, ``args.test_batch_size``, else ``args.val_batch_size``), or pass
     ``batches`` = an iterable of model-kwargs dicts (keys other than ``input_ids`` / ``token_type_ids`` / ``attention_mask``, such as
     labels, are ignored).  Returns the predictions as one float32 array [N, 1] -- from a model with a C-class head (``num_labels=C``
-    / ``set_num_labels``) the predicted classes, one int64 array [N] --: one device->host transfer at the end.  Leaves
+    / ``set_num_labels``) the predicted classes, one int64 array [N], with a multi-label head the decisions, int64 [N, C] --: one
+    device->host transfer at the end.  Leaves
     ``model.training`` as it found it.
 
     ``return_attention`` = ``"top"`` | ``"all"`` (``model.predict``'s argument): returns ``(preds, dict)`` with ``attention`` and
@@ -370,7 +396,9 @@ def predict_epoch(args, model, data, *, device="cuda", batches=None, return_atte
         batches = (pack_predict_inputs(b, device) for b in loader)
     preds = [model.predict(kw["input_ids"], kw["token_type_ids"], kw["attention_mask"]) for kw in batches]
     if not preds:
-        from .model import _class_head
+        from .model import _class_head, _multi_head
+        if _multi_head(model):
+            return np.zeros((0, _multi_head(model)), dtype=np.int64)
         return np.zeros((0,), dtype=np.int64) if _class_head(model) else np.zeros((0, 1), dtype=np.float32)
     preds = torch.cat(preds)
     return (preds.float() if preds.is_floating_point() else preds).cpu().numpy()
@@ -480,6 +508,33 @@ def test_MSE_score_model(preds, y_test, use_zero=False):
         p = p.reshape(-1)
     return float(np.mean(p == y)), mae, _weighted_f1(y, p)
 
+def test_multilabel_score_model(preds, y_test):
+    """Multi-label heads (decisions [N, C] against multi-hot targets [N, C]; entries with ``y_test < 0`` are left out, a target counts as
+    positive above 0.5): per label and averaged over the labels, ``accuracy``, ``weighted_accuracy`` = (TPR + TNR) / 2 -- a rate over
+    no entries counts 0 -- and ``f1`` (2 TP / (2 TP + FP + FN), 0 without positives on either side); ``mae`` = the mean |decision - target|
+    over the annotated entries.  Returns dict(accuracy, weighted_accuracy, f1, mae: floats; per_label: dict of three [C] lists).  CMU-MOSEI's
+    emotion protocol (weighted accuracy and F1 per emotion)."""
+    import numpy as np
+    preds, y = np.asarray(preds), np.asarray(y_test, dtype=np.float64)
+    if preds.shape != y.shape or y.ndim != 2:
+        raise ValueError(f"test_multilabel_score_model: decisions {preds.shape} against targets {y.shape}; both [N, C]")
+    acc, wacc, f1 = [], [], []
+    for c in range(y.shape[1]):
+        v = y[:, c] >= 0
+        p, t = preds[v, c] > 0, y[v, c] > 0.5
+        tp, tn = float(np.sum(p & t)), float(np.sum(~p & ~t))
+        fp, fn = float(np.sum(p & ~t)), float(np.sum(~p & t))
+        n = tp + tn + fp + fn
+        acc.append((tp + tn) / n if n else 0.0)
+        wacc.append(((tp / (tp + fn) if tp + fn else 0.0) + (tn / (tn + fp) if tn + fp else 0.0)) / 2.0)
+        f1.append(2 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else 0.0)
+    valid = y >= 0
+    mae = float(np.mean(np.absolute(preds[valid] - y[valid]))) if valid.any() else 0.0
+    mean = lambda x: float(np.mean(x)) if len(x) else 0.0
+    return dict(accuracy=mean(acc), weighted_accuracy=mean(wacc), f1=mean(f1), mae=mae, per_label=dict(accuracy=acc, weighted_accuracy=wacc, f1=f1))
+
+
+test_multilabel_score_model.__test__ = False
 test_CE_score_model.__test__ = False                                # names start with "test_": not pytest cases
 test_MSE_score_model.__test__ = False
 
@@ -507,7 +562,8 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
     ``epoch_batches``: optional callable ``(split, epoch) -> iterable of model kwargs`` replacing the datasets (synthetic data).
     ``args.max_grad_norm``, when present, reaches every epoch's train_epoch (global-norm clipping).
     ``args.label_loss`` / ``huber_delta`` / ``class_weights`` / ``label_smoothing`` / ``mlm_label_smoothing``, when present, are set on the
-    model first (apply_loss_options).
+    model first (apply_loss_options).  A multi-label model is scored by ``test_multilabel_score_model``: "acc" is then the mean weighted
+    accuracy over the labels, "f_score" the mean F1.
     An optimizer with a weight EMA (``AdamW.ema``; ``args.ema_decay`` through build_optimizer): each epoch's validation, test and saved
     state dict use the averaged weights (``optimizer.ema_weights()``); training goes on from the trained ones.
     Returns a dict with the best epoch's numbers and the per-epoch history."""
@@ -518,6 +574,10 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
     save_dir = _dated_dir(save_root)
     log("Model save path: {}".format(save_dir))
     score = test_MSE_score_model if getattr(args, "num_labels", 7) in (1, 7) else test_CE_score_model
+    if getattr(model, "multi_label", False):                          # the model-selection number: the mean weighted accuracy
+        def score(preds, y):
+            r = test_multilabel_score_model(preds, y)
+            return r["weighted_accuracy"], r["mae"], r["f1"]
     best = dict(epoch=-1, acc=0.0, loss=float("inf"), mae=None, f_score=None, preds=None, labels=None, path=None)
     history = []
     patience = 0
