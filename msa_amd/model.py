@@ -1497,7 +1497,9 @@ class _GpuModelBase(nn.Module):
         cfg = self.config
         if T > cfg.max_position_embeddings:
             raise ValueError("text length exceeds max_position_embeddings")
-        seed = 0 if predict else self._next_seed()         # (predict: no dropout site is live, the seed is never read)
+        # (predict, eval mode: no dropout site is live, the seed is never read -- and none is DRAWN: an evaluation pass between two train
+        # steps leaves the steps' dropout masks what they are without it, tests/test_session_twin_gpu.py)
+        seed = self._next_seed() if (self.training and not predict) else 0
         je = bert.jointEmbeddings
         rowset = bool(rowset and labels is not None and torch.is_grad_enabled() and getattr(self, "skip_padded_backward", True)
                       and getattr(self, "skip_masked_keys", True))
