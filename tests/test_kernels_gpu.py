@@ -279,7 +279,10 @@ def test_dropout_hash_pairwise_keep_correlations(ops):
     element, so rates alone do not show whether the two halves of a word, neighbouring pairs or neighbouring rows are independent.
     Pearson correlation of the keep flags at p = 0.1 and 0.5 over 2^23 elements laid out as rows of H = 768: element 2i vs 2i + 1 (the
     two halves of one word), pair i vs i + 1 (same half of neighbouring words), row r vs r + 1 (768 elements = 384 words apart), and
-    two different sites (streams) at the same index.  Independent bits give |rho| ~ 1 / sqrt(n) = 3.5e-4; bound 2e-3."""
+    two different sites (streams) at the same index -- ONE pair of streams (seed 12345, sites 77 / 78); the survey over every pair of the
+    model's own sites and over consecutive seeds lives in tests/test_rng_reference_cpu.py::test_stream_pair_survey_meets_the_projects_bound
+    (on the integer reference, which tests/test_rng_gpu.py holds the device to bit for bit), and records the pairs that miss this bound.
+    Independent bits give |rho| ~ 1 / sqrt(n) = 3.5e-4; bound 2e-3."""
     H, rows = 768, 8192
     n = H * rows
     for p_drop in (0.1, 0.5):
