@@ -99,6 +99,15 @@ int mmbert_gemm_tn_grouped_rows(mmbert_stream_t stream, int nprob, const void* c
 
 /* out[n] += alpha * alpha_dev[0] * sum_m X[m][n]   (bias gradients) */
 int mmbert_colsum(mmbert_stream_t stream, const void* X, int ldx, int M, int N, float* out, float alpha, const float* alpha_dev);
+/* ... for up to 52 matrices in one call: out_p[n] (+)= alpha * alpha_dev[0] * sum_m X_p[m][n]  (X_p bf16 [M_p, N_p], row pitch ldx_p,
+ * 16-byte aligned; fp32 sums) -- the bias gradients of an encoder layer whose weight gradients do not run (frozen weights, HF:175-177,
+ * 289-293, 334-351).  The token axis is split as well as the columns, through fp32 partial sums in `workspace`
+ * (>= mmbert_colsum_grouped_workspace bytes, 16-byte aligned) that a second launch folds in a fixed order: one adder per output address,
+ * no atomics, the same bits in either deterministic setting.  accumulate_each (may be null: `accumulate` for all): per problem, whether
+ * it adds to out_p or overwrites it.  N_p % 8 != 0 or ldx_p % 8 != 0: -1; a problem with M_p == 0 is skipped; an empty call returns 0. */
+size_t mmbert_colsum_grouped_workspace(int nprob, const int* M, const int* N);
+int mmbert_colsum_grouped(mmbert_stream_t stream, int nprob, const void* const* X, const int* ldx, const int* M, const int* N, float* const* out,
+                          int accumulate, const int* accumulate_each, float alpha, const float* alpha_dev, void* workspace);
 
 /* ---- dropout RNG (counter based; forward and backward regenerate the same mask) ---- */
 uint32_t mmbert_rng_stream(uint64_t seed, uint32_t site);
@@ -488,7 +497,8 @@ typedef struct {
     int rows, H, I, lddy;
 } mmbert_layer_bwd_args;
 int mmbert_layer_fwd(mmbert_stream_t stream, const mmbert_attn_layout* layout, const mmbert_layer_fwd_args* a);
-/* dx = the gradient of the layer input; the caller then launches the layer's weight gradients from (du, y1), (dz2d, g), (dqkv, x), (dz1d, actx). */
+/* dx = the gradient of the layer input (NULL: not computed -- the layer is the lowest one with a trainable parameter and everything below
+ * it is frozen, so its last product, dqkv . Wqkv + dz1, does not run); the caller then launches the layer's weight gradients from (du, y1), (dz2d, g), (dqkv, x), (dz1d, actx). */
 int mmbert_layer_bwd(mmbert_stream_t stream, const mmbert_attn_layout* layout, const mmbert_layer_bwd_args* a);
 int mmbert_layer_struct_sizes(int* out /* [3]: sizeof the three structures above, for a binding's self-check */);
 

@@ -1473,3 +1473,142 @@ int mmbert_colsum(hipStream_t stream, const void* X, int ldx, int M, int N, floa
 }
 
 }  // extern "C"
+
+// ---- grouped column sums (bias gradients of a layer whose weights are frozen: no weight-gradient launch carries them) ----
+// out_p[n] (+)= alpha * alpha_dev[0] * sum_m X_p[m][n] for up to CSG_MAXP problems in one call, WITHOUT atomics: pass 1 splits every
+// problem into (512-column block) x (row chunk) workgroups that leave fp32 partial sums in the workspace, pass 2 folds a column's chunks in
+// a fixed order with one adder per output address.  The chunking is a function of M alone (not of the device, not of deterministic mode):
+// the same bits always.  Pass 1 is the streaming read: a lane owns 8 columns (16-byte loads), the 4 waves take interleaved rows, 8
+// independent loads in flight per lane.
+#define CSG_MAXP 52
+#define CSG_MAX_CHUNKS 128
+struct CSGProb { const bf16_t* X; float* out; long long part; int M, N, ldx, rows, chunks, cblocks, wg0, col0, acc; };
+struct CSGArgs { CSGProb pr[CSG_MAXP]; int nprob; float alpha; const float* alpha_dev; float* ws; };
+
+static inline void csg_chunks(int M, int* rows, int* chunks) {
+    int c = (M + 63) / 64;
+    if (c > CSG_MAX_CHUNKS) c = CSG_MAX_CHUNKS;
+    if (c < 1) c = 1;
+    const int r = ((M + c - 1) / c + 31) / 32 * 32;             // whole 32-row steps (4 waves x 8 loads)
+    *rows = r; *chunks = (M + r - 1) / r;
+}
+
+__global__ __launch_bounds__(256) void colsum_grouped_partial_kernel(const CSGArgs a) {
+    int p = 0;
+    while (p + 1 < a.nprob && (int)blockIdx.x >= a.pr[p + 1].wg0) ++p;
+    const CSGProb& q = a.pr[p];
+    const int w = blockIdx.x - q.wg0;
+    const int cb = w % q.cblocks, chunk = w / q.cblocks;
+    const int lane = threadIdx.x & 63, sub = threadIdx.x >> 6;
+    const int n = (cb * 64 + lane) * 8;
+    const int mbeg = chunk * q.rows, mend = min(q.M, mbeg + q.rows);
+    const bf16_t* __restrict__ X = q.X;
+    const size_t ldx = (size_t)q.ldx;
+    float s[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) s[r] = 0.f;
+    if (n < q.N) {
+        int m = mbeg + sub;
+        for (; m + 28 < mend; m += 32) {                          // 8 independent 16-byte loads in flight
+            bf16x8 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = *(const bf16x8*)(X + (size_t)(m + 4 * u) * ldx + n);
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int r = 0; r < 8; ++r) s[r] += bf2f(v[u][r]);
+        }
+        for (; m < mend; m += 4) {
+            const bf16x8 v = *(const bf16x8*)(X + (size_t)m * ldx + n);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) s[r] += bf2f(v[r]);
+        }
+    }
+    __shared__ float red[4][64][9];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) red[sub][lane][r] = s[r];
+    __syncthreads();
+    if (sub == 0 && n < q.N) {
+        float* dst = a.ws + q.part + (size_t)chunk * q.N + n;      // [chunks][N] of this problem; n + 8 <= N (N % 8 == 0)
+        float o[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) o[r] = (red[0][lane][r] + red[1][lane][r]) + (red[2][lane][r] + red[3][lane][r]);
+        *(float4*)dst = make_float4(o[0], o[1], o[2], o[3]);
+        *(float4*)(dst + 4) = make_float4(o[4], o[5], o[6], o[7]);
+    }
+}
+
+// pass 2: a workgroup folds 256 columns (64 lanes x 4); its 4 waves take the chunks c = wave, wave + 4, ... and are added in wave order
+__global__ __launch_bounds__(256) void colsum_grouped_fold_kernel(const CSGArgs a) {
+    int p = 0;
+    while (p + 1 < a.nprob && (int)blockIdx.x >= a.pr[p + 1].col0) ++p;
+    const CSGProb& q = a.pr[p];
+    const int lane = threadIdx.x & 63, sub = threadIdx.x >> 6;
+    const int n = ((blockIdx.x - q.col0) * 64 + lane) * 4;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (n < q.N) {
+        const float* src = a.ws + q.part + n;
+        for (int c = sub; c < q.chunks; c += 4) {
+            const float4 t = *(const float4*)(src + (size_t)c * q.N);
+            s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+        }
+    }
+    __shared__ float4 red[4][64];
+    red[sub][lane] = s;
+    __syncthreads();
+    if (sub == 0 && n < q.N) {
+        const float al = a.alpha * (a.alpha_dev ? *a.alpha_dev : 1.0f);
+        const float4 t0 = red[0][lane], t1 = red[1][lane], t2 = red[2][lane], t3 = red[3][lane];
+        float4 v = make_float4(((t0.x + t1.x) + (t2.x + t3.x)) * al, ((t0.y + t1.y) + (t2.y + t3.y)) * al,
+                               ((t0.z + t1.z) + (t2.z + t3.z)) * al, ((t0.w + t1.w) + (t2.w + t3.w)) * al);
+        float* o = q.out + n;                                      // (a bias gradient inside the flat buffer: 4-byte aligned only)
+        if (q.acc) { v.x += o[0]; v.y += o[1]; v.z += o[2]; v.w += o[3]; }
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+}
+
+extern "C" {
+
+// workspace bytes of a mmbert_colsum_grouped call over these problems (0 for an empty call; the call itself refuses more than 52)
+size_t mmbert_colsum_grouped_workspace(int nprob, const int* M, const int* N) {
+    size_t fl = 0;
+    for (int i = 0; i < nprob; ++i) {
+        if (M[i] <= 0 || N[i] <= 0) continue;
+        int rows, chunks;
+        csg_chunks(M[i], &rows, &chunks);
+        fl += (size_t)chunks * (size_t)N[i];
+    }
+    return fl * sizeof(float);
+}
+
+int mmbert_colsum_grouped(hipStream_t stream, int nprob, const void* const* X, const int* ldx, const int* M, const int* N, float* const* out,
+                          int accumulate, const int* accumulate_each, float alpha, const float* alpha_dev, void* workspace) {
+    if (nprob <= 0) return 0;
+    if (nprob > CSG_MAXP) return -1;
+    CSGArgs a = {};                                               // (the kernels read pr[0 .. nprob) only)
+    int k = 0, wg = 0, col = 0;
+    long long part = 0;
+    for (int i = 0; i < nprob; ++i) {
+        if (N[i] < 0 || (N[i] & 7) || (ldx[i] & 7) || ldx[i] < N[i]) return -1;
+        if (M[i] <= 0 || N[i] == 0) continue;                     // nothing to sum: the output is left as it is
+        if (!X[i] || !out[i] || ((uintptr_t)X[i] & 15)) return -1;
+        CSGProb& q = a.pr[k++];
+        q.X = (const bf16_t*)X[i]; q.out = out[i]; q.M = M[i]; q.N = N[i]; q.ldx = ldx[i];
+        csg_chunks(M[i], &q.rows, &q.chunks);
+        q.cblocks = (N[i] + 511) / 512; q.wg0 = wg; q.col0 = col; q.part = part;
+        q.acc = accumulate_each ? accumulate_each[i] : accumulate;
+        wg += q.cblocks * q.chunks;
+        col += (N[i] + 255) / 256;
+        part += (long long)q.chunks * N[i];
+    }
+    if (k == 0) return 0;
+    if (!workspace || ((uintptr_t)workspace & 15)) return -3;
+    a.nprob = k; a.alpha = alpha; a.alpha_dev = alpha_dev; a.ws = (float*)workspace;
+    hipLaunchKernelGGL(colsum_grouped_partial_kernel, dim3(wg), dim3(256), 0, stream, a);
+    MMB_CHECK_LAUNCH();
+    hipLaunchKernelGGL(colsum_grouped_fold_kernel, dim3(col), dim3(256), 0, stream, a);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"

@@ -58,6 +58,7 @@ int mmbert_layer_bwd(mmbert_stream_t s, const mmbert_attn_layout* L, const mmber
     MMB_TRY(mmbert_attn_bwd(s, a->qkv, a->actx, a->dctx, a->dqkv, a->lse, a->delta, L->key_bias, L->bias_start, H, L->heads, L->seq_start, L->seq_len,
                             L->elem_base, L->qtile_seq, L->qtile_r0, L->nqtiles, L->tile_seq, L->tile_r0, L->ntiles,
                             a->att.stream, a->att.thr16, a->att.scale, L->kv_len, L->qtile_qshift, L->qtile_qend, L->split, nullptr));
+    if (!a->dx) return 0;                  // the lowest layer that backward runs: nothing below it takes an input gradient
     MMB_TRY(mmbert_gemm_nt(s, a->dqkv, 3 * H, a->WqkvT, 3 * H, a->dx, H, M, H, 3 * H, MMBERT_EPI_RESID, nullptr, a->dz1, H, nullptr, 0, nullptr, 0,
                            1.0f, nullptr, 0, 0, 1.0f, a->tile_queue));
     return 0;

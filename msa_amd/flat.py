@@ -15,8 +15,8 @@ have pre-transposed bf16 copies (``halfT``) so that input gradients are NT GEMMs
 What torch code may do to them and still be seen (tests/test_flat_semantics_gpu.py): in-place edits that bump a parameter's version
 counter (``load_state_dict``, ``nn.init.*``, ``with torch.no_grad(): p.mul_()``, ``p.detach().add_()``, a foreign optimizer) are picked up
 by the next forward; writes through ``p.data`` and re-pointed parameters after ``model.parameters_changed()``; a ``.grad`` set to None
-(``zero_grad(set_to_none=True)``, any subset) is a dropped gradient (reconcile_grads).  Not covered: a ``.grad`` replaced by a tensor of
-the caller's, ``requires_grad_(False)``.  The storage is never copied or pickled: a copy of the model re-flattens on its first use.
+(``zero_grad(set_to_none=True)``, any subset) is a dropped gradient (reconcile_grads); ``requires_grad_(False)`` freezes a
+parameter from the next forward on (set_frozen; msa_amd/freeze.py).  Not covered: a ``.grad`` replaced by a tensor of the caller's.  The storage is never copied or pickled: a copy of the model re-flattens on its first use.
 The layout order follows the order in which backward finishes gradients (heads, layer L-1..0,
 embeddings; the tied word embedding last) so buckets can be reduced while backward still runs.
 """
@@ -187,6 +187,9 @@ class FlatParams:
         self.stale: set = set()
         self.lazy_detached = False
         self._detached: frozenset = frozenset()     # the names detach_lazy() set to None (reconcile_grads: not a caller's drop)
+        # the parameters the model's last forward saw with requires_grad == False (set_frozen): their .grad is None and stays None, nothing
+        # reads their part of ``grads``, the optimizer does not step them
+        self.frozen: frozenset = frozenset()
         self._reconciled_task = -1                  # the backward pass (autograd graph task) reconcile_in_backward() last ran in
         # the factor the optimizer applies to ``grads`` (1 / world under parallel.DataParallel, which sets it): the torch-semantics
         # clip (optim.clip_grad_norm_) measures the gradient the step will apply, the mean over ranks
@@ -239,8 +242,31 @@ class FlatParams:
             self.stale.discard(i)
 
     def drop_lazy(self):
-        """After the optimizer's fused zero_grad: the lazy gradients are dropped, not zeroed."""
-        self.stale = set(self.lazy)
+        """After the optimizer's fused zero_grad: the lazy gradients are dropped, not zeroed (a frozen one has no writer: not stale)."""
+        fz = self.frozen
+        self.stale = set(self.lazy) if not fz else {i for i, (_, names) in self.lazy.items() if not all(n in fz for n in names)}
+
+    def set_frozen(self, names: frozenset):
+        """The set of frozen parameters as the model's forward has just read it.  Entering the set: ``.grad`` reads None from now on (no
+        lazy-zero or reconcile call attaches it again, and it is no caller's dropped gradient).  Leaving it: the parameter's part of
+        ``grads`` -- unspecified while frozen -- is zero-filled and attached again, like a dropped gradient.
+        LIMIT: the storage holds ONE set, that of the latest forward that went ahead.  Which launches a backward makes follows the set
+        its own forward saw (the record travels with the graph), but which ``.grad`` views exist follows this set: two forwards with
+        different sets ahead of one backward leave ``.grad`` attached by the later one."""
+        if names == self.frozen:
+            return
+        was, self.frozen = self.frozen, frozenset(names)
+        for n in self.frozen - was:
+            self.named[n].grad = None
+        back = [n for n in was - self.frozen if self.named[n].grad is None]
+        if back:
+            self.join_side_writers()
+            for n in back:
+                o = self.offset[n]
+                self.grads[o:o + self.numel[n]].zero_()
+                self._attach(n)
+        fz = self.frozen
+        self.stale = {i for i in self.stale if not all(n in fz for n in self.lazy[i][1])}
 
     def detach_lazy(self):
         """zero_grad(): .grad of the parameters whose buffer is stale reads None (torch's set_to_none), until the next backward."""
@@ -258,7 +284,7 @@ class FlatParams:
         for _, names in self.lazy.values():
             for n in names:
                 p = self.named[n]
-                if p.grad is None:
+                if p.grad is None and n not in self.frozen:
                     o = self.offset[n]
                     p.grad = self.grads[o:o + self.numel[n]].view(p.shape)
         self.lazy_detached = False
@@ -390,7 +416,8 @@ class FlatParams:
         forward (owns), at the first gradient stage of every backward pass (a drop between forward and backward) and at every optimizer
         call: one scan of ``p.grad is None`` on the host; everything dropped = one fill of the buffer."""
         named = self.named
-        none = [n for n, p in named.items() if p.grad is None]
+        fz = self.frozen
+        none = [n for n, p in named.items() if p.grad is None and n not in fz]
         if not none:
             return
         ours = self._detached if self.lazy_detached else ()
@@ -398,7 +425,7 @@ class FlatParams:
         if not dropped:
             return
         self.join_side_writers()             # (a backward that raised may still have launches adding into the gradients filled here)
-        if len(none) == len(named):
+        if len(none) == len(named) - len(fz):
             self.grads.zero_()
             self.stale.clear()
             self.grads_dirty = False

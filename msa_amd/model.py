@@ -30,6 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from . import freeze as _freeze
 from .flat import FlatParams
 
 MODALITY_DIMS = {"mosi": (47, 74), "mosei": (35, 74), "ur_funny": (371, 81)}      # REF:config.py:13-17
@@ -102,7 +103,7 @@ def _make_bert_holder(cfg) -> nn.Module:
 # points the ``_owner`` references of its parts at the copy.
 _RUNTIME_STATE = ("_flat", "_lw", "_w", "_plans", "_lnd", "_input_stream", "_input_stream_batch", "_wgrad_join", "_heads_join",
                   "_late_wgrads", "_row_inverse", "_pro_calls", "_pro_marks", "_pro_bufs", "_last_valid_dev", "_deferred_embed_rows",
-                  "_private_top", "outputs")
+                  "_private_top", "outputs", "_tplan", "_tplan_key", "_anchor")
 
 
 def _copyable_state(module: nn.Module) -> dict:
@@ -241,6 +242,16 @@ class _JointFn(torch.autograd.Function):
         return de1, None, None, None, None, None, None, None
 
 
+def _gv(p):
+    """A head parameter's view of the flat gradient buffer: ``p.grad``, or for a frozen parameter (``.grad`` is None) the part of the
+    buffer where its gradient is computed and dropped (nothing reads it)."""
+    g = p.grad
+    if g is None:
+        f, o = p._mmb_flat
+        g = f.grads[o:o + p.numel()].view(p.shape)
+    return g
+
+
 def _pair_features(f, dev):
     """The pair features as the projection kernels take them: contiguous fp32 or float64 on the device.  The reference's collate hands over
     float64 (REF:model_utils.py:94-99) and JointEmbeddings casts with ``.float()`` (REF:MMBertEmbedding.py:62,64); the kernels read float64
@@ -302,12 +313,23 @@ def _wgrad(top, probs):
     """One weight-gradient launch for ``probs`` = [(dY, X, gW (view of the flat gradient buffer), gb)]: it OVERWRITES gradients the
     optimizer has dropped (lazy zero, flat.FlatParams.take_accumulate) and accumulates otherwise."""
     f = top._flat
+    if not probs:                                                 # (every problem of the launch belongs to frozen parameters)
+        return
     if not f.stale:
         ops.gemm_tn_grouped(probs, accumulate=True)
     else:
         # per problem: a gradient outside the lazy set (the MLM transform's: zeroed by the optimizer) in one call with dropped ones must not
         # make take_accumulate settle those with zero fills
         ops.gemm_tn_grouped(probs, accumulate=[f.take_accumulate([q[2]]) for q in probs])
+
+
+def _trainable_probs(keyed, modes):
+    """``keyed`` = [(key, (dY, X, gW, gb))] of a layer's weight-gradient problems, ``modes`` = freeze.TrainablePlan.layers[i] (None: nothing
+    frozen).  Returns (the problems that run, [(dY, gb)] whose bias gradient alone is wanted: ops.colsum_grouped); a problem whose weight
+    and bias are frozen is in neither."""
+    if modes is None:
+        return [q for _, q in keyed], []
+    return [q for k, q in keyed if modes[k] == _freeze.FULL], [(q[0], q[3]) for k, q in keyed if modes[k] == _freeze.BIAS]
 
 
 def _late_wgrad(top, prob, defer: bool):
@@ -407,17 +429,20 @@ class _EncoderFn:
     autograd between its stages)."""
 
     @staticmethod
-    def run_forward(top, x, layout, key_bias, seed, kv_len, keep, y_out=None, y_rows=None, stop=None, train=None, probe=None):
+    def run_forward(top, x, layout, key_bias, seed, kv_len, keep, y_out=None, y_rows=None, stop=None, train=None, probe=None, keep_from=0):
         """Returns (y, saved).  ``y_out`` / ``y_rows``: the LAST layer's LayerNorm writes row i of its output to y_out[y_rows[i]] --
         the un-packing of the valid-first layout (ops.SplitLayout.perm32) rides on that store instead of a [tokens, H] gather.
         ``stop``: run layers 0 .. stop - 1 only; ``train``: the dropout decision, when it is not the module's mode (both: predict()).
-        ``probe`` (predict(return_attention="all")): called as probe(layer index, qkv) once a layer's QKV matrix is final; it only reads."""
+        ``probe`` (predict(return_attention="all")): called as probe(layer index, qkv) once a layer's QKV matrix is final; it only reads.
+        ``keep_from``: the lowest layer whose backward will run (a frozen prefix below it, freeze.TrainablePlan.stop): the layers below keep
+        nothing -- no pre-activation, no LayerNorm statistics, ``saved[i]`` is None -- and compute the same bits (dropout included)."""
         cfg = top.config
         H, L = cfg.hidden_size, cfg.num_hidden_layers
         nl = L if stop is None else stop
         train = top.training if train is None else train
         ph = cfg.hidden_dropout_prob if train else 0.0
         pa = cfg.attention_probs_dropout_prob if train else 0.0
+        keep_all = keep
         saved = []
         # One C call per layer (mmbert_layer_fwd: the same seven launches with the same arguments, bit-identical) unless somebody wrapped
         # the per-launch functions (bench.py's event timing, tests that spy on launches) or switched it off (model.composite_layers)
@@ -432,6 +457,7 @@ class _EncoderFn:
             tq = ops._tile_queue(dev)
             for i in range(nl):
                 lw = top._lw[i]
+                keep = keep_all and i >= keep_from
                 d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
                 last = i == L - 1 and y_out is not None
                 qkv, actx, z1, y1 = (torch.empty((M_, 3 * H), device=dev, dtype=bf), torch.empty((M_, H), device=dev, dtype=bf),
@@ -460,12 +486,13 @@ class _EncoderFn:
                 ops.layer_fwd(AL, a)
                 if probe is not None:
                     probe(i, qkv)
-                if keep:
-                    saved.append((x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2))
+                if keep_all:
+                    saved.append((x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2) if keep else None)
                 x = y2
             return x, saved
         for i in range(nl):
             lw = top._lw[i]
+            keep = keep_all and i >= keep_from
             d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
             qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
             actx, lse = ops.attn_fwd(qkv, key_bias, layout, H, drop=d_att, kv_len=kv_len)
@@ -479,8 +506,8 @@ class _EncoderFn:
             last = i == L - 1 and y_out is not None
             y2, m2, r2 = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=keep,
                                     out=y_out if last else None, out_rows=y_rows if last else None)
-            if keep:
-                saved.append((x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2))
+            if keep_all:
+                saved.append((x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2) if keep else None)
             x = y2
             if top.debug_hidden is not None:
                 top.debug_hidden.setdefault("_layers_packed", []).append(None if last else y2.detach())
@@ -512,13 +539,18 @@ class _EncoderFn:
         return y2
 
     @staticmethod
-    def run_backward(top, layout, key_bias, kv_len, saved, dy, dy_rows, top_rows, compact=None, lnd=None):
+    def run_backward(top, layout, key_bias, kv_len, saved, dy, dy_rows, top_rows, compact=None, lnd=None, fz=None):
         """``dy``: gradient of the encoder output -- in the encoder's own row order, or (``dy_rows`` = the int32 row list
         ops.SplitLayout.perm32[:rows_a]) in the caller's order, read through the map by the top layer's LayerNorm'.  ``compact`` =
         (rows in the caller's order int64, their gradients [n, H] bf16): the only rows of the output that carry a gradient, handed
-        over by the MLM head (no dense [tokens, H] gradient exists then; ``dy`` is ignored).  Returns dx for the leading rows_a rows."""
+        over by the MLM head (no dense [tokens, H] gradient exists then; ``dy`` is ignored).  Returns dx for the leading rows_a rows.
+        ``fz`` (freeze.TrainablePlan, None: nothing frozen): the layers below ``fz.stop`` do not run (``saved[i]`` is None there); when the
+        embedding stage does not run either, layer ``fz.stop`` computes no input gradient and None is returned; a layer's weight-gradient
+        problems follow ``fz.layers[i]``.  The gradient hook still fires for every layer, L-1 .. 0."""
         H = top.config.hidden_size
         L = top.config.num_hidden_layers
+        stop = 0 if fz is None else fz.stop
+        no_dx = fz is not None and not fz.embedding_stage           # layer ``stop`` is where backward ends
         top._flat.reconcile_in_backward()
         top._flat.grads_dirty = True
         top._flat.attach_lazy()
@@ -527,7 +559,13 @@ class _EncoderFn:
         _join_heads(top)
         # split (valid-first) layout: the rows behind rows_a have exactly-zero gradients in every layer (see _encode), so the
         # whole backward -- dgrads, weight gradients, LayerNorm', attention -- runs on the leading rows_a rows only
-        M_all = saved[0][0].shape[0]
+        own_lnd = lnd is None
+        if stop >= L:                                             # no encoder layer is trainable: the MLM head's few-row gradients and the hooks
+            _flush_late_wgrads(top)
+            for i in reversed(range(L)):
+                top._layer_grads_done(i)
+            return None
+        M_all = saved[stop][0].shape[0]
         ra = layout.rows_a if getattr(layout, "split", False) else M_all
         if dy is not None and dy_rows is None and ra < dy.shape[0]:
             dy = dy[:ra]
@@ -536,7 +574,6 @@ class _EncoderFn:
         # A/B against round 1's form (bias sums inside LayerNorm', one reduce launch per call): 16.58 vs 16.76 ms per step
         # (lnd handed in by the trunk's backward: ITS collector, which already holds the MLM head's call and goes on through the
         # embedding stage -- one reduce launch for all of them; it flushes at its end)
-        own_lnd = lnd is None
         if own_lnd:
             lnd = ops.LnDeferred(2 * L)
         pair_wgrads, held = getattr(top, "pair_wgrads", True), None
@@ -545,12 +582,14 @@ class _EncoderFn:
         if dw is None and _DEFER_ENV:
             dw = _DEFER_ENV != "0"
         if dw is None:
-            dw = _auto_defer_wgrads(H, top.config.intermediate_size, L, x_dev=saved[0][0].device, rows=ra)
+            dw = _auto_defer_wgrads(H, top.config.intermediate_size, L, x_dev=saved[stop][0].device, rows=ra)
         defer_wgrads, deferred = (top.grad_hook is None and bool(dw)), []
         composite_bwd = getattr(top, "composite_layers", True) and ops.launches_unwrapped()
         AL = tq = None
-        for i in reversed(range(L)):
+        for i in reversed(range(stop, L)):
             lw = top._lw[i]
+            modes = None if fz is None else fz.layers[i]
+            skip_dx = no_dx and i == stop
             saved_i = saved[i]
             saved[i] = None
             if ra < M_all:
@@ -574,7 +613,7 @@ class _EncoderFn:
                         (dy_c,) = ops.gather_rows([dy], src_rows.int())
                 if R is not None:
                     dy = _EncoderFn._last_layer_sparse(top, lw, layout, key_bias, kv_len, saved_i, dy_c, R, H, ra, R32, lnd,
-                                                       rinv if compact is not None else None, deferred if defer_wgrads else None)
+                                                       rinv if compact is not None else None, deferred if defer_wgrads else None, modes, skip_dx)
                     if top.grad_hook is not None:
                         lnd.flush()
                     dy_rows = None
@@ -591,7 +630,8 @@ class _EncoderFn:
                     if kv_len is not None and not getattr(layout, "split", False):
                         AL.kv_len = kv_len.data_ptr()
                     tq = ops._tile_queue(dev)
-                dz2, dz1, dy1, dctx, dx_ = (torch.empty((ra, H), device=dev, dtype=bf) for _ in range(5))
+                dz2, dz1, dy1, dctx = (torch.empty((ra, H), device=dev, dtype=bf) for _ in range(4))
+                dx_ = None if skip_dx else torch.empty((ra, H), device=dev, dtype=bf)
                 dz2d = torch.empty((ra, H), device=dev, dtype=bf) if d_h2[1] else None
                 dz1d = torch.empty((ra, H), device=dev, dtype=bf) if d_h1[1] else None
                 du, dqkv = torch.empty((ra, I_), device=dev, dtype=bf), torch.empty((ra, 3 * H), device=dev, dtype=bf)
@@ -610,7 +650,7 @@ class _EncoderFn:
                 b.z2, b.m2, b.r2, b.ln2_ws, b.z1, b.m1, b.r1, b.ln1_ws = z2.data_ptr(), m2.data_ptr(), r2.data_ptr(), ws2, z1.data_ptr(), m1.data_ptr(), r1.data_ptr(), ws1
                 b.u, b.qkv, b.actx, b.lse = u.data_ptr(), qkv.data_ptr(), actx.data_ptr(), lse.data_ptr()
                 b.dz2, b.dz2d, b.du, b.dy1, b.dz1, b.dz1d = dz2.data_ptr(), ops._ptr(dz2d), du.data_ptr(), dy1.data_ptr(), dz1.data_ptr(), ops._ptr(dz1d)
-                b.dctx, b.dqkv, b.delta, b.dx, b.tile_queue = dctx.data_ptr(), dqkv.data_ptr(), delta.data_ptr(), dx_.data_ptr(), tq
+                b.dctx, b.dqkv, b.delta, b.dx, b.tile_queue = dctx.data_ptr(), dqkv.data_ptr(), delta.data_ptr(), ops._ptr(dx_), tq
                 ops._set_drop(b.att, d_att); ops._set_drop(b.h1, d_h1); ops._set_drop(b.h2, d_h2)
                 ops.layer_bwd(AL, b)
                 dy_rows = None
@@ -636,11 +676,17 @@ class _EncoderFn:
                   dz1d = dz1
               dctx = ops.gemm_nt(dz1d, lw["WoT"])
               dqkv = ops.attn_bwd(qkv, actx, dctx, lse, key_bias, layout, H, drop=d_att, kv_len=kv_len)
-              dy = ops.gemm_nt(dqkv, lw["WqkvT"], resid=dz1)
+              dy = None if skip_dx else ops.gemm_nt(dqkv, lw["WqkvT"], resid=dz1)
             # --- all four weight gradients (+ their bias gradients) of the layer in ONE launch.  (They are off the critical path of backward;
             # a side stream for them was measured a loss in rounds 1, 3 and 4 -- the chip's power envelope is shared -- and is gone.)
             probs = [(du, y1, lw["g_W1"], lw["g_b1"]), (dz2d, g, lw["g_W2"], lw["g_b2"]),
                      (dqkv, x, lw["g_Wqkv"], lw["g_bqkv"]), (dz1d, actx, lw["g_Wo"], lw["g_bo"])]
+            if modes is not None:
+                # frozen weights: their problems leave the launch; a trainable bias of a frozen weight gets its column sum from ONE grouped
+                # launch per layer (the bias gradients are zero-filled by the optimizer: always added)
+                probs, sums = _trainable_probs(list(zip(("w1", "w2", "qkv", "o"), probs)), modes)
+                if sums:
+                    ops.colsum_grouped(sums, accumulate=True)
             if defer_wgrads:
                 # One GPU (no gradient hook): nothing needs this layer's weight gradients before the optimizer, so ALL dense layers'
                 # weight gradients can go out as ONE call at the end of backward, in whole rounds of 256 tiles (11 layers = 1188
@@ -657,7 +703,7 @@ class _EncoderFn:
                 # Two layers per launch: a layer's 108 tiles leave the chip half empty, so a single layer splits the token axis in two
                 # (fp32 slabs + a reduce launch, 12 us and 85 MB per layer); two layers' 216 tiles fill it in one round unsplit.  The
                 # upper layer of a pair just keeps its operands alive for one more layer (fresh buffers from the caching allocator)
-                if held is None and i > 0:
+                if held is None and i > stop:
                     held = (i, probs)
                     continue
                 if held is not None:
@@ -675,6 +721,8 @@ class _EncoderFn:
             top._layer_grads_done(i)
         if own_lnd:
             lnd.flush()
+        for i in reversed(range(stop)):                           # the frozen prefix: nothing ran, its (zero) slices are final
+            top._layer_grads_done(i)
         # (mmbert_gemm_tn_grouped_rows: 12 layers per call; round 6: the few-row weight gradients of the MLM head and of the sparse top layer
         # ride behind the last call's tiles)
         _flush_late_wgrads(top, deferred, deferred=defer_wgrads)
@@ -695,11 +743,13 @@ class _EncoderFn:
         return R
 
     @staticmethod
-    def _last_layer_sparse(top, lw, layout, key_bias, kv_len, saved_i, dy_c, R, H, ra, R32=None, lnd=None, rinv=None, deferred=None):
+    def _last_layer_sparse(top, lw, layout, key_bias, kv_len, saved_i, dy_c, R, H, ra, R32=None, lnd=None, rinv=None, deferred=None, modes=None,
+                           skip_dx=False):
         """Backward of the top encoder layer when only the rows R of its output carry a gradient: the output sublayer (LayerNorm',
         FFN-down and FFN-up input gradients, their weight gradients), LayerNorm' and the output projection of the attention
         sublayer run on those rows only (gathered operands, the dropout masks of the ORIGINAL rows); attention's backward is
-        dense again (every unmasked key receives a gradient), as is everything below."""
+        dense again (every unmasked key receives a gradient), as is everything below.  ``modes`` / ``skip_dx``: as in run_backward (the
+        layer's frozen weights; no input gradient when the layer is where backward ends)."""
         cfg = top.config
         x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i
         if R32 is None:
@@ -734,9 +784,22 @@ class _EncoderFn:
         if rinv is None:
             dz1 = torch.zeros((ra, H), device=dy.device, dtype=torch.bfloat16)
             dz1.index_copy_(0, R, dz1_c)
-        out = ops.gemm_nt(dqkv, lw["WqkvT"], resid=dz1)
+        out = None if skip_dx else ops.gemm_nt(dqkv, lw["WqkvT"], resid=dz1)
         # (bias gradients b1 / b2 / bo: column sums of the bf16 gradients on the ones-operand MFMA, as in the dense layers)
         few = [(du_c, y1_c, lw["g_W1"], lw["g_b1"]), (dz2d_c, g_c, lw["g_W2"], lw["g_b2"]), (dz1d_c, actx_c, lw["g_Wo"], lw["g_bo"])]
+        if modes is not None:
+            few, sums = _trainable_probs(list(zip(("w1", "w2", "o"), few)), modes)
+            wide, sums_w = _trainable_probs([("qkv", (dqkv, x, lw["g_Wqkv"], lw["g_bqkv"]))], modes)
+            if sums + sums_w:
+                ops.colsum_grouped(sums + sums_w, accumulate=True)
+            if deferred is not None and getattr(top, "late_wgrads", True):
+                deferred.extend(wide)
+                for q in few:
+                    _late_wgrad(top, q, True)
+            else:
+                _wgrad(top, few)
+                _wgrad(top, wide)
+            return out
         if deferred is not None and getattr(top, "late_wgrads", True):
             # the deferred multi-layer call takes them: the QKV gradient (all rows of the backward) as one more of its problems -- it was a
             # launch of 27 tiles with the token axis split 8 ways + a reduce launch --, the three few-row ones behind its tiles
@@ -774,7 +837,7 @@ def _trunk_static(plan, B, T, lens, joff, dev):
 class _Trunk:
     """What one _TrunkFn call works on (plain attributes; built by _encode)."""
     __slots__ = ("ids", "tts", "B", "T", "lens", "pair_info", "feats", "feat_versions", "plan", "layout", "split", "key_bias", "kv_len", "seed", "top_rows",
-                 "d_emb", "d_joint", "infer", "late_split", "compact", "J_pre", "predict", "attention", "dense")
+                 "d_emb", "d_joint", "infer", "late_split", "compact", "J_pre", "predict", "attention", "dense", "freeze")
 
 
 class _TrunkFn(torch.autograd.Function):
@@ -800,6 +863,7 @@ class _TrunkFn(torch.autograd.Function):
         # (a stateless inference call saves nothing for a backward pass: needs_input_grad stays set under no_grad, and the saved
         # operands of every layer -- 5 GB at the headline shape -- would otherwise live to the end of the encoder)
         keep = ctx.needs_input_grad[0] and not t.predict
+        fz = t.freeze if keep else None                           # (freeze.TrainablePlan of this forward; None: nothing frozen)
         late = t.layout                                           # callable: the packing is decided after the embedding launches
         npass = len(lens)
         joint = [k for k in range(npass) if t.pair_info[k] is not None]
@@ -892,11 +956,11 @@ class _TrunkFn(torch.autograd.Function):
             return _EncoderFn.run_top_first(top, y, layout, t.key_bias, kvl, q_rows, probe=probe)
         # (predict_tokens(): every layer dense, in inference arithmetic whatever the module's mode is)
         y, saved = _EncoderFn.run_forward(top, x, layout, t.key_bias, t.seed, None if split is not None else t.kv_len, keep, y_out, y_rows,
-                                          train=False if t.predict else None)
+                                          train=False if t.predict else None, keep_from=0 if fz is None else fz.stop)
         if split is not None and t.infer:
             y = y.index_select(0, split.inv)                      # every masked-out row reads its sequence's representative
         ctx.top, ctx.t, ctx.saved, ctx.joff, ctx.early = top, t, saved, joff, early
-        if keep:
+        if keep and (fz is None or fz.embedding_stage):          # (a frozen embedding stage has no backward: nothing of it is kept)
             ctx.save_for_backward(e0, mean0, rstd0, J, *[x_ for k in joint for x_ in jstats[k]])
         return y
 
@@ -906,10 +970,13 @@ class _TrunkFn(torch.autograd.Function):
         top._flat.reconcile_in_backward()
         cfg, w = top.config, top._w
         H = cfg.hidden_size
-        e0, mean0, rstd0, J, *js = ctx.saved_tensors
+        fz = t.freeze                                             # the trainable set this pass's FORWARD saw
+        emb_stage = fz is None or fz.embedding_stage
         B, T, lens, plan, split = t.B, t.T, t.lens, t.plan, t.split
         bounds = plan["bounds"]
-        st = _trunk_static(plan, B, T, lens, ctx.joff, e0.device)
+        if emb_stage:
+            e0, mean0, rstd0, J, *js = ctx.saved_tensors
+            st = _trunk_static(plan, B, T, lens, ctx.joff, e0.device)
         npass = len(lens)
         layout = split if split is not None else plan["layout"]
         compact, t.compact = t.compact, None                      # (rows in the caller's order, their gradients): set by the MLM head
@@ -930,11 +997,17 @@ class _TrunkFn(torch.autograd.Function):
             if split is not None:
                 dy_rows = split.perm32[:split.rows_a]             # dy is in the caller's order: the top LayerNorm' reads it through the map
         dx = _EncoderFn.run_backward(top, layout, t.key_bias, None if split is not None else t.kv_len, ctx.saved, dy, dy_rows, t.top_rows,
-                                     compact, lnd)
+                                     compact, lnd, fz)
         ctx.saved = None
         top._flat.settle([w["g_word_pad"]])
         if split is not None:
             top.last_backward_row_fraction = float(split.rows_a) / split.tokens
+        if not emb_stage:
+            # every embedding parameter is frozen: backward ended at layer fz.stop (no input gradient there) -- no LayerNorm', no pair
+            # projection gradients, no scatter; the collector still holds the sums of the layers that ran and of the MLM transform
+            lnd.flush()
+            _join_wgrads(top)
+            return None, None, None
         # ---- embedding stage: dx holds the leading rows_a rows of the packed order (all rows without the packing)
         ra = dx.shape[0]
         inv32 = split.inv32 if split is not None else None
@@ -974,7 +1047,9 @@ class _TrunkFn(torch.autograd.Function):
         # the deferred call writes the tied table's gradient whole; the rows below add to it.  (Measured: that gradient on a side stream of
         # its own at the start of backward, so that embed_scatter could run beside the deferred call: +0.1 %, profiles/r6_ab_side_streams.log)
         _join_wgrads(top)
-        if top.defer_embed_rows:
+        if fz is not None and not fz.word_table:
+            ops.embed_scatter(t.ids, t.tts, de0, T, None, w["g_type"], w["g_pos"], vocab=cfg.vocab_size)     # frozen table: no word rows
+        elif top.defer_embed_rows:
             ops.embed_scatter(t.ids, t.tts, de0, T, None, w["g_type"], w["g_pos"], vocab=cfg.vocab_size)
             # a LIST: every differentiated trunk backward between two finish_backward() calls hands over its rows (a second
             # backward must not overwrite the first one's -- parallel.DataParallel exchanges all of them)
@@ -1177,12 +1252,15 @@ class _MLMHeadFn(torch.autograd.Function):
         return 4 * (n + first.numel()) <= ra and int(host[1]) == 0 and n == _active_row_count(t.top_rows[0])
 
     @staticmethod
-    def _few_rows_backward(top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows):
+    def _few_rows_backward(top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows, fz=None):
         """The head's backward over the n labelled rows alone (the sparse paths of _backward), from their dlogits ``dl`` [n, Vpad]: returns
         [n + extra_rows, H] bf16 with the rows' gradient wrt y in its first n rows."""
         w = top._w
         n = dl.shape[0]
-        _late_wgrad(top, (dl, t_c, w["g_word_pad"], w["g_pred_bias"]), late)
+        if fz is not None and not fz.word_table:
+            _MLMHeadFn._pred_bias_grad(w, dl, fz)
+        else:
+            _late_wgrad(top, (dl, t_c, w["g_word_pad"], w["g_pred_bias"]), late)
         dt = ops.gemm_nt_splitk(dl, w["wordT"])                     # K = vocabulary, a few hundred rows: split-K
         dt0 = ops.ln_bwd(dt, t0_c, mean_c, rstd_c, w["mlm_ln_g"], w["g_mlm_ln_g"], w["g_mlm_ln_b"], deferred=lnd)
         dpre = ops.gelu_bwd(dt0, pre_c)
@@ -1192,8 +1270,16 @@ class _MLMHeadFn(torch.autograd.Function):
         return dy_all
 
     @staticmethod
+    def _pred_bias_grad(w, dl, fz):
+        """Frozen word-embedding table: the tied decoder's weight gradient does not run, so the prediction bias's gradient -- a rider on
+        that launch -- is the column sum of the dlogits (ops.colsum_grouped), unless the bias is frozen too."""
+        if "cls.predictions.bias" not in fz.frozen:
+            ops.colsum_grouped([(dl, w["g_pred_bias"])], accumulate=True)
+
+    @staticmethod
     def _backward(ctx, dloss, extra_rows=0):
         w = ctx.top._w
+        fz = ctx.trunk.freeze if ctx.trunk is not None else None
         V = ctx.top.config.vocab_size
         if dloss is None:
             return None
@@ -1215,7 +1301,7 @@ class _MLMHeadFn(torch.autograd.Function):
         if ctx.compact:
             y_c, pre_c, t0_c, mean_c, rstd_c, t_c, logits_c, labels_c, bounds_c, inv, lse, sel = ctx.saved_tensors
             dl = ops.ce_bwd(logits_c, V, labels_c, bounds_c, ctx.nseg, inv, gs, lse, logits_c, smoothing=ctx.smoothing)       # in place: the scores go nowhere
-            return sel, _MLMHeadFn._few_rows_backward(ctx.top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows)
+            return sel, _MLMHeadFn._few_rows_backward(ctx.top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows, fz)
         y, pre, t0, mean, rstd, t, logits, labels, seg_bounds, inv, lse = ctx.saved_tensors
         M = y.shape[0]
         if ctx.rows is not None:
@@ -1228,11 +1314,14 @@ class _MLMHeadFn(torch.autograd.Function):
                 dl = torch.empty((n, logits.shape[1]), device=y.device, dtype=torch.bfloat16)
                 ops.ce_bwd(logits, V, labels, seg_bounds, ctx.nseg, inv, gs, lse, dl, rows=idx, smoothing=ctx.smoothing)
                 t_c, t0_c, pre_c, y_c, mean_c, rstd_c = ops.gather_rows([t, t0, pre, y, mean, rstd], idx)      # one launch
-                return idx, _MLMHeadFn._few_rows_backward(ctx.top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows)
+                return idx, _MLMHeadFn._few_rows_backward(ctx.top, dl, t_c, t0_c, pre_c, y_c, mean_c, rstd_c, lnd, late, extra_rows, fz)
         # dense path: dlogits with the per-pass upstream gradients folded in; in place unless the scores were handed to the caller
         dl = torch.empty(logits.shape, device=logits.device, dtype=torch.bfloat16) if (ctx.keep_logits or logits.dtype != torch.bfloat16) else logits
         ops.ce_bwd(logits, V, labels, seg_bounds, ctx.nseg, inv, gs, lse, dl, smoothing=ctx.smoothing)
-        ops.gemm_tn(dl, t, w["g_word_pad"], bias_out=w["g_pred_bias"], accumulate=ctx.top._flat.take_accumulate([w["g_word_pad"]]))   # tied decoder weight + prediction bias gradient
+        if fz is not None and not fz.word_table:
+            _MLMHeadFn._pred_bias_grad(w, dl, fz)
+        else:
+            ops.gemm_tn(dl, t, w["g_word_pad"], bias_out=w["g_pred_bias"], accumulate=ctx.top._flat.take_accumulate([w["g_word_pad"]]))   # tied decoder weight + prediction bias gradient
         dt = ops.gemm_nt(dl, w["wordT"])
         dt0 = ops.ln_bwd(dt, t0, mean, rstd, w["mlm_ln_g"], w["g_mlm_ln_g"], w["g_mlm_ln_b"], deferred=lnd)
         dpre = ops.gelu_bwd(dt0, pre)
@@ -1341,6 +1430,37 @@ class _GpuModelBase(nn.Module):
             self._build_views()
         else:
             self._flat.maybe_refresh()
+        self._read_trainable()
+
+    def _read_trainable(self):
+        """``requires_grad`` of every parameter, read at every forward: the record of the set (freeze.trainable_plan; None while everything
+        is trainable) is rebuilt when the flags differ from the last look.  Packed neighbours that differ raise NotImplementedError here.
+        Nothing else changes yet: a forward that goes ahead tells the storage which ``.grad`` read None (_apply_trainable)."""
+        f = self._flat
+        key = tuple([p.requires_grad for p in f.named.values()])
+        d = self.__dict__
+        if key != d.get("_tplan_key"):
+            plan = None
+            if not all(key):
+                plan = _freeze.trainable_plan(dict(zip(f.named, key)), self.config.num_hidden_layers, f.offset, f.numel)
+            d["_tplan"], d["_tplan_key"] = plan, key
+
+    def _apply_trainable(self):
+        """The frozen set of the record goes to the storage (FlatParams.set_frozen): from a forward that was not refused."""
+        plan, f = self.__dict__.get("_tplan"), self._flat
+        if plan is not None or f.frozen:
+            f.set_frozen(plan.frozen if plan is not None else frozenset())
+
+    def _trunk_anchor(self, dev):
+        """The tensor that makes autograd call the trunk's backward: the embedding LayerNorm's weight, or -- when that is frozen -- a
+        scalar of the model's own that requires a gradient and never receives one (the heads' parameters may still be trainable)."""
+        p = self._bert().embeddings.LayerNorm.weight
+        if p.requires_grad:
+            return p
+        a = self.__dict__.get("_anchor")
+        if a is None or a.device != dev:
+            a = self.__dict__["_anchor"] = torch.zeros((), device=dev, requires_grad=True)
+        return a
 
     def _build_views(self):
         f, cfg = self._flat, self.config
@@ -1468,7 +1588,7 @@ class _GpuModelBase(nn.Module):
             labels.record_stream(torch.cuda.current_stream())
         return labels, None
 
-    def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None, predict=False, attention=None):
+    def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None, predict=False, attention=None, freeze_ok=False):
         """passes: list of dict(ids[B,T], tt[B,T]|None, mask, pair[B,P,D]|None, pair_mask|None).
         Returns (Y [tokens,H] bf16, plan, lens_per_pass, rows, trunk) -- ``rows`` = (labelled-row list, host words, event) when asked for;
         ``trunk`` = the _Trunk record of the call (forward() hands it to the MLM head: compact output gradient), None for ``predict``.
@@ -1488,6 +1608,16 @@ class _GpuModelBase(nn.Module):
         bert = self._bert()
         dev = passes[0]["ids"].device
         self._ensure_ready(dev)
+        fz = None if predict else self.__dict__.get("_tplan")
+        if fz is not None and not freeze_ok:
+            diff = sorted(n for n in fz.frozen if not _freeze.never_trainable(n))
+            if diff:
+                raise NotImplementedError("frozen parameters (requires_grad == False) are honoured by MMBertForPretraining.forward only: "
+                                          f"this path would differentiate them all the same ({len(diff)} frozen, e.g. {diff[0]}) -- "
+                                          "call model.unfreeze() or use forward()")
+            fz = None                      # (only parameters that are never differentiated carry the flag: nothing to honour on this path)
+        if not predict:
+            self._apply_trainable()
         if not predict:
             lnd = self.__dict__.get("_lnd")
             if lnd is not None and lnd.items and torch.is_grad_enabled():
@@ -1593,6 +1723,7 @@ class _GpuModelBase(nn.Module):
         p_joint = je.dropout_prob if (self.training and je.training and not predict) else 0.0
         t = _Trunk()
         t.compact = None
+        t.freeze = fz if torch.is_grad_enabled() else None
         t.predict = bool(predict)
         t.dense = predict == "dense"
         t.attention = attention if predict else None
@@ -1644,7 +1775,7 @@ class _GpuModelBase(nn.Module):
             t.split = get_split()
             get_split = None
         t.layout = get_split                                      # (late: _TrunkFn calls it once the embedding kernels are queued)
-        y = _TrunkFn.apply(bert.embeddings.LayerNorm.weight, self, t)
+        y = _TrunkFn.apply(bert.embeddings.LayerNorm.weight if fz is None else self._trunk_anchor(dev), self, t)
         split = t.split
         if predict:
             return y, plan, lens, rows, None
@@ -2031,12 +2162,12 @@ class _HeadsStepFn(torch.autograd.Function):
         c1, c2 = top.classifier1_1, top.classifier1_2
         qs = (top.cpc_zt.net, top.cpc_zv.net, top.cpc_za.net)
         a.dloss, a.dfirst, a.dmlm = d1.data_ptr(), dfirst.data_ptr(), ops._ptr(dmlm)
-        a.gWp, a.gbp, a.gWal, a.gbal = (t.grad.data_ptr() for t in (pool.weight, pool.bias, al.weight, al.bias))
-        a.gWat, a.gbat, a.gWc1, a.gbc1, a.gWc2, a.gbc2 = (t.grad.data_ptr() for t in (at.weight, at.bias, c1.weight, c1.bias, c2.weight, c2.bias))
+        a.gWp, a.gbp, a.gWal, a.gbal = (_gv(t).data_ptr() for t in (pool.weight, pool.bias, al.weight, al.bias))
+        a.gWat, a.gbat, a.gWc1, a.gbc1, a.gWc2, a.gbc2 = (_gv(t).data_ptr() for t in (at.weight, at.bias, c1.weight, c1.bias, c2.weight, c2.bias))
         for m in range(3):
-            a.gvw[m], a.gvb[m], a.gWq[m], a.gbq[m] = (vs3[m].weight.grad.data_ptr(), vs3[m].bias.grad.data_ptr(), qs[m].weight.grad.data_ptr(),
-                                                      qs[m].bias.grad.data_ptr())
-        assert at.weight.grad.is_contiguous() and c2.weight.grad.is_contiguous() and c2.weight.grad.shape == c2.weight.shape
+            a.gvw[m], a.gvb[m], a.gWq[m], a.gbq[m] = (_gv(vs3[m].weight).data_ptr(), _gv(vs3[m].bias).data_ptr(), _gv(qs[m].weight).data_ptr(),
+                                                      _gv(qs[m].bias).data_ptr())
+        assert _gv(at.weight).is_contiguous() and _gv(c2.weight).is_contiguous() and _gv(c2.weight).shape == c2.weight.shape
         a.sync = ops.heads_step_sync(dev).data_ptr()
         if ctx.side and dmlm is not None and getattr(top, "heads_side_stream", True):
             # round 6: the six levels on a side stream, beside the MLM head's sparse backward (which needs nothing of the heads' but the
@@ -2152,12 +2283,12 @@ class _HeadsFn(torch.autograd.Function):
         dpre = ops.heads_tanh_bwd(dP, P)
         ops.skinny_mm([(dfirst, None, 0, False, [(dpre, pool.weight, 1, 0), (drel, al.weight, 1, B)])])
         # every weight / bias gradient of the heads' dense layers in ONE launch
-        ops.skinny_wgrad([(dXP[m], T, qs[m].weight.grad, qs[m].bias.grad) for m in range(3)]
-                         + [(dlo, T, c2.weight.grad, c2.bias.grad), (dT, Cc, c1.weight.grad, c1.bias.grad),
-                            (dA, P, at.weight.grad[:, :H], at.bias.grad), (dA, P, at.weight.grad[:, H:], None),
-                            (dpre, first, pool.weight.grad, pool.bias.grad), (drel, first[B:], al.weight.grad, al.bias.grad)])
+        ops.skinny_wgrad([(dXP[m], T, _gv(qs[m].weight), _gv(qs[m].bias)) for m in range(3)]
+                         + [(dlo, T, _gv(c2.weight), _gv(c2.bias)), (dT, Cc, _gv(c1.weight), _gv(c1.bias)),
+                            (dA, P, _gv(at.weight)[:, :H], _gv(at.bias)), (dA, P, _gv(at.weight)[:, H:], None),
+                            (dpre, first, _gv(pool.weight), _gv(pool.bias)), (drel, first[B:], _gv(al.weight), _gv(al.bias))])
         E3, dg3 = E.view(3, B, H), dg.view(3, B, 1)
-        ops.heads_colsum([(E3[m], vs3[m].weight.grad) for m in range(3)] + [(dg3[m], vs3[m].bias.grad) for m in range(3)])
+        ops.heads_colsum([(E3[m], _gv(vs3[m].weight)) for m in range(3)] + [(dg3[m], _gv(vs3[m].bias)) for m in range(3)])
         return dfirst, dmlm
 
 
@@ -2454,6 +2585,34 @@ class MMBertForPretraining(_GpuModelBase):
         if hasattr(self.bert, "jointEmbeddings"):
             self.bert.jointEmbeddings._owner = ref
 
+    def freeze(self, *, embeddings=False, layers=0, layer_weights=False):
+        """Sets ``requires_grad_(False)`` on: ``embeddings`` -- every ``bert.embeddings.*`` and ``bert.jointEmbeddings.*`` parameter;
+        ``layers`` -- encoder layers 0 .. k-1 for an int k, or the layers of an iterable of indices; ``layer_weights`` -- additionally the
+        dense weight matrices (q / k / v, attention output, intermediate, output) of the layers left trainable, whose biases and LayerNorms
+        stay trainable (BitFit-style).  The same as ``p.requires_grad_(False)`` by hand: the next ``forward`` reads the flags, its backward
+        stops at the lowest trainable layer and skips the frozen weights' gradients.  Returns the affected names; an
+        out-of-range layer raises ValueError."""
+        named = dict(self.named_parameters())
+        names = _freeze.resolve_freeze(list(named), self.config.num_hidden_layers, embeddings=embeddings, layers=layers, layer_weights=layer_weights)
+        for n in names:
+            named[n].requires_grad_(False)
+        return names
+
+    def unfreeze(self):
+        """Every parameter trainable again (the flat.FROZEN ones, which the reference never differentiates, stay without a gradient)."""
+        for p in self.parameters():
+            p.requires_grad_(True)
+
+    def trainable_plan(self):
+        """The read-only record of the current ``requires_grad`` flags that the next ``forward`` will use (freeze.TrainablePlan: where
+        backward stops, whether the embedding stage runs, per running layer which weight-gradient problems run and which run as bias
+        only, whether the tied table's gradient runs), or None when every parameter is trainable.  Before the flat storage exists (a model
+        that has not run on the GPU yet) packed neighbours are not checked."""
+        named = dict(self.named_parameters())
+        f = self._flat
+        return _freeze.trainable_plan({n: p.requires_grad for n, p in named.items()}, self.config.num_hidden_layers,
+                                      f.offset if f is not None else {}, f.numel if f is not None else {})
+
     def parameters_changed(self):
         """Tell the model that parameter VALUES were written in a way torch does not report.  In-place tensor operations on a parameter
         (``load_state_dict``, ``nn.init.*``, ``with torch.no_grad(): p.copy_() / p.mul_()``, ``p.detach().add_()``, a torch optimizer)
@@ -2574,7 +2733,7 @@ class MMBertForPretraining(_GpuModelBase):
         that kernel to read (no gather / cast launch)."""
         return bool(self.fused_heads and getattr(self, "coop_heads", True) and sentiment is not None and (self.num_labels in (1, 7) or _class_head(self)) and B <= 128
                     and self.config.hidden_size % 16 == 0
-                    and all(q.grad is not None for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight)))
+                    and all(q.grad is not None or not q.requires_grad for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight)))
 
     def _run_heads(self, first, ap_v, ap_s, sentiment, dev, B, mlm=None, coop=False, src=None, pre=None):
         """The heads on the [3B, H] [CLS] rows: the fused kernels (csrc/heads.hip) where they apply, else the eager form.
@@ -2583,7 +2742,7 @@ class MMBertForPretraining(_GpuModelBase):
         ``src``: (y, first_rows) when the rows were left there, else None; ``pre``: the record of _HeadsStepFn.prelaunch, if that ran.
         (A captured hipGraph of the eager [B,H]-sized glue -- forward and backward, ~200 dependent launches -- was built and
         measured in round 1: no gain; the device time of the tiny kernels, not their dispatch, is the cost.)"""
-        grads_ok = all(q.grad is not None for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight))
+        grads_ok = all(q.grad is not None or not q.requires_grad for q in (self.attn.weight, self.vt.weight, self.classifier1_1.weight))
         ncls = _class_head(self)
         fused = coop or (self.fused_heads and sentiment is not None and first.is_cuda and (self.num_labels in (1, 7) or ncls) and grads_ok)
         if src is not None and not coop:
@@ -2664,7 +2823,7 @@ class MMBertForPretraining(_GpuModelBase):
         if labels.numel() != B * (T + (T + visual.shape[1]) + (T + speech.shape[1])):
             raise ValueError("masked_labels must cover text (+ pair) positions of every pass")
         want_rows = torch.is_grad_enabled() and getattr(self, "sparse_mlm_backward", True) and labels.is_cuda
-        y, plan, lens, rows, trunk = self._encode(passes, labels, want_rows, packed=pk)
+        y, plan, lens, rows, trunk = self._encode(passes, labels, want_rows, packed=pk, freeze_ok=True)
         y = y.contiguous()
         coop = self._heads_read_rows = self._coop_heads_apply(sentiment, B)     # (a record of the decision; nothing reads it back)
         src = (y, plan["first"]) if coop else None          # the [CLS] rows stay in y for the level-launch heads

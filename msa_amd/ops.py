@@ -246,6 +246,33 @@ def colsum(X, out, *, alpha=1.0, alpha_dev=None):
     return out
 
 
+def colsum_grouped(problems, *, accumulate=True, alpha=1.0, alpha_dev=None):
+    """problems: up to 52 pairs (X[M,N] bf16, out[N] fp32): every out (+)= alpha * alpha_dev[0] * X.sum(0) in ONE call that splits the token
+    axis as well as the columns and adds without atomics (see mmbert_colsum_grouped): the bias gradients of a layer whose weight gradients
+    do not run.  ``accumulate``: one flag, or one per problem."""
+    lib = _lib.load()
+    n = len(problems)
+    if n == 0:
+        return
+    if n > TN_MAX_PROBLEMS:
+        raise ValueError(f"colsum_grouped: {n} problems, one call takes at most {TN_MAX_PROBLEMS}")
+    each = None
+    if isinstance(accumulate, (list, tuple)):
+        each = [1 if a else 0 for a in accumulate]
+        assert len(each) == n
+        accumulate = all(each)
+    for X, out in problems:
+        assert X.dtype == torch.bfloat16 and X.dim() == 2 and (X.shape[0] == 0 or X.stride(1) == 1)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == X.shape[1]
+    PA, IA = _PtrArr[n], _IntArr[n]
+    Ms, Ns = IA(*[p[0].shape[0] for p in problems]), IA(*[p[0].shape[1] for p in problems])
+    ws = _ws_f32((lib.mmbert_colsum_grouped_workspace(n, Ms, Ns) + 3) // 4, problems[0][0].device)
+    _lib.check(lib.mmbert_colsum_grouped(
+        _stream(), n, PA(*[p[0].data_ptr() for p in problems]), IA(*[(p[0].stride(0) if p[0].shape[0] > 1 else max(p[0].stride(0), p[0].shape[1])) for p in problems]), Ms, Ns,
+        PA(*[p[1].data_ptr() for p in problems]), 1 if accumulate else 0, IA(*each) if each is not None else None, float(alpha),
+        _ptr(alpha_dev), ws.data_ptr()), "mmbert_colsum_grouped")
+
+
 def dropout_mask(n: int, drop: Tuple[int, int, float], device) -> torch.Tensor:
     lib = _lib.load()
     out = torch.empty(n, device=device, dtype=torch.uint8)

@@ -139,7 +139,6 @@ class AdamW:
         self._m = torch.zeros_like(flat.params)
         self._v = torch.zeros_like(flat.params)
         self._flat = flat
-        self._names = [flat.name_at(p._mmb_flat[1]) for g in self.param_groups for p in g["params"]]
         self._build_flags()
         if self._ema_decay is not None:
             self._ema = flat.params.clone()
@@ -156,7 +155,10 @@ class AdamW:
     def _build_maps(self, flat):
         """The kernel's per-block maps: flags (decay bit from each group's weight_decay > 0; blocks this optimizer does not step are
         frozen) and group_of_block.  A 256-element block holds one group: packed neighbours that share a block (the q/k/v biases, a
-        LayerNorm's weight and bias; the q/k/v weights when H * H % 256 != 0) in different groups raise."""
+        LayerNorm's weight and bias; the q/k/v weights when H * H % 256 != 0) in different groups raise.  Listed parameters that the
+        model's last forward saw frozen (flat.frozen) are skipped as torch skips ``grad is None``: their blocks stay "not owned"."""
+        frozen = self._frozen = flat.frozen
+        self._listed = frozenset(flat.name_at(p._mmb_flat[1]) for g in self.param_groups for p in g["params"])
         flags = flat.flags.clone().cpu()
         flags[flags != 2] = 3                # 3 = not owned by this optimizer -> treated as frozen below
         group = torch.zeros_like(flags)
@@ -168,8 +170,8 @@ class AdamW:
             for p in g["params"]:
                 _, off = p._mmb_flat
                 name = flat.name_at(off)
-                if any(name.startswith(fr) for fr in FROZEN):
-                    continue                 # grad is always None in the reference -> optimizer skips it
+                if any(name.startswith(fr) for fr in FROZEN) or name in frozen:
+                    continue                 # grad is always None in the reference / the parameter is frozen -> optimizer skips it
                 b0, b1 = off // 256, (off + p.numel() + 255) // 256
                 prev = owner[b0:b1]
                 for j in sorted(set(prev[prev >= 0].tolist())):
@@ -189,6 +191,21 @@ class AdamW:
         self._group_of_block = group.to(flat.device)
         self._active = sorted(active)
         self._decay = tuple(decay)
+        self._names = names                  # the parameters this optimizer steps (clip_grad_norm_ measures these)
+
+    def _follow_frozen(self):
+        """The model's frozen set changed since the maps were built: rebuilt.  Freezing more parameters keeps their m and v; a parameter
+        of this optimizer that became trainable after the first step() raises."""
+        flat = self._flat
+        if flat.frozen == self._frozen:
+            return
+        back = sorted(n for n in (self._frozen - flat.frozen) & self._listed if not any(n.startswith(fr) for fr in FROZEN))
+        if back and self._steps > 0:
+            raise NotImplementedError(f"AdamW: {back[0]}" + (f" (and {len(back) - 1} more)" if len(back) > 1 else "") + " became trainable after this "
+                                      "optimizer's first step(): the fused step keeps ONE step count for all parameters, so the parameter's "
+                                      "bias correction would be wrong -- build a new optimizer")
+        self._build_maps(flat)
+        self._build_flags()
 
     def clip_grad_norm_(self, max_norm, norm_type=2.0) -> torch.Tensor:
         """Global gradient-norm clipping fused into the next ``step()``: returns the total norm (0-d fp32 device tensor) of the gradient
@@ -206,6 +223,7 @@ class AdamW:
         flat.join_side_writers()             # (see step(): nothing may still add into the gradients read here)
         flat.reconcile_grads()               # a .grad the caller set to None counts as zero
         flat.settle()                        # a dropped lazy gradient counts as zero
+        self._follow_frozen()                # (frozen parameters are left out of the norm)
         segs, nseg = flat.segments(self._names, FROZEN)
         out = ops.grad_norm(flat.grads, segs, nseg, max_norm=max_norm, norm_type=norm_type, gscale=self.grad_scale,
                             workspace=flat.norm_workspace())
@@ -296,6 +314,7 @@ class AdamW:
         if self._flat is None:
             self._bind()
         self._check_current(self._flat)
+        self._follow_frozen()
         if tuple(h[4] > 0 for h in hyper) != self._decay:
             self._build_maps(self._flat)     # a group's weight_decay turned on or off since the flags were built
             self._build_flags()
@@ -400,6 +419,8 @@ def layerwise_param_groups(model, lr, *, weight_decay=0.01, layer_decay=1.0, hea
     head_lr = lr if head_lr is None else head_lr
     groups = {}
     for n, p in named:
+        if not p.requires_grad:
+            continue                         # frozen (model.freeze / requires_grad_(False)): in no group
         m = layer.match(n)
         if m:
             glr = lr * layer_decay ** (L - int(m.group(1)))

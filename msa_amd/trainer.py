@@ -298,20 +298,33 @@ def apply_loss_options(model, args, train_dataset=None):
     return True
 
 
+def apply_freeze(model, args):
+    """``model.freeze`` from the optional ``args.freeze_embeddings`` (bool), ``args.freeze_layers`` (a count k for layers 0 .. k-1, or an
+    iterable of layer indices) and ``args.freeze_layer_weights`` (bool: the dense weight matrices of the layers left trainable).
+    ``default_args()`` has none of them: a model is then left exactly as it is (``requires_grad`` flags set by hand stay).  Call it before
+    ``build_optimizer``, which leaves frozen parameters out of its groups.  Returns the names it froze."""
+    names = ("freeze_embeddings", "freeze_layers", "freeze_layer_weights")
+    if not any(hasattr(args, n) for n in names):
+        return []
+    return model.freeze(embeddings=bool(getattr(args, "freeze_embeddings", False)), layers=getattr(args, "freeze_layers", 0),
+                        layer_weights=bool(getattr(args, "freeze_layer_weights", False)))
+
+
 def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
     """REF:train.py:76-97: two parameter groups by NAME substring, AdamW, linear warm-up with
     warmup = N and total = warmup_proportion * N.
     ``args.layer_lr_decay`` / ``args.head_learning_rate`` (optional; not reference arguments, ``default_args()`` leaves them out): the
     groups of optim.layerwise_param_groups (layer-wise lr decay, a learning rate of its own for the parts a BERT checkpoint lacks).
     ``args.ema_decay`` / ``args.ema_warmup`` (optional, likewise): an exponential moving average of the weights, kept inside the
-    optimizer step (``AdamW.ema``); ``train`` then validates, tests and saves under the averaged weights."""
+    optimizer step (``AdamW.ema``); ``train`` then validates, tests and saves under the averaged weights.
+    Frozen parameters (``requires_grad == False``: apply_freeze, model.freeze) are in no group."""
     from .optim import AdamW, get_linear_schedule_with_warmup, layerwise_param_groups
     layer_decay, head_lr = getattr(args, "layer_lr_decay", None), getattr(args, "head_learning_rate", None)
     if layer_decay is not None or head_lr is not None:
         groups = layerwise_param_groups(model, args.learning_rate, layer_decay=1.0 if layer_decay is None else layer_decay, head_lr=head_lr)
     else:
         no_decay = ["bias", "LayerNorm.bias", "LayerNorm.weight"]
-        named = list(model.named_parameters())
+        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         groups = [{"params": [p for n, p in named if not any(nd in n for nd in no_decay)], "weight_decay": 0.01},
                   {"params": [p for n, p in named if any(nd in n for nd in no_decay)], "weight_decay": 0.0}]
     opt = AdamW(groups, lr=args.learning_rate, mode=mode)
@@ -562,7 +575,7 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
     ``epoch_batches``: optional callable ``(split, epoch) -> iterable of model kwargs`` replacing the datasets (synthetic data).
     ``args.max_grad_norm``, when present, reaches every epoch's train_epoch (global-norm clipping).
     ``args.label_loss`` / ``huber_delta`` / ``class_weights`` / ``label_smoothing`` / ``mlm_label_smoothing``, when present, are set on the
-    model first (apply_loss_options).  A multi-label model is scored by ``test_multilabel_score_model``: "acc" is then the mean weighted
+    model first (apply_loss_options); ``args.freeze_embeddings`` / ``freeze_layers`` / ``freeze_layer_weights`` likewise (apply_freeze).  A multi-label model is scored by ``test_multilabel_score_model``: "acc" is then the mean weighted
     accuracy over the labels, "f_score" the mean F1.
     An optimizer with a weight EMA (``AdamW.ema``; ``args.ema_decay`` through build_optimizer): each epoch's validation, test and saved
     state dict use the averaged weights (``optimizer.ema_weights()``); training goes on from the trained ones.
@@ -571,6 +584,7 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
     import numpy as np
     log = logger.info if logger is not None else (lambda *a, **k: None)
     apply_loss_options(model, args, train_dataset)
+    apply_freeze(model, args)
     save_dir = _dated_dir(save_root)
     log("Model save path: {}".format(save_dir))
     score = test_MSE_score_model if getattr(args, "num_labels", 7) in (1, 7) else test_CE_score_model
