@@ -610,6 +610,31 @@ int mmbert_gather_rows(mmbert_stream_t stream, int nseg, const void* const* src,
 /* the same from a bf16 source with the fp32 source's element offsets (the working copy mmbert_adamw has just written) */
 int mmbert_transpose_bf16(mmbert_stream_t stream, const void* src, void* dst, const void* descs, int ndesc, int total_tiles);
 
+/* ---- low-rank adapters on the packed Q | K | V projection (a declared extension; csrc/lora.hip) ----
+ * x [M, H] bf16 (row pitch ldx) is the layer input, qkv [M, 3H] bf16 (row pitch ldq) what mmbert_gemm_nt(x, Wqkv, bias) left.  `targets` is a
+ * bit mask of the adapted column thirds (1 = query, 2 = key, 4 = value); A and B are host arrays of THREE device pointers indexed by the
+ * third (entries of untargeted thirds are not read): A_t [r, H] and B_t [H, r] bf16, contiguous, 16-byte aligned.  r in {4, 8, 16},
+ * H % 64 == 0, ldx % 8 == 0, ldq % 8 == 0, x / qkv 16-byte aligned; anything else returns -1; a shape whose staged operands
+ * (targets * 16 * (H + 8) * 2 bytes of LDS) exceed 160 KiB returns -2.  M == 0 returns 0 without a launch.
+ * fwd (one launch, in place):  h_t = bf16(x . A_t^T) with fp32 accumulation;  qkv[:, tH:(t+1)H] = bf16(fma(scale, h_t . B_t^T, float(qkv)))
+ *   (the rank-r product in fp32).  h_out (may be NULL; 8-byte aligned, ldh % 4 == 0): h [M, ntargets * r] bf16, the targets in q, k, v
+ *   order.  Untargeted thirds and rows >= M are not written.
+ * bwd, from dqkv [M, 3H] bf16 (row pitch lddq):
+ *   g_t = bf16(dqkv_t . B_t);  dres_out = bf16(fma(scale, sum_t g_t . A_t, float(dres_in)))  [M, H] -- a buffer of its own (dres_out == dres_in
+ *   is refused: the caller's residual gradient may still be read elsewhere); dres_out == NULL: no input-gradient part;
+ *   gA[t] [r, H] (+)= scale * g_t^T . x;   gB[t] [H, r] (+)= scale * dqkv_t^T . h_t   -- fp32, 16-byte aligned, host arrays of three pointers
+ *   indexed like A / B; a NULL array or entry: that gradient is not computed.  accumulate != 0 adds to gA / gB, 0 overwrites them.
+ *   h: what forward wrote to h_out (row pitch ldh), or NULL -- it is then recomputed from x and A (the same bits) into the workspace.
+ *   The token sums go through fp32 partial sums of 128-token slabs in `workspace` (mmbert_lora_qkv_bwd_workspace bytes, 16-byte aligned;
+ *   -3 without it) that one launch folds in ascending order, one adder per output address: no atomics, the same bits in either
+ *   deterministic setting and on every device.  Up to three launches; nothing is allocated or synchronised. */
+int mmbert_lora_qkv_fwd(mmbert_stream_t stream, const void* x, int ldx, void* qkv, int ldq, int M, int H, int r, int targets,
+                        const void* const* A, const void* const* B, float scale, void* h_out, int ldh);
+size_t mmbert_lora_qkv_bwd_workspace(int M, int H, int r, int targets);
+int mmbert_lora_qkv_bwd(mmbert_stream_t stream, const void* dqkv, int lddq, const void* x, int ldx, const void* h, int ldh, int M, int H, int r,
+                        int targets, const void* const* A, const void* const* B, float scale, const void* dres_in, int lddi,
+                        void* dres_out, int lddo, float* const* gA, float* const* gB, int accumulate, void* workspace);
+
 #ifdef __cplusplus
 }
 #endif

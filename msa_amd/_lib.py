@@ -115,6 +115,9 @@ SIGNATURES = {
     "mmbert_pack_i64": (I, [P, I, P, P, P, P, P]),
     "mmbert_rows_to_block": (I, [P, P, P, I, I, I, I, P, I, I, P]),
     "mmbert_split_layout": (I, [P, P, P, I, I, I, I, I, P]),
+    "mmbert_lora_qkv_fwd": (I, [P, P, I, P, I, I, I, I, I, P, P, F, P, I]),
+    "mmbert_lora_qkv_bwd_workspace": (SZ, [I, I, I, I]),
+    "mmbert_lora_qkv_bwd": (I, [P, P, I, P, I, P, I, I, I, I, I, P, P, F, P, I, P, I, P, P, I, P]),
 }
 
 _lib = None

@@ -1,0 +1,464 @@
+// Low-rank adapters (LoRA) on the packed Q | K | V projection of an encoder layer (a declared extension; the reference has
+// none).  For every targeted third t of qkv [M, 3H]:   qkv_t += s * (x . A_t^T) . B_t^T,   A_t [r, H], B_t [H, r], r in {4, 8, 16}.
+//
+//   forward   mmbert_lora_qkv_fwd : ONE launch, in place on qkv.  h_t = bf16(x . A_t^T) (fp32 MFMA accumulation), then
+//             qkv_t = bf16(fma(s, h_t . B_t^T, float(qkv_t))).
+//   backward  mmbert_lora_qkv_bwd : three launches.  (1) g_t = bf16(dqkv_t . B_t), dres_out = bf16(fma(s, sum_t g_t . A_t, float(dres_in)));
+//             (2) fp32 partial sums of g_t^T . x and dqkv_t^T . h_t over 128-token slabs; (3) the fold: every output address has ONE adder
+//             that takes the slabs in ascending order -- no atomics, the same bits on every device and in either deterministic setting.
+//
+// A workgroup is 4 waves x 16 token rows.  The rank-r operands are staged ONCE per workgroup into LDS as zero-padded 16-wide tiles (so one
+// code path serves r = 4, 8, 16) and all products over H or r run on v_mfma_f32_16x16x32_bf16:
+//   * contraction over H (h, g):  D[n][m] = sum_k T[n][k] X[m][k], T = the padded [16, H] tile (LDS), X = 16 rows of x / dqkv_t straight from
+//     global memory (16-byte loads).  The result has the token m on the LANE and the rank index n = 4 (lane >> 4) + reg in registers --
+//     exactly an operand fragment of the next product, which sums over n: no transpose, no LDS round trip.
+//   * contraction over r (the update of qkv_t / dres): the K = 32 instruction with logical k = 4 (lane >> 4) + j for fragment elements j < 4
+//     and zeros in j >= 4, on both operands.  Two MFMAs whose operand rows are the columns c0 + 8 (i >> 2) + 4 sub + (i & 3) leave EIGHT
+//     consecutive columns of one token row in a lane: the read-modify-write of qkv / dres is a 16-byte load and a 16-byte store.
+// The token-axis contraction (dA, dB) has no MFMA form without a transpose of the two big streams (x and dqkv are row-major in the token:
+// a fragment would need four tokens of one column in a lane); it runs as fp32 FMAs on 16-byte loads -- r FMAs per loaded element, below
+// the memory time of the pass -- a lane owns 8 columns x r rank entries.
+#include "common.h"
+#include "../../include/mmbert_hip.h"
+
+#define LORA_ROWS 64          // token rows per workgroup of the MFMA kernels (4 waves x 16)
+#define LORA_SLAB 128         // token rows per partial sum of the weight gradients
+#define LORA_LDS_MAX 163840   // 160 KiB per CU (gfx950)
+
+struct LoraTarget { const bf16_t* A; const bf16_t* B; int third; int pad; };
+struct LoraFwdArgs {
+    LoraTarget t[3]; int nt, M, H, r, ldx, ldq, ldh; float s;
+    const bf16_t* x; bf16_t* qkv; bf16_t* h;
+};
+struct LoraBwdArgs {
+    LoraTarget t[3]; int nt, M, H, r, ldx, lddq, lddi, lddo, recompute; float s;
+    const bf16_t* x; const bf16_t* dqkv; const bf16_t* dres_in; bf16_t* dres_out;
+    bf16_t* gbuf; bf16_t* hbuf;            // [M, nt * r] each (workspace)
+};
+struct LoraStream { const bf16_t* src; const bf16_t* coef; float* out; int lds, ldc, colmajor, acc; };   // colmajor: out is [H, r] (dB), else [r, H] (dA)
+struct LoraWArgs { LoraStream st[6]; int ns, M, H, r, nslab; float s; float* part; };
+
+
+__device__ __forceinline__ bf16x8 lora_zero8() { bf16x8 z; for (int j = 0; j < 8; ++j) z[j] = (bf16_t)0.0f; return z; }
+// the low four fragment elements from 8 bytes, zeros above (logical k = 4 (lane >> 4) + j, see the head of the file)
+__device__ __forceinline__ bf16x8 lora_low4(bf16x4 v) {
+    bf16x8 o = lora_zero8();
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
+    return o;
+}
+__device__ __forceinline__ bf16x4 lora_round4(f32x4 a) {
+    bf16x4 o;
+    o[0] = f2bf(a[0]); o[1] = f2bf(a[1]); o[2] = f2bf(a[2]); o[3] = f2bf(a[3]);
+    return o;
+}
+
+// T[ti][k][0 .. H) = W_ti[k][0 .. H) for k < r, zeros for r <= k < 16 (W = A: [r, H] row-major).  Row pitch HP = H + 8 elements.
+__device__ __forceinline__ void lora_stage_rows(bf16_t* T, const LoraTarget* t, int nt, int H, int r) {
+    const int CH = H >> 3, HP = H + 8, total = nt * 16 * CH;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+        const int ti = idx / (16 * CH), rem = idx - ti * 16 * CH, k = rem / CH, c = rem - k * CH;
+        bf16x8 v = lora_zero8();
+        if (k < r) v = *(const bf16x8*)(t[ti].A + (size_t)k * H + 8 * c);
+        *(bf16x8*)(T + (size_t)(ti * 16 + k) * HP + 8 * c) = v;
+    }
+}
+// T[ti][k][c] = B_ti[c][k] for k < r, zeros above (B: [H, r] row-major): the transposed tile for the contraction over H in backward
+__device__ __forceinline__ void lora_stage_cols_t(bf16_t* T, const LoraTarget* t, int nt, int H, int r) {
+    const int HP = H + 8, total = nt * H;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+        const int ti = idx / H, c = idx - ti * H;
+        const bf16_t* src = t[ti].B + (size_t)c * r;
+        bf16_t* dst = T + (size_t)(ti * 16) * HP + c;
+        for (int k0 = 0; k0 < r; k0 += 4) {
+            const bf16x4 v = *(const bf16x4*)(src + k0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dst[(size_t)(k0 + j) * HP] = v[j];
+        }
+        for (int k = r; k < 16; ++k) dst[(size_t)k * HP] = (bf16_t)0.0f;
+    }
+}
+// U[ti][c][k] = W[c][k] for k < r, zeros for r <= k < 16, from a [H, r] row-major matrix (B), 16 elements per column c
+__device__ __forceinline__ void lora_stage_pad16(bf16_t* U, const LoraTarget* t, int nt, int H, int r) {
+    const int total = nt * H;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+        const int ti = idx / H, c = idx - ti * H;
+        const bf16_t* src = t[ti].B + (size_t)c * r;
+        bf16x8 lo = lora_zero8(), hi = lora_zero8();
+        if (r == 16) { lo = *(const bf16x8*)src; hi = *(const bf16x8*)(src + 8); }
+        else if (r == 8) lo = *(const bf16x8*)src;
+        else lo = lora_low4(*(const bf16x4*)src);
+        bf16_t* dst = U + (size_t)idx * 16;
+        *(bf16x8*)dst = lo; *(bf16x8*)(dst + 8) = hi;
+    }
+}
+// U[ti][c][k] = A_ti[k][c] for k < r, zeros above (A: [r, H] row-major): the transposed form, for the input gradient
+__device__ __forceinline__ void lora_stage_pad16_t(bf16_t* U, const LoraTarget* t, int nt, int H, int r) {
+    const int CH = H >> 3, total = nt * 16 * CH;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+        const int ti = idx / (16 * CH), rem = idx - ti * 16 * CH, k = rem / CH, c = rem - k * CH;
+        bf16x8 v = lora_zero8();
+        if (k < r) v = *(const bf16x8*)(t[ti].A + (size_t)k * H + 8 * c);
+        bf16_t* dst = U + ((size_t)ti * H + 8 * c) * 16 + k;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dst[j * 16] = v[j];
+    }
+}
+
+// acc[n][m] += sum_k T[n][k] X[m][k] over k < H: T = a padded tile in LDS (pitch H + 8), X = the wave's 16 rows (row `xrow` of this lane)
+__device__ __forceinline__ f32x4 lora_contract_h(const bf16_t* T, const bf16_t* xrow, int H, int lane) {
+    const int i = lane & 15, g = lane >> 4;
+    const bf16_t* tr = T + (size_t)i * (H + 8) + 8 * g;
+    const bf16_t* xr = xrow + 8 * g;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+
+    for (int k0 = 0; k0 < H; k0 += 32) {
+        const bf16x8 xf = *(const bf16x8*)(xr + k0);
+        const bf16x8 tf = *(const bf16x8*)(tr + k0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, xf, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// the two MFMAs of one 32-column block: d[sub][reg] = sum_k U[c0 + 8 g + 4 sub + reg][k] v[m][k]  (token m = lane & 15, g = lane >> 4)
+__device__ __forceinline__ void lora_expand32(const bf16_t* U, int c0, bf16x8 vf, int lane, f32x4& d0, f32x4& d1) {
+    const int i = lane & 15, g = lane >> 4;
+    const bf16_t* u = U + (size_t)(c0 + 8 * (i >> 2) + (i & 3)) * 16 + 4 * g;
+    const bf16x8 u0 = lora_low4(*(const bf16x4*)u), u1 = lora_low4(*(const bf16x4*)(u + 4 * 16));
+    d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u0, vf, d0, 0, 0, 0);
+    d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u1, vf, d1, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void lora_qkv_fwd_kernel(const LoraFwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    bf16_t* T = (bf16_t*)smem;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+    const int H = a.H, r = a.r, nt = a.nt;
+    const int m = blockIdx.x * LORA_ROWS + wave * 16 + (lane & 15);
+    const bool live = m < a.M;
+    const bool wave_live = blockIdx.x * LORA_ROWS + wave * 16 < a.M;
+    const int mr = live ? m : a.M - 1;                              // rows past M read row M - 1 and store nothing
+    lora_stage_rows(T, a.t, nt, H, r);
+    __syncthreads();
+    bf16x8 hf[3];
+    for (int ti = 0; ti < 3; ++ti) hf[ti] = lora_zero8();
+    if (wave_live) {
+        const bf16_t* xrow = a.x + (size_t)mr * a.ldx;
+#pragma unroll
+        for (int ti = 0; ti < 3; ++ti) {
+            if (ti < nt) {
+                const bf16x4 hb = lora_round4(lora_contract_h(T + (size_t)ti * 16 * (H + 8), xrow, H, lane));
+                hf[ti] = lora_low4(hb);
+                if (a.h && live && 4 * g < r) *(bf16x4*)(a.h + (size_t)m * a.ldh + ti * r + 4 * g) = hb;
+            }
+        }
+    }
+    __syncthreads();
+    lora_stage_pad16(T, a.t, nt, H, r);
+    __syncthreads();
+    if (!wave_live) return;
+#pragma unroll
+    for (int ti = 0; ti < 3; ++ti) {
+        if (ti >= nt) break;
+        const bf16_t* U = T + (size_t)ti * H * 16;
+        bf16_t* q = a.qkv + (size_t)mr * a.ldq + (size_t)a.t[ti].third * H + 8 * g;
+
+        for (int c0 = 0; c0 < H; c0 += 32) {
+            const bf16x8 old = *(const bf16x8*)(q + c0);
+            f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+            lora_expand32(U, c0, hf[ti], lane, d0, d1);
+            bf16x8 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { o[j] = f2bf(fmaf(a.s, d0[j], bf2f(old[j]))); o[4 + j] = f2bf(fmaf(a.s, d1[j], bf2f(old[4 + j]))); }
+            if (live) *(bf16x8*)(q + c0) = o;
+        }
+    }
+}
+
+// backward launch 1: g (and h, when it is recomputed) into the workspace, and the input-gradient part
+__global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    bf16_t* T = (bf16_t*)smem;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+    const int H = a.H, r = a.r, nt = a.nt;
+    const int m = blockIdx.x * LORA_ROWS + wave * 16 + (lane & 15);
+    const bool live = m < a.M;
+    const bool wave_live = blockIdx.x * LORA_ROWS + wave * 16 < a.M;
+    const int mr = live ? m : a.M - 1;
+    const int ldw = nt * r;
+    if (a.recompute) {                                               // h = bf16(x . A^T), as forward formed it
+        lora_stage_rows(T, a.t, nt, H, r);
+        __syncthreads();
+        if (wave_live) {
+            const bf16_t* xrow = a.x + (size_t)mr * a.ldx;
+#pragma unroll
+            for (int ti = 0; ti < 3; ++ti) {
+                if (ti < nt) {
+                    const bf16x4 hb = lora_round4(lora_contract_h(T + (size_t)ti * 16 * (H + 8), xrow, H, lane));
+                    if (live && 4 * g < r) *(bf16x4*)(a.hbuf + (size_t)m * ldw + ti * r + 4 * g) = hb;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    lora_stage_cols_t(T, a.t, nt, H, r);
+    __syncthreads();
+    bf16x8 gf[3];
+    for (int ti = 0; ti < 3; ++ti) gf[ti] = lora_zero8();
+    if (wave_live) {
+#pragma unroll
+        for (int ti = 0; ti < 3; ++ti) {
+            if (ti < nt) {
+                const bf16_t* drow = a.dqkv + (size_t)mr * a.lddq + (size_t)a.t[ti].third * H;
+                const bf16x4 gb = lora_round4(lora_contract_h(T + (size_t)ti * 16 * (H + 8), drow, H, lane));
+                gf[ti] = lora_low4(gb);
+                if (live && 4 * g < r) *(bf16x4*)(a.gbuf + (size_t)m * ldw + ti * r + 4 * g) = gb;
+            }
+        }
+    }
+    if (!a.dres_out) return;                                         // (uniform over the grid)
+    __syncthreads();
+    lora_stage_pad16_t(T, a.t, nt, H, r);
+    __syncthreads();
+    if (!wave_live) return;
+    const bf16_t* din = a.dres_in + (size_t)mr * a.lddi + 8 * g;
+    bf16_t* dout = a.dres_out + (size_t)mr * a.lddo + 8 * g;
+
+    for (int c0 = 0; c0 < H; c0 += 32) {
+        const bf16x8 old = *(const bf16x8*)(din + c0);
+        f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ti = 0; ti < 3; ++ti)
+            if (ti < nt) lora_expand32(T + (size_t)ti * H * 16, c0, gf[ti], lane, d0, d1);
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { o[j] = f2bf(fmaf(a.s, d0[j], bf2f(old[j]))); o[4 + j] = f2bf(fmaf(a.s, d1[j], bf2f(old[4 + j]))); }
+        if (live) *(bf16x8*)(dout + c0) = o;
+    }
+}
+
+// backward launch 2: part[stream][slab][k, c] = sum over the slab's tokens m of coef[m][k] * src[m][c]  (fp32; not yet scaled by s).
+// A lane owns 8 columns and all R rank entries; the workgroup's row lanes take interleaved tokens and are added in row-lane order.
+template <int R>
+__global__ __launch_bounds__(256) void lora_qkv_bwd_w_kernel(const LoraWArgs a) {
+    __shared__ __attribute__((aligned(16))) float red[256 * 8];
+    const LoraStream& st = a.st[blockIdx.y];
+    const int H = a.H, CH = H >> 3;
+    const int CHW = CH < 256 ? CH : 256, RL = 256 / CHW;
+    const int cc = threadIdx.x % CHW, rl = threadIdx.x / CHW;
+    const int mbeg = blockIdx.x * LORA_SLAB, mend = min(a.M, mbeg + LORA_SLAB);
+    float* part = a.part + ((size_t)blockIdx.y * a.nslab + blockIdx.x) * (size_t)(R * H);
+    for (int cb = 0; cb < CH; cb += CHW) {                           // (one round for H <= 2048)
+        const int c = cb + cc;
+        const bool act = rl < RL && c < CH;
+        float acc[R][8];
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
+        if (act) {
+            const bf16_t* src = st.src + 8 * c;
+            int m = mbeg + rl;
+            for (; m + 3 * RL < mend; m += 4 * RL) {                  // four independent 16-byte loads in flight
+                bf16x8 v[4];
+                bf16x4 w[4][R / 4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    v[u] = *(const bf16x8*)(src + (size_t)(m + u * RL) * st.lds);
+#pragma unroll
+                    for (int q = 0; q < R / 4; ++q) w[u][q] = *(const bf16x4*)(st.coef + (size_t)(m + u * RL) * st.ldc + 4 * q);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int k = 0; k < R; ++k) {
+                        const float wk = bf2f(w[u][k >> 2][k & 3]);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[u][j]), acc[k][j]);
+                    }
+            }
+            for (; m < mend; m += RL) {
+                const bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
+#pragma unroll
+                for (int k = 0; k < R; ++k) {
+                    const float wk = bf2f(st.coef[(size_t)m * st.ldc + k]);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[j]), acc[k][j]);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {                                // row lanes 1 .. RL-1 are added onto row lane 0, in order
+            if (act && rl > 0) {
+                *(float4*)(red + (size_t)threadIdx.x * 8) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+                *(float4*)(red + (size_t)threadIdx.x * 8 + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
+            }
+            __syncthreads();
+            if (act && rl == 0) {
+                for (int q = 1; q < RL; ++q)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[k][j] += red[(size_t)(q * CHW + cc) * 8 + j];
+            }
+            __syncthreads();
+        }
+        if (act && rl == 0) {
+            if (st.colmajor) {                                       // [H, R]: R consecutive floats per column
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+#pragma unroll
+                    for (int k = 0; k < R; k += 4)
+                        *(float4*)(part + (size_t)(8 * c + j) * R + k) = make_float4(acc[k][j], acc[k + 1][j], acc[k + 2][j], acc[k + 3][j]);
+            } else {                                                 // [R, H]
+#pragma unroll
+                for (int k = 0; k < R; ++k) {
+                    *(float4*)(part + (size_t)k * H + 8 * c) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+                    *(float4*)(part + (size_t)k * H + 8 * c + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
+                }
+            }
+        }
+    }
+}
+
+// backward launch 3: out[e] = (acc ? out[e] : 0) + s * (slab 0 + slab 1 + ... in ascending order); a lane owns 4 consecutive elements
+__global__ __launch_bounds__(256) void lora_qkv_fold_kernel(const LoraWArgs a) {
+    const LoraStream& st = a.st[blockIdx.y];
+    const size_t n = (size_t)a.r * a.H;
+    const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e >= n) return;
+    const float* p = a.part + (size_t)blockIdx.y * a.nslab * n + e;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    int q = 0;
+    for (; q + 4 <= a.nslab; q += 4) {                               // loads four slabs ahead, adds in order
+        float4 t[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) t[u] = *(const float4*)(p + (size_t)(q + u) * n);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { s.x += t[u].x; s.y += t[u].y; s.z += t[u].z; s.w += t[u].w; }
+    }
+    for (; q < a.nslab; ++q) {
+        const float4 t = *(const float4*)(p + (size_t)q * n);
+        s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+    }
+    float4* o = (float4*)(st.out + e);
+    float4 v = make_float4(a.s * s.x, a.s * s.y, a.s * s.z, a.s * s.w);
+    if (st.acc) { const float4 w = *o; v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w; }
+    *o = v;
+}
+
+static inline bool lora_shape_ok(int M, int H, int r, int targets) {
+    return M >= 0 && H > 0 && (H & 63) == 0 && (r == 4 || r == 8 || r == 16) && targets >= 1 && targets <= 7;
+}
+static inline int lora_count(int targets) { return (targets & 1) + ((targets >> 1) & 1) + ((targets >> 2) & 1); }
+static inline size_t lora_lds_bytes(int nt, int H) { return (size_t)nt * 16 * (size_t)(H + 8) * sizeof(bf16_t); }
+static inline size_t lora_up16(size_t b) { return (b + 15) & ~(size_t)15; }
+static inline bool lora_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool lora_al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+static int lora_targets(LoraTarget* t, int targets, const void* const* A, const void* const* B) {
+    int nt = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!((targets >> k) & 1)) continue;
+        if (!A || !B || !A[k] || !B[k] || !lora_al16(A[k]) || !lora_al16(B[k])) return -1;
+        t[nt].A = (const bf16_t*)A[k]; t[nt].B = (const bf16_t*)B[k]; t[nt].third = k; t[nt].pad = 0;
+        ++nt;
+    }
+    return nt;
+}
+
+extern "C" {
+
+int mmbert_lora_qkv_fwd(hipStream_t stream, const void* x, int ldx, void* qkv, int ldq, int M, int H, int r, int targets,
+                        const void* const* A, const void* const* B, float scale, void* h_out, int ldh) {
+    if (!lora_shape_ok(M, H, r, targets)) return -1;
+    if (M == 0) return 0;
+    LoraFwdArgs a = {};
+    a.nt = lora_targets(a.t, targets, A, B);
+    if (a.nt < 0) return -1;
+    if (!x || !qkv || !lora_al16(x) || !lora_al16(qkv) || ldx < H || (ldx & 7) || ldq < 3 * H || (ldq & 7)) return -1;
+    if (h_out && (!lora_al8(h_out) || ldh < a.nt * r || (ldh & 3))) return -1;
+    const size_t lds = lora_lds_bytes(a.nt, H);
+    if (lds > LORA_LDS_MAX) return -2;
+    if (lds > 65536) {
+        static std::atomic<unsigned long long> done{0};
+        const int e = mmb_allow_lds((const void*)lora_qkv_fwd_kernel, (int)lds, done);
+        if (e) return e;
+    }
+    a.M = M; a.H = H; a.r = r; a.ldx = ldx; a.ldq = ldq; a.ldh = ldh; a.s = scale;
+    a.x = (const bf16_t*)x; a.qkv = (bf16_t*)qkv; a.h = (bf16_t*)h_out;
+    hipLaunchKernelGGL(lora_qkv_fwd_kernel, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+// [partial sums: 2 nt streams x slabs x r H floats][g: M x nt r bf16][h, when backward recomputes it: the same]; 0 for M == 0 or a bad shape
+size_t mmbert_lora_qkv_bwd_workspace(int M, int H, int r, int targets) {
+    if (!lora_shape_ok(M, H, r, targets) || M == 0) return 0;
+    const int nt = lora_count(targets);
+    const size_t nslab = (size_t)(M + LORA_SLAB - 1) / LORA_SLAB;
+    const size_t part = (size_t)2 * nt * nslab * (size_t)r * H * sizeof(float);
+    const size_t gb = lora_up16((size_t)M * nt * r * sizeof(bf16_t));
+    return part + 2 * gb;
+}
+
+int mmbert_lora_qkv_bwd(hipStream_t stream, const void* dqkv, int lddq, const void* x, int ldx, const void* h, int ldh, int M, int H, int r,
+                        int targets, const void* const* A, const void* const* B, float scale, const void* dres_in, int lddi,
+                        void* dres_out, int lddo, float* const* gA, float* const* gB, int accumulate, void* workspace) {
+    if (!lora_shape_ok(M, H, r, targets)) return -1;
+    if (M == 0) return 0;
+    LoraBwdArgs a = {};
+    a.nt = lora_targets(a.t, targets, A, B);
+    if (a.nt < 0) return -1;
+    const int nt = a.nt;
+    if (!dqkv || !x || !lora_al16(dqkv) || !lora_al16(x) || lddq < 3 * H || (lddq & 7) || ldx < H || (ldx & 7)) return -1;
+    if (h && (!lora_al8(h) || ldh < nt * r || (ldh & 3))) return -1;
+    if (dres_out && (!dres_in || dres_in == dres_out || !lora_al16(dres_in) || !lora_al16(dres_out) || lddi < H || (lddi & 7) || lddo < H || (lddo & 7))) return -1;
+    if (!workspace || !lora_al16(workspace)) return -3;
+    const size_t lds = lora_lds_bytes(nt, H);
+    if (lds > LORA_LDS_MAX) return -2;
+    if (lds > 65536) {
+        static std::atomic<unsigned long long> done{0};
+        const int e = mmb_allow_lds((const void*)lora_qkv_bwd_g_kernel, (int)lds, done);
+        if (e) return e;
+    }
+    const int nslab = (M + LORA_SLAB - 1) / LORA_SLAB;
+    const size_t part = (size_t)2 * nt * nslab * (size_t)r * H * sizeof(float);
+    const size_t gb = lora_up16((size_t)M * nt * r * sizeof(bf16_t));
+    a.M = M; a.H = H; a.r = r; a.ldx = ldx; a.lddq = lddq; a.lddi = lddi; a.lddo = lddo; a.s = scale;
+    a.x = (const bf16_t*)x; a.dqkv = (const bf16_t*)dqkv; a.dres_in = (const bf16_t*)dres_in; a.dres_out = (bf16_t*)dres_out;
+    a.gbuf = (bf16_t*)((char*)workspace + part); a.hbuf = (bf16_t*)((char*)workspace + part + gb);
+    // the weight-gradient streams that run: a target's dA needs g and x, its dB needs dqkv and h
+    LoraWArgs w = {};
+    bool need_h = false;
+    for (int ti = 0; ti < nt; ++ti) {
+        const int k = a.t[ti].third;
+        float* ga = gA ? gA[k] : nullptr;
+        float* gb_ = gB ? gB[k] : nullptr;
+        if (ga) {
+            if (!lora_al16(ga)) return -1;
+            LoraStream& s = w.st[w.ns++];
+            s.src = a.x; s.lds = ldx; s.coef = a.gbuf + ti * r; s.ldc = nt * r; s.out = ga; s.colmajor = 0; s.acc = accumulate ? 1 : 0;
+        }
+        if (gb_) {
+            if (!lora_al16(gb_)) return -1;
+            LoraStream& s = w.st[w.ns++];
+            s.src = a.dqkv + (size_t)k * H; s.lds = lddq; s.out = gb_; s.colmajor = 1; s.acc = accumulate ? 1 : 0;
+            if (h) { s.coef = (const bf16_t*)h + ti * r; s.ldc = ldh; }
+            else { s.coef = a.hbuf + ti * r; s.ldc = nt * r; need_h = true; }
+        }
+    }
+    a.recompute = need_h ? 1 : 0;
+    if (!dres_out && w.ns == 0) return 0;                            // nothing asked for
+    hipLaunchKernelGGL(lora_qkv_bwd_g_kernel, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
+    MMB_CHECK_LAUNCH();
+    if (w.ns == 0) return 0;
+    w.M = M; w.H = H; w.r = r; w.nslab = nslab; w.s = scale; w.part = (float*)workspace;
+    const dim3 grid(nslab, w.ns);
+    if (r == 4) hipLaunchKernelGGL(lora_qkv_bwd_w_kernel<4>, grid, dim3(256), 0, stream, w);
+    else if (r == 8) hipLaunchKernelGGL(lora_qkv_bwd_w_kernel<8>, grid, dim3(256), 0, stream, w);
+    else hipLaunchKernelGGL(lora_qkv_bwd_w_kernel<16>, grid, dim3(256), 0, stream, w);
+    MMB_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lora_qkv_fold_kernel, dim3((unsigned)(((size_t)r * H / 4 + 255) / 256), w.ns), dim3(256), 0, stream, w);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"

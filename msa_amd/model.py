@@ -20,6 +20,7 @@ libmmbert_hip.so or a CPU tensor raises.
 from __future__ import annotations
 
 import json
+import math
 import os
 from typing import Optional
 
@@ -458,6 +459,11 @@ class _EncoderFn:
             for i in range(nl):
                 lw = top._lw[i]
                 keep = keep_all and i >= keep_from
+                if lw["lora"] is not None:                           # a layer with adapters takes the per-launch form (the composite call has no seam)
+                    x, s_i = _EncoderFn._layer_forward(top, i, x, layout, key_bias, seed, kv_len, keep, pa, ph, y_out, y_rows, probe)
+                    if keep_all:
+                        saved.append(s_i)
+                    continue
                 d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
                 last = i == L - 1 and y_out is not None
                 qkv, actx, z1, y1 = (torch.empty((M_, 3 * H), device=dev, dtype=bf), torch.empty((M_, H), device=dev, dtype=bf),
@@ -491,27 +497,61 @@ class _EncoderFn:
                 x = y2
             return x, saved
         for i in range(nl):
-            lw = top._lw[i]
             keep = keep_all and i >= keep_from
-            d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
-            qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
-            actx, lse = ops.attn_fwd(qkv, key_bias, layout, H, drop=d_att, kv_len=kv_len)
-            if probe is not None:
-                probe(i, qkv)
-            z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=x, drop=d_h1)
-            y1, m1, r1 = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=keep)
-            u = torch.empty((x.shape[0], cfg.intermediate_size), device=x.device, dtype=torch.bfloat16) if keep else None
-            g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True, aux=u)
-            z2 = ops.gemm_nt(g, lw["W2"], bias=lw["b2"], resid=y1, drop=d_h2)
-            last = i == L - 1 and y_out is not None
-            y2, m2, r2 = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=keep,
-                                    out=y_out if last else None, out_rows=y_rows if last else None)
+            x, s_i = _EncoderFn._layer_forward(top, i, x, layout, key_bias, seed, kv_len, keep, pa, ph, y_out, y_rows, probe)
             if keep_all:
-                saved.append((x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2) if keep else None)
-            x = y2
+                saved.append(s_i)
             if top.debug_hidden is not None:
-                top.debug_hidden.setdefault("_layers_packed", []).append(None if last else y2.detach())
+                top.debug_hidden.setdefault("_layers_packed", []).append(None if (i == L - 1 and y_out is not None) else x.detach())
         return x, saved
+
+    @staticmethod
+    def _lora_forward(lo, x, qkv, keep):
+        """The adapters' update of ``qkv`` in place (ops.lora_qkv_fwd), directly behind the QKV product.  Returns what the layer's backward
+        needs (None when nothing is kept): the rank-r activations h and, per target, whether A / B take a gradient."""
+        h = torch.empty((x.shape[0], len(lo["targets"]) * lo["r"]), device=x.device, dtype=torch.bfloat16) if keep else None
+        ops.lora_qkv_fwd(x, qkv, lo["A"], lo["B"], lo["targets"], lo["scale"], h_out=h)
+        if not keep:
+            return None
+        return (h, {t: (lo["pA"][t].requires_grad, lo["pB"][t].requires_grad) for t in lo["targets"]})
+
+    @staticmethod
+    def _lora_backward(top, lo, ls, dqkv, x, dres):
+        """The adapters' backward directly behind the attention backward (ops.lora_qkv_bwd): their gradients (added: the optimizer zero-fills
+        them) and, with ``dres`` (the residual gradient the input-gradient GEMM adds), the NEW tensor that takes its place there."""
+        h, flags = ls
+        gA = {t: lo["gA"][t] for t in lo["targets"] if flags[t][0]}
+        gB = {t: lo["gB"][t] for t in lo["targets"] if flags[t][1]}
+        if dres is None and not gA and not gB:
+            return None
+        return ops.lora_qkv_bwd(dqkv, x, h[:dqkv.shape[0]], lo["A"], lo["B"], gA, gB, lo["targets"], lo["scale"], dres=dres, accumulate=True)
+
+    @staticmethod
+    def _layer_forward(top, i, x, layout, key_bias, seed, kv_len, keep, pa, ph, y_out, y_rows, probe):
+        """One encoder layer, one call per launch.  Returns (output, what backward keeps or None)."""
+        cfg = top.config
+        H, L = cfg.hidden_size, cfg.num_hidden_layers
+        lw = top._lw[i]
+        d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
+        qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
+        ls = _EncoderFn._lora_forward(lw["lora"], x, qkv, keep) if lw["lora"] is not None else None
+        actx, lse = ops.attn_fwd(qkv, key_bias, layout, H, drop=d_att, kv_len=kv_len)
+        if probe is not None:
+            probe(i, qkv)
+        z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=x, drop=d_h1)
+        y1, m1, r1 = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=keep)
+        u = torch.empty((x.shape[0], cfg.intermediate_size), device=x.device, dtype=torch.bfloat16) if keep else None
+        g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True, aux=u)
+        z2 = ops.gemm_nt(g, lw["W2"], bias=lw["b2"], resid=y1, drop=d_h2)
+        last = i == L - 1 and y_out is not None
+        y2, m2, r2 = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=keep,
+                                out=y_out if last else None, out_rows=y_rows if last else None)
+        s_i = None
+        if keep:
+            s_i = (x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2)
+            if ls is not None:
+                s_i = s_i + (ls,)                                # (a 17th entry on layers with adapters only)
+        return y2, s_i
 
     @staticmethod
     def run_top_first(top, x, layout, key_bias, kv_len, q_rows, probe=None):
@@ -526,6 +566,8 @@ class _EncoderFn:
         H = cfg.hidden_size
         lw = top._lw[cfg.num_hidden_layers - 1]
         qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
+        if lw["lora"] is not None:
+            _EncoderFn._lora_forward(lw["lora"], x, qkv, False)
         actx = ops.attn_fwd_first(qkv, key_bias, layout, H, q_rows, kv_len=kv_len)
         if probe is not None:
             probe(cfg.num_hidden_layers - 1, qkv)
@@ -594,7 +636,8 @@ class _EncoderFn:
             saved[i] = None
             if ra < M_all:
                 saved_i = tuple(t[:ra] if torch.is_tensor(t) else t for t in saved_i)
-            x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i
+            x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i[:16]
+            lora_s = saved_i[16] if len(saved_i) > 16 else None          # (h, gradient flags) of a layer with adapters
             if i == L - 1 and (top_rows is not None or compact is not None):
                 R = None
                 R32 = None
@@ -621,7 +664,7 @@ class _EncoderFn:
                     continue
                 if compact is not None:
                     raise RuntimeError("compact output gradient without the sparse top-layer path")
-            if composite_bwd:
+            if composite_bwd and lora_s is None:
                 # the seven launches of the dense backward body from ONE C call (mmbert_layer_bwd: same kernels, same arguments, bit-identical)
                 dev, bf = z2.device, torch.bfloat16
                 I_ = top.config.intermediate_size
@@ -676,7 +719,11 @@ class _EncoderFn:
                   dz1d = dz1
               dctx = ops.gemm_nt(dz1d, lw["WoT"])
               dqkv = ops.attn_bwd(qkv, actx, dctx, lse, key_bias, layout, H, drop=d_att, kv_len=kv_len)
-              dy = None if skip_dx else ops.gemm_nt(dqkv, lw["WqkvT"], resid=dz1)
+              dres = dz1
+              if lora_s is not None:
+                  # (a buffer of its own: dz1 can be dz1d, which the Wo weight gradient below still reads)
+                  dres = _EncoderFn._lora_backward(top, lw["lora"], lora_s, dqkv, x, None if skip_dx else dz1)
+              dy = None if skip_dx else ops.gemm_nt(dqkv, lw["WqkvT"], resid=dres)
             # --- all four weight gradients (+ their bias gradients) of the layer in ONE launch.  (They are off the critical path of backward;
             # a side stream for them was measured a loss in rounds 1, 3 and 4 -- the chip's power envelope is shared -- and is gone.)
             probs = [(du, y1, lw["g_W1"], lw["g_b1"]), (dz2d, g, lw["g_W2"], lw["g_b2"]),
@@ -751,7 +798,8 @@ class _EncoderFn:
         dense again (every unmasked key receives a gradient), as is everything below.  ``modes`` / ``skip_dx``: as in run_backward (the
         layer's frozen weights; no input gradient when the layer is where backward ends)."""
         cfg = top.config
-        x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i
+        x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i[:16]
+        lora_s = saved_i[16] if len(saved_i) > 16 else None
         if R32 is None:
             R32 = R.int()
         # the rows R of every saved activation this path reads, in ONE launch (9 index_select launches before)
@@ -784,6 +832,8 @@ class _EncoderFn:
         if rinv is None:
             dz1 = torch.zeros((ra, H), device=dy.device, dtype=torch.bfloat16)
             dz1.index_copy_(0, R, dz1_c)
+        if lora_s is not None:
+            dz1 = _EncoderFn._lora_backward(top, lw["lora"], lora_s, dqkv, x, None if skip_dx else dz1)
         out = None if skip_dx else ops.gemm_nt(dqkv, lw["WqkvT"], resid=dz1)
         # (bias gradients b1 / b2 / bo: column sums of the bf16 gradients on the ones-operand MFMA, as in the dense layers)
         few = [(du_c, y1_c, lw["g_W1"], lw["g_b1"]), (dz2d_c, g_c, lw["g_W2"], lw["g_b2"]), (dz1d_c, actx_c, lw["g_Wo"], lw["g_bo"])]
@@ -1494,6 +1544,7 @@ class _GpuModelBase(nn.Module):
             f.register_lazy(d["g_Wo"], [p + "attention.output.dense.weight"])
             f.register_lazy(d["g_W1"], [p + "intermediate.dense.weight"])
             f.register_lazy(d["g_W2"], [p + "output.dense.weight"])
+            d["lora"] = self._lora_views(i, p)
             self._lw.append(d)
         w = {}
         e = "bert.embeddings."
@@ -1523,6 +1574,21 @@ class _GpuModelBase(nn.Module):
         w["WtT"], w["wordT"] = f.tview("transform"), f.tview("word")
         f.register_lazy(w["g_word_pad"], [e + "word_embeddings.weight"])     # the tied decoder's weight gradient: the MLM head's first launch
         self._w = w
+
+    def _lora_views(self, i, prefix):
+        """Layer ``i``'s adapters as the encoder paths read them (None: the layer has none): per target the bf16 working copies of A [r, H]
+        and B [H, r], their fp32 gradient views and their Parameters (whose ``requires_grad`` decides which gradients a backward computes)."""
+        lc = getattr(self, "_lora", None)
+        if not lc or i not in lc["layers"]:
+            return None
+        f, H, r = self._flat, self.config.hidden_size, lc["r"]
+        lo = dict(targets=tuple(lc["targets"]), r=r, scale=float(lc["alpha"]) / r, A={}, B={}, gA={}, gB={}, pA={}, pB={})
+        for t in lo["targets"]:
+            na, nb = f"{prefix}attention.self.{t}.lora_A", f"{prefix}attention.self.{t}.lora_B"
+            lo["A"][t], lo["B"][t] = f.span(f.half, na, r * H, (r, H)), f.span(f.half, nb, r * H, (H, r))
+            lo["gA"][t], lo["gB"][t] = f.span(f.grads, na, r * H, (r, H)), f.span(f.grads, nb, r * H, (H, r))
+            lo["pA"][t], lo["pB"][t] = f.named[na], f.named[nb]
+        return lo
 
     # ---- pass packing --------------------------------------------------------------------------
     def _plan(self, lens_per_pass, B, device):
@@ -1882,6 +1948,9 @@ class MMBertModel(_GpuModelBase):
         if top is None:
             if not hasattr(self, "jointEmbeddings"):
                 raise RuntimeError("call .set_joint_embeddings(dataset) first (REF:train.py:72)")
+            if any(".lora_" in n for n, _ in self.named_parameters()):
+                raise NotImplementedError("a stand-alone MMBertModel does not apply low-rank adapters: their rank, scale and layers live with "
+                                          "the MMBertForPretraining that add_lora() was called on -- run that model, or merge_lora() first")
             top = MMBertForPretraining(self.config, _bert=self)
             top.to(device)
             top._seed, top._calls = self._seed, self._calls
@@ -2322,6 +2391,7 @@ class MMBertForPretraining(_GpuModelBase):
         # x_size = hidden size: the reference hard-codes 1024 (:327-344) and only runs with bert-large
         self.cpc_zt, self.cpc_zv, self.cpc_za = (CPC(H, H, 1, "Tanh") for _ in range(3))
         self._init_runtime()
+        self._lora = None                                            # add_lora: {"r", "alpha", "targets", "layers"}
         self.return_scores = True
         # dtype of the returned prediction-score tensors (outputs[7], [9], [11]): zero-copy [B, S, vocab] views of the logits the
         # vocabulary GEMM writes.  DEVIATION from the reference (fp32 scores): the default stores bf16, the compute dtype of the path;
@@ -2584,6 +2654,119 @@ class MMBertForPretraining(_GpuModelBase):
         self.bert._owner = self.cls._owner = ref
         if hasattr(self.bert, "jointEmbeddings"):
             self.bert.jointEmbeddings._owner = ref
+
+    # ---- low-rank adapters on the Q / K / V projections (a declared extension) ------------------------------------
+    _LORA_BASE = ("bert.embeddings.", "bert.jointEmbeddings.", "bert.encoder.")
+
+    def _lora_linears(self):
+        """(layer index, target name, the projection's nn.Linear) for every adapter the model holds."""
+        lc = getattr(self, "_lora", None)
+        if not lc:
+            return []
+        return [(i, t, getattr(self.bert.encoder.layer[i].attention.self, t)) for i in lc["layers"] for t in lc["targets"]]
+
+    def add_lora(self, r=8, alpha=16.0, targets=("query", "value"), layers=None, freeze_base=True, seed=None):
+        """DECLARED EXTENSION: low-rank adapters on the attention projections.  For every layer of ``layers`` (None: all) and every name of
+        ``targets`` (a non-empty subset of query / key / value) registers ``bert.encoder.layer.<i>.attention.self.<target>.lora_A`` [r, H]
+        (kaiming-uniform, a = sqrt 5, from a generator seeded by ``seed``) and ``.lora_B`` [H, r] (zeros); the projection then computes
+        x W^T + b + (alpha / r) (x A^T) B^T.  r in {4, 8, 16}.  ``freeze_base``: ``requires_grad_(False)`` on every ``bert.embeddings.*``,
+        ``bert.jointEmbeddings.*`` and ``bert.encoder.*`` parameter but the adapters (pooler and heads keep their flags).  The flat storage
+        is dropped (rebuilt on the next use): call it BEFORE the optimizer is built, like ``set_num_labels``.  Invalid arguments, or
+        adapters already present (``remove_lora`` / ``merge_lora`` first), raise ValueError."""
+        cfg = self.config
+        H, L = cfg.hidden_size, cfg.num_hidden_layers
+        if getattr(self, "_lora", None):
+            raise ValueError("add_lora: the model already has adapters -- remove_lora() or merge_lora() first")
+        if isinstance(r, bool) or not isinstance(r, int) or r not in ops.LORA_RANKS:
+            raise ValueError(f"add_lora: r must be one of {ops.LORA_RANKS}, got {r!r}")
+        if H % 64:
+            raise ValueError(f"add_lora: the adapter kernels need hidden_size % 64 == 0, got {H}")
+        mask = ops.lora_mask(targets)                                # (ValueError for an empty / unknown / repeated target)
+        names = tuple(t for k, t in enumerate(ops.LORA_TARGETS) if mask >> k & 1)
+        alpha = float(alpha)
+        if not math.isfinite(alpha):
+            raise ValueError(f"add_lora: alpha must be finite, got {alpha!r}")
+        idx = list(range(L)) if layers is None else list(layers)
+        if not idx or any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < L for i in idx) or len(set(idx)) != len(idx):
+            raise ValueError(f"add_lora: layers must be distinct indices in 0 .. {L - 1} (None: all), got {layers!r}")
+        gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
+        bound = 1.0 / math.sqrt(H)                                   # kaiming_uniform_(a = sqrt 5) on [r, H]: gain sqrt(1 / 3), fan_in H
+        for i in sorted(idx):
+            for t in names:
+                lin = getattr(self.bert.encoder.layer[i].attention.self, t)
+                w = lin.weight
+                A = torch.empty((r, H), dtype=torch.float32).uniform_(-bound, bound, generator=gen)
+                lin.lora_A = nn.Parameter(A.to(device=w.device, dtype=w.dtype))
+                lin.lora_B = nn.Parameter(torch.zeros((H, r), device=w.device, dtype=w.dtype))
+        self._lora = dict(r=r, alpha=alpha, targets=names, layers=tuple(sorted(idx)))
+        if freeze_base:
+            for n, p in self.named_parameters():
+                if n.startswith(self._LORA_BASE) and ".lora_" not in n:
+                    p.requires_grad_(False)
+        self._flat = None
+        return self
+
+    def remove_lora(self):
+        """Drops the adapters without merging them (``requires_grad`` flags stay as they are; ``unfreeze()`` resets them) and the flat
+        storage with them: an optimizer built before is stale."""
+        for _, _, lin in self._lora_linears():
+            del lin.lora_A
+            del lin.lora_B
+        self._lora = None
+        self._flat = None
+        return self
+
+    def merge_lora(self):
+        """Folds every adapter into its projection's fp32 master, W_t += (alpha / r) B_t A_t (the fp32 values of A and B), then drops the
+        adapters and the flat storage: ``state_dict()`` has the reference's keys again."""
+        lc = getattr(self, "_lora", None)
+        if not lc:
+            raise ValueError("merge_lora: the model has no adapters")
+        s = lc["alpha"] / lc["r"]
+        with torch.no_grad():
+            for _, _, lin in self._lora_linears():
+                lin.weight.add_(s * (lin.lora_B.detach().float() @ lin.lora_A.detach().float()).to(lin.weight.dtype))
+        return self.remove_lora()
+
+    def lora_state_dict(self):
+        """The adapter tensors by their state-dict names (clones) and {"r", "alpha", "targets", "layers"}: the per-task file."""
+        lc = getattr(self, "_lora", None)
+        if not lc:
+            raise ValueError("lora_state_dict: the model has no adapters")
+        sd = {"r": lc["r"], "alpha": lc["alpha"], "targets": tuple(lc["targets"]), "layers": tuple(lc["layers"])}
+        for i, t, lin in self._lora_linears():
+            for m in ("lora_A", "lora_B"):
+                sd[f"bert.encoder.layer.{i}.attention.self.{t}.{m}"] = getattr(lin, m).detach().clone()
+        return sd
+
+    def load_lora_state_dict(self, sd, freeze_base=True):
+        """Loads what ``lora_state_dict`` returned: creates the adapters when the model has none (``add_lora`` with the file's r, alpha,
+        targets and layers, and ``freeze_base``), raises ValueError when existing ones differ in any of the four or a tensor is missing or
+        has another shape, copies the values and calls ``parameters_changed()``."""
+        meta = dict(r=int(sd["r"]), alpha=float(sd["alpha"]), targets=tuple(t for t in ops.LORA_TARGETS if t in tuple(sd["targets"])),
+                    layers=tuple(sorted(int(i) for i in sd["layers"])))
+        if not getattr(self, "_lora", None):
+            self.add_lora(meta["r"], meta["alpha"], meta["targets"], meta["layers"], freeze_base=freeze_base)
+        if self._lora != meta:
+            raise ValueError(f"load_lora_state_dict: the model's adapters {self._lora} differ from the file's {meta}")
+        todo = []
+        for i, t, lin in self._lora_linears():
+            for m in ("lora_A", "lora_B"):
+                k = f"bert.encoder.layer.{i}.attention.self.{t}.{m}"
+                p = getattr(lin, m)
+                if k not in sd or tuple(sd[k].shape) != tuple(p.shape):
+                    raise ValueError(f"load_lora_state_dict: {k} is missing or not of shape {tuple(p.shape)}")
+                todo.append((p, sd[k]))
+        with torch.no_grad():
+            for p, v in todo:
+                p.copy_(v.to(device=p.device, dtype=p.dtype))
+        self.parameters_changed()
+        return self
+
+    def _refuse_lora(self, what):
+        if getattr(self, "_lora", None):
+            raise NotImplementedError(f"{what} does not apply the low-rank adapters this model holds (add_lora): its encoder path has no "
+                                      "adapter launches -- merge_lora() or remove_lora() first")
 
     def freeze(self, *, embeddings=False, layers=0, layer_weights=False):
         """Sets ``requires_grad_(False)`` on: ``embeddings`` -- every ``bert.embeddings.*`` and ``bert.jointEmbeddings.*`` parameter;
@@ -3042,6 +3225,7 @@ class MMBertForPretraining(_GpuModelBase):
         attention_mask=(text_mask[B,T], visual_mask[B,V,Dv], speech_mask[B,A,Ds]); masked_labels [B, T+V+A] (-100 = ignore).
         Returns ((joint_loss, None, None, None, ap_loss, label_loss, nce, scores[B,S,V] | None, rel[B,2]), logits[B,1]).
         Checked against oracle.fused_forward (the same extension of the CPU restatement)."""
+        self._refuse_lora("forward_fused")
         self._check_class_labels(sentiment)
         text_ids, visual, speech = input_ids
         am_t, am_v, am_s = attention_mask

@@ -1547,9 +1547,90 @@ def layer_bwd(L: _AttnLayout, a: _LayerBwd):
     _lib.check(_lib.load().mmbert_layer_bwd(_stream(), ctypes.addressof(L), ctypes.addressof(a)), "mmbert_layer_bwd")
 
 
+LORA_TARGETS = ("query", "key", "value")          # the column thirds of the packed projection, in mmbert_lora_qkv_*'s mask order
+LORA_RANKS = (4, 8, 16)
+_Ptr3 = ctypes.c_void_p * 3
+
+
+def lora_mask(targets) -> int:
+    """The C ABI's bit mask (1 query, 2 key, 4 value) of a non-empty collection of LORA_TARGETS names."""
+    names = [targets] if isinstance(targets, str) else list(targets)
+    if not names or any(t not in LORA_TARGETS for t in names) or len(set(names)) != len(names):
+        raise ValueError(f"lora targets must be a non-empty subset of {LORA_TARGETS} without repeats, got {targets!r}")
+    return sum(1 << LORA_TARGETS.index(t) for t in names)
+
+
+def _lora_operands(A, B, targets, H, what):
+    """(mask, r, ordered names, A pointers, B pointers) of the adapters ``A`` / ``B`` = {name: tensor} (bf16 [r, H] / [H, r], contiguous)."""
+    mask = lora_mask(targets)
+    names = [t for t in LORA_TARGETS if mask >> LORA_TARGETS.index(t) & 1]
+    r = A[names[0]].shape[0]
+    pa, pb = [None] * 3, [None] * 3
+    for t in names:
+        a, b = A[t], B[t]
+        if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or tuple(a.shape) != (r, H) or tuple(b.shape) != (H, r) \
+                or not a.is_contiguous() or not b.is_contiguous():
+            raise ValueError(f"{what}: adapter {t!r} must be contiguous bf16 A [{r}, {H}] and B [{H}, {r}], got {tuple(a.shape)} {a.dtype} / {tuple(b.shape)} {b.dtype}")
+        k = LORA_TARGETS.index(t)
+        pa[k], pb[k] = a.data_ptr(), b.data_ptr()
+    return mask, r, names, _Ptr3(*pa), _Ptr3(*pb)
+
+
+def _pitch(t) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def lora_qkv_fwd(x, qkv, A, B, targets, scale, h_out=None):
+    """In place on ``qkv`` [M, 3H] bf16: for every target t, qkv_t += scale * bf16(x @ A[t]^T) @ B[t]^T (see mmbert_lora_qkv_fwd).
+    ``A`` / ``B``: {target name: bf16 tensor}; ``h_out`` [M, len(targets) * r] bf16 receives the rank-r activations.  Returns qkv."""
+    M, H = x.shape
+    assert x.dtype == torch.bfloat16 and qkv.dtype == torch.bfloat16 and qkv.shape == (M, 3 * H) and (M == 0 or (x.stride(1) == 1 and qkv.stride(1) == 1))
+    mask, r, names, pa, pb = _lora_operands(A, B, targets, H, "lora_qkv_fwd")
+    if h_out is not None:
+        assert h_out.dtype == torch.bfloat16 and h_out.shape == (M, len(names) * r) and (M == 0 or h_out.stride(1) == 1)
+    _lib.check(_lib.load().mmbert_lora_qkv_fwd(_stream(), x.data_ptr(), _pitch(x), qkv.data_ptr(), _pitch(qkv), M, H, r, mask, pa, pb, float(scale),
+                                               _ptr(h_out), _pitch(h_out) if h_out is not None else 0), "mmbert_lora_qkv_fwd")
+    return qkv
+
+
+def lora_qkv_bwd_workspace(M: int, H: int, r: int, targets) -> int:
+    return int(_lib.load().mmbert_lora_qkv_bwd_workspace(int(M), int(H), int(r), lora_mask(targets)))
+
+
+def lora_qkv_bwd(dqkv, x, h, A, B, gA, gB, targets, scale, dres=None, accumulate=True, workspace=None):
+    """The adapters' backward from ``dqkv`` [M, 3H] bf16 (see mmbert_lora_qkv_bwd): gA[t] [r, H] (+)= scale * g_t^T @ x and
+    gB[t] [H, r] (+)= scale * dqkv_t^T @ h_t (fp32; a missing name or None: not computed; ``gA`` / ``gB`` may be None), g_t = bf16(dqkv_t @ B[t]).
+    ``h``: forward's h_out, or None (recomputed from x and A).  ``dres`` [M, H] bf16: returns a NEW tensor bf16(dres + scale * sum_t g_t @ A[t])
+    (``dres`` itself is not written); None: no input-gradient part, returns None.  ``workspace``: a caller's buffer (tests)."""
+    lib = _lib.load()
+    M, H = x.shape
+    assert dqkv.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and dqkv.shape == (M, 3 * H) and (M == 0 or (x.stride(1) == 1 and dqkv.stride(1) == 1))
+    mask, r, names, pa, pb = _lora_operands(A, B, targets, H, "lora_qkv_bwd")
+    if h is not None:
+        assert h.dtype == torch.bfloat16 and h.shape == (M, len(names) * r) and (M == 0 or h.stride(1) == 1)
+    out = None
+    if dres is not None:
+        assert dres.dtype == torch.bfloat16 and dres.shape == (M, H) and (M == 0 or dres.stride(1) == 1)
+        out = torch.empty((M, H), device=x.device, dtype=torch.bfloat16)
+    ga, gb = [None] * 3, [None] * 3
+    for dst, src, shape in ((ga, gA, (r, H)), (gb, gB, (H, r))):
+        for t in names:
+            g = None if src is None else src.get(t)
+            if g is not None:
+                assert g.dtype == torch.float32 and tuple(g.shape) == shape and g.is_contiguous()
+                dst[LORA_TARGETS.index(t)] = g.data_ptr()
+    if workspace is None:
+        workspace = _ws_f32((lib.mmbert_lora_qkv_bwd_workspace(M, H, r, mask) + 3) // 4, x.device)
+    _lib.check(lib.mmbert_lora_qkv_bwd(_stream(), dqkv.data_ptr(), _pitch(dqkv), x.data_ptr(), _pitch(x), _ptr(h), _pitch(h) if h is not None else 0,
+                                       M, H, r, mask, pa, pb, float(scale), _ptr(dres), _pitch(dres) if dres is not None else 0,
+                                       _ptr(out), H, _Ptr3(*ga), _Ptr3(*gb), 1 if accumulate else 0, workspace.data_ptr()), "mmbert_lora_qkv_bwd")
+    return out
+
+
 # the per-launch wrappers as defined here: model.py takes the composite path only while nobody has wrapped them (bench.py's per-launch
 # event timing, tests that spy on launches)
-_UNWRAPPED = dict(gemm_nt=gemm_nt, attn_fwd=attn_fwd, attn_fwd_first=attn_fwd_first, attn_probs_first=attn_probs_first, attn_bwd=attn_bwd, ln_fwd=ln_fwd, ln_bwd=ln_bwd)
+_UNWRAPPED = dict(gemm_nt=gemm_nt, attn_fwd=attn_fwd, attn_fwd_first=attn_fwd_first, attn_probs_first=attn_probs_first, attn_bwd=attn_bwd, ln_fwd=ln_fwd, ln_bwd=ln_bwd,
+                  lora_qkv_fwd=lora_qkv_fwd, lora_qkv_bwd=lora_qkv_bwd)
 
 
 def launches_unwrapped() -> bool:

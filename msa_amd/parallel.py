@@ -162,6 +162,9 @@ class DataParallel:
                  wire_dtype: Optional[torch.dtype] = None, early_word_embedding: bool = True, equal_batch_shapes: bool = False):
         """``equal_batch_shapes``: the caller guarantees that every rank's token-id tensor has the same element count in every step
         (DeviceBatchBuilder / bench.py batches do) -- the id exchange then skips its size agreement (gather_union)."""
+        if getattr(model, "_lora", None):
+            raise NotImplementedError("parallel.DataParallel: a model with low-rank adapters (add_lora) is not supported -- the bucket "
+                                      "boundaries and the per-layer hooks are not laid out for adapter gradients; merge_lora() first")
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
         self.model, self.group = model, group

@@ -310,6 +310,20 @@ def apply_freeze(model, args):
                         layer_weights=bool(getattr(args, "freeze_layer_weights", False)))
 
 
+def apply_lora(model, args):
+    """``model.add_lora`` from the optional ``args.lora_rank`` (4, 8 or 16), ``args.lora_alpha`` (default 2 x rank), ``args.lora_targets``
+    (default query + value), ``args.lora_layers`` (default all), ``args.lora_freeze_base`` (default True) and ``args.lora_seed``.
+    ``default_args()`` has none of them: without ``lora_rank`` (or with None) nothing happens.  Call it before the optimizer is built
+    (``build_optimizer`` does, for a model that has no adapters yet).  Returns whether adapters were added."""
+    r = getattr(args, "lora_rank", None)
+    if r is None:
+        return False
+    model.add_lora(r=r, alpha=getattr(args, "lora_alpha", None) or 2.0 * r, targets=getattr(args, "lora_targets", None) or ("query", "value"),
+                   layers=getattr(args, "lora_layers", None), freeze_base=bool(getattr(args, "lora_freeze_base", True)),
+                   seed=getattr(args, "lora_seed", None))
+    return True
+
+
 def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
     """REF:train.py:76-97: two parameter groups by NAME substring, AdamW, linear warm-up with
     warmup = N and total = warmup_proportion * N.
@@ -317,8 +331,11 @@ def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
     groups of optim.layerwise_param_groups (layer-wise lr decay, a learning rate of its own for the parts a BERT checkpoint lacks).
     ``args.ema_decay`` / ``args.ema_warmup`` (optional, likewise): an exponential moving average of the weights, kept inside the
     optimizer step (``AdamW.ema``); ``train`` then validates, tests and saves under the averaged weights.
-    Frozen parameters (``requires_grad == False``: apply_freeze, model.freeze) are in no group."""
+    Frozen parameters (``requires_grad == False``: apply_freeze, model.freeze) are in no group.
+    ``args.lora_rank`` (optional, likewise): ``apply_lora`` runs first when the model has no adapters yet, so the groups hold them."""
     from .optim import AdamW, get_linear_schedule_with_warmup, layerwise_param_groups
+    if not getattr(model, "_lora", None):
+        apply_lora(model, args)
     layer_decay, head_lr = getattr(args, "layer_lr_decay", None), getattr(args, "head_learning_rate", None)
     if layer_decay is not None or head_lr is not None:
         groups = layerwise_param_groups(model, args.learning_rate, layer_decay=1.0 if layer_decay is None else layer_decay, head_lr=head_lr)
@@ -621,6 +638,8 @@ def train(args, model, train_dataset, val_dataset, test_dataset, optimizer, sche
                 path = os.path.join(save_dir, "model_" + str(epoch + 1) + ".pt")
                 if rank0:
                     torch.save(model.state_dict(), path)
+                    if getattr(model, "_lora", None):                # ... and the small per-task adapter file beside it
+                        torch.save(model.lora_state_dict(), os.path.join(save_dir, "lora_" + str(epoch + 1) + ".pt"))
                 best.update(epoch=epoch, acc=acc, loss=va[0], mae=mae, f_score=f_score, preds=te[6], labels=te[7], path=path if rank0 else None)
                 patience = 0
         if patience == patience_limit:
