@@ -333,6 +333,25 @@ def _trainable_probs(keyed, modes):
     return [q for k, q in keyed if modes[k] == _freeze.FULL], [(q[0], q[3]) for k, q in keyed if modes[k] == _freeze.BIAS]
 
 
+_LN_NAMES = ("output.LayerNorm.weight", "output.LayerNorm.bias", "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias")
+
+
+def _ln_grads(lw, fz, i):
+    """Where LayerNorm' of running layer ``i`` folds its gamma / beta sums: (g_ln2_g, g_ln2_b, g_ln1_g, g_ln1_b) of the layer's views -- a
+    FROZEN one (``fz`` = freeze.TrainablePlan; LayerNorm' needs a target) replaced by a row of a scratch matrix the layer's views keep, so
+    that no launch writes a frozen parameter's part of the flat gradient buffer."""
+    out = [lw["g_ln2_g"], lw["g_ln2_b"], lw["g_ln1_g"], lw["g_ln1_b"]]
+    if fz is None:
+        return out
+    for k, n in enumerate(_LN_NAMES):
+        if f"bert.encoder.layer.{i}.{n}" in fz.frozen:
+            s = lw.get("_ln_dropped")
+            if s is None:
+                s = lw["_ln_dropped"] = torch.zeros((4, out[k].numel()), device=out[k].device, dtype=torch.float32)
+            out[k] = s[k]
+    return out
+
+
 def _late_wgrad(top, prob, defer: bool):
     """A weight gradient of the FEW rows that carry a loss (tied decoder, MLM transform, the top layer's row-sparse sublayers).  ``defer``:
     it waits in ``top._late_wgrads`` for the end of the trunk's backward, where _EncoderFn.run_backward hands it to the deferred
@@ -638,6 +657,7 @@ class _EncoderFn:
                 saved_i = tuple(t[:ra] if torch.is_tensor(t) else t for t in saved_i)
             x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i[:16]
             lora_s = saved_i[16] if len(saved_i) > 16 else None          # (h, gradient flags) of a layer with adapters
+            g2g, g2b, g1g, g1b = _ln_grads(lw, fz, i)
             if i == L - 1 and (top_rows is not None or compact is not None):
                 R = None
                 R32 = None
@@ -656,7 +676,8 @@ class _EncoderFn:
                         (dy_c,) = ops.gather_rows([dy], src_rows.int())
                 if R is not None:
                     dy = _EncoderFn._last_layer_sparse(top, lw, layout, key_bias, kv_len, saved_i, dy_c, R, H, ra, R32, lnd,
-                                                       rinv if compact is not None else None, deferred if defer_wgrads else None, modes, skip_dx)
+                                                       rinv if compact is not None else None, deferred if defer_wgrads else None, modes, skip_dx,
+                                                       (g2g, g2b, g1g, g1b))
                     if top.grad_hook is not None:
                         lnd.flush()
                     dy_rows = None
@@ -680,8 +701,8 @@ class _EncoderFn:
                 du, dqkv = torch.empty((ra, I_), device=dev, dtype=bf), torch.empty((ra, 3 * H), device=dev, dtype=bf)
                 delta = torch.empty((ra, layout.heads), device=dev, dtype=torch.float32)
                 lnd.reserve(2, ra, H, dev)                           # (both slots are taken before their launches: no flush in between)
-                ws2 = lnd.slot(ra, H, dev, lw["g_ln2_g"], lw["g_ln2_b"], None)
-                ws1 = lnd.slot(ra, H, dev, lw["g_ln1_g"], lw["g_ln1_b"], None)
+                ws2 = lnd.slot(ra, H, dev, g2g, g2b, None)
+                ws1 = lnd.slot(ra, H, dev, g1g, g1b, None)
                 b = lw.get("_bwd_args")
                 if b is None:
                     b = lw["_bwd_args"] = ops._LayerBwd()
@@ -706,7 +727,7 @@ class _EncoderFn:
               # --- output sublayer: y2 = LN(dropout(g.W2^T + b2) + y1)      (b2 / bo gradients = column sums of dz2d / dz1d: they ride
               # on the weight-gradient launch below, like b1 and bqkv, on an all-ones MFMA operand)
               dz2d = torch.empty((ra, H), device=z2.device, dtype=torch.bfloat16) if d_h2[1] else None
-              dz2 = ops.ln_bwd(dy, z2, m2, r2, lw["ln2_g"], lw["g_ln2_g"], lw["g_ln2_b"], dx2=dz2d, pre_drop=d_h2, deferred=lnd, dy_rows=dy_rows)
+              dz2 = ops.ln_bwd(dy, z2, m2, r2, lw["ln2_g"], g2g, g2b, dx2=dz2d, pre_drop=d_h2, deferred=lnd, dy_rows=dy_rows)
               dy_rows = None
               if dz2d is None:
                   dz2d = dz2
@@ -714,7 +735,7 @@ class _EncoderFn:
               dy1 = ops.gemm_nt(du, lw["W1T"], resid=dz2)
               # --- attention sublayer: y1 = LN(dropout(ctx.Wo^T + bo) + x)
               dz1d = torch.empty((ra, H), device=z2.device, dtype=torch.bfloat16) if d_h1[1] else None
-              dz1 = ops.ln_bwd(dy1, z1, m1, r1, lw["ln1_g"], lw["g_ln1_g"], lw["g_ln1_b"], dx2=dz1d, pre_drop=d_h1, deferred=lnd)
+              dz1 = ops.ln_bwd(dy1, z1, m1, r1, lw["ln1_g"], g1g, g1b, dx2=dz1d, pre_drop=d_h1, deferred=lnd)
               if dz1d is None:
                   dz1d = dz1
               dctx = ops.gemm_nt(dz1d, lw["WoT"])
@@ -791,13 +812,14 @@ class _EncoderFn:
 
     @staticmethod
     def _last_layer_sparse(top, lw, layout, key_bias, kv_len, saved_i, dy_c, R, H, ra, R32=None, lnd=None, rinv=None, deferred=None, modes=None,
-                           skip_dx=False):
+                           skip_dx=False, ln_grads=None):
         """Backward of the top encoder layer when only the rows R of its output carry a gradient: the output sublayer (LayerNorm',
         FFN-down and FFN-up input gradients, their weight gradients), LayerNorm' and the output projection of the attention
         sublayer run on those rows only (gathered operands, the dropout masks of the ORIGINAL rows); attention's backward is
         dense again (every unmasked key receives a gradient), as is everything below.  ``modes`` / ``skip_dx``: as in run_backward (the
-        layer's frozen weights; no input gradient when the layer is where backward ends)."""
+        layer's frozen weights; no input gradient when the layer is where backward ends); ``ln_grads``: _ln_grads of the layer."""
         cfg = top.config
+        g2g, g2b, g1g, g1b = ln_grads if ln_grads is not None else _ln_grads(lw, None, cfg.num_hidden_layers - 1)
         x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i[:16]
         lora_s = saved_i[16] if len(saved_i) > 16 else None
         if R32 is None:
@@ -806,7 +828,7 @@ class _EncoderFn:
         m2_c, r2_c, u_c, m1_c, r1_c, y1_c, g_c, actx_c = ops.gather_rows([m2, r2, u, m1, r1, y1, g, actx], R32)
         dy = dy_c
         dz2d_c = torch.empty_like(dy_c) if d_h2[1] else None
-        dz2_c = ops.ln_bwd(dy_c, z2, m2_c, r2_c, lw["ln2_g"], lw["g_ln2_g"], lw["g_ln2_b"], x_rows=R32, dx2=dz2d_c, pre_drop=d_h2,
+        dz2_c = ops.ln_bwd(dy_c, z2, m2_c, r2_c, lw["ln2_g"], g2g, g2b, x_rows=R32, dx2=dz2d_c, pre_drop=d_h2,
                            drop_rows=R32, deferred=lnd)
         if dz2d_c is None:
             dz2d_c = dz2_c
@@ -814,7 +836,7 @@ class _EncoderFn:
         # K = 4H with a few hundred rows: 18 output tiles -> split-K (50 -> 15 us at the headline shape)
         dy1_c = ops.gemm_nt_splitk(du_c, lw["W1T"], resid=dz2_c) if du_c.shape[0] <= 1024 else ops.gemm_nt(du_c, lw["W1T"], resid=dz2_c)
         dz1d_c = torch.empty_like(dy_c) if d_h1[1] else None
-        dz1_c = ops.ln_bwd(dy1_c, z1, m1_c, r1_c, lw["ln1_g"], lw["g_ln1_g"], lw["g_ln1_b"], x_rows=R32, dx2=dz1d_c, pre_drop=d_h1,
+        dz1_c = ops.ln_bwd(dy1_c, z1, m1_c, r1_c, lw["ln1_g"], g1g, g1b, x_rows=R32, dx2=dz1d_c, pre_drop=d_h1,
                            drop_rows=R32, deferred=lnd)
         if dz1d_c is None:
             dz1d_c = dz1_c

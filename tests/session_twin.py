@@ -19,7 +19,26 @@ copies in the flat storage and the optimizer.  Each is right only while an invar
 * ``snapshot`` at an optimizer-step boundary holds everything that DEFINES the state (parameters, optimizer state, schedule position,
   dropout seed counter, switches) and nothing of what merely caches it; ``twin`` builds a fresh session holding exactly that;
 * ``check_against_twins`` replays, per boundary, the items since on a twin and compares with ``assert_same_bits``; a training item's
-  twin never runs the inference items in between."""
+  twin never runs the inference items in between.
+
+The fine-tuning lifecycle.  Besides the items above a script may hold **mutations** (``MUTATIONS``): ``freeze`` /
+``unfreeze`` / ``add_lora`` / ``merge_lora`` / ``remove_lora`` / ``reload_lora``.  They take no batch (shape ``None``), their arguments are
+the item's ``options``, and they stand only at an optimizer-step boundary -- no micro-batch pending: at item 0, or where the last
+training item in front is a ``train`` (inference items and other mutations, which leave the optimizer alone, may stand in between;
+``misplaced_mutations``).  THE OPTIMIZER RULE that makes the twin well defined: ``freeze`` keeps the optimizer (it follows through
+``AdamW._follow_frozen`` and keeps m, v and the step count); every other mutation replaces it by a fresh ``AdamW`` -- same lr, weight
+decay, mode, ``lazy_zero``, ``grad_scale``, the EMA restarted with the same decay and warm-up, step count 0, zero moments -- and re-binds
+the warm-up schedule to it at the position it had (msa_amd/optim.py: "build a new optimizer" behind an unfreeze that follows a step and
+behind a dropped storage).  ``snapshot`` also records ``{name: requires_grad}`` and the adapter record; a snapshot behind such a rebuild
+holds an UNBOUND optimizer (m / v / ema None), which the twin reproduces.  ``play`` snapshots in front of the first batch item behind a
+boundary, so a twin never runs a mutation.
+
+The gradient buffer under freezing: msa_amd/flat.py leaves the ``grads`` span of a frozen parameter unspecified while it is frozen (a
+lazily dropped weight gradient that is then frozen is never zero-filled).  ``Session.finish`` therefore zero-fills, on its CLONE only, the
+spans of exactly ``grad_mask(plan)`` = the plan's frozen names (asserted equal to ``model._flat.frozen``) -- a condition derived from the
+names alone, empty wherever nothing is frozen, not a tolerance: trainable spans, the padding between parameters and the whole of params,
+half, m, v and ema stay compared bit for bit, and the first training item behind an ``unfreeze`` compares those spans again
+(``set_frozen`` must have zero-filled them)."""
 from __future__ import annotations
 
 import contextlib
@@ -29,6 +48,7 @@ import torch
 
 KINDS = ("accumulate", "train", "eval", "predict", "predict_attention", "predict_tokens", "ema_eval")
 TRAINING = ("accumulate", "train")
+MUTATIONS = ("freeze", "unfreeze", "add_lora", "merge_lora", "remove_lora", "reload_lora")
 
 # the main script's shapes, taken from what the suite already runs (tests/test_train_gpu.py, tests/test_step_stages_gpu.py); the last one is
 # #6's (T, Pv, Pa) at ANOTHER batch size: the plan cache must not answer it with #6's plan
@@ -47,6 +67,205 @@ MODES_SCRIPT = [("train", (3, 20, 60, 40), 950, {}), ("predict", (5, 24, 200, 17
                 ("predict_attention", (5, 24, 170, 200), 956, {}), ("train", (4, 24, 200, 130, True), 957, {})]
 
 
+def _mut(kind, **options):
+    return (kind, None, None, options)
+
+
+# the one-sample batch runs the DENSE top-layer backward only when enough of its 40 rows carry a label (``top_layer_is_dense``): seeds at
+# which they do (906: the main script's item 7)
+DENSE_TOP_SEEDS = (906, 1003)
+
+
+def _seeded(items, seed0):
+    """(kind, shape) -> seed0 + index; (kind, shape, seed) and whole items as they are."""
+    return [it if len(it) == 4 else (it[0], it[1], it[2] if len(it) == 3 else seed0 + i, {}) for i, it in enumerate(items)]
+
+
+def freeze_script(L, seed0=1000):
+    """Freezing over a model's life (L encoder layers): a frozen prefix that grows until backward is the top layer alone and ends there
+    without an input gradient, a bias-only top layer, everything trainable again behind steps, a frozen layer between trainable ones, a
+    freeze that is taken back before any optimizer step --
+    with two micro-batches per step, the largest batch, the small one right behind it, the one-sample batch (dense top-layer backward)
+    and the inference paths in between."""
+    a, b, c, d, e, f, g, h = (MAIN_SHAPES[k] for k in (0, 1, 2, 4, 5, 6, 7, 9))
+    items = [("train", a), _mut("freeze", embeddings=True, layers=1), ("accumulate", b), ("train", c), ("predict", e),
+             _mut("freeze", layers=L - 1), ("train", d), ("ema_eval", c), _mut("freeze", layer_weights=True), ("accumulate", a), ("train", f, DENSE_TOP_SEEDS[0]),
+             ("predict_tokens", e), _mut("unfreeze"), ("train", g), _mut("freeze", layers=[1]), ("train", h), ("eval", b),
+             # a freeze taken back before any optimizer step: layer 0's lazily dropped weight gradients are still in the buffer when an
+             # eval forward reads the flags (they leave the stale set) and when the next forward finds them trainable again -- only
+             # set_frozen's zero fill stands between them and the first weight-gradient launch, which accumulates.  (Behind a step the
+             # optimizer's fused zero_grad has zero-filled every frozen block already: the unfreeze above cannot show it.)
+             _mut("freeze", layers=1), ("eval", c), _mut("unfreeze"), ("train", a)]
+    return _seeded(items, seed0)
+
+
+def lora_script(L, seed0=1100):
+    """Adapters over a model's life: rank 4 on query + value of every layer over a frozen base, saved / removed / loaded again, merged
+    (after which NO encoder layer is trainable: backward is the heads and the MLM head's few rows), everything trainable again, rank 16
+    on the key projection of the top layer alone over a trainable base, removed."""
+    a, b, c, d, e, f, g, h = (MAIN_SHAPES[k] for k in (0, 1, 2, 4, 5, 6, 7, 9))
+    items = [("train", a), _mut("add_lora", r=4, alpha=8.0, targets=("query", "value"), freeze_base=True, seed=77), ("accumulate", b), ("train", f, DENSE_TOP_SEEDS[1]),
+             ("predict_tokens", e), ("train", d), ("predict_attention", c), _mut("reload_lora"), ("train", e), ("ema_eval", a), _mut("merge_lora"),
+             ("train", g), ("predict", c), _mut("unfreeze"), _mut("add_lora", r=16, alpha=16.0, targets=("key",), layers=[L - 1], freeze_base=False, seed=78),
+             ("train", h), ("eval", b), _mut("remove_lora"), ("train", c)]
+    return _seeded(items, seed0)
+
+
+# ------------------------------------------------------------------------------------------------ what the names alone say
+LORA_BASE = ("bert.embeddings.", "bert.jointEmbeddings.", "bert.encoder.")          # what add_lora(freeze_base=True) freezes
+LIFECYCLE = ("stop_rises", "stop_is_top_layer_without_input_gradient", "bias_only_layer", "frozen_layer_between_trainable_ones",
+             "unfreeze_behind_steps", "unfreeze_without_a_step_since_the_freeze", "no_encoder_layer_trainable", "adapters_on_frozen_base", "adapters_on_trainable_base",
+             "adapters_on_a_subset_of_layers", "rank_changes", "targets_change", "merge", "remove", "reload")
+
+
+def misplaced_mutations(script):
+    """The indices of the mutations that do NOT stand at an optimizer-step boundary (a micro-batch is pending: the last training item in
+    front is an ``accumulate``), and of those that carry a shape or, for ``add_lora``, no seed."""
+    bad, pending = [], False
+    for i, (kind, shape, _seed, options) in enumerate(script):
+        if kind in MUTATIONS:
+            if pending or shape is not None or (kind == "add_lora" and "seed" not in options):
+                bad.append(i)
+        elif kind in TRAINING:
+            pending = kind == "accumulate"
+    return bad
+
+
+def base_frozen(flags):
+    """Whether every base parameter (``LORA_BASE``, the adapters left out) has ``requires_grad == False``: ``reload_lora``'s ``freeze_base``."""
+    return not any(t for n, t in flags.items() if n.startswith(LORA_BASE) and ".lora_" not in n)
+
+
+def _lora_record(options, L):
+    layers = options.get("layers")
+    return dict(r=options.get("r", 8), alpha=float(options.get("alpha", 16.0)),
+                targets=tuple(t for t in ("query", "key", "value") if t in options.get("targets", ("query", "value"))),
+                layers=tuple(range(L)) if layers is None else tuple(sorted(layers)))
+
+
+def _with_adapters(flags, rec, freeze_base):
+    out = dict(flags)
+    for i in rec["layers"]:
+        for t in rec["targets"]:
+            for m in ("lora_A", "lora_B"):
+                out[f"bert.encoder.layer.{i}.attention.self.{t}.{m}"] = True
+    if freeze_base:
+        for n in out:
+            if n.startswith(LORA_BASE) and ".lora_" not in n:
+                out[n] = False
+    return out
+
+
+def lifecycle_states(script, names, L):
+    """Per item of ``script``: (``{name: requires_grad}`` in force, the adapter record or None, the freeze.TrainablePlan of a training item
+    -- None for other items and while everything is trainable).  Pure: ``names`` = the parameter names of a model WITHOUT adapters (a
+    CPU-built MMBertForPretraining), the flags behind each mutation from freeze.resolve_freeze and add_lora's rule, the plan from
+    freeze.trainable_plan(flags, L, {}, {})."""
+    from msa_amd import freeze as FZ
+    flags, lora, out = {n: True for n in names}, None, []
+    for kind, _shape, _seed, options in script:
+        if kind == "freeze":
+            flags = dict(flags)
+            for n in FZ.resolve_freeze(list(flags), L, **options):
+                flags[n] = False
+        elif kind == "unfreeze":
+            flags = {n: True for n in flags}
+        elif kind == "add_lora":
+            assert lora is None, "add_lora on a model that has adapters"
+            lora = _lora_record(options, L)
+            flags = _with_adapters(flags, lora, options.get("freeze_base", True))
+        elif kind in ("merge_lora", "remove_lora"):
+            assert lora is not None, kind + " without adapters"
+            lora, flags = None, {n: t for n, t in flags.items() if ".lora_" not in n}
+        elif kind == "reload_lora":
+            assert lora is not None, "reload_lora without adapters"
+            fb = base_frozen(flags)
+            flags = _with_adapters({n: t for n, t in flags.items() if ".lora_" not in n}, lora, fb)
+        out.append((flags, lora, FZ.trainable_plan(flags, L, {}, {}) if kind in TRAINING else None))
+    return out
+
+
+def grad_mask(plan):
+    """The names whose span of the gradient buffer ``Session.finish`` zero-fills on its clone: the plan's frozen names; nothing without a plan."""
+    return frozenset() if plan is None else frozenset(plan.frozen)
+
+
+def zero_spans(g, offset, numel, names):
+    """Zero-fills, in the flat buffer ``g`` (a clone), the spans of ``names`` and nothing else -- not the padding behind them."""
+    for n in names:
+        g[offset[n]:offset[n] + numel[n]] = 0
+    return g
+
+
+def lifecycle_facts(script, names, L):
+    """Which of the lifecycle transitions (``LIFECYCLE``) a script really contains, from the names alone: name -> item indices (0-based,
+    counting every item of the script) at which it happens; the states of a training item are judged at that item, what a mutation does
+    at the mutation."""
+    from msa_amd import freeze as FZ
+    out = {k: [] for k in LIFECYCLE}
+    states = lifecycle_states(script, names, L)
+    prev_stop, steps, last_lora = 0, 0, None
+    since_freeze = None                                            # the kinds of the batch items since the last ``freeze`` (None: none yet)
+    for i, (item, (flags, lora, plan)) in enumerate(zip(script, states)):
+        kind = item[0]
+        if kind in TRAINING:
+            stop = 0 if plan is None else plan.stop
+            if stop > prev_stop:
+                out["stop_rises"].append(i)
+            prev_stop = stop
+            if plan is not None:
+                if plan.stop == L - 1 and not plan.embedding_stage:
+                    out["stop_is_top_layer_without_input_gradient"].append(i)
+                if any(m == FZ.BIAS for modes in plan.layers.values() for m in modes.values()):
+                    out["bias_only_layer"].append(i)
+                dead = lambda j: all(m == FZ.NONE for m in plan.layers[j].values())           # noqa: E731
+                if any(dead(j) and not dead(plan.stop) and any(not dead(k) for k in range(j + 1, L)) for j in range(plan.stop + 1, L)):
+                    out["frozen_layer_between_trainable_ones"].append(i)
+                if plan.stop >= L and any(t for n, t in flags.items() if not FZ.never_trainable(n)):
+                    out["no_encoder_layer_trainable"].append(i)
+            if lora is not None:
+                out["adapters_on_frozen_base" if base_frozen(flags) else "adapters_on_trainable_base"].append(i)
+                if lora["layers"] != tuple(range(L)):
+                    out["adapters_on_a_subset_of_layers"].append(i)
+            steps += kind == "train"
+        elif kind == "unfreeze" and steps:
+            out["unfreeze_behind_steps"].append(i)
+            if since_freeze is not None and "train" not in since_freeze and (set(since_freeze) & {"eval", "accumulate"}):
+                out["unfreeze_without_a_step_since_the_freeze"].append(i)      # (a forward read the frozen flags, no step zero-filled the spans)
+        elif kind == "add_lora":
+            if last_lora is not None and lora["r"] != last_lora["r"]:
+                out["rank_changes"].append(i)
+            if last_lora is not None and lora["targets"] != last_lora["targets"]:
+                out["targets_change"].append(i)
+        elif kind in ("merge_lora", "remove_lora", "reload_lora"):
+            out[kind.split("_")[0]].append(i)
+        if lora is not None:
+            last_lora = lora
+        if kind == "freeze":
+            since_freeze = []
+        elif kind == "unfreeze":
+            since_freeze = None
+        elif since_freeze is not None and kind not in MUTATIONS:
+            since_freeze.append(kind)
+    return out
+
+
+def top_layer_is_dense(item, cfg, device="cpu"):
+    """Whether a training item's top encoder layer runs the DENSE backward, from the batch alone (model._EncoderFn._sparse_rows: the
+    sparse path needs 4 (n + 3 B) <= ra; n = MLM-labelled rows, ra = the rows backward visits -- tests/test_session_twin_gpu.py::_counts)."""
+    b = batch(item[1], item[2], cfg, device)
+    B = b["input_ids"][0].shape[0]
+    am = b["attention_mask"]
+    masks = [am[0] != 0] + [torch.cat((m[0] != 0, m[1][:, :, 0] != 0), 1) for m in am[1:]]
+    n = ra = 0
+    for mask, lab in zip(masks, b["masked_labels"]):
+        pos = torch.arange(1, mask.shape[1] + 1, device=mask.device)
+        on = (lab >= 0) & (lab < cfg["vocab"])
+        n += int(on.sum())
+        ra += int(torch.maximum((mask * pos).amax(1), (on * pos).amax(1)).sum())
+    return 4 * (n + 3 * B) > ra
+
+
 # ------------------------------------------------------------------------------------------------ what the shapes alone say
 def shape_facts(shape):
     """(packed rows B (3T + Pv + Pa), longest sequence, the prologue's (floats, ints), (T, Pv, Pa), B, full_length) of a script shape."""
@@ -60,7 +279,8 @@ def shape_facts(shape):
 
 def transitions(script):
     """Which of the cache transitions a script is there for it really contains, from its shapes alone: name -> item indices (0-based)
-    at which the transition happens (empty = missing)."""
+    at which the transition happens (empty = missing).  Mutations have no shape: the indices count the batch items of the script."""
+    script = [it for it in script if it[0] not in MUTATIONS]
     f = [shape_facts(it[1]) for it in script]
     out = {k: [] for k in ("grows_past_everything", "shrinks_right_after_the_largest", "exact_repeat", "same_lens_other_batch",
                            "pair_lengths_exchanged", "longer_than_256", "one_sample_labels_on_pair_rows", "full_length")}
@@ -160,7 +380,9 @@ def _switches(model):
 def snapshot(model, opt, sched):
     """What defines the session at an optimizer-step boundary, as deep copies: ``model.state_dict()``, ``opt.state_dict()`` (steps, m, v,
     the EMA and its decay state, the groups' learning rates), the schedule's position, the dropout seed counter, the model's switches
-    (mode, deterministic mode, launch paths, short cuts, loss options).  Nothing of what the session merely caches."""
+    (mode, deterministic mode, launch paths, short cuts, loss options), ``{name: requires_grad}`` and the adapter record (``model._lora``
+    or None; the adapter tensors are in the state dict).  Nothing of what the session merely caches.  An optimizer that has not been
+    bound yet (fresh behind a mutation) gives m / v / ema None."""
     from msa_amd import ops
     osd = opt.state_dict()
     return dict(model={k: v.detach().clone() for k, v in model.state_dict().items()},
@@ -169,16 +391,19 @@ def snapshot(model, opt, sched):
                 opt_kw=dict(mode={0: "hf", 1: "torch"}[opt.mode], lazy_zero=opt.lazy_zero, grad_scale=opt.grad_scale),
                 sched=dict(warmup=sched.warmup, total=sched.total, last_step=sched.last_step),
                 seed=(model._seed, model._calls), training=model.training, je_training=model.bert.jointEmbeddings.training,
-                deterministic=ops.deterministic(), switches=_switches(model), max_norm=None)
+                deterministic=ops.deterministic(), switches=_switches(model), max_norm=None,
+                flags={n: bool(p.requires_grad) for n, p in model.named_parameters()}, lora=copy.deepcopy(getattr(model, "_lora", None)))
 
 
 class Session:
     """One model, one optimizer (EMA on, clipping), one warm-up schedule.  ``build``: tests.test_model_gpu.build."""
 
     def __init__(self, cfg, build, *, seed=29, lr=2e-3, weight_decay=0.01, ema_decay=0.9, warmup=4, total=40, max_norm=1.0, train=True,
-                 setup=None, _snapshot=None):
+                 setup=None, _snapshot=None, _overrides=None):
         from msa_amd.optim import AdamW, LinearWarmupSchedule
         self.cfg, self.build, self.max_norm, self.setup = cfg, build, max_norm, setup
+        self.lr, self.weight_decay = lr, weight_decay
+        self.moves = None                        # a list: finish() appends (trainable names a step moved, frozen names it moved)
         snap = _snapshot
         m = self.model = build(cfg, train=train)
         if snap is None:
@@ -191,7 +416,13 @@ class Session:
         else:
             from msa_amd import ops
             assert ops.deterministic() == snap["deterministic"], "the twin runs in the snapshot's mode"
+            if snap.get("lora"):
+                m.add_lora(**snap["lora"], freeze_base=False)
             m.load_state_dict(snap["model"])
+            named = dict(m.named_parameters())
+            assert set(named) == set(snap.get("flags", named)), "the twin's parameter names are not the snapshot's"
+            for n, t in snap.get("flags", {}).items():
+                named[n].requires_grad_(t)
             for k, v in snap["switches"].items():
                 if k in SWITCH_BUFFERS:
                     if v is not None or getattr(m, k, None) is not None:
@@ -201,6 +432,8 @@ class Session:
             m.train(snap["training"])
             m.bert.jointEmbeddings.train(snap["je_training"])
             m._seed, m._calls = snap["seed"]
+            for k, v in (_overrides or {}).items():
+                setattr(m, k, v)
             m._ensure_ready(next(m.parameters()).device)              # (the optimizer binds to the flat storage)
             self.opt = AdamW(m.parameters(), lr=lr, weight_decay=weight_decay, mode=snap["opt_kw"]["mode"])
             for g, s in zip(self.opt.param_groups, snap["groups"]):
@@ -244,15 +477,64 @@ class Session:
         return self._forward(batch(item[1], item[2], self.cfg), res, tag), res
 
     def finish(self, item, res):
-        """Behind the backward pass of a training item: the whole gradient buffer, and for ``train`` the optimizer step."""
-        res["grads"] = self.model._flat.grads.clone()
+        """Behind the backward pass of a training item: the whole gradient buffer -- on the clone, the spans of the frozen parameters
+        zero-filled (``grad_mask``; see the module docstring) --, and for ``train`` the optimizer step."""
+        f = self.model._flat
+        g = res["grads"] = f.grads.clone()
+        mask = grad_mask(self.model.__dict__.get("_tplan"))
+        assert mask == f.frozen, "the storage's frozen set is not the one of the plan this step ran under"
+        zero_spans(g, f.offset, f.numel, mask)
         if item[0] == "train":
+            before = f.params.clone() if self.moves is not None else None
             res["norm"] = self.opt.clip_grad_norm_(self.max_norm).detach().clone()
             self.opt.step()
             self.sched.step()
             self.opt.zero_grad()
             self._after_step(res)
+            if before is not None:
+                from msa_amd.freeze import never_trainable
+                moved = {n for n in f.order if f.numel[n] and not torch.equal(before[f.offset[n]:f.offset[n] + f.numel[n]], f.params[f.offset[n]:f.offset[n] + f.numel[n]])}
+                still = {n for n, p in f.named.items() if not p.requires_grad or never_trainable(n)}
+                self.moves.append((sorted(moved - still), sorted(moved & still)))
         return res
+
+    # ---- a mutation
+    def mutate(self, item):
+        """A mutation item, at an optimizer-step boundary; the optimizer rule of the module docstring."""
+        kind, shape, _seed, options = item
+        assert kind in MUTATIONS and shape is None, item
+        m = self.model
+        if kind == "freeze":
+            m.freeze(**options)
+            return
+        if kind == "unfreeze":
+            m.unfreeze()
+        elif kind == "add_lora":
+            assert "seed" in options
+            m.add_lora(**options)
+        elif kind == "merge_lora":
+            m.merge_lora()
+        elif kind == "remove_lora":
+            m.remove_lora()
+        else:
+            fb = base_frozen({n: p.requires_grad for n, p in m.named_parameters()})
+            sd = m.lora_state_dict()
+            m.remove_lora()
+            m.load_lora_state_dict(sd, freeze_base=fb)
+        self.rebuild_optimizer()
+
+    def rebuild_optimizer(self):
+        """A fresh AdamW on the model's parameters as they are now (unbound until its first use), the EMA restarted, the schedule re-bound
+        at its position.  Returns the optimizer it replaces."""
+        from msa_amd.optim import AdamW, LinearWarmupSchedule
+        old, s = self.opt, self.sched
+        self.opt = AdamW(self.model.parameters(), lr=self.lr, weight_decay=self.weight_decay, mode={0: "hf", 1: "torch"}[old.mode])
+        self.opt.ema(old._ema_decay, warmup=old._ema_warmup)
+        self.opt.lazy_zero, self.opt.grad_scale = old.lazy_zero, old.grad_scale
+        self.sched = LinearWarmupSchedule(self.opt, s.warmup, s.total)
+        self.sched.last_step = s.last_step
+        self.sched._apply()
+        return old
 
     def run(self, item, around_step=None, after_backward=None):
         """Plays one item; returns its result.  ``around_step``: a context manager factory entered around forward + backward of a
@@ -311,45 +593,55 @@ def _tensors(d, prefix=""):
     return out
 
 
-def twin(snap, cfg, build):
-    """A fresh Session -- new model, new flat storage, new optimizer and schedule -- that holds exactly the snapshot's state."""
-    return Session(cfg, build, _snapshot=snap, max_norm=snap["max_norm"])
+def twin(snap, cfg, build, overrides=None):
+    """A fresh Session -- new model, new flat storage, new optimizer and schedule -- that holds exactly the snapshot's state: the model
+    built, the adapters of the record added (``freeze_base=False``), the state dict loaded, every ``requires_grad`` flag set by name, and
+    only then the flat storage and the optimizer.  ``overrides``: model switches set on top of the snapshot's ({"composite_layers": False})."""
+    return Session(cfg, build, _snapshot=snap, max_norm=snap["max_norm"], _overrides=overrides)
 
 
 def play(sess, script, enter=None, around=None, snapshots=True):
     """The long-lived run: every item in turn on ``sess``.  Returns (results, snapshots): snapshots[i] = the state in front of item i
-    where item i is the first behind an optimizer-step boundary (item 0, and every item behind a ``train``).
+    where item i is the first batch item behind an optimizer-step boundary (item 0, every item behind a ``train``, and the first item
+    behind a run of mutations); a mutation's result is None.
     ``enter(i)``: a context manager for item i (a stream); ``around[i]``: (``around_step``, ``after_backward``) of item i."""
     results, snaps = [], {}
     for i, item in enumerate(script):
         with (enter(i) if enter is not None else contextlib.nullcontext()):
-            if snapshots and (i == 0 or script[i - 1][0] == "train"):
+            if item[0] in MUTATIONS:
+                sess.mutate(item)
+                results.append(None)
+                continue
+            if snapshots and (i == 0 or script[i - 1][0] == "train" or script[i - 1][0] in MUTATIONS):
                 snaps[i] = sess.snapshot()
                 snaps[i]["max_norm"] = sess.max_norm
             results.append(sess.run(item, *(around or {}).get(i, ())))
     return results, snaps
 
 
-def check_against_twins(results, snaps, script, cfg, build):
+def check_against_twins(results, snaps, script, cfg, build, overrides=None):
     """Every item of the long-lived run against a fresh twin of the last boundary in front of it.  The TRAINING items since that boundary
     are replayed on one twin that runs nothing else (an ``accumulate`` item together with the ``train`` item that consumes it, never the
     inference items in between); every inference item gets a twin of its own that replays the ``accumulate`` items in front of it (they
     move the dropout seed counter and the gradients, which an inference call must not read) and then the item.  Returns the number of
-    items compared: the caller asserts it is the script's length."""
+    items compared: the caller asserts it is the number of the script's batch items (mutations are not replayed: every snapshot is taken
+    behind them).  ``overrides``: see ``twin``."""
     compared, lay = 0, None
     starts = sorted(snaps)
     for n, s0 in enumerate(starts):
         s1 = starts[n + 1] if n + 1 < len(starts) else len(script)
-        t = twin(snaps[s0], cfg, build)
+        t = twin(snaps[s0], cfg, build, overrides)
         lay = t.layout()
         acc = []
         for i in range(s0, s1):
             item = script[i]
+            if item[0] in MUTATIONS:
+                continue
             if item[0] in TRAINING:
                 assert_same_bits(results[i], t.run(item), where(i, item) + " against its fresh twin", lay)
                 acc.append(item)
             else:
-                t2 = twin(snaps[s0], cfg, build)
+                t2 = twin(snaps[s0], cfg, build, overrides)
                 for a in acc:
                     t2.run(a)
                 assert_same_bits(results[i], t2.run(item), where(i, item) + " against its fresh twin", lay)

@@ -23,6 +23,8 @@ outputs by THAT reference's ``check`` -- no tolerance of its own:
     embed_gather / embed_scatter / pair_proj_fwd / pair_proj_bwd       embed_ref.gather / scatter / pair_fwd / pair_bwd
     gather_rows / scatter_rows_zero / attn_q_limit                     exact (layout_ref.scatter_ref for the stamped inverse)
     gelu_bwd                                                           ``gelu_bwd_ref`` below
+    lora_qkv_fwd / lora_qkv_bwd (dict operands, h row slices, dres=None) lora_ref.fwd / bwd, judged by lora_ref.check
+    colsum_grouped (per-problem accumulate flags)                      colsum_ref: M 2^-24 sum|x| + 2^-23 |ref|
 
 Dropout keep masks are rebuilt from the (stream, thr16, scale) triple recorded IN the call, through ``ops.dropout_mask`` /
 ``ops.attn_dropout_mask`` on a GPU and through their exact CPU references (tests/layout_ref.py) without one.  An adapter that cannot
@@ -47,6 +49,13 @@ bf16 rounding of the output; judged by ``gemm_ref.check``.  Its emulation (fp32 
  5. forward and backward of a dropout site carry the same triple, two different sites different streams;
  6. every gradient buffer a stage wrote is the view named for that stage, at the address of the parameter's ``.grad``.
 
+A step under a freeze.TrainablePlan and / or with adapters is judged by ``check_dataflow_frozen``: the frozen form of check 1 (forward all
+L layers, backward L-1 .. ``stop``, no ``dx`` stage where backward ends without an embedding stage, ``lora_fwd`` directly behind ``qkv`` and
+``lora_bwd`` directly behind ``attn_bwd`` on adapter layers), checks 2, 4, 5 and ``kv_len`` unchanged, and one more exact check,
+``check_frozen_writes``: no recorded call writes into the part of the flat gradient buffer that belongs to a frozen parameter, and the
+weight-gradient problems written are exactly the weights whose mode is "full", the MLM transform and -- iff ``word_table`` -- the tied
+table.  Checks 3 and 6 (``_wiring``, ``check_grad_views``) assume a full backward and are not extended to it.
+
 Not covered: the fused pretraining / classification heads (``heads_step_*``) and the step prologue.  tests/test_heads_gpu.py and
 tests/test_layout_gpu.py hold them to references at the operands the model passes; the recorder takes their outputs as given inputs.
 """
@@ -61,20 +70,25 @@ import numpy as np
 import torch
 
 from tests import attention_ref as A
+from tests import colsum_ref as CS
 from tests import embed_ref as E
 from tests import gemm_ref as G
 from tests import layout_ref as LR
+from tests import lora_ref as LO
 from tests import rowwise_ref as R
 
 SPIED = ("gemm_nt", "gemm_nt_splitk", "gemm_tn", "gemm_tn_grouped", "attn_fwd", "attn_bwd", "attn_q_limit", "ln_fwd", "ln_bwd", "gelu_bwd",
-         "embed_gather", "embed_scatter", "pair_proj_fwd", "pair_proj_bwd", "ce_fwd", "ce_bwd", "gather_rows", "scatter_rows_zero")
+         "embed_gather", "embed_scatter", "pair_proj_fwd", "pair_proj_bwd", "ce_fwd", "ce_bwd", "gather_rows", "scatter_rows_zero",
+         "lora_qkv_fwd", "lora_qkv_bwd", "colsum_grouped")
 # operands an op writes (cloned again after the call); ACCUMULATES: of those, the ones whose previous value the op reads
 WRITES = {"gemm_nt": ("out", "aux"), "gemm_nt_splitk": ("out",), "gemm_tn": ("W", "bias_out"), "gemm_tn_grouped": ("problems",),
           "attn_fwd": ("ctx", "lse"), "attn_bwd": ("dqkv",), "ln_fwd": ("out", "stats"), "ln_bwd": ("dx", "dx2", "dgamma", "dbeta", "dbias2"),
           "gelu_bwd": ("du",), "embed_gather": ("out",), "embed_scatter": ("gword", "gtype", "gpos"), "pair_proj_fwd": ("out",),
-          "pair_proj_bwd": ("dW", "db"), "ce_bwd": ("dlogits",)}
+          "pair_proj_bwd": ("dW", "db"), "ce_bwd": ("dlogits",), "lora_qkv_fwd": ("qkv", "h_out"), "lora_qkv_bwd": ("gA", "gB"),
+          "colsum_grouped": ("problems",)}
 ACCUMULATES = {"gemm_tn": ("bias_out",), "embed_scatter": ("gword", "gtype", "gpos"), "pair_proj_bwd": ("dW", "db"), "pair_proj_fwd": ("out",),
-               "ln_fwd": ("out",)}          # (the last two write some rows of a larger matrix: the others keep their values)
+               "ln_fwd": ("out",),          # (the last two write some rows of a larger matrix: the others keep their values)
+               "lora_qkv_fwd": ("qkv",), "lora_qkv_bwd": ("gA", "gB")}    # (colsum_grouped: per problem, like gemm_tn_grouped)
 
 # ---- the op sequence of the trunk (check 1): stage names, see ``_stage``
 FWD_LAYER = ("qkv", "attn_fwd", "z1", "ln1", "g", "z2", "ln2")                                  # model._EncoderFn.run_forward, per-launch body
@@ -164,6 +178,8 @@ def _snap(v, hold=True):
         return Rec(v, hold)
     if isinstance(v, (list, tuple)):
         return type(v)(_snap(x, hold) for x in v)
+    if type(v) is dict:                                          # (the adapters' {target: tensor} operands)
+        return {k: _snap(x, hold) for k, x in v.items()}
     if hasattr(v, "lens") and hasattr(v, "heads") and hasattr(v, "seq_start"):
         base = getattr(v, "base", v)
         split = bool(getattr(v, "split", False))
@@ -182,6 +198,9 @@ def _recs(v):
         yield v
     elif isinstance(v, (list, tuple)):
         for x in v:
+            yield from _recs(x)
+    elif type(v) is dict:
+        for x in v.values():
             yield from _recs(x)
 
 
@@ -598,10 +617,71 @@ def _r_scatter_rows(c):
     return [("out", 0.0)]
 
 
+def _cd(d):
+    return {t: _c(v) for t, v in (d or {}).items()}
+
+
+def _r_lora_fwd(c):
+    """ops.lora_qkv_fwd against tests/lora_ref.fwd on the qkv the call FOUND: the updated qkv (untargeted thirds bit for bit) and h_out."""
+    a = c.a
+    ref = LO.fwd(_c(a["x"]), _c(a["qkv"]), _cd(a["A"]), _cd(a["B"]), a["targets"], a["scale"])
+    res = [("qkv", LO.check(_c(c.post["qkv"]), ref["qkv"], "lora_qkv_fwd qkv"))]
+    if a["h_out"] is not None:
+        res.append(("h", LO.check(_c(c.post["h_out"]), ref["h"], "lora_qkv_fwd h")))
+    return res
+
+
+def _r_lora_bwd(c):
+    """ops.lora_qkv_bwd against tests/lora_ref.bwd: the gradients of the entries of gA / gB the call was handed, from the values it found
+    there, and the new residual gradient it returned."""
+    a = c.a
+    if a["h"] is None:
+        raise NotImplementedError("lora_qkv_bwd: h recomputed from x and A")
+    if a.get("workspace") is not None:
+        raise NotImplementedError("lora_qkv_bwd: a caller's workspace")
+    A_, B_ = _cd(a["A"]), _cd(a["B"])
+    gA0, gB0 = _cd(a["gA"]), _cd(a["gB"])
+    names = LO._names(a["targets"])
+    zero = lambda d, like: {t: d.get(t, torch.zeros(like[t].shape)) for t in names}           # noqa: E731
+    ref = LO.bwd(_c(a["dqkv"]), _c(a["x"]), _c(a["h"]), A_, B_, a["targets"], a["scale"], dres=_c(a["dres"]), gA0=zero(gA0, A_), gB0=zero(gB0, B_),
+                 accumulate=bool(a["accumulate"]))
+    res = []
+    for key, k, g0 in (("gA", "dA", gA0), ("gB", "dB", gB0)):
+        for t in g0:
+            res.append((f"{k}[{t}]", LO.check(_c(c.post[key][t]), ref[k][t], f"lora_qkv_bwd {k}[{t}]")))
+    if a["dres"] is not None:
+        res.append(("dres", LO.check(_c(c.ret), ref["dres"], "lora_qkv_bwd dres")))
+    else:
+        assert c.ret is None, "lora_qkv_bwd returned a tensor without dres"
+    return res
+
+
+def colsum_flags(c):
+    acc, n = c.a["accumulate"], len(c.a["problems"])
+    return [bool(x) for x in acc] if isinstance(acc, (list, tuple)) else [bool(acc)] * n
+
+
+def _r_colsum(c):
+    """ops.colsum_grouped, per problem, against the float64 column sum within tests/colsum_ref.py's bound."""
+    ad = c.a.get("alpha_dev")
+    scale = float(c.a["alpha"]) * (1.0 if ad is None else float(_c(ad).reshape(-1)[0]))
+    res = []
+    for j, ((x, out0), (_x, out1), acc) in enumerate(zip(c.a["problems"], c.post["problems"], colsum_flags(c))):
+        x, out0, out1 = _c(x), _c(out0), _c(out1)
+        if x.shape[0] == 0:
+            assert torch.equal(out0, out1), f"colsum_grouped problem {j}: M = 0 and the output changed"
+            continue
+        q = CS.ratio(out1, x, out0, acc, scale)
+        assert q <= 1.0, f"colsum_grouped problem {j} ({x.shape[0]} x {x.shape[1]}): error / bound = {q:.3g}"
+        res.append(("out", q))
+    return res
+
+
 ADAPTERS = {"gemm_nt": _r_gemm_nt, "gemm_nt_splitk": _r_splitk, "gemm_tn": _r_gemm_tn, "gemm_tn_grouped": _r_tn_grouped, "attn_fwd": _r_attn_fwd,
             "attn_bwd": _r_attn_bwd, "attn_q_limit": _r_q_limit, "ln_fwd": _r_ln_fwd, "ln_bwd": _r_ln_bwd, "ln_bwd_reduce": _r_ln_reduce,
             "gelu_bwd": _r_gelu_bwd, "ce_fwd": _r_ce_fwd, "ce_bwd": _r_ce_bwd, "embed_gather": _r_embed_gather, "embed_scatter": _r_embed_scatter,
-            "pair_proj_fwd": _r_pair_fwd, "pair_proj_bwd": _r_pair_bwd, "gather_rows": _r_gather_rows, "scatter_rows_zero": _r_scatter_rows}
+            "pair_proj_fwd": _r_pair_fwd, "pair_proj_bwd": _r_pair_bwd, "gather_rows": _r_gather_rows, "scatter_rows_zero": _r_scatter_rows,
+            "lora_qkv_fwd": _r_lora_fwd, "lora_qkv_bwd": _r_lora_bwd, "colsum_grouped": _r_colsum}
 
 
 def recompute(call):
@@ -650,9 +730,14 @@ def _name(names, rec, among=None):
     return None
 
 
-def _stage(c, names, qkv_layer):
-    """(stage name, layer or None) of a call, from the weight / gamma operand it carries."""
+def _stage(c, names, qkv_layer, dqkv_layer=None):
+    """(stage name, layer or None) of a call, from the weight / gamma operand it carries (the adapter launches: from the qkv / dqkv
+    matrix they work on)."""
     op = c.op
+    if op == "lora_qkv_fwd":
+        return "lora_fwd", qkv_layer.get(c.a["qkv"].region())
+    if op == "lora_qkv_bwd":
+        return "lora_bwd", (dqkv_layer or {}).get(c.a["dqkv"].region())
     if op in ("gemm_nt", "gemm_nt_splitk"):
         n = _name(names, c.a["B"], _NT_STAGE)
         if n is None:
@@ -674,19 +759,36 @@ def _stage(c, names, qkv_layer):
 
 def annotate(calls, model):
     names = names_of(model)
-    qkv_layer = {}
+    qkv_layer, dqkv_layer = {}, {}
     for c in calls:
-        st, layer = _stage(c, names, qkv_layer)
+        st, layer = _stage(c, names, qkv_layer, dqkv_layer)
         c.meta["stage"], c.meta["layer"] = st, layer
         if st == "qkv":
             qkv_layer[c.ret.region()] = layer
+        elif st == "attn_bwd":
+            dqkv_layer[c.ret.region()] = layer
     return names
 
 
-def check_sequence(calls, L):
+def _with(form, behind, stage, drop=None):
+    out = []
+    for s in form:
+        if s != drop:
+            out.append(s)
+        if s == behind:
+            out.append(stage)
+    return tuple(out)
+
+
+def check_sequence(calls, L, stop=0, no_dx=False, lora_layers=()):
     """Check 1: the trunk's stages in issue order are, per forward pass, FWD_LAYER for layers 0 .. L-1 and, per backward pass, for
-    layers L-1 .. 0, BWD_DENSE or (top layer only) one of BWD_TOP_SPARSE."""
+    layers L-1 .. ``stop``, BWD_DENSE or (top layer only) one of BWD_TOP_SPARSE.  The frozen form (freeze.TrainablePlan): forward runs all
+    L layers, backward the layers L-1 .. ``stop`` (none when ``stop >= L``), and with ``no_dx`` (the embedding stage does not run) layer
+    ``stop`` has no ``dx`` stage.  On the layers of ``lora_layers`` ``lora_fwd`` sits directly behind ``qkv`` and ``lora_bwd`` directly
+    behind ``attn_bwd``."""
     helpers = ("gather_rows8", "gather_rows1", "scatter_rows_zero", "attn_q_limit")
+    if stop or no_dx or lora_layers:
+        return _check_sequence_frozen(calls, L, stop, no_dx, set(lora_layers), helpers)
     trunk = [c for c in calls if c.meta["layer"] is not None or c.meta["stage"] in helpers]
     seq = [(c.meta["stage"], c.meta["layer"]) for c in trunk]
     i, passes = 0, {"fwd": 0, "bwd": 0}
@@ -710,6 +812,40 @@ def check_sequence(calls, L):
                 raise AssertionError(f"backward of layer {l}: {seq[i:i + 10]} is none of {forms}")
         passes["bwd"] += 1
     assert passes["fwd"] >= 1 and passes["fwd"] == passes["bwd"], passes
+    return passes
+
+
+def _check_sequence_frozen(calls, L, stop, no_dx, lora_layers, helpers):
+    trunk = [c for c in calls if c.meta["layer"] is not None or c.meta["stage"] in helpers]
+    assert not any(c.meta["stage"] in ("lora_fwd", "lora_bwd") and c.meta["layer"] is None for c in calls), "an adapter launch on no layer's qkv / dqkv"
+    seq = [(c.meta["stage"], c.meta["layer"]) for c in trunk]
+    i, passes = 0, {"fwd": 0, "bwd": 0}
+    strip = lambda part: [s for s, _ in part]                    # noqa: E731
+    while i < len(seq):
+        if seq[i] == ("qkv", 0):
+            for l in range(L):
+                f = _with(FWD_LAYER, "qkv", "lora_fwd") if l in lora_layers else FWD_LAYER
+                part = seq[i:i + len(f)]
+                assert strip(part) == list(f) and all(x[1] == l for x in part), f"forward of layer {l}: {part}"
+                i += len(f)
+            passes["fwd"] += 1
+            continue
+        assert stop < L, f"no encoder layer is trainable, yet the trunk ran {seq[i:i + 5]} behind its forward pass"
+        for l in reversed(range(stop, L)):
+            forms = [BWD_DENSE] + (list(BWD_TOP_SPARSE) if l == L - 1 else [])
+            if l in lora_layers:
+                forms = [_with(f, "attn_bwd", "lora_bwd") for f in forms]
+            if no_dx and l == stop:
+                forms = [_with(f, None, None, drop="dx") for f in forms]
+            for f in forms:
+                part = seq[i:i + len(f)]
+                if strip(part) == list(f) and all(x[1] in (l, None) for x in part):
+                    i += len(f)
+                    break
+            else:
+                raise AssertionError(f"backward of layer {l}: {seq[i:i + 11]} is none of {forms}")
+        passes["bwd"] += 1
+    assert passes["fwd"] >= 1 and passes["bwd"] == (passes["fwd"] if stop < L else 0), passes
     return passes
 
 
@@ -757,6 +893,14 @@ def check_producers(calls, cls_rows=None):
                     for q, r in enumerate(p):
                         if r is not None and (q != 2 or acc):
                             sh.read(r, f"call {c.index} ({c.op}) problem {j} operand {q}")
+                continue
+            if c.op == "colsum_grouped" and k == "problems":
+                for j, (p, acc) in enumerate(zip(v, colsum_flags(c))):
+                    sh.read(p[0], f"call {c.index} ({c.op}) problem {j} operand X")
+                    if acc:
+                        sh.read(p[1], f"call {c.index} ({c.op}) problem {j} output (accumulated onto)")
+                continue
+            if c.op == "lora_qkv_bwd" and k in ("gA", "gB") and not c.a["accumulate"]:
                 continue
             if c.op == "gemm_tn" and k == "W" and not c.a["accumulate"]:
                 continue
@@ -1004,6 +1148,79 @@ def check_dataflow(calls, model):
     sites = check_dropout_sites(calls)
     check_grad_views(calls, names, model)
     return passes, sites
+
+
+_MODE_KEY = {"w1": "W1", "w2": "W2", "qkv": "Wqkv", "o": "Wo"}
+
+
+def expected_wgrad_problems(plan, L):
+    """The gradient views the step's weight-gradient problems write, from the plan alone (None: nothing frozen): the weights whose mode
+    is "full", the MLM transform, and the tied table iff ``word_table``."""
+    from msa_amd import freeze as FZ
+    if plan is None:
+        return {f"l{i}.g_{k}" for i in range(L) for k in _MODE_KEY.values()} | {"g_Wt", "g_word_pad"}
+    out = {f"l{i}.g_{_MODE_KEY[key]}" for i, modes in plan.layers.items() for key, m in modes.items() if m == FZ.FULL} | {"g_Wt"}
+    return out | ({"g_word_pad"} if plan.word_table else set())
+
+
+def _extent(r: Rec):
+    """[first, last + 1) of the storage elements a recorded view covers."""
+    if not all(r.shape):
+        return r.off, r.off
+    return r.off, r.off + sum((n - 1) * st for n, st in zip(r.shape, r.stride)) + 1
+
+
+def check_frozen_writes(calls, names, plan, L, grads, offset, numel):
+    """Exact: no recorded call writes into the part of the flat gradient buffer ``grads`` that belongs to a parameter the plan has
+    frozen -- every region a call wrote (``post``, ``ret``) inside that buffer lies in trainable spans or in the padding between
+    parameters -- and the weight-gradient problems written are exactly ``expected_wgrad_problems``.  ``grads``: the buffer (its storage
+    address and size are all that is used; a ``Rec`` will do), ``offset`` / ``numel``: the storage's maps.  Returns the number of write
+    regions inside the buffer."""
+    g = grads if isinstance(grads, Rec) else Rec(grads, False)
+    frozen = sorted((offset[n], offset[n] + numel[n], n) for n in (plan.frozen if plan is not None else ()) if numel[n] > 0)
+    inside = 0
+    for c in calls:
+        for r in list(_recs(list(c.post.values()))) + list(_recs(c.ret)):
+            if r.sptr != g.sptr or r.dtype != g.dtype or not r.sbytes:
+                continue
+            lo, hi = _extent(r)
+            inside += 1
+            for a, b, n in frozen:
+                assert hi <= a or lo >= b, (f"call {c.index} ({c.op}, stage {c.meta.get('stage')} layer {c.meta.get('layer')}) writes elements "
+                                            f"[{max(lo, a)}, {min(hi, b)}) of the gradient buffer: the span of the frozen {n}")
+    wrote = set()
+    for c in calls:
+        if c.op in ("gemm_tn_grouped", "gemm_tn"):
+            for W in ([p[2] for p in c.a["problems"]] if c.op == "gemm_tn_grouped" else [c.a["W"]]):
+                n = _name(names, W, {"g_" + k for k in _MODE_KEY.values()} | {"g_Wt", "g_word_pad"})
+                assert n is not None, f"call {c.index} ({c.op}): a weight-gradient problem writes no gradient view of the model"
+                wrote.add(n)
+    want = expected_wgrad_problems(plan, L)
+    assert wrote == want, f"weight-gradient problems written: unexpected {sorted(wrote - want)}, missing {sorted(want - wrote)}"
+    return inside
+
+
+def check_dataflow_frozen(calls, model, plan, lora=None):
+    """The dataflow checks for a step under a freeze.TrainablePlan and / or adapters (``lora`` = model._lora): the frozen form of check 1,
+    checks 2 (``check_producers``), ``check_kv_len``, 4 (``check_transposes``) and 5 (``check_dropout_sites``) unchanged, and
+    ``check_frozen_writes``.  ``_wiring`` and ``check_grad_views`` (checks 3 and 6) assume a full backward and are NOT part of it.
+    Returns (passes, dropout sites, write regions inside the gradient buffer)."""
+    names = annotate(calls, model)
+    L = len(model._lw)
+    n = 0
+    for c in calls:
+        if c.op == "embed_gather":
+            n += 1
+        c.meta["pass"] = n
+    stop = 0 if plan is None else plan.stop
+    passes = check_sequence(calls, L, stop, plan is not None and not plan.embedding_stage, tuple(lora["layers"]) if lora else ())
+    lens = next((c.a["layout"].lens for c in calls if c.op == "attn_fwd"), None)
+    check_producers(calls, None if lens is None else torch.tensor([0] + lens[:-1]).cumsum(0))
+    check_kv_len(calls)
+    check_transposes(calls, names, model)
+    sites = check_dropout_sites(calls)
+    f = model._flat
+    return passes, sites, check_frozen_writes(calls, names, plan, L, f.grads, f.offset, f.numel)
 
 
 def check_accumulation(calls, names):

@@ -2,9 +2,12 @@
 
 Bound per output: ``M * 2^-24 * sum_m |x| + 2^-23 * |ref|`` -- the worst case of ANY fp32 summation order of M terms (each of the at most
 M - 1 additions rounds by at most 2^-24 of a partial sum that |x|'s sum bounds, the scaling by alpha rounds once more) plus the rounding of
-the output (where the call accumulates: of the final addition; ``ref`` then includes the prior value)."""
+the output (where the call accumulates: of the final addition; ``ref`` then includes the prior value).  Reference and bound live in
+tests/colsum_ref.py, which tests/step_stages.py shares."""
 import pytest
 import torch
+
+from tests import colsum_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -48,10 +51,7 @@ def _check(x, prior, out, acc, scale):
     if M == 0:
         assert torch.equal(out, prior)
         return
-    x64 = x.double()
-    ref = scale * x64.sum(0) + (prior.double() if acc else 0.0)
-    bound = scale * M * 2.0 ** -24 * x64.abs().sum(0) + 2.0 ** -23 * ref.abs()
-    err = (out.double() - ref).abs()
+    err, bound = colsum_ref.errors(out, x, prior, acc, scale)
     print(f"M={M} N={x.shape[1]} acc={acc} max err {float(err.max()):.3e} max bound {float(bound.max()):.3e}")
     assert bool((err <= bound).all()), (M, x.shape[1], float((err - bound).max()))
 

@@ -125,6 +125,130 @@ def test_the_shape_changes_at_every_item_of_the_modes_script():
     assert set(it[0] for it in s) | {"accumulate"} == set(ST.KINDS)
 
 
+# ------------------------------------------------------------------------------------------------ the fine-tuning lifecycle scripts
+_BATCH_CFG = dict(vocab=4096, dataset="mosei")                  # what both configurations of tests/test_lifecycle_twin_gpu.py share
+_FREEZE_FACTS = ("stop_rises", "stop_is_top_layer_without_input_gradient", "bias_only_layer", "frozen_layer_between_trainable_ones",
+                 "unfreeze_behind_steps", "unfreeze_without_a_step_since_the_freeze")
+_LORA_FACTS = ("stop_rises", "unfreeze_behind_steps", "no_encoder_layer_trainable", "adapters_on_frozen_base", "adapters_on_trainable_base",
+               "adapters_on_a_subset_of_layers", "rank_changes", "targets_change", "merge", "remove", "reload")
+
+
+def _names(L):
+    """The parameter names of a CPU-built model of L layers (no adapters), as tests/test_freeze_cpu.py takes them."""
+    from msa_amd.model import MMBertConfig, MMBertForPretraining
+    m = MMBertForPretraining(MMBertConfig(vocab_size=64, hidden_size=32, num_hidden_layers=L, num_attention_heads=2, intermediate_size=64))
+    m.bert.set_joint_embeddings("mosei")
+    return [n for n, _ in m.named_parameters()]
+
+
+@pytest.mark.parametrize("L", [3, 4])
+def test_the_lifecycle_scripts_contain_every_transition_they_are_there_for(L):
+    """Between them the two scripts contain every transition of ``ST.LIFECYCLE`` (the freeze script has no adapters, the adapter script
+    freezes through ``add_lora`` alone: each is held to its own list), and each the shape transitions it is to cross."""
+    names = _names(L)
+    fz, lo = ST.lifecycle_facts(ST.freeze_script(L), names, L), ST.lifecycle_facts(ST.lora_script(L), names, L)
+    assert set(fz) == set(lo) == set(ST.LIFECYCLE) == set(_FREEZE_FACTS) | set(_LORA_FACTS)
+    assert all(fz[k] for k in _FREEZE_FACTS), {k: fz[k] for k in _FREEZE_FACTS}
+    assert all(lo[k] for k in _LORA_FACTS), {k: lo[k] for k in _LORA_FACTS}
+    assert all(fz[k] or lo[k] for k in ST.LIFECYCLE)
+    # where, as the scripts are written down in tests/session_twin.py
+    assert fz["stop_rises"] == [2, 6] and fz["stop_is_top_layer_without_input_gradient"] == [6, 9, 10] and fz["bias_only_layer"] == [9, 10]
+    assert fz["unfreeze_behind_steps"] == [12, 19] and fz["frozen_layer_between_trainable_ones"] == [15]
+    assert fz["unfreeze_without_a_step_since_the_freeze"] == [19] and not lo["unfreeze_without_a_step_since_the_freeze"]
+    assert lo["adapters_on_frozen_base"] == [2, 3, 5, 8] and lo["reload"] == [7] and lo["merge"] == [10] and lo["no_encoder_layer_trainable"] == [11]
+    assert lo["rank_changes"] == lo["targets_change"] == [14] and lo["adapters_on_trainable_base"] == lo["adapters_on_a_subset_of_layers"] == [15]
+    assert lo["remove"] == [17]
+    for script, under in ((ST.freeze_script(L), fz["stop_is_top_layer_without_input_gradient"]),
+                          (ST.lora_script(L), lo["adapters_on_frozen_base"] + lo["adapters_on_trainable_base"])):
+        tr = ST.transitions(script)
+        for k in ("grows_past_everything", "shrinks_right_after_the_largest", "longer_than_256", "one_sample_labels_on_pair_rows"):
+            assert tr[k], k
+        shapes = [it[1] for it in script if it[0] not in ST.MUTATIONS]
+        assert (1, 8, 8, 8) in shapes and (6, 30, 260, 90) in shapes and set(shapes) <= set(ST.MAIN_SHAPES)
+        # the sparse and the dense top-layer backward each occur there, decided from the batches
+        assert {ST.top_layer_is_dense(script[i], _BATCH_CFG) for i in under} == {False, True}
+        kinds = {it[0] for it in script}
+        assert set(ST.TRAINING) <= kinds and len(kinds & set(ST.KINDS)) >= 5
+        assert len({it[2] for it in script if it[0] not in ST.MUTATIONS}) == len(shapes)
+
+
+def test_the_lifecycle_facts_are_computed_not_assumed():
+    """Each fact goes missing when the mutation that carries it does."""
+    L = 3
+    names = _names(L)
+    fs, ls = ST.freeze_script(L), ST.lora_script(L)
+    drop = lambda s, *idx: [it for i, it in enumerate(s) if i not in idx]           # noqa: E731
+    assert not ST.lifecycle_facts(drop(fs, 5), names, L)["stop_is_top_layer_without_input_gradient"]
+    assert not ST.lifecycle_facts(drop(fs, 8), names, L)["bias_only_layer"]
+    assert not ST.lifecycle_facts(drop(fs, 14), names, L)["frozen_layer_between_trainable_ones"]
+    assert ST.lifecycle_facts(drop(fs, 12), names, L)["unfreeze_behind_steps"] == [18]
+    assert not ST.lifecycle_facts(drop(fs, 12, 19), names, L)["unfreeze_behind_steps"]
+    assert not ST.lifecycle_facts(drop(fs, 18), names, L)["unfreeze_without_a_step_since_the_freeze"]          # (no forward read the frozen flags)
+    f = ST.lifecycle_facts(drop(ls, 10, 14), names, L)                               # no merge (and no second add_lora): the first adapters stay
+    assert not f["merge"] and not f["no_encoder_layer_trainable"]
+    f = ST.lifecycle_facts(drop(ls, 13), names, L)                                   # no unfreeze in front of the second adapters: the base stays frozen
+    assert not f["adapters_on_trainable_base"] and not f["unfreeze_behind_steps"] and f["adapters_on_a_subset_of_layers"]
+
+
+@pytest.mark.parametrize("L", [3, 4])
+def test_mutations_sit_only_at_optimizer_step_boundaries(L):
+    for script in (ST.freeze_script(L), ST.lora_script(L), ST.main_script(), ST.MODES_SCRIPT):
+        assert ST.misplaced_mutations(script) == []
+        for kind, shape, _seed, options in script:
+            assert (shape is None) == (kind in ST.MUTATIONS) and kind in ST.KINDS + ST.MUTATIONS
+            assert kind != "add_lora" or "seed" in options
+    s = ST.freeze_script(L)
+    # ... and the check sees a mutation behind a pending micro-batch, one with a shape, an add_lora without a seed
+    assert ST.misplaced_mutations(s[:3] + [ST._mut("unfreeze")] + s[3:]) == [3]
+    assert ST.misplaced_mutations([("accumulate", (1, 8, 8, 8), 1, {}), ("predict", (1, 8, 8, 8), 2, {}), ST._mut("freeze", layers=1)]) == [2]
+    assert ST.misplaced_mutations([("freeze", (1, 8, 8, 8), None, {})]) == [0]
+    assert ST.misplaced_mutations([ST._mut("add_lora", r=4)]) == [0]
+
+
+@pytest.mark.parametrize("L", [3, 4])
+def test_the_gradient_mask_is_empty_where_nothing_is_frozen_and_the_plans_frozen_names_elsewhere(L):
+    names = _names(L)
+    seen = {"empty": 0, "frozen": 0}
+    for script in (ST.freeze_script(L), ST.lora_script(L)):
+        for item, (flags, lora, plan) in zip(script, ST.lifecycle_states(script, names, L)):
+            if item[0] not in ST.TRAINING:
+                assert plan is None
+                continue
+            off = frozenset(n for n, t in flags.items() if not t)
+            mask = ST.grad_mask(plan)
+            assert mask == off == (frozenset() if plan is None else plan.frozen)
+            assert (lora is None) == (not any(".lora_" in n for n in flags))
+            seen["frozen" if mask else "empty"] += 1
+    assert seen["empty"] >= 5 and seen["frozen"] >= 9, seen
+    assert ST.grad_mask(None) == frozenset()
+
+
+def test_one_ulp_inside_a_trainable_span_of_a_masked_buffer_still_fails():
+    """The mask zero-fills the frozen parameters' spans on both clones and nothing else: garbage there passes, one ulp in a trainable
+    span, or in the padding behind the frozen span, does not."""
+    offset, numel = {n: o for o, _k, n in LAYOUT}, {n: k for o, k, n in LAYOUT}
+    a, b = _result(), _result()
+    b["grads"][520:700] = 7.0                                            # what a dropped, then frozen weight gradient leaves behind
+    with pytest.raises(AssertionError, match=r"owned by b.weight\[8\]"):
+        ST.assert_same_bits(a, b, "item 9 (accumulate)", LAYOUT)
+    for r in (a, b):
+        ST.zero_spans(r["grads"], offset, numel, ST.grad_mask(None))
+    with pytest.raises(AssertionError, match=r"owned by b.weight\[8\]"):
+        ST.assert_same_bits(a, b, "item 9 (accumulate)", LAYOUT)          # (an empty mask changes nothing)
+    for r in (a, b):
+        ST.zero_spans(r["grads"], offset, numel, frozenset({"b.weight"}))
+    ST.assert_same_bits(a, b, "item 9 (accumulate)", LAYOUT)
+    for index, owner in ((100, r"a.weight\[100\]"), (768, r"c.bias\[0\]"), (400, "padding between parameters")):
+        c = dict(b, grads=_one_ulp(b["grads"], index))
+        with pytest.raises(AssertionError, match="owned by " + owner):
+            ST.assert_same_bits(a, c, "item 9 (accumulate)", LAYOUT)
+    c = dict(b, grads=b["grads"].clone())
+    c["grads"][768] = 3.0                                                # the first element behind the masked span
+    ST.zero_spans(c["grads"], offset, numel, frozenset({"b.weight"}))
+    with pytest.raises(AssertionError, match=r"c.bias\[0\]"):
+        ST.assert_same_bits(a, c, "item 9 (accumulate)", LAYOUT)
+
+
 def test_a_plan_is_the_plan_of_one_batch_size():
     """``_plan`` at the same lengths and another batch size gives another plan (the library loads without a GPU; the plan's tensors are
     built on the CPU here)."""

@@ -345,3 +345,150 @@ def test_each_single_change_fails_the_harness(clean, mut):
         print(mut, "worst end-to-end relative error of a gradient:", round(worst, 4))
         assert (worst < 0.045) == E2E_INSIDE[mut], (mut, worst)
         assert worst > 0.0
+
+
+# ------------------------------------------------------------------------------------------------ the adapter and column-sum launches
+from tests import lora_ref as LO                             # noqa: E402
+from tests.test_lora_reference_cpu import MUTATIONS as LORA_MUTATIONS            # noqa: E402
+
+LM, LR_, LT = 257, 8, ("query", "value")                     # (tests/test_lora_reference_cpu.py's mutation case: 257 rows, H = 128, r = 8, q + v)
+COLSUM_ROWS = 200                                            # rows of the column-sum problem; a dropped row block = its last 32
+
+
+def lora_chain(mutation=None, colsum_rows=COLSUM_ROWS, stray=None):
+    """The three new launches as a recorded chain on the CPU, outputs from the references' emulations: ``lora_qkv_fwd`` (in place on the
+    qkv a gemm left, h kept), ``lora_qkv_bwd`` reading that h (a row slice of it, as the model passes it), accumulating onto the adapter
+    gradients, and ``colsum_grouped`` of a bias gradient -- all gradients views of ONE flat buffer laid out by ``offset`` / ``numel``.
+    ``mutation``: a tests/lora_ref.py Mutation applied to what the "kernels" computed; ``colsum_rows``: the rows the column sum really
+    summed; ``stray``: a parameter name whose span the column sum writes instead of its own.  Returns (calls, flat buffer, offset, numel)."""
+    inp = LO.inputs(LM, H, LR_, LT, "real", 4242 + LR_)
+    s = 16.0 / LR_
+    names = [f"{t}.lora_{m}" for t in LT for m in ("A", "B")] + ["bqkv", "ln.weight", "ln.bias"]
+    numel = {n: LR_ * H for n in names[:4]}
+    numel.update({"bqkv": 3 * H, "ln.weight": H, "ln.bias": H})
+    offset, off = {}, 0
+    for n in names:
+        offset[n] = off
+        off = (off + numel[n] + 255) // 256 * 256 + (256 if n == "bqkv" else 0)            # (a block of padding behind the bias)
+    flat = torch.randn(off, generator=torch.Generator().manual_seed(9)) * 0.01
+    view = lambda n, shape: flat[offset[n]:offset[n] + numel[n]].view(shape)                 # noqa: E731
+    gA = {t: view(f"{t}.lora_A", (LR_, H)) for t in LT}
+    gB = {t: view(f"{t}.lora_B", (H, LR_)) for t in LT}
+    calls = []
+    # forward
+    qkv = inp["qkv"].clone()
+    hbuf = torch.zeros(LM + 7, len(LT) * LR_, dtype=bf)
+    a = dict(x=inp["x"], qkv=qkv, A=inp["A"], B=inp["B"], targets=LT, scale=s, h_out=hbuf[:LM])
+    pre = {k: SS._snap(v) for k, v in a.items()}
+    e = LO.fwd(inp["x"], inp["qkv"], inp["A"], inp["B"], LT, s, emu=True, mutation=mutation)
+    qkv.copy_(e["qkv"].val.to(bf))
+    hbuf[:LM].copy_(e["h"].val.to(bf))
+    calls.append(SS.Call("lora_qkv_fwd", pre, {"qkv": SS._snap(qkv), "h_out": SS._snap(hbuf[:LM])}, SS._snap(qkv)))
+    # backward
+    a = dict(dqkv=inp["dqkv"], x=inp["x"], h=hbuf[:LM], A=inp["A"], B=inp["B"], gA=gA, gB=gB, targets=LT, scale=s, dres=inp["dres"], accumulate=True,
+             workspace=None)
+    pre = {k: SS._snap(v) for k, v in a.items()}
+    e = LO.bwd(inp["dqkv"], inp["x"], hbuf[:LM], inp["A"], inp["B"], LT, s, dres=inp["dres"], gA0={t: g.clone() for t, g in gA.items()},
+               gB0={t: g.clone() for t, g in gB.items()}, accumulate=True, emu=True, mutation=mutation)
+    for t in LT:
+        gA[t].copy_(e["dA"][t].val.float())
+        gB[t].copy_(e["dB"][t].val.float())
+    calls.append(SS.Call("lora_qkv_bwd", pre, {"gA": SS._snap(gA), "gB": SS._snap(gB)}, SS._snap(e["dres"].val.to(bf))))
+    # the bias gradient of the frozen Wqkv: the column sum of dqkv's first rows
+    X = inp["dqkv"][:COLSUM_ROWS]
+    out = view(stray, (-1,))[:3 * H] if stray == "bqkv" else (view("bqkv", (3 * H,)) if stray is None else flat[offset[stray]:offset[stray] + 3 * H])
+    a = dict(problems=[(X, out)], accumulate=True, alpha=1.0, alpha_dev=None)
+    pre = {k: SS._snap(v) for k, v in a.items()}
+    out.add_(X[:colsum_rows].float().sum(0))
+    calls.append(SS.Call("colsum_grouped", pre, {"problems": SS._snap([(X, out)])}, None))
+    for i, c in enumerate(calls):
+        c.index = i
+        c.meta.update(stage=c.op, layer=None)
+    return calls, flat, offset, numel
+
+
+def test_the_chain_through_the_adapter_and_column_sum_launches_passes():
+    calls, flat, offset, numel = lora_chain()
+    per = SS.recompute_all(calls)
+    assert {k: n for k, (n, _w) in per.items()} == {"lora_qkv_fwd": 1, "lora_qkv_bwd": 1, "colsum_grouped": 1}
+    print({k: round(w, 3) for k, (_n, w) in per.items()})
+    assert 0.2 < per["lora_qkv_fwd"][1] <= 0.55 and 0.2 < per["lora_qkv_bwd"][1] <= 0.55 and per["colsum_grouped"][1] <= 0.5, per
+    SS.check_producers(calls)                                   # backward read the h forward wrote, bit for bit
+
+
+@pytest.mark.parametrize("name", list(LORA_MUTATIONS))
+def test_each_adapter_mutation_fails_the_recomputation(name):
+    """tests/lora_ref.py's six mutations (a rank column dropped, s off by 2^-6, q and v swapped, the last partial row block skipped, a
+    partial sum left out of the fold, accumulate ignored), each applied to what the chain's adapter launches computed."""
+    calls, *_ = lora_chain(LORA_MUTATIONS[name][0]())
+    with pytest.raises(AssertionError, match="lora_qkv_(fwd|bwd)"):
+        SS.recompute_all(calls)
+
+
+def test_a_dropped_row_block_of_the_column_sum_fails():
+    calls, *_ = lora_chain(colsum_rows=COLSUM_ROWS - 32)
+    with pytest.raises(AssertionError, match=r"colsum_grouped problem 0 \(200 x 384\)"):
+        SS.recompute_all(calls)
+
+
+def test_a_backward_that_reads_another_h_than_forward_wrote_fails_the_producer_check():
+    calls, *_ = lora_chain()
+    h = calls[1].a["h"]
+    h.t.view(torch.int16)[5, 3] += 1
+    h._cpu = None
+    with pytest.raises(AssertionError, match="lora_qkv_bwd.* operand h: 1 of"):
+        SS.check_producers(calls)
+
+
+def test_a_write_into_a_frozen_span_trips_the_check():
+    """``check_frozen_writes``: the chain's writes lie in trainable spans (the adapters, the bias) -- fine while the LayerNorm is what is
+    frozen, a failure as soon as the bias is, or as the column sum lands in the frozen LayerNorm's span; padding is nobody's span."""
+    plan = lambda *frozen: types.SimpleNamespace(frozen=frozenset(frozen), layers={}, word_table=False)      # noqa: E731
+    model = _params()
+    names = SS.names_of(model)
+    wg = SS.synth("gemm_tn_grouped", dict(problems=[(torch.zeros(4, H, dtype=bf), torch.zeros(4, H, dtype=bf), model._w["g_Wt"], model._w["g_bt"])],
+                                          accumulate=True, alpha=1.0), post=dict(problems=[(model._w["g_Wt"], model._w["g_bt"])]))
+    wg.meta.update(stage="gemm_tn_grouped", layer=None)
+    calls, flat, offset, numel = lora_chain()
+    assert SS.check_frozen_writes(calls + [wg], names, plan("ln.weight", "ln.bias"), 1, flat, offset, numel) == 5     # 2 x 2 adapter gradients, the bias
+    with pytest.raises(AssertionError, match=r"colsum_grouped.* writes elements \[\d+, \d+\) of the gradient buffer: the span of the frozen bqkv"):
+        SS.check_frozen_writes(calls + [wg], names, plan("bqkv"), 1, flat, offset, numel)
+    with pytest.raises(AssertionError, match="lora_qkv_bwd.*the span of the frozen value.lora_B"):
+        SS.check_frozen_writes(calls + [wg], names, plan("value.lora_B"), 1, flat, offset, numel)
+    stray, flat2, *_ = lora_chain(stray="ln.weight")
+    with pytest.raises(AssertionError, match="the span of the frozen ln.weight"):
+        SS.check_frozen_writes(stray + [wg], names, plan("ln.weight", "ln.bias"), 1, flat2, offset, numel)
+    # the weight-gradient problems written are exactly the plan's: the MLM transform alone here; a missing or an extra one fails
+    with pytest.raises(AssertionError, match=r"missing \['g_Wt'\]"):
+        SS.check_frozen_writes(calls, names, plan("ln.weight"), 1, flat, offset, numel)
+    full = types.SimpleNamespace(frozen=frozenset({"ln.weight"}), layers={0: dict(w1="full", w2="none", qkv="bias", o="none")}, word_table=True)
+    assert SS.expected_wgrad_problems(full, 1) == {"l0.g_W1", "g_Wt", "g_word_pad"}
+    assert SS.expected_wgrad_problems(None, 2) == {f"l{i}.g_{k}" for i in (0, 1) for k in ("W1", "W2", "Wqkv", "Wo")} | {"g_Wt", "g_word_pad"}
+    with pytest.raises(AssertionError, match=r"missing \['g_word_pad', 'l0.g_W1'\]"):
+        SS.check_frozen_writes(calls + [wg], names, full, 1, flat, offset, numel)
+
+
+def test_the_frozen_form_of_the_sequence_check():
+    """``check_sequence`` with a plan: forward all L layers, backward L-1 .. stop, no ``dx`` where backward ends without an embedding
+    stage, the adapter stages directly behind ``qkv`` / ``attn_bwd`` -- and each deviation fails."""
+    def calls_of(seq):
+        out = []
+        for st, l in seq:
+            c = SS.Call(st, {})
+            c.meta.update(stage=st, layer=l)
+            out.append(c)
+        return out
+    L = 3
+    fwd = lambda lora=(): [(s, l) for l in range(L) for s in (SS._with(SS.FWD_LAYER, "qkv", "lora_fwd") if l in lora else SS.FWD_LAYER)]      # noqa: E731
+    dense = lambda l, lora=(), dx=True: [(s, l) for s in SS._with(SS._with(SS.BWD_DENSE, "attn_bwd", "lora_bwd") if l in lora else SS.BWD_DENSE, None, None, drop=None if dx else "dx")]      # noqa: E731
+    assert SS.check_sequence(calls_of(fwd() + dense(2) + dense(1, dx=False)), L, stop=1, no_dx=True) == {"fwd": 1, "bwd": 1}
+    assert SS.check_sequence(calls_of(fwd((0, 1, 2)) + dense(2, (2,)) + dense(1, (1,)) + dense(0, (0,), dx=False)), L, 0, True, (0, 1, 2)) == {"fwd": 1, "bwd": 1}
+    assert SS.check_sequence(calls_of(fwd((2,)) + dense(2, (2,)) + dense(1) + dense(0)), L, 0, False, (2,)) == {"fwd": 1, "bwd": 1}
+    assert SS.check_sequence(calls_of(fwd()), L, stop=3, no_dx=True) == {"fwd": 1, "bwd": 0}
+    for bad, kw in ((fwd() + dense(2) + dense(1), dict(stop=1, no_dx=True)),                        # an input gradient where backward ends
+                    (fwd() + dense(2) + dense(1, dx=False) + dense(0, dx=False), dict(stop=1, no_dx=True)),     # a layer below stop runs
+                    (fwd() + dense(2), dict(stop=3, no_dx=True)),                                  # a layer runs though none is trainable
+                    (fwd((2,)) + dense(2) + dense(1) + dense(0), dict(lora_layers=(2,))),           # the adapter backward is missing
+                    (fwd() + dense(2, (2,)) + dense(1) + dense(0), dict(lora_layers=(2,)))):        # the adapter forward is missing
+        with pytest.raises(AssertionError):
+            SS.check_sequence(calls_of(bad), L, **kw)
