@@ -635,6 +635,38 @@ int mmbert_lora_qkv_bwd(mmbert_stream_t stream, const void* dqkv, int lddq, cons
                         int targets, const void* const* A, const void* const* B, float scale, const void* dres_in, int lddi,
                         void* dres_out, int lddo, float* const* gA, float* const* gB, int accumulate, void* workspace);
 
+/* ---- low-rank adapters on the three other dense seams of an encoder layer (a declared extension; csrc/lora.hip) ----
+ * One projection per call: x [M, K] bf16 (row pitch ldx) is its input, y [M, N] bf16 (row pitch ldy) what its own mmbert_gemm_nt call left,
+ * A [r, K] and B [N, r] bf16, contiguous, 16-byte aligned.  r in {4, 8, 16}, K % 64 == 0, N % 64 == 0, every bf16 pitch % 8 == 0, x / y / dy /
+ * dx / aux / gelu_u 16-byte aligned; anything else returns -1.  A and B are staged in 768-column chunks (24.8 KB of LDS whatever K and N
+ * are), so the -2 of the convention (staged operands beyond 160 KiB) cannot occur here; -3: no workspace.  M == 0 returns 0 without a launch.
+ * h = bf16(x . A^T) with fp32 accumulation over K (ascending, 32-wide blocks), p = h . B^T in fp32.
+ * fwd (one launch, in place on y):
+ *   mode MMBERT_LORA_DENSE_ADD  (y = dropout(v) + R from the GEMM's bias / resid / drop epilogue):  y = bf16(fma(scale * c, p, float(y))), where
+ *     c(m, n) = drop_scale where the GEMM's dropout kept element m * N + n (N, not the pitch) of the stream drop_stream at the threshold
+ *     drop_thr16 -- pass the triple the GEMM call got -- and the element keeps its bits where it dropped.  drop_thr16 = 0: no dropout,
+ *     c = drop_scale everywhere.  scale * drop_scale is ONE fp32 product.  aux must be NULL.
+ *   mode MMBERT_LORA_DENSE_GELU (y = bf16(v) from the GEMM with its bias only):  w = fma(scale, p, float(y));  aux (may be NULL; row pitch
+ *     ldaux) = bf16(w), the pre-activation backward reads;  y = bf16(gelu(w)).  The dropout triple is not read.
+ *   h_out (may be NULL; 8-byte aligned, ldh % 4 == 0): h [M, r] bf16.  Rows >= M are not written.
+ * bwd, from dy [M, N] bf16 (row pitch lddy), the gradient of the projection's own output before its dropout:
+ *   g = bf16(dy . B);  dx (may be NULL: no input-gradient part; row pitch lddx) is updated IN PLACE: dx = bf16(fma(scale, q, float(dx))) with
+ *   q = g . A in fp32, or q = (g . A) * gelu'(float(gelu_u)) when gelu_u [M, K] bf16 (row pitch ldu) is given (needs dx);
+ *   gA [r, K] (+)= scale * g^T . x;  gB [N, r] (+)= scale * dy^T . h  -- fp32, 16-byte aligned, NULL: not computed.  accumulate != 0 adds.
+ *   h: what forward wrote to h_out (row pitch ldh), or NULL -- it is then recomputed from x and A (the same bits) into the workspace.
+ *   The token sums go through fp32 partial sums of 128-token slabs in `workspace` (mmbert_lora_dense_bwd_workspace bytes, 16-byte aligned)
+ *   that one launch folds in ascending order, one adder per output address: no atomics, the same bits in either deterministic setting.
+ *   Up to three launches; nothing is allocated or synchronised. */
+#define MMBERT_LORA_DENSE_ADD 0
+#define MMBERT_LORA_DENSE_GELU 1
+int mmbert_lora_dense_fwd(mmbert_stream_t stream, const void* x, int ldx, void* y, int ldy, int M, int K, int N, int r, const void* A, const void* B,
+                          float scale, int mode, unsigned drop_stream, unsigned drop_thr16, float drop_scale, void* aux, int ldaux,
+                          void* h_out, int ldh);
+size_t mmbert_lora_dense_bwd_workspace(int M, int K, int N, int r);
+int mmbert_lora_dense_bwd(mmbert_stream_t stream, const void* dy, int lddy, const void* x, int ldx, const void* h, int ldh, int M, int K, int N, int r,
+                          const void* A, const void* B, float scale, void* dx, int lddx, const void* gelu_u, int ldu, float* gA, float* gB,
+                          int accumulate, void* workspace);
+
 #ifdef __cplusplus
 }
 #endif

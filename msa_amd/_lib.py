@@ -118,6 +118,9 @@ SIGNATURES = {
     "mmbert_lora_qkv_fwd": (I, [P, P, I, P, I, I, I, I, I, P, P, F, P, I]),
     "mmbert_lora_qkv_bwd_workspace": (SZ, [I, I, I, I]),
     "mmbert_lora_qkv_bwd": (I, [P, P, I, P, I, P, I, I, I, I, I, P, P, F, P, I, P, I, P, P, I, P]),
+    "mmbert_lora_dense_fwd": (I, [P, P, I, P, I, I, I, I, I, P, P, F, I, U32, U32, F, P, I, P, I]),
+    "mmbert_lora_dense_bwd_workspace": (SZ, [I, I, I, I]),
+    "mmbert_lora_dense_bwd": (I, [P, P, I, P, I, P, I, I, I, I, I, P, P, F, P, I, P, I, P, P, I, P]),
 }
 
 _lib = None

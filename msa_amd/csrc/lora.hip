@@ -462,3 +462,406 @@ int mmbert_lora_qkv_bwd(hipStream_t stream, const void* dqkv, int lddq, const vo
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Adapters on the three remaining dense seams of an encoder layer (attention.output.dense, intermediate.dense, output.dense; DESIGN.md
+// S3.15): y [M, N] behind the projection's own GEMM, x [M, K] its input, A [r, K], B [N, r], K != N in general.  The fragment scheme is the
+// one above, unchanged in its arithmetic; what differs:
+//   * A and B are staged in column CHUNKS of LORA_DCHUNK (768) columns into ONE static 24.8 KB tile, so the LDS footprint does not grow
+//     with the FFN width and several workgroups share a CU.  The fp32 accumulator of a contraction lives across the chunks: k ascends in
+//     32-wide blocks exactly as in lora_contract_h, chunking changes no rounding.
+//   * the epilogue of the forward update: ADD  y = bf16(fma(s * c, p, float(y))), c = drop_scale on the elements the GEMM's dropout kept
+//     (same stream, threshold, flat index m * N + n) and the element untouched where it dropped;  GELU  w = fma(s, p, float(y)),
+//     aux = bf16(w), y = bf16(gelu(w)).
+//   * the input gradient is updated IN PLACE, optionally times gelu'(float(u)).
+//   * the token sums take one stream of width K (dA) and one of width N (dB); the column axis is split over blockIdx.z in chunks of 1024.
+#define LORA_DCHUNK 768
+#define LORA_DPITCH (LORA_DCHUNK + 8)
+#define LORA_DTILE (16 * LORA_DPITCH)                      // elements; >= LORA_DCHUNK * 16 (the [columns, 16] form)
+
+struct LoraDenseFwdArgs {
+    const bf16_t* x; bf16_t* y; const bf16_t* A; const bf16_t* B; bf16_t* aux; bf16_t* h;
+    int M, K, N, r, ldx, ldy, ldaux, ldh, gelu;
+    float s, sc;                                           // sc = s * drop_scale (ONE fp32 product, formed on the host)
+    uint32_t dstream, thr16, thr_pk;
+};
+struct LoraDenseBwdArgs {
+    const bf16_t* dy; const bf16_t* x; const bf16_t* A; const bf16_t* B; const bf16_t* u; bf16_t* dx; bf16_t* gbuf; bf16_t* hbuf;
+    int M, K, N, r, lddy, ldx, lddx, ldu, recompute; float s;
+};
+struct LoraDStream { const bf16_t* src; const bf16_t* coef; float* out; size_t part_off; int lds, ldc, colmajor, acc, W, pad; };
+struct LoraDWArgs { LoraDStream st[2]; int ns, M, r, nslab; float s; float* part; };
+
+// T[k][0 .. w) = A[k][k0 .. k0 + w) for k < r, zeros for r <= k < 16 (A: [r, K] row-major); row pitch LORA_DPITCH
+__device__ __forceinline__ void lora_stage_rows_chunk(bf16_t* T, const bf16_t* A, int K, int k0, int w, int r) {
+    const int CH = w >> 3, total = 16 * CH;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+        const int k = idx / CH, c = idx - k * CH;
+        bf16x8 v = lora_zero8();
+        if (k < r) v = *(const bf16x8*)(A + (size_t)k * K + k0 + 8 * c);
+        *(bf16x8*)(T + (size_t)k * LORA_DPITCH + 8 * c) = v;
+    }
+}
+// T[k][c] = B[n0 + c][k] for k < r, zeros above (B: [N, r] row-major), c < w: the transposed tile for the contraction over N in backward
+__device__ __forceinline__ void lora_stage_cols_t_chunk(bf16_t* T, const bf16_t* B, int n0, int w, int r) {
+    for (int c = threadIdx.x; c < w; c += blockDim.x) {
+        const bf16_t* src = B + (size_t)(n0 + c) * r;
+        bf16_t* dst = T + c;
+        for (int k0 = 0; k0 < r; k0 += 4) {
+            const bf16x4 v = *(const bf16x4*)(src + k0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dst[(size_t)(k0 + j) * LORA_DPITCH] = v[j];
+        }
+        for (int k = r; k < 16; ++k) dst[(size_t)k * LORA_DPITCH] = (bf16_t)0.0f;
+    }
+}
+// U[c][k] = B[n0 + c][k] for k < r, zeros for r <= k < 16: 16 elements per column c < w
+__device__ __forceinline__ void lora_stage_pad16_chunk(bf16_t* U, const bf16_t* B, int n0, int w, int r) {
+    for (int c = threadIdx.x; c < w; c += blockDim.x) {
+        const bf16_t* src = B + (size_t)(n0 + c) * r;
+        bf16x8 lo = lora_zero8(), hi = lora_zero8();
+        if (r == 16) { lo = *(const bf16x8*)src; hi = *(const bf16x8*)(src + 8); }
+        else if (r == 8) lo = *(const bf16x8*)src;
+        else lo = lora_low4(*(const bf16x4*)src);
+        bf16_t* dst = U + (size_t)c * 16;
+        *(bf16x8*)dst = lo; *(bf16x8*)(dst + 8) = hi;
+    }
+}
+// U[c][k] = A[k][k0 + c] for k < r, zeros above (A: [r, K] row-major), c < w: the transposed form, for the input gradient
+__device__ __forceinline__ void lora_stage_pad16_t_chunk(bf16_t* U, const bf16_t* A, int K, int k0, int w, int r) {
+    const int CH = w >> 3, total = 16 * CH;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+        const int k = idx / CH, c = idx - k * CH;
+        bf16x8 v = lora_zero8();
+        if (k < r) v = *(const bf16x8*)(A + (size_t)k * K + k0 + 8 * c);
+        bf16_t* dst = U + (size_t)(8 * c) * 16 + k;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dst[j * 16] = v[j];
+    }
+}
+// acc[n][m] += sum_k T[n][k] X[m][k0 + k] over the chunk's w columns (xrow already points at column k0 of this lane's row)
+__device__ __forceinline__ void lora_contract_chunk(f32x4& acc, const bf16_t* T, const bf16_t* xrow, int w, int lane) {
+    const int i = lane & 15, g = lane >> 4;
+    const bf16_t* tr = T + (size_t)i * LORA_DPITCH + 8 * g;
+    const bf16_t* xr = xrow + 8 * g;
+    for (int k = 0; k < w; k += 32) {
+        const bf16x8 xf = *(const bf16x8*)(xr + k);
+        const bf16x8 tf = *(const bf16x8*)(tr + k);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, xf, acc, 0, 0, 0);
+    }
+}
+// h = x . A^T of the wave's 16 rows over all of K, chunk by chunk (every thread of the workgroup calls it: it synchronises)
+__device__ __forceinline__ f32x4 lora_dense_contract(bf16_t* T, const bf16_t* W, bool rows_form, const bf16_t* xrow, int K, int r, bool wave_live, int lane) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < K; k0 += LORA_DCHUNK) {
+        const int w = min(LORA_DCHUNK, K - k0);
+        if (rows_form) lora_stage_rows_chunk(T, W, K, k0, w, r);
+        else lora_stage_cols_t_chunk(T, W, k0, w, r);
+        __syncthreads();
+        if (wave_live) lora_contract_chunk(acc, T, xrow + k0, w, lane);
+        __syncthreads();
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void lora_dense_fwd_kernel(const LoraDenseFwdArgs a) {
+    __shared__ __attribute__((aligned(16))) bf16_t T[LORA_DTILE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+    const int K = a.K, N = a.N, r = a.r;
+    const int m = blockIdx.x * LORA_ROWS + wave * 16 + (lane & 15);
+    const bool live = m < a.M;
+    const bool wave_live = blockIdx.x * LORA_ROWS + wave * 16 < a.M;
+    const int mr = live ? m : a.M - 1;                              // rows past M read row M - 1 and store nothing
+    const bf16x4 hb = lora_round4(lora_dense_contract(T, a.A, true, a.x + (size_t)mr * a.ldx, K, r, wave_live, lane));
+    const bf16x8 hf = lora_low4(hb);
+    if (a.h && live && 4 * g < r) *(bf16x4*)(a.h + (size_t)m * a.ldh + 4 * g) = hb;
+    bf16_t* yrow = a.y + (size_t)mr * a.ldy + 8 * g;
+    bf16_t* arow = a.aux ? a.aux + (size_t)mr * a.ldaux + 8 * g : nullptr;
+    const uint64_t flat = (uint64_t)mr * (uint64_t)N + (uint64_t)(8 * g);   // the GEMM's dropout index: LOGICAL column count, not the pitch
+    for (int n0 = 0; n0 < N; n0 += LORA_DCHUNK) {
+        const int w = min(LORA_DCHUNK, N - n0);
+        lora_stage_pad16_chunk(T, a.B, n0, w, r);
+        __syncthreads();
+        if (wave_live) {
+            for (int c0 = 0; c0 < w; c0 += 32) {
+                const bf16x8 old = *(const bf16x8*)(yrow + n0 + c0);
+                f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+                lora_expand32(T, c0, hf, lane, d0, d1);
+                float p[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { p[j] = d0[j]; p[4 + j] = d1[j]; }
+                bf16x8 o;
+                if (a.gelu) {
+                    bf16x8 uo;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const float wv = fmaf(a.s, p[j], bf2f(old[j]));
+                        uo[j] = f2bf(wv);
+                        o[j] = f2bf(gelu_erf(wv));
+                    }
+                    if (arow && live) *(bf16x8*)(arow + n0 + c0) = uo;
+                } else if (a.thr16 == 0) {                          // no dropout: c = drop_scale everywhere
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) o[j] = f2bf(fmaf(a.sc, p[j], bf2f(old[j])));
+                } else {
+                    const uint32_t pair0 = (uint32_t)((flat + (uint64_t)(n0 + c0)) >> 1);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {                   // one hash word per element pair, decided on the packed halves
+                        const uint32_t dm = mmb_drop_mask2(mmb_pair_bits(a.dstream, pair0 + q), a.thr_pk);
+                        const bf16_t v0 = f2bf(fmaf(a.sc, p[2 * q], bf2f(old[2 * q])));
+                        const bf16_t v1 = f2bf(fmaf(a.sc, p[2 * q + 1], bf2f(old[2 * q + 1])));
+                        o[2 * q] = (dm & 0xFFFFu) ? old[2 * q] : v0;
+                        o[2 * q + 1] = (dm >> 16) ? old[2 * q + 1] : v1;
+                    }
+                }
+                if (live) *(bf16x8*)(yrow + n0 + c0) = o;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// backward launch 1: g (and h, when it is recomputed) into the workspace, and the in-place update of the input gradient
+__global__ __launch_bounds__(256) void lora_dense_bwd_g_kernel(const LoraDenseBwdArgs a) {
+    __shared__ __attribute__((aligned(16))) bf16_t T[LORA_DTILE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+    const int K = a.K, N = a.N, r = a.r;
+    const int m = blockIdx.x * LORA_ROWS + wave * 16 + (lane & 15);
+    const bool live = m < a.M;
+    const bool wave_live = blockIdx.x * LORA_ROWS + wave * 16 < a.M;
+    const int mr = live ? m : a.M - 1;
+    if (a.recompute) {                                               // h = bf16(x . A^T), as forward formed it
+        const bf16x4 hb = lora_round4(lora_dense_contract(T, a.A, true, a.x + (size_t)mr * a.ldx, K, r, wave_live, lane));
+        if (live && 4 * g < r) *(bf16x4*)(a.hbuf + (size_t)m * r + 4 * g) = hb;
+    }
+    const bf16x4 gb = lora_round4(lora_dense_contract(T, a.B, false, a.dy + (size_t)mr * a.lddy, N, r, wave_live, lane));
+    const bf16x8 gf = lora_low4(gb);
+    if (live && 4 * g < r) *(bf16x4*)(a.gbuf + (size_t)m * r + 4 * g) = gb;
+    if (!a.dx) return;                                               // (uniform over the grid)
+    bf16_t* drow = a.dx + (size_t)mr * a.lddx + 8 * g;
+    const bf16_t* urow = a.u ? a.u + (size_t)mr * a.ldu + 8 * g : nullptr;
+    for (int k0 = 0; k0 < K; k0 += LORA_DCHUNK) {
+        const int w = min(LORA_DCHUNK, K - k0);
+        lora_stage_pad16_t_chunk(T, a.A, K, k0, w, r);
+        __syncthreads();
+        if (wave_live) {
+            for (int c0 = 0; c0 < w; c0 += 32) {
+                const bf16x8 old = *(const bf16x8*)(drow + k0 + c0);
+                f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+                lora_expand32(T, c0, gf, lane, d0, d1);
+                float q[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { q[j] = d0[j]; q[4 + j] = d1[j]; }
+                if (urow) {                                          // the FFN-down seam: the base input gradient carries the same gelu' factor
+                    const bf16x8 uv = *(const bf16x8*)(urow + k0 + c0);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) q[j] *= gelu_erf_grad(bf2f(uv[j]));
+                }
+                bf16x8 o;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = f2bf(fmaf(a.s, q[j], bf2f(old[j])));
+                if (live) *(bf16x8*)(drow + k0 + c0) = o;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// backward launch 2: part[stream][slab][k, c] = sum over the slab's tokens m of coef[m][k] * src[m][c] (fp32; not yet scaled by s); the FMA form
+// of lora_qkv_bwd_w_kernel with a width per stream and the column axis over blockIdx.z (128 lanes x 8 columns per workgroup: an I-wide
+// stream runs on 3 (bert-base) or 4 (bert-large) workgroups per slab with two row lanes each)
+template <int R>
+__global__ __launch_bounds__(256) void lora_dense_bwd_w_kernel(const LoraDWArgs a) {
+    __shared__ __attribute__((aligned(16))) float red[256 * 8];
+    const LoraDStream& st = a.st[blockIdx.y];
+    const int W = st.W, CH = W >> 3;
+    const int CHW = CH < 128 ? CH : 128, RL = 256 / CHW;
+    const int cb = blockIdx.z * CHW;
+    if (cb >= CH) return;                                            // (uniform over the workgroup: the narrower stream has fewer column blocks)
+    const int cc = threadIdx.x % CHW, rl = threadIdx.x / CHW;
+    const int mbeg = blockIdx.x * LORA_SLAB, mend = min(a.M, mbeg + LORA_SLAB);
+    float* part = a.part + st.part_off + (size_t)blockIdx.x * (size_t)(R * W);
+    const int c = cb + cc;
+    const bool act = rl < RL && c < CH;
+    float acc[R][8];
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
+    if (act) {
+        const bf16_t* src = st.src + 8 * c;
+        int m = mbeg + rl;
+        for (; m + 3 * RL < mend; m += 4 * RL) {                      // four independent 16-byte loads in flight
+            bf16x8 v[4];
+            bf16x4 w[4][R / 4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                v[u] = *(const bf16x8*)(src + (size_t)(m + u * RL) * st.lds);
+#pragma unroll
+                for (int q = 0; q < R / 4; ++q) w[u][q] = *(const bf16x4*)(st.coef + (size_t)(m + u * RL) * st.ldc + 4 * q);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int k = 0; k < R; ++k) {
+                    const float wk = bf2f(w[u][k >> 2][k & 3]);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[u][j]), acc[k][j]);
+                }
+        }
+        for (; m < mend; m += RL) {
+            const bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                const float wk = bf2f(st.coef[(size_t)m * st.ldc + k]);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[j]), acc[k][j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k) {                                    // row lanes 1 .. RL-1 are added onto row lane 0, in order
+        if (act && rl > 0) {
+            *(float4*)(red + (size_t)threadIdx.x * 8) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+            *(float4*)(red + (size_t)threadIdx.x * 8 + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
+        }
+        __syncthreads();
+        if (act && rl == 0) {
+            for (int q = 1; q < RL; ++q)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[k][j] += red[(size_t)(q * CHW + cc) * 8 + j];
+        }
+        __syncthreads();
+    }
+    if (act && rl == 0) {
+        if (st.colmajor) {                                           // [W, R]: R consecutive floats per column
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+#pragma unroll
+                for (int k = 0; k < R; k += 4)
+                    *(float4*)(part + (size_t)(8 * c + j) * R + k) = make_float4(acc[k][j], acc[k + 1][j], acc[k + 2][j], acc[k + 3][j]);
+        } else {                                                     // [R, W]
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                *(float4*)(part + (size_t)k * W + 8 * c) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+                *(float4*)(part + (size_t)k * W + 8 * c + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
+            }
+        }
+    }
+}
+
+// backward launch 3: out[e] = (acc ? out[e] : 0) + s * (slab 0 + slab 1 + ... in ascending order); a lane owns 4 consecutive elements
+__global__ __launch_bounds__(256) void lora_dense_fold_kernel(const LoraDWArgs a) {
+    const LoraDStream& st = a.st[blockIdx.y];
+    const size_t n = (size_t)a.r * st.W;
+    const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e >= n) return;
+    const float* p = a.part + st.part_off + e;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    int q = 0;
+    for (; q + 4 <= a.nslab; q += 4) {                               // loads four slabs ahead, adds in order
+        float4 t[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) t[u] = *(const float4*)(p + (size_t)(q + u) * n);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { s.x += t[u].x; s.y += t[u].y; s.z += t[u].z; s.w += t[u].w; }
+    }
+    for (; q < a.nslab; ++q) {
+        const float4 t = *(const float4*)(p + (size_t)q * n);
+        s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+    }
+    float4* o = (float4*)(st.out + e);
+    float4 v = make_float4(a.s * s.x, a.s * s.y, a.s * s.z, a.s * s.w);
+    if (st.acc) { const float4 w = *o; v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w; }
+    *o = v;
+}
+
+static inline bool lora_dense_shape_ok(int M, int K, int N, int r) {
+    return M >= 0 && K > 0 && N > 0 && (K & 63) == 0 && (N & 63) == 0 && (r == 4 || r == 8 || r == 16);
+}
+// what ONE workgroup stages at a time; constant in K and N (the chunking), so the -2 of the convention cannot occur for these kernels
+static inline size_t lora_dense_lds_bytes() { return (size_t)LORA_DTILE * sizeof(bf16_t); }
+
+extern "C" {
+
+int mmbert_lora_dense_fwd(hipStream_t stream, const void* x, int ldx, void* y, int ldy, int M, int K, int N, int r, const void* A, const void* B,
+                          float scale, int mode, unsigned drop_stream, unsigned drop_thr16, float drop_scale, void* aux, int ldaux,
+                          void* h_out, int ldh) {
+    if (!lora_dense_shape_ok(M, K, N, r) || (mode != MMBERT_LORA_DENSE_ADD && mode != MMBERT_LORA_DENSE_GELU)) return -1;
+    if (M == 0) return 0;
+    if (!x || !y || !A || !B || !lora_al16(x) || !lora_al16(y) || !lora_al16(A) || !lora_al16(B)) return -1;
+    if (ldx < K || (ldx & 7) || ldy < N || (ldy & 7) || drop_thr16 > 65535u) return -1;
+    if (aux && (mode != MMBERT_LORA_DENSE_GELU || !lora_al16(aux) || ldaux < N || (ldaux & 7))) return -1;
+    if (h_out && (!lora_al8(h_out) || ldh < r || (ldh & 3))) return -1;
+    if (lora_dense_lds_bytes() > LORA_LDS_MAX) return -2;
+    LoraDenseFwdArgs a = {};
+    a.x = (const bf16_t*)x; a.y = (bf16_t*)y; a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.aux = (bf16_t*)aux; a.h = (bf16_t*)h_out;
+    a.M = M; a.K = K; a.N = N; a.r = r; a.ldx = ldx; a.ldy = ldy; a.ldaux = ldaux; a.ldh = ldh; a.gelu = mode == MMBERT_LORA_DENSE_GELU;
+    a.s = scale; a.sc = scale * drop_scale;
+    a.dstream = drop_stream; a.thr16 = a.gelu ? 0u : drop_thr16; a.thr_pk = mmb_thr_packed(drop_thr16);
+    hipLaunchKernelGGL(lora_dense_fwd_kernel, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+// [partial sums: slabs x r (K + N) floats][g: M x r bf16][h, when backward recomputes it: the same]; 0 for M == 0 or a bad shape
+size_t mmbert_lora_dense_bwd_workspace(int M, int K, int N, int r) {
+    if (!lora_dense_shape_ok(M, K, N, r) || M == 0) return 0;
+    const size_t nslab = (size_t)(M + LORA_SLAB - 1) / LORA_SLAB;
+    const size_t part = nslab * (size_t)r * ((size_t)K + (size_t)N) * sizeof(float);
+    const size_t gb = lora_up16((size_t)M * r * sizeof(bf16_t));
+    return part + 2 * gb;
+}
+
+int mmbert_lora_dense_bwd(hipStream_t stream, const void* dy, int lddy, const void* x, int ldx, const void* h, int ldh, int M, int K, int N, int r,
+                          const void* A, const void* B, float scale, void* dx, int lddx, const void* gelu_u, int ldu, float* gA, float* gB,
+                          int accumulate, void* workspace) {
+    if (!lora_dense_shape_ok(M, K, N, r)) return -1;
+    if (M == 0) return 0;
+    if (!dy || !x || !A || !B || !lora_al16(dy) || !lora_al16(x) || !lora_al16(A) || !lora_al16(B)) return -1;
+    if (lddy < N || (lddy & 7) || ldx < K || (ldx & 7)) return -1;
+    if (h && (!lora_al8(h) || ldh < r || (ldh & 3))) return -1;
+    if (dx && (!lora_al16(dx) || lddx < K || (lddx & 7))) return -1;
+    if (gelu_u && (!dx || !lora_al16(gelu_u) || ldu < K || (ldu & 7))) return -1;
+    if ((gA && !lora_al16(gA)) || (gB && !lora_al16(gB))) return -1;
+    if (!workspace || !lora_al16(workspace)) return -3;
+    if (lora_dense_lds_bytes() > LORA_LDS_MAX) return -2;
+    if (!dx && !gA && !gB) return 0;                                 // nothing asked for
+    const int nslab = (M + LORA_SLAB - 1) / LORA_SLAB;
+    const size_t part = (size_t)nslab * (size_t)r * ((size_t)K + (size_t)N) * sizeof(float);
+    const size_t gb = lora_up16((size_t)M * r * sizeof(bf16_t));
+    LoraDenseBwdArgs a = {};
+    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.u = (const bf16_t*)gelu_u; a.dx = (bf16_t*)dx;
+    a.gbuf = (bf16_t*)((char*)workspace + part); a.hbuf = (bf16_t*)((char*)workspace + part + gb);
+    a.M = M; a.K = K; a.N = N; a.r = r; a.lddy = lddy; a.ldx = ldx; a.lddx = lddx; a.ldu = ldu; a.s = scale;
+    a.recompute = (gB && !h) ? 1 : 0;
+    // the weight-gradient streams that run: dA needs g and x (width K), dB needs dy and h (width N)
+    LoraDWArgs w = {};
+    int wmax = 0;
+    if (gA) {
+        LoraDStream& s = w.st[w.ns++];
+        s.src = a.x; s.lds = ldx; s.coef = a.gbuf; s.ldc = r; s.out = gA; s.colmajor = 0; s.acc = accumulate ? 1 : 0; s.W = K; s.part_off = 0;
+        wmax = K;
+    }
+    if (gB) {
+        LoraDStream& s = w.st[w.ns++];
+        s.src = a.dy; s.lds = lddy; s.out = gB; s.colmajor = 1; s.acc = accumulate ? 1 : 0; s.W = N; s.part_off = (size_t)nslab * (size_t)r * (size_t)K;
+        if (h) { s.coef = (const bf16_t*)h; s.ldc = ldh; }
+        else { s.coef = a.hbuf; s.ldc = r; }
+        if (N > wmax) wmax = N;
+    }
+    hipLaunchKernelGGL(lora_dense_bwd_g_kernel, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
+    MMB_CHECK_LAUNCH();
+    if (w.ns == 0) return 0;
+    w.M = M; w.r = r; w.nslab = nslab; w.s = scale; w.part = (float*)workspace;
+    const dim3 grid(nslab, w.ns, (wmax / 8 + 127) / 128);
+    if (r == 4) hipLaunchKernelGGL(lora_dense_bwd_w_kernel<4>, grid, dim3(256), 0, stream, w);
+    else if (r == 8) hipLaunchKernelGGL(lora_dense_bwd_w_kernel<8>, grid, dim3(256), 0, stream, w);
+    else hipLaunchKernelGGL(lora_dense_bwd_w_kernel<16>, grid, dim3(256), 0, stream, w);
+    MMB_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lora_dense_fold_kernel, dim3((unsigned)(((size_t)r * wmax / 4 + 255) / 256), w.ns), dim3(256), 0, stream, w);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"

@@ -101,8 +101,9 @@ class FlatParams:
             add(p + "attention.self.query.weight", p + "attention.self.key.weight", p + "attention.self.value.weight")
             add(p + "attention.self.query.bias", p + "attention.self.key.bias", p + "attention.self.value.bias")
             # low-rank adapters (model.add_lora; absent names are skipped: a model without adapters keeps its layout bit for bit).  Every
-            # one is r * H elements, a multiple of 256: each starts a block of its own, 16-byte aligned in all three buffers
+            # one is r * H or r * I elements, a multiple of 256: each starts a block of its own, 16-byte aligned in all three buffers
             add(*[p + f"attention.self.{t}.lora_{m}" for t in ("query", "key", "value") for m in ("A", "B")])
+            add(*[p + f"{t}.lora_{m}" for t in ("attention.output.dense", "intermediate.dense", "output.dense") for m in ("A", "B")])
         for n in sorted(named):
             if n.startswith("bert.jointEmbeddings."):
                 add(n)

@@ -478,7 +478,7 @@ class _EncoderFn:
             for i in range(nl):
                 lw = top._lw[i]
                 keep = keep_all and i >= keep_from
-                if lw["lora"] is not None:                           # a layer with adapters takes the per-launch form (the composite call has no seam)
+                if lw["lora"] is not None or lw.get("lora_dense") is not None:   # a layer with adapters takes the per-launch form (the composite call has no seam)
                     x, s_i = _EncoderFn._layer_forward(top, i, x, layout, key_bias, seed, kv_len, keep, pa, ph, y_out, y_rows, probe)
                     if keep_all:
                         saved.append(s_i)
@@ -546,6 +546,27 @@ class _EncoderFn:
         return ops.lora_qkv_bwd(dqkv, x, h[:dqkv.shape[0]], lo["A"], lo["B"], gA, gB, lo["targets"], lo["scale"], dres=dres, accumulate=True)
 
     @staticmethod
+    def _dense_forward(dl, t, x, y, keep, mode=ops.LORA_DENSE_ADD, drop=None, aux=None):
+        """The adapter of the dense target ``t`` (when the layer has one), in place on ``y`` directly behind the projection's own GEMM
+        (ops.lora_dense_fwd; ``drop``: the triple that GEMM got).  Returns what backward needs, or None: (h, A takes a gradient, B takes one)."""
+        if dl is None or t not in dl["targets"]:
+            return None
+        h = torch.empty((x.shape[0], dl["r"]), device=x.device, dtype=torch.bfloat16) if keep else None
+        ops.lora_dense_fwd(x, y, dl["A"][t], dl["B"][t], dl["scale"], mode=mode, drop=drop, aux=aux, h_out=h)
+        return (h, dl["pA"][t].requires_grad, dl["pB"][t].requires_grad) if keep else None
+
+    @staticmethod
+    def _dense_backward(dl, ds, t, dy, x, dx, gelu_u=None, saved_h=True):
+        """The backward of the dense target ``t`` (when the layer has one) directly behind the input-gradient GEMM of its projection: its
+        gradients (added: the optimizer zero-fills them) and the update of ``dx`` in place (ops.lora_dense_bwd).  ``saved_h`` False: the
+        operands are gathered rows, h is recomputed from them (the same bits)."""
+        if dl is None or ds is None or t not in ds:
+            return
+        h, fa, fb = ds[t]
+        ops.lora_dense_bwd(dy, x, h[:dy.shape[0]] if saved_h else None, dl["A"][t], dl["B"][t], dl["gA"][t] if fa else None,
+                           dl["gB"][t] if fb else None, dl["scale"], dx=dx, gelu_u=gelu_u, accumulate=True)
+
+    @staticmethod
     def _layer_forward(top, i, x, layout, key_bias, seed, kv_len, keep, pa, ph, y_out, y_rows, probe):
         """One encoder layer, one call per launch.  Returns (output, what backward keeps or None)."""
         cfg = top.config
@@ -557,19 +578,29 @@ class _EncoderFn:
         actx, lse = ops.attn_fwd(qkv, key_bias, layout, H, drop=d_att, kv_len=kv_len)
         if probe is not None:
             probe(i, qkv)
+        dl, ds = lw.get("lora_dense"), {}
         z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=x, drop=d_h1)
+        ds["attention_output"] = _EncoderFn._dense_forward(dl, "attention_output", actx, z1, keep, drop=d_h1)
         y1, m1, r1 = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=keep)
         u = torch.empty((x.shape[0], cfg.intermediate_size), device=x.device, dtype=torch.bfloat16) if keep else None
-        g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True, aux=u)
+        if dl is not None and "intermediate" in dl["targets"]:
+            # GELU is not linear: the GEMM leaves bf16(v) (bias only), the adapter launch adds its delta, stores the pre-activation and applies GELU
+            g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"])
+            ds["intermediate"] = _EncoderFn._dense_forward(dl, "intermediate", y1, g, keep, mode=ops.LORA_DENSE_GELU, aux=u)
+        else:
+            g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True, aux=u)
         z2 = ops.gemm_nt(g, lw["W2"], bias=lw["b2"], resid=y1, drop=d_h2)
+        ds["ffn_output"] = _EncoderFn._dense_forward(dl, "ffn_output", g, z2, keep, drop=d_h2)
         last = i == L - 1 and y_out is not None
         y2, m2, r2 = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=keep,
                                 out=y_out if last else None, out_rows=y_rows if last else None)
         s_i = None
         if keep:
             s_i = (x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2)
-            if ls is not None:
-                s_i = s_i + (ls,)                                # (a 17th entry on layers with adapters only)
+            if ls is not None or dl is not None:
+                s_i = s_i + (ls,)                                # (a 17th entry on layers with adapters only; None without Q / K / V adapters)
+            if dl is not None:
+                s_i = s_i + ({t: v for t, v in ds.items() if v is not None},)   # (an 18th with dense adapters: {target: (h, flags)})
         return y2, s_i
 
     @staticmethod
@@ -592,10 +623,17 @@ class _EncoderFn:
             probe(cfg.num_hidden_layers - 1, qkv)
         del qkv
         xr = ops.gather_rows([x], q_rows)[0]
+        dl = lw.get("lora_dense")                                 # (the dense adapters on the gathered rows; no dropout here: c = 1)
         z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=xr)
+        _EncoderFn._dense_forward(dl, "attention_output", actx, z1, False)
         y1, _, _ = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=False)
-        g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True)
+        if dl is not None and "intermediate" in dl["targets"]:
+            g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"])
+            _EncoderFn._dense_forward(dl, "intermediate", y1, g, False, mode=ops.LORA_DENSE_GELU)
+        else:
+            g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True)
         z2 = ops.gemm_nt(g, lw["W2"], bias=lw["b2"], resid=y1)
+        _EncoderFn._dense_forward(dl, "ffn_output", g, z2, False)
         y2, _, _ = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=False)
         return y2
 
@@ -657,6 +695,8 @@ class _EncoderFn:
                 saved_i = tuple(t[:ra] if torch.is_tensor(t) else t for t in saved_i)
             x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i[:16]
             lora_s = saved_i[16] if len(saved_i) > 16 else None          # (h, gradient flags) of a layer with adapters
+            dense_s = saved_i[17] if len(saved_i) > 17 else None         # {dense target: (h, gradient flags)}
+            dl = lw.get("lora_dense")
             g2g, g2b, g1g, g1b = _ln_grads(lw, fz, i)
             if i == L - 1 and (top_rows is not None or compact is not None):
                 R = None
@@ -685,7 +725,7 @@ class _EncoderFn:
                     continue
                 if compact is not None:
                     raise RuntimeError("compact output gradient without the sparse top-layer path")
-            if composite_bwd and lora_s is None:
+            if composite_bwd and lora_s is None and dense_s is None:
                 # the seven launches of the dense backward body from ONE C call (mmbert_layer_bwd: same kernels, same arguments, bit-identical)
                 dev, bf = z2.device, torch.bfloat16
                 I_ = top.config.intermediate_size
@@ -732,13 +772,18 @@ class _EncoderFn:
               if dz2d is None:
                   dz2d = dz2
               du = ops.gemm_nt(dz2d, lw["W2T"], gelu_bwd_u=u)
+              # (the dense adapters update the input gradients in place, each directly behind the GEMM that wrote it: the buffers are fresh
+              # and nothing launched earlier reads them; the weight-gradient problems below read the final du)
+              _EncoderFn._dense_backward(dl, dense_s, "ffn_output", dz2d, g, du, gelu_u=u)
               dy1 = ops.gemm_nt(du, lw["W1T"], resid=dz2)
+              _EncoderFn._dense_backward(dl, dense_s, "intermediate", du, y1, dy1)
               # --- attention sublayer: y1 = LN(dropout(ctx.Wo^T + bo) + x)
               dz1d = torch.empty((ra, H), device=z2.device, dtype=torch.bfloat16) if d_h1[1] else None
               dz1 = ops.ln_bwd(dy1, z1, m1, r1, lw["ln1_g"], g1g, g1b, dx2=dz1d, pre_drop=d_h1, deferred=lnd)
               if dz1d is None:
                   dz1d = dz1
               dctx = ops.gemm_nt(dz1d, lw["WoT"])
+              _EncoderFn._dense_backward(dl, dense_s, "attention_output", dz1d, actx, dctx)
               dqkv = ops.attn_bwd(qkv, actx, dctx, lse, key_bias, layout, H, drop=d_att, kv_len=kv_len)
               dres = dz1
               if lora_s is not None:
@@ -822,6 +867,8 @@ class _EncoderFn:
         g2g, g2b, g1g, g1b = ln_grads if ln_grads is not None else _ln_grads(lw, None, cfg.num_hidden_layers - 1)
         x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i[:16]
         lora_s = saved_i[16] if len(saved_i) > 16 else None
+        dense_s = saved_i[17] if len(saved_i) > 17 else None
+        dl = lw.get("lora_dense")
         if R32 is None:
             R32 = R.int()
         # the rows R of every saved activation this path reads, in ONE launch (9 index_select launches before)
@@ -833,14 +880,18 @@ class _EncoderFn:
         if dz2d_c is None:
             dz2d_c = dz2_c
         du_c = ops.gemm_nt(dz2d_c, lw["W2T"], gelu_bwd_u=u_c)
+        # (dense adapters on the gathered rows; h is recomputed from them -- the same bits as the saved rows -- instead of widening the gather)
+        _EncoderFn._dense_backward(dl, dense_s, "ffn_output", dz2d_c, g_c, du_c, gelu_u=u_c, saved_h=False)
         # K = 4H with a few hundred rows: 18 output tiles -> split-K (50 -> 15 us at the headline shape)
         dy1_c = ops.gemm_nt_splitk(du_c, lw["W1T"], resid=dz2_c) if du_c.shape[0] <= 1024 else ops.gemm_nt(du_c, lw["W1T"], resid=dz2_c)
+        _EncoderFn._dense_backward(dl, dense_s, "intermediate", du_c, y1_c, dy1_c, saved_h=False)
         dz1d_c = torch.empty_like(dy_c) if d_h1[1] else None
         dz1_c = ops.ln_bwd(dy1_c, z1, m1_c, r1_c, lw["ln1_g"], g1g, g1b, x_rows=R32, dx2=dz1d_c, pre_drop=d_h1,
                            drop_rows=R32, deferred=lnd)
         if dz1d_c is None:
             dz1d_c = dz1_c
         dctx_c = ops.gemm_nt(dz1d_c, lw["WoT"])
+        _EncoderFn._dense_backward(dl, dense_s, "attention_output", dz1d_c, actx_c, dctx_c, saved_h=False)
         if rinv is not None:                                      # both full-height gradients in ONE launch (zero fill + index_copy_, twice, before)
             dctx, dz1 = ops.scatter_rows_zero([dctx_c, dz1_c], rinv, ra)
         else:
@@ -1567,6 +1618,7 @@ class _GpuModelBase(nn.Module):
             f.register_lazy(d["g_W1"], [p + "intermediate.dense.weight"])
             f.register_lazy(d["g_W2"], [p + "output.dense.weight"])
             d["lora"] = self._lora_views(i, p)
+            d["lora_dense"] = self._lora_dense_views(i, p)
             self._lw.append(d)
         w = {}
         e = "bert.embeddings."
@@ -1601,14 +1653,32 @@ class _GpuModelBase(nn.Module):
         """Layer ``i``'s adapters as the encoder paths read them (None: the layer has none): per target the bf16 working copies of A [r, H]
         and B [H, r], their fp32 gradient views and their Parameters (whose ``requires_grad`` decides which gradients a backward computes)."""
         lc = getattr(self, "_lora", None)
-        if not lc or i not in lc["layers"]:
+        qkv = tuple(t for t in lc["targets"] if t in ops.LORA_TARGETS) if lc else ()
+        if not lc or i not in lc["layers"] or not qkv:
             return None
         f, H, r = self._flat, self.config.hidden_size, lc["r"]
-        lo = dict(targets=tuple(lc["targets"]), r=r, scale=float(lc["alpha"]) / r, A={}, B={}, gA={}, gB={}, pA={}, pB={})
+        lo = dict(targets=qkv, r=r, scale=float(lc["alpha"]) / r, A={}, B={}, gA={}, gB={}, pA={}, pB={})
         for t in lo["targets"]:
             na, nb = f"{prefix}attention.self.{t}.lora_A", f"{prefix}attention.self.{t}.lora_B"
             lo["A"][t], lo["B"][t] = f.span(f.half, na, r * H, (r, H)), f.span(f.half, nb, r * H, (H, r))
             lo["gA"][t], lo["gB"][t] = f.span(f.grads, na, r * H, (r, H)), f.span(f.grads, nb, r * H, (H, r))
+            lo["pA"][t], lo["pB"][t] = f.named[na], f.named[nb]
+        return lo
+
+    def _lora_dense_views(self, i, prefix):
+        """Layer ``i``'s adapters on attention.output.dense / intermediate.dense / output.dense (ops.LORA_DENSE_TARGETS; None: the layer has
+        none), in the form of ``_lora_views``: A [r, K] and B [N, r] of each target's own projection K -> N."""
+        lc = getattr(self, "_lora", None)
+        dense = tuple(t for t in lc["targets"] if t in ops.LORA_DENSE_TARGETS) if lc else ()
+        if not lc or i not in lc["layers"] or not dense:
+            return None
+        f, cfg, r = self._flat, self.config, lc["r"]
+        lo = dict(targets=dense, r=r, scale=float(lc["alpha"]) / r, A={}, B={}, gA={}, gB={}, pA={}, pB={})
+        for t in dense:
+            K, N = ops.lora_dense_dims(t, cfg.hidden_size, cfg.intermediate_size)
+            na, nb = (f"{prefix}{ops.LORA_DENSE_MODULES[t]}.lora_{m}" for m in ("A", "B"))
+            lo["A"][t], lo["B"][t] = f.span(f.half, na, r * K, (r, K)), f.span(f.half, nb, N * r, (N, r))
+            lo["gA"][t], lo["gB"][t] = f.span(f.grads, na, r * K, (r, K)), f.span(f.grads, nb, N * r, (N, r))
             lo["pA"][t], lo["pB"][t] = f.named[na], f.named[nb]
         return lo
 
@@ -2677,21 +2747,36 @@ class MMBertForPretraining(_GpuModelBase):
         if hasattr(self.bert, "jointEmbeddings"):
             self.bert.jointEmbeddings._owner = ref
 
-    # ---- low-rank adapters on the Q / K / V projections (a declared extension) ------------------------------------
+    # ---- low-rank adapters on the six dense projections of a layer (a declared extension) ------------------
     _LORA_BASE = ("bert.embeddings.", "bert.jointEmbeddings.", "bert.encoder.")
+
+    @staticmethod
+    def _lora_module_path(t):
+        """The adapted nn.Linear of target ``t`` below ``bert.encoder.layer.<i>.`` (the state-dict keys are this path + .lora_A / .lora_B)."""
+        return "attention.self." + t if t in ops.LORA_TARGETS else ops.LORA_DENSE_MODULES[t]
+
+    def _lora_linear(self, i, t):
+        m = self.bert.encoder.layer[i]
+        for a in self._lora_module_path(t).split("."):
+            m = getattr(m, a)
+        return m
 
     def _lora_linears(self):
         """(layer index, target name, the projection's nn.Linear) for every adapter the model holds."""
         lc = getattr(self, "_lora", None)
         if not lc:
             return []
-        return [(i, t, getattr(self.bert.encoder.layer[i].attention.self, t)) for i in lc["layers"] for t in lc["targets"]]
+        return [(i, t, self._lora_linear(i, t)) for i in lc["layers"] for t in lc["targets"]]
 
     def add_lora(self, r=8, alpha=16.0, targets=("query", "value"), layers=None, freeze_base=True, seed=None):
-        """DECLARED EXTENSION: low-rank adapters on the attention projections.  For every layer of ``layers`` (None: all) and every name of
-        ``targets`` (a non-empty subset of query / key / value) registers ``bert.encoder.layer.<i>.attention.self.<target>.lora_A`` [r, H]
-        (kaiming-uniform, a = sqrt 5, from a generator seeded by ``seed``) and ``.lora_B`` [H, r] (zeros); the projection then computes
-        x W^T + b + (alpha / r) (x A^T) B^T.  r in {4, 8, 16}.  ``freeze_base``: ``requires_grad_(False)`` on every ``bert.embeddings.*``,
+        """DECLARED EXTENSION: low-rank adapters on a layer's dense projections.  For every layer of ``layers`` (None: all) and every name of
+        ``targets`` (a non-empty subset of query / key / value / attention_output / intermediate / ffn_output, or "all-linear" for all six)
+        registers ``lora_A`` [r, K] (kaiming-uniform, a = sqrt 5: bound 1 / sqrt(K), K the projection's own fan-in) and ``lora_B`` [N, r]
+        (zeros) on the projection's nn.Linear K -> N: ``attention.self.<target>`` (H -> H), ``attention.output.dense`` (H -> H),
+        ``intermediate.dense`` (H -> I), ``output.dense`` (I -> H); the projection then computes x W^T + b + (alpha / r) (x A^T) B^T.  The As
+        are drawn from ONE generator seeded by ``seed``, in this order: first query / key / value for every layer in ascending order (so a
+        seed gives those the As it always gave), then attention_output / intermediate / ffn_output for every layer in ascending order.
+        r in {4, 8, 16}; the dense targets need intermediate_size % 64 == 0.  ``freeze_base``: ``requires_grad_(False)`` on every ``bert.embeddings.*``,
         ``bert.jointEmbeddings.*`` and ``bert.encoder.*`` parameter but the adapters (pooler and heads keep their flags).  The flat storage
         is dropped (rebuilt on the next use): call it BEFORE the optimizer is built, like ``set_num_labels``.  Invalid arguments, or
         adapters already present (``remove_lora`` / ``merge_lora`` first), raise ValueError."""
@@ -2703,8 +2788,10 @@ class MMBertForPretraining(_GpuModelBase):
             raise ValueError(f"add_lora: r must be one of {ops.LORA_RANKS}, got {r!r}")
         if H % 64:
             raise ValueError(f"add_lora: the adapter kernels need hidden_size % 64 == 0, got {H}")
-        mask = ops.lora_mask(targets)                                # (ValueError for an empty / unknown / repeated target)
-        names = tuple(t for k, t in enumerate(ops.LORA_TARGETS) if mask >> k & 1)
+        qkv_names, dense_names = ops.lora_split_targets(targets)     # (ValueError for an empty / unknown / repeated target)
+        names = qkv_names + dense_names
+        if dense_names and cfg.intermediate_size % 64:
+            raise ValueError(f"add_lora: the adapter kernels need intermediate_size % 64 == 0, got {cfg.intermediate_size}")
         alpha = float(alpha)
         if not math.isfinite(alpha):
             raise ValueError(f"add_lora: alpha must be finite, got {alpha!r}")
@@ -2712,14 +2799,16 @@ class MMBertForPretraining(_GpuModelBase):
         if not idx or any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < L for i in idx) or len(set(idx)) != len(idx):
             raise ValueError(f"add_lora: layers must be distinct indices in 0 .. {L - 1} (None: all), got {layers!r}")
         gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
-        bound = 1.0 / math.sqrt(H)                                   # kaiming_uniform_(a = sqrt 5) on [r, H]: gain sqrt(1 / 3), fan_in H
-        for i in sorted(idx):
-            for t in names:
-                lin = getattr(self.bert.encoder.layer[i].attention.self, t)
-                w = lin.weight
-                A = torch.empty((r, H), dtype=torch.float32).uniform_(-bound, bound, generator=gen)
-                lin.lora_A = nn.Parameter(A.to(device=w.device, dtype=w.dtype))
-                lin.lora_B = nn.Parameter(torch.zeros((H, r), device=w.device, dtype=w.dtype))
+        for group in (qkv_names, dense_names):                       # (the order of the draws: see the docstring)
+            for i in sorted(idx):
+                for t in group:
+                    lin = self._lora_linear(i, t)
+                    w = lin.weight
+                    N, K = w.shape
+                    bound = 1.0 / math.sqrt(K)                       # kaiming_uniform_(a = sqrt 5) on [r, K]: gain sqrt(1 / 3), fan_in K
+                    A = torch.empty((r, K), dtype=torch.float32).uniform_(-bound, bound, generator=gen)
+                    lin.lora_A = nn.Parameter(A.to(device=w.device, dtype=w.dtype))
+                    lin.lora_B = nn.Parameter(torch.zeros((N, r), device=w.device, dtype=w.dtype))
         self._lora = dict(r=r, alpha=alpha, targets=names, layers=tuple(sorted(idx)))
         if freeze_base:
             for n, p in self.named_parameters():
@@ -2758,14 +2847,14 @@ class MMBertForPretraining(_GpuModelBase):
         sd = {"r": lc["r"], "alpha": lc["alpha"], "targets": tuple(lc["targets"]), "layers": tuple(lc["layers"])}
         for i, t, lin in self._lora_linears():
             for m in ("lora_A", "lora_B"):
-                sd[f"bert.encoder.layer.{i}.attention.self.{t}.{m}"] = getattr(lin, m).detach().clone()
+                sd[f"bert.encoder.layer.{i}.{self._lora_module_path(t)}.{m}"] = getattr(lin, m).detach().clone()
         return sd
 
     def load_lora_state_dict(self, sd, freeze_base=True):
         """Loads what ``lora_state_dict`` returned: creates the adapters when the model has none (``add_lora`` with the file's r, alpha,
         targets and layers, and ``freeze_base``), raises ValueError when existing ones differ in any of the four or a tensor is missing or
         has another shape, copies the values and calls ``parameters_changed()``."""
-        meta = dict(r=int(sd["r"]), alpha=float(sd["alpha"]), targets=tuple(t for t in ops.LORA_TARGETS if t in tuple(sd["targets"])),
+        meta = dict(r=int(sd["r"]), alpha=float(sd["alpha"]), targets=tuple(t for t in ops.LORA_ALL_TARGETS if t in tuple(sd["targets"])),
                     layers=tuple(sorted(int(i) for i in sd["layers"])))
         if not getattr(self, "_lora", None):
             self.add_lora(meta["r"], meta["alpha"], meta["targets"], meta["layers"], freeze_base=freeze_base)
@@ -2774,7 +2863,7 @@ class MMBertForPretraining(_GpuModelBase):
         todo = []
         for i, t, lin in self._lora_linears():
             for m in ("lora_A", "lora_B"):
-                k = f"bert.encoder.layer.{i}.attention.self.{t}.{m}"
+                k = f"bert.encoder.layer.{i}.{self._lora_module_path(t)}.{m}"
                 p = getattr(lin, m)
                 if k not in sd or tuple(sd[k].shape) != tuple(p.shape):
                     raise ValueError(f"load_lora_state_dict: {k} is missing or not of shape {tuple(p.shape)}")

@@ -1627,10 +1627,90 @@ def lora_qkv_bwd(dqkv, x, h, A, B, gA, gB, targets, scale, dres=None, accumulate
     return out
 
 
+# the adapters on the three other dense seams of a layer (mmbert_lora_dense_*): target name -> (module path below the layer, K, N) by
+# (H, I); the epilogue the seam sits behind is ADD (dropout + residual) for attention_output / ffn_output, GELU for intermediate
+LORA_DENSE_TARGETS = ("attention_output", "intermediate", "ffn_output")
+LORA_ALL_TARGETS = LORA_TARGETS + LORA_DENSE_TARGETS          # the canonical order (model._lora["targets"], the seeded draws of A)
+LORA_DENSE_MODULES = {"attention_output": "attention.output.dense", "intermediate": "intermediate.dense", "ffn_output": "output.dense"}
+LORA_DENSE_ADD, LORA_DENSE_GELU = 0, 1
+
+
+def lora_dense_dims(target: str, H: int, I: int):
+    """(K, N) of a dense target's projection."""
+    return {"attention_output": (H, H), "intermediate": (H, I), "ffn_output": (I, H)}[target]
+
+
+def lora_split_targets(targets):
+    """(QKV names, dense names), each in canonical order, of a non-empty collection of LORA_ALL_TARGETS names or "all-linear"; ValueError for
+    an empty, unknown or repeated name (the bare "output" among them: it would be ambiguous between the two output projections)."""
+    if isinstance(targets, str):
+        names = list(LORA_ALL_TARGETS) if targets == "all-linear" else [targets]
+    else:
+        names = list(targets)
+    if not names or any(t not in LORA_ALL_TARGETS for t in names) or len(set(names)) != len(names):
+        raise ValueError(f"lora targets must be a non-empty subset of {LORA_ALL_TARGETS} without repeats (or 'all-linear'), got {targets!r}")
+    return tuple(t for t in LORA_TARGETS if t in names), tuple(t for t in LORA_DENSE_TARGETS if t in names)
+
+
+def _lora_dense_check(x, y, A, B, what):
+    M, K = x.shape
+    N = y.shape[1]
+    r = A.shape[0]
+    assert x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and y.shape[0] == M and (M == 0 or (x.stride(1) == 1 and y.stride(1) == 1))
+    if A.dtype != torch.bfloat16 or B.dtype != torch.bfloat16 or tuple(A.shape) != (r, K) or tuple(B.shape) != (N, r) \
+            or not A.is_contiguous() or not B.is_contiguous():
+        raise ValueError(f"{what}: the adapter must be contiguous bf16 A [{r}, {K}] and B [{N}, {r}], got {tuple(A.shape)} {A.dtype} / {tuple(B.shape)} {B.dtype}")
+    return M, K, N, r
+
+
+def lora_dense_fwd(x, y, A, B, scale, mode=LORA_DENSE_ADD, drop: Drop = None, aux=None, h_out=None):
+    """In place on ``y`` [M, N] bf16, what the projection's own gemm_nt left (see mmbert_lora_dense_fwd), with p = bf16(x @ A^T) @ B^T:
+    LORA_DENSE_ADD: y += scale * c * p, c = the dropout scale where the GEMM's ``drop`` (the same triple) kept the element, 0 where it dropped;
+    LORA_DENSE_GELU: w = y + scale * p, ``aux`` [M, N] bf16 (optional) = w, y = gelu(w).  ``h_out`` [M, r] bf16 receives x @ A^T.  Returns y."""
+    M, K, N, r = _lora_dense_check(x, y, A, B, "lora_dense_fwd")
+    if aux is not None:
+        assert aux.dtype == torch.bfloat16 and aux.shape == (M, N) and (M == 0 or aux.stride(1) == 1)
+    if h_out is not None:
+        assert h_out.dtype == torch.bfloat16 and h_out.shape == (M, r) and (M == 0 or h_out.stride(1) == 1)
+    ds, dt, dsc = drop or NO_DROP
+    _lib.check(_lib.load().mmbert_lora_dense_fwd(_stream(), x.data_ptr(), _pitch(x), y.data_ptr(), _pitch(y), M, K, N, r, A.data_ptr(), B.data_ptr(),
+                                                 float(scale), int(mode), ds, dt, dsc, _ptr(aux), _pitch(aux) if aux is not None else 0,
+                                                 _ptr(h_out), _pitch(h_out) if h_out is not None else 0), "mmbert_lora_dense_fwd")
+    return y
+
+
+def lora_dense_bwd_workspace(M: int, K: int, N: int, r: int) -> int:
+    return int(_lib.load().mmbert_lora_dense_bwd_workspace(int(M), int(K), int(N), int(r)))
+
+
+def lora_dense_bwd(dy, x, h, A, B, gA, gB, scale, dx=None, gelu_u=None, accumulate=True, workspace=None):
+    """One dense adapter's backward from ``dy`` [M, N] bf16, the gradient of the projection's output before its dropout (see
+    mmbert_lora_dense_bwd): gA [r, K] (+)= scale * g^T @ x, gB [N, r] (+)= scale * dy^T @ h (fp32; None: not computed), g = bf16(dy @ B);
+    ``dx`` [M, K] bf16 is updated IN PLACE, dx += scale * (g @ A) (* gelu'(``gelu_u``) when given); None: no input-gradient part.  ``h``:
+    forward's h_out, or None (recomputed from x and A).  ``workspace``: a caller's buffer (tests).  Returns dx."""
+    lib = _lib.load()
+    M, K, N, r = _lora_dense_check(x, dy, A, B, "lora_dense_bwd")
+    if h is not None:
+        assert h.dtype == torch.bfloat16 and h.shape == (M, r) and (M == 0 or h.stride(1) == 1)
+    for t in (dx, gelu_u):
+        if t is not None:
+            assert t.dtype == torch.bfloat16 and t.shape == (M, K) and (M == 0 or t.stride(1) == 1)
+    for g, shape in ((gA, (r, K)), (gB, (N, r))):
+        if g is not None:
+            assert g.dtype == torch.float32 and tuple(g.shape) == shape and g.is_contiguous()
+    if workspace is None:
+        workspace = _ws_f32((lib.mmbert_lora_dense_bwd_workspace(M, K, N, r) + 3) // 4, x.device)
+    _lib.check(lib.mmbert_lora_dense_bwd(_stream(), dy.data_ptr(), _pitch(dy), x.data_ptr(), _pitch(x), _ptr(h), _pitch(h) if h is not None else 0,
+                                         M, K, N, r, A.data_ptr(), B.data_ptr(), float(scale), _ptr(dx), _pitch(dx) if dx is not None else 0,
+                                         _ptr(gelu_u), _pitch(gelu_u) if gelu_u is not None else 0, _ptr(gA), _ptr(gB), 1 if accumulate else 0,
+                                         workspace.data_ptr()), "mmbert_lora_dense_bwd")
+    return dx
+
+
 # the per-launch wrappers as defined here: model.py takes the composite path only while nobody has wrapped them (bench.py's per-launch
 # event timing, tests that spy on launches)
 _UNWRAPPED = dict(gemm_nt=gemm_nt, attn_fwd=attn_fwd, attn_fwd_first=attn_fwd_first, attn_probs_first=attn_probs_first, attn_bwd=attn_bwd, ln_fwd=ln_fwd, ln_bwd=ln_bwd,
-                  lora_qkv_fwd=lora_qkv_fwd, lora_qkv_bwd=lora_qkv_bwd)
+                  lora_qkv_fwd=lora_qkv_fwd, lora_qkv_bwd=lora_qkv_bwd, lora_dense_fwd=lora_dense_fwd, lora_dense_bwd=lora_dense_bwd)
 
 
 def launches_unwrapped() -> bool:

@@ -312,7 +312,8 @@ def apply_freeze(model, args):
 
 def apply_lora(model, args):
     """``model.add_lora`` from the optional ``args.lora_rank`` (4, 8 or 16), ``args.lora_alpha`` (default 2 x rank), ``args.lora_targets``
-    (default query + value), ``args.lora_layers`` (default all), ``args.lora_freeze_base`` (default True) and ``args.lora_seed``.
+    (default query + value; any of query / key / value / attention_output / intermediate / ffn_output, or "all-linear"),
+    ``args.lora_layers`` (default all), ``args.lora_freeze_base`` (default True) and ``args.lora_seed``.
     ``default_args()`` has none of them: without ``lora_rank`` (or with None) nothing happens.  Call it before the optimizer is built
     (``build_optimizer`` does, for a model that has no adapters yet).  Returns whether adapters were added."""
     r = getattr(args, "lora_rank", None)
