@@ -111,11 +111,34 @@ def lora_script(L, seed0=1100):
     return _seeded(items, seed0)
 
 
+def dense_lora_script(L, seed0=1300):
+    """Adapters on the dense seams over a model's life (attention.output.dense, intermediate.dense, output.dense: DESIGN 3.15): rank 8 on all
+    six targets of every layer over a frozen base behind a step -- two micro-batches onto the adapter gradients, the one-sample batch (dense
+    top-layer backward, saved h slices), the largest batch, ``predict`` / ``predict_tokens`` / ``predict_attention`` / ``eval`` / the EMA swap
+    while they are live --, saved / removed / loaded again, merged (the FFN-up GEMM gets its GELU epilogue back; no encoder layer is
+    trainable), everything trainable again; rank 4 on the key projection of layer 0 alone (no dense target), removed; rank 16 on
+    intermediate + ffn_output of the top layer alone over a trainable base (a layer with dense adapters and no Q/K/V ones, next to layers
+    on the composite path), ``predict`` through the [CLS]-only top layer on its gathered rows, removed."""
+    a, b, c, d, e, f, g, h = (MAIN_SHAPES[k] for k in (0, 1, 2, 4, 5, 6, 7, 9))
+    items = [("train", a), _mut("add_lora", r=8, alpha=16.0, targets="all-linear", freeze_base=True, seed=81), ("accumulate", b), ("train", f, DENSE_TOP_SEEDS[0]),
+             ("predict", e), ("predict_tokens", c), ("train", d), ("predict_attention", c), _mut("reload_lora"), ("train", e), ("ema_eval", a), ("eval", b),
+             _mut("merge_lora"), ("train", g), _mut("unfreeze"), _mut("add_lora", r=4, alpha=8.0, targets=("key",), layers=[0], freeze_base=False, seed=82),
+             ("train", h), _mut("remove_lora"),
+             _mut("add_lora", r=16, alpha=16.0, targets=("intermediate", "ffn_output"), layers=[L - 1], freeze_base=False, seed=83), ("train", a), ("predict", c),
+             _mut("remove_lora"), ("train", c)]
+    return _seeded(items, seed0)
+
+
 # ------------------------------------------------------------------------------------------------ what the names alone say
 LORA_BASE = ("bert.embeddings.", "bert.jointEmbeddings.", "bert.encoder.")          # what add_lora(freeze_base=True) freezes
 LIFECYCLE = ("stop_rises", "stop_is_top_layer_without_input_gradient", "bias_only_layer", "frozen_layer_between_trainable_ones",
              "unfreeze_behind_steps", "unfreeze_without_a_step_since_the_freeze", "no_encoder_layer_trainable", "adapters_on_frozen_base", "adapters_on_trainable_base",
-             "adapters_on_a_subset_of_layers", "rank_changes", "targets_change", "merge", "remove", "reload")
+             "adapters_on_a_subset_of_layers", "rank_changes", "targets_change", "merge", "remove", "reload",
+             # the dense seams: a training item with a dense target adapted / with ``intermediate`` adapted (the FFN-up GEMM loses its GELU
+             # epilogue to the adapter launch) / with adapted layers that have no Q/K/V adapters
+             "dense_targets", "ffn_up_adapter", "dense_only_layer")
+LORA_QKV = ("query", "key", "value")
+LORA_DENSE_PATHS = {"attention_output": "attention.output.dense", "intermediate": "intermediate.dense", "ffn_output": "output.dense"}
 
 
 def misplaced_mutations(script):
@@ -137,10 +160,19 @@ def base_frozen(flags):
 
 
 def _lora_record(options, L):
+    """model._lora behind ``add_lora(**options)``: the targets (any of the six names, or "all-linear") in ops.lora_split_targets' canonical
+    order, Q/K/V first."""
+    from msa_amd import ops
     layers = options.get("layers")
-    return dict(r=options.get("r", 8), alpha=float(options.get("alpha", 16.0)),
-                targets=tuple(t for t in ("query", "key", "value") if t in options.get("targets", ("query", "value"))),
+    qkv, dense = ops.lora_split_targets(options.get("targets", ("query", "value")))
+    assert qkv == tuple(t for t in LORA_QKV if t in qkv) and dense == tuple(t for t in LORA_DENSE_PATHS if t in dense)
+    return dict(r=options.get("r", 8), alpha=float(options.get("alpha", 16.0)), targets=qkv + dense,
                 layers=tuple(range(L)) if layers is None else tuple(sorted(layers)))
+
+
+def lora_module_path(target):
+    """The module below an encoder layer that carries a target's ``lora_A`` / ``lora_B``."""
+    return "attention.self." + target if target in LORA_QKV else LORA_DENSE_PATHS[target]
 
 
 def _with_adapters(flags, rec, freeze_base):
@@ -148,7 +180,7 @@ def _with_adapters(flags, rec, freeze_base):
     for i in rec["layers"]:
         for t in rec["targets"]:
             for m in ("lora_A", "lora_B"):
-                out[f"bert.encoder.layer.{i}.attention.self.{t}.{m}"] = True
+                out[f"bert.encoder.layer.{i}.{lora_module_path(t)}.{m}"] = True
     if freeze_base:
         for n in out:
             if n.startswith(LORA_BASE) and ".lora_" not in n:
@@ -227,6 +259,13 @@ def lifecycle_facts(script, names, L):
                 out["adapters_on_frozen_base" if base_frozen(flags) else "adapters_on_trainable_base"].append(i)
                 if lora["layers"] != tuple(range(L)):
                     out["adapters_on_a_subset_of_layers"].append(i)
+                dense = [t for t in lora["targets"] if t in LORA_DENSE_PATHS]
+                if dense:
+                    out["dense_targets"].append(i)
+                    if "intermediate" in dense:
+                        out["ffn_up_adapter"].append(i)
+                    if not any(t in LORA_QKV for t in lora["targets"]):
+                        out["dense_only_layer"].append(i)
             steps += kind == "train"
         elif kind == "unfreeze" and steps:
             out["unfreeze_behind_steps"].append(i)

@@ -24,6 +24,8 @@ outputs by THAT reference's ``check`` -- no tolerance of its own:
     gather_rows / scatter_rows_zero / attn_q_limit                     exact (layout_ref.scatter_ref for the stamped inverse)
     gelu_bwd                                                           ``gelu_bwd_ref`` below
     lora_qkv_fwd / lora_qkv_bwd (dict operands, h row slices, dres=None) lora_ref.fwd / bwd, judged by lora_ref.check
+    lora_dense_fwd / lora_dense_bwd (ADD with the GEMM's triple, GELU + aux,   lora_dense_ref.fwd / bwd, judged by lora_dense_ref.check
+        dx in place, gelu_u, h row slices, h=None on gathered rows)
     colsum_grouped (per-problem accumulate flags)                      colsum_ref: M 2^-24 sum|x| + 2^-23 |ref|
 
 Dropout keep masks are rebuilt from the (stream, thr16, scale) triple recorded IN the call, through ``ops.dropout_mask`` /
@@ -47,11 +49,20 @@ bf16 rounding of the output; judged by ``gemm_ref.check``.  Its emulation (fp32 
     of the sparse top layer agree with each other; ``kv_len`` is the count the recorded key bias implies;
  4. every ``W*T`` operand is the transpose of the bf16 working copy the forward read, and that copy is the parameter rounded to bf16;
  5. forward and backward of a dropout site carry the same triple, two different sites different streams;
- 6. every gradient buffer a stage wrote is the view named for that stage, at the address of the parameter's ``.grad``.
+ 6. every gradient buffer a stage wrote is the view named for that stage, at the address of the parameter's ``.grad``;
+ 7. ``check_dense_adapter_wiring``: every dense-seam adapter launch against its neighbours -- forward, its ``x`` / ``y`` are the ``A`` operand
+    and the output of the GEMM directly in front, which carried the residual and the SAME dropout triple (ADD mode) or neither GELU nor
+    ``aux`` (GELU mode: the adapter's ``aux`` is what the layer's ``du`` stage reads as ``gelu_bwd_u``); backward, ``dx`` / ``dy`` / ``gelu_u``
+    are the output, the ``A`` operand and the ``gelu_bwd_u`` of the GEMM directly in front, ``x`` the layer's forward activation, ``h`` a
+    leading-row view of the forward adapter's ``h_out`` (None exactly on gathered rows), ``accumulate is True`` and ``gA`` / ``gB`` the
+    ``.grad`` views of the adapter's parameters.  (Check 5 counts an ADD-mode adapter launch to its GEMM's site: ``lora_z1`` -> ``z1``,
+    ``lora_z2`` -> ``z2``; recomputing the launch from its own recorded triple would pass with any triple.)
 
 A step under a freeze.TrainablePlan and / or with adapters is judged by ``check_dataflow_frozen``: the frozen form of check 1 (forward all
 L layers, backward L-1 .. ``stop``, no ``dx`` stage where backward ends without an embedding stage, ``lora_fwd`` directly behind ``qkv`` and
-``lora_bwd`` directly behind ``attn_bwd`` on adapter layers), checks 2, 4, 5 and ``kv_len`` unchanged, and one more exact check,
+``lora_bwd`` directly behind ``attn_bwd`` on adapter layers, the dense targets' stages ``lora_z1`` / ``lora_g`` / ``lora_z2`` directly behind
+``z1`` / ``g`` / ``z2`` and ``lora_du`` / ``lora_dy1`` / ``lora_dctx`` directly behind ``du`` / ``dy1`` / ``dctx``), checks 2, 4, 5, 7 and ``kv_len``
+unchanged, and one more exact check,
 ``check_frozen_writes``: no recorded call writes into the part of the flat gradient buffer that belongs to a frozen parameter, and the
 weight-gradient problems written are exactly the weights whose mode is "full", the MLM transform and -- iff ``word_table`` -- the tied
 table.  Checks 3 and 6 (``_wiring``, ``check_grad_views``) assume a full backward and are not extended to it.
@@ -74,21 +85,23 @@ from tests import colsum_ref as CS
 from tests import embed_ref as E
 from tests import gemm_ref as G
 from tests import layout_ref as LR
+from tests import lora_dense_ref as DR
 from tests import lora_ref as LO
 from tests import rowwise_ref as R
 
 SPIED = ("gemm_nt", "gemm_nt_splitk", "gemm_tn", "gemm_tn_grouped", "attn_fwd", "attn_bwd", "attn_q_limit", "ln_fwd", "ln_bwd", "gelu_bwd",
          "embed_gather", "embed_scatter", "pair_proj_fwd", "pair_proj_bwd", "ce_fwd", "ce_bwd", "gather_rows", "scatter_rows_zero",
-         "lora_qkv_fwd", "lora_qkv_bwd", "colsum_grouped")
+         "lora_qkv_fwd", "lora_qkv_bwd", "lora_dense_fwd", "lora_dense_bwd", "colsum_grouped")
 # operands an op writes (cloned again after the call); ACCUMULATES: of those, the ones whose previous value the op reads
 WRITES = {"gemm_nt": ("out", "aux"), "gemm_nt_splitk": ("out",), "gemm_tn": ("W", "bias_out"), "gemm_tn_grouped": ("problems",),
           "attn_fwd": ("ctx", "lse"), "attn_bwd": ("dqkv",), "ln_fwd": ("out", "stats"), "ln_bwd": ("dx", "dx2", "dgamma", "dbeta", "dbias2"),
           "gelu_bwd": ("du",), "embed_gather": ("out",), "embed_scatter": ("gword", "gtype", "gpos"), "pair_proj_fwd": ("out",),
           "pair_proj_bwd": ("dW", "db"), "ce_bwd": ("dlogits",), "lora_qkv_fwd": ("qkv", "h_out"), "lora_qkv_bwd": ("gA", "gB"),
-          "colsum_grouped": ("problems",)}
+          "lora_dense_fwd": ("y", "aux", "h_out"), "lora_dense_bwd": ("dx", "gA", "gB"), "colsum_grouped": ("problems",)}
 ACCUMULATES = {"gemm_tn": ("bias_out",), "embed_scatter": ("gword", "gtype", "gpos"), "pair_proj_bwd": ("dW", "db"), "pair_proj_fwd": ("out",),
                "ln_fwd": ("out",),          # (the last two write some rows of a larger matrix: the others keep their values)
-               "lora_qkv_fwd": ("qkv",), "lora_qkv_bwd": ("gA", "gB")}    # (colsum_grouped: per problem, like gemm_tn_grouped)
+               "lora_qkv_fwd": ("qkv",), "lora_qkv_bwd": ("gA", "gB"),    # (colsum_grouped: per problem, like gemm_tn_grouped)
+               "lora_dense_fwd": ("y",), "lora_dense_bwd": ("dx", "gA", "gB")}    # (gA / gB of both adapter backwards: when ``accumulate``)
 
 # ---- the op sequence of the trunk (check 1): stage names, see ``_stage``
 FWD_LAYER = ("qkv", "attn_fwd", "z1", "ln1", "g", "z2", "ln2")                                  # model._EncoderFn.run_forward, per-launch body
@@ -100,6 +113,10 @@ BWD_TOP_SPARSE = (                                                              
 # gather of 6 is not part of the trunk)
 _NT_STAGE = {"Wqkv": "qkv", "Wo": "z1", "W1": "g", "W2": "z2", "W2T": "du", "W1T": "dy1", "WoT": "dctx", "WqkvT": "dx",
              "Wt": "mlm_t0", "word_h": "logits", "wordT": "mlm_dt", "WtT": "mlm_dy"}
+# the dense-seam adapter launches: target -> stage (forward: directly behind the GEMM stage z1 / g / z2, backward: behind du / dy1 / dctx)
+DENSE_FWD_STAGE = {"attention_output": "lora_z1", "intermediate": "lora_g", "ffn_output": "lora_z2"}
+DENSE_BWD_STAGE = {"ffn_output": "lora_du", "intermediate": "lora_dy1", "attention_output": "lora_dctx"}
+_QKV_TARGETS = ("query", "key", "value")
 _LN_STAGE = {"ln1_g": "ln1", "ln2_g": "ln2", "emb_ln_g": "emb_ln", "joint_ln_g": "joint_ln", "mlm_ln_g": "mlm_ln"}
 _TRANSPOSED = {"W2T": "W2", "W1T": "W1", "WoT": "Wo", "WqkvT": "Wqkv", "WtT": "Wt", "wordT": "word_h"}
 _PARAM_OF = {"Wqkv": "attention.self.query.weight", "Wo": "attention.output.dense.weight", "W1": "intermediate.dense.weight",
@@ -656,6 +673,42 @@ def _r_lora_bwd(c):
     return res
 
 
+def _r_lora_dense_fwd(c):
+    """ops.lora_dense_fwd against tests/lora_dense_ref.fwd on the y the call FOUND (what the projection's GEMM left): the updated y --
+    in ADD mode the elements the recorded triple drops bit for bit (the reference builds its own keep mask from it) --, aux and h_out
+    where they were handed in."""
+    a = c.a
+    drop = a.get("drop")
+    ref = DR.fwd(_c(a["x"]), _c(a["y"]), _c(a["A"]), _c(a["B"]), a["scale"], int(a["mode"]), drop=None if drop is None else tuple(drop))
+    res = [("y", DR.check(_c(c.post["y"]), ref["y"], "lora_dense_fwd y"))]
+    if a["aux"] is not None:
+        if int(a["mode"]) != DR.GELU:
+            raise NotImplementedError("lora_dense_fwd: aux outside the GELU mode")
+        res.append(("aux", DR.check(_c(c.post["aux"]), ref["aux"], "lora_dense_fwd aux")))
+    if a["h_out"] is not None:
+        res.append(("h", DR.check(_c(c.post["h_out"]), ref["h"], "lora_dense_fwd h")))
+    return res
+
+
+def _r_lora_dense_bwd(c):
+    """ops.lora_dense_bwd against tests/lora_dense_ref.bwd: dx on the dx the call found, gA / gB from the values found there (from zeros
+    when ``accumulate`` is false); ``h=None`` (the gathered rows of the sparse top layer): the reference recomputes h from x and A."""
+    a = c.a
+    if a.get("workspace") is not None:
+        raise NotImplementedError("lora_dense_bwd: a caller's workspace")
+    ref = DR.bwd(_c(a["dy"]), _c(a["x"]), _c(a["h"]), _c(a["A"]), _c(a["B"]), a["scale"], dx=_c(a["dx"]), gelu_u=_c(a["gelu_u"]),
+                 gA0=_c(a["gA"]), gB0=_c(a["gB"]), accumulate=bool(a["accumulate"]))
+    res = []
+    for key, k in (("gA", "dA"), ("gB", "dB")):
+        if a[key] is not None:
+            res.append((k, DR.check(_c(c.post[key]), ref[k], f"lora_dense_bwd {k}")))
+    if a["dx"] is not None:
+        res.append(("dx", DR.check(_c(c.post["dx"]), ref["dx"], "lora_dense_bwd dx")))
+    else:
+        assert c.ret is None, "lora_dense_bwd returned a tensor without dx"
+    return res
+
+
 def colsum_flags(c):
     acc, n = c.a["accumulate"], len(c.a["problems"])
     return [bool(x) for x in acc] if isinstance(acc, (list, tuple)) else [bool(acc)] * n
@@ -681,7 +734,8 @@ ADAPTERS = {"gemm_nt": _r_gemm_nt, "gemm_nt_splitk": _r_splitk, "gemm_tn": _r_ge
             "attn_bwd": _r_attn_bwd, "attn_q_limit": _r_q_limit, "ln_fwd": _r_ln_fwd, "ln_bwd": _r_ln_bwd, "ln_bwd_reduce": _r_ln_reduce,
             "gelu_bwd": _r_gelu_bwd, "ce_fwd": _r_ce_fwd, "ce_bwd": _r_ce_bwd, "embed_gather": _r_embed_gather, "embed_scatter": _r_embed_scatter,
             "pair_proj_fwd": _r_pair_fwd, "pair_proj_bwd": _r_pair_bwd, "gather_rows": _r_gather_rows, "scatter_rows_zero": _r_scatter_rows,
-            "lora_qkv_fwd": _r_lora_fwd, "lora_qkv_bwd": _r_lora_bwd, "colsum_grouped": _r_colsum}
+            "lora_qkv_fwd": _r_lora_fwd, "lora_qkv_bwd": _r_lora_bwd, "lora_dense_fwd": _r_lora_dense_fwd, "lora_dense_bwd": _r_lora_dense_bwd,
+            "colsum_grouped": _r_colsum}
 
 
 def recompute(call):
@@ -716,6 +770,10 @@ def names_of(model):
         for k, v in lw.items():
             if torch.is_tensor(v):
                 out.setdefault(v.data_ptr(), []).append(f"l{i}.{k}")
+        dl = lw.get("lora_dense")                                # the dense-seam adapters: "l3.dense:A:ffn_output", ...
+        for k in ("A", "B", "gA", "gB") if dl else ():
+            for t, v in dl[k].items():
+                out.setdefault(v.data_ptr(), []).append(f"l{i}.dense:{k}:{t}")
     for k, v in model._w.items():
         if torch.is_tensor(v):
             out.setdefault(v.data_ptr(), []).append(k)
@@ -734,6 +792,13 @@ def _stage(c, names, qkv_layer, dqkv_layer=None):
     """(stage name, layer or None) of a call, from the weight / gamma operand it carries (the adapter launches: from the qkv / dqkv
     matrix they work on)."""
     op = c.op
+    if op in ("lora_dense_fwd", "lora_dense_bwd"):               # (layer and target from the A operand's address)
+        n = next((n for n in names.get(c.a["A"].ptr, []) if ".dense:A:" in n), None)
+        if n is None:
+            return op, None
+        t = n.rsplit(":", 1)[1]
+        c.meta["target"] = t
+        return (DENSE_FWD_STAGE if op == "lora_dense_fwd" else DENSE_BWD_STAGE)[t], int(n.split(".", 1)[0][1:])
     if op == "lora_qkv_fwd":
         return "lora_fwd", qkv_layer.get(c.a["qkv"].region())
     if op == "lora_qkv_bwd":
@@ -780,15 +845,52 @@ def _with(form, behind, stage, drop=None):
     return tuple(out)
 
 
-def check_sequence(calls, L, stop=0, no_dx=False, lora_layers=()):
+def adapter_stages(lora):
+    """{layer: (has Q/K/V adapters, the dense targets it has)} of an adapter record (model._lora: "targets", "layers"); a bare collection of
+    layer indices stands for Q/K/V adapters on those layers (the older form of the argument)."""
+    if not lora:
+        return {}
+    if isinstance(lora, dict):
+        layers, targets = tuple(lora["layers"]), tuple(lora["targets"])
+    else:
+        layers, targets = tuple(lora), _QKV_TARGETS[:1]
+    qkv = any(t in _QKV_TARGETS for t in targets)
+    return {l: (qkv, tuple(t for t in DENSE_FWD_STAGE if t in targets)) for l in layers}
+
+
+def _fwd_form(ad):
+    f = FWD_LAYER
+    if ad is not None:
+        if ad[0]:
+            f = _with(f, "qkv", "lora_fwd")
+        for t in ad[1]:
+            f = _with(f, DENSE_FWD_STAGE[t][len("lora_"):], DENSE_FWD_STAGE[t])
+    return f
+
+
+def _bwd_form(f, ad):
+    if ad is not None:
+        if ad[0]:
+            f = _with(f, "attn_bwd", "lora_bwd")
+        for t in ad[1]:
+            f = _with(f, DENSE_BWD_STAGE[t][len("lora_"):], DENSE_BWD_STAGE[t])
+    return f
+
+
+def check_sequence(calls, L, stop=0, no_dx=False, lora=(), backward=True, lora_layers=None):
     """Check 1: the trunk's stages in issue order are, per forward pass, FWD_LAYER for layers 0 .. L-1 and, per backward pass, for
     layers L-1 .. ``stop``, BWD_DENSE or (top layer only) one of BWD_TOP_SPARSE.  The frozen form (freeze.TrainablePlan): forward runs all
     L layers, backward the layers L-1 .. ``stop`` (none when ``stop >= L``), and with ``no_dx`` (the embedding stage does not run) layer
-    ``stop`` has no ``dx`` stage.  On the layers of ``lora_layers`` ``lora_fwd`` sits directly behind ``qkv`` and ``lora_bwd`` directly
-    behind ``attn_bwd``."""
+    ``stop`` has no ``dx`` stage.  ``lora``: the adapter record (``adapter_stages``; a bare collection of layers: Q/K/V adapters there).  On
+    its layers ``lora_fwd`` sits directly behind ``qkv`` and ``lora_bwd`` directly behind ``attn_bwd`` (Q/K/V targets), and each dense
+    target's stage directly behind its GEMM's: ``lora_z1`` / ``lora_g`` / ``lora_z2`` behind ``z1`` / ``g`` / ``z2``, ``lora_du`` / ``lora_dy1``
+    / ``lora_dctx`` behind ``du`` / ``dy1`` / ``dctx`` -- in BWD_DENSE and in both BWD_TOP_SPARSE forms.  ``backward`` False (a forward
+    under ``no_grad``): no backward stage at all.  ``lora_layers``: the older name of ``lora``."""
+    if lora_layers is not None:
+        lora = lora_layers
     helpers = ("gather_rows8", "gather_rows1", "scatter_rows_zero", "attn_q_limit")
-    if stop or no_dx or lora_layers:
-        return _check_sequence_frozen(calls, L, stop, no_dx, set(lora_layers), helpers)
+    if stop or no_dx or lora or not backward:
+        return _check_sequence_frozen(calls, L, stop, no_dx, adapter_stages(lora), helpers, backward)
     trunk = [c for c in calls if c.meta["layer"] is not None or c.meta["stage"] in helpers]
     seq = [(c.meta["stage"], c.meta["layer"]) for c in trunk]
     i, passes = 0, {"fwd": 0, "bwd": 0}
@@ -815,26 +917,27 @@ def check_sequence(calls, L, stop=0, no_dx=False, lora_layers=()):
     return passes
 
 
-def _check_sequence_frozen(calls, L, stop, no_dx, lora_layers, helpers):
+def _check_sequence_frozen(calls, L, stop, no_dx, adapters, helpers, backward=True):
     trunk = [c for c in calls if c.meta["layer"] is not None or c.meta["stage"] in helpers]
     assert not any(c.meta["stage"] in ("lora_fwd", "lora_bwd") and c.meta["layer"] is None for c in calls), "an adapter launch on no layer's qkv / dqkv"
+    assert not any(c.op in ("lora_dense_fwd", "lora_dense_bwd") and c.meta["layer"] is None for c in calls), "a dense adapter launch on no layer's adapter"
     seq = [(c.meta["stage"], c.meta["layer"]) for c in trunk]
     i, passes = 0, {"fwd": 0, "bwd": 0}
     strip = lambda part: [s for s, _ in part]                    # noqa: E731
     while i < len(seq):
         if seq[i] == ("qkv", 0):
             for l in range(L):
-                f = _with(FWD_LAYER, "qkv", "lora_fwd") if l in lora_layers else FWD_LAYER
+                f = _fwd_form(adapters.get(l))
                 part = seq[i:i + len(f)]
-                assert strip(part) == list(f) and all(x[1] == l for x in part), f"forward of layer {l}: {part}"
+                assert strip(part) == list(f) and all(x[1] == l for x in part), f"forward of layer {l}: {part} is not {f}"
                 i += len(f)
             passes["fwd"] += 1
             continue
+        assert backward, f"a forward pass without backward, yet the trunk ran {seq[i:i + 5]} behind it"
         assert stop < L, f"no encoder layer is trainable, yet the trunk ran {seq[i:i + 5]} behind its forward pass"
         for l in reversed(range(stop, L)):
             forms = [BWD_DENSE] + (list(BWD_TOP_SPARSE) if l == L - 1 else [])
-            if l in lora_layers:
-                forms = [_with(f, "attn_bwd", "lora_bwd") for f in forms]
+            forms = [_bwd_form(f, adapters.get(l)) for f in forms]
             if no_dx and l == stop:
                 forms = [_with(f, None, None, drop="dx") for f in forms]
             for f in forms:
@@ -843,9 +946,9 @@ def _check_sequence_frozen(calls, L, stop, no_dx, lora_layers, helpers):
                     i += len(f)
                     break
             else:
-                raise AssertionError(f"backward of layer {l}: {seq[i:i + 11]} is none of {forms}")
+                raise AssertionError(f"backward of layer {l}: {seq[i:i + 14]} is none of {forms}")
         passes["bwd"] += 1
-    assert passes["fwd"] >= 1 and passes["bwd"] == (passes["fwd"] if stop < L else 0), passes
+    assert passes["fwd"] >= 1 and passes["bwd"] == (passes["fwd"] if stop < L and backward else 0), passes
     return passes
 
 
@@ -900,7 +1003,7 @@ def check_producers(calls, cls_rows=None):
                     if acc:
                         sh.read(p[1], f"call {c.index} ({c.op}) problem {j} output (accumulated onto)")
                 continue
-            if c.op == "lora_qkv_bwd" and k in ("gA", "gB") and not c.a["accumulate"]:
+            if c.op in ("lora_qkv_bwd", "lora_dense_bwd") and k in ("gA", "gB") and not c.a["accumulate"]:
                 continue
             if c.op == "gemm_tn" and k == "W" and not c.a["accumulate"]:
                 continue
@@ -1066,7 +1169,7 @@ def check_dropout_sites(calls):
     site = {}
     for c in calls:
         st, l = c.meta["stage"], c.meta["layer"]
-        for k, key in (("drop", st), ("pre_drop", {"ln2_bwd": "z2", "ln1_bwd": "z1"}.get(st)), ("post_drop", {"emb_ln_bwd": "emb_ln", "joint_ln_bwd": "joint_ln"}.get(st))):
+        for k, key in (("drop", {"lora_z1": "z1", "lora_z2": "z2"}.get(st, st)), ("pre_drop", {"ln2_bwd": "z2", "ln1_bwd": "z1"}.get(st)), ("post_drop", {"emb_ln_bwd": "emb_ln", "joint_ln_bwd": "joint_ln"}.get(st))):
             d = c.a.get(k)
             if not _on(d) or key is None:
                 continue
@@ -1130,6 +1233,93 @@ def check_grad_views(calls, names, model):
             assert g is not None and g.data_ptr() == model._w["g_" + k].data_ptr(), f"g_{k} is not the .grad of {pn}"
 
 
+def _drop_of(d):
+    return None if d is None else tuple(d)
+
+
+def check_dense_adapter_wiring(calls, model):
+    """Exact: every dense-seam adapter launch (``lora_dense_fwd`` / ``lora_dense_bwd``) against its neighbours -- the GEMM directly in
+    front, the same layer's forward stages, the layer's adapter views -- and nothing else, so it holds for the full and the frozen form
+    of a step (the calls are annotated).  Forward: ``x`` is the region of that GEMM's ``A`` operand, ``y`` the region it returned; ADD
+    mode: the GEMM carried ``resid`` and the same ``drop``, ``aux is None``; GELU mode: the GEMM carried no ``gelu``, ``aux``, ``resid`` or
+    ``drop``, and where the same layer's ``du`` stage runs later, the adapter was handed an ``aux`` and it is the region that stage reads as
+    ``gelu_bwd_u`` (through the gather on the sparse top layer).  Backward: ``dx`` is what the GEMM in front returned, ``dy`` its ``A`` operand, ``gelu_u`` its ``gelu_bwd_u`` for
+    ``lora_du`` and None for the other two; ``x`` is the layer's forward ``g`` output / ``ln1`` output / attention context (or a gather of
+    it); ``h`` a leading-row view of what the layer's forward adapter wrote to ``h_out`` -- None exactly on the gathered path;
+    ``accumulate is True``; ``gA`` / ``gB`` sit at ``model._lw[l]["lora_dense"]["gA" / "gB"][t]``, the ``.grad`` of the adapter's parameters
+    (check 6 for the adapters), and are left out exactly for a parameter that takes no gradient.  Returns the number of launches checked."""
+    fwd, fad, aux_of, gathered, n = {}, {}, {}, {}, 0
+    root = lambda r: gathered[r.region()] if r is not None and r.region() in gathered else r      # noqa: E731
+    for i, c in enumerate(calls):
+        st, l = c.meta.get("stage"), c.meta.get("layer")
+        if c.op == "gather_rows":
+            for s, o in zip(c.a["srcs"], c.ret):
+                gathered[o.region()] = s
+        if l is not None and st in FWD_LAYER:
+            if st == "qkv":
+                fwd[l], fad[l] = {}, {}
+                aux_of.pop(l, None)
+            fwd.setdefault(l, {})[st] = c
+        if st == "du" and "intermediate" in fad.get(l, {}):      # (the GEMM in front of that adapter wrote no aux: the adapter must have)
+            assert l in aux_of, f"layer {l} du: backward reads a pre-activation, yet the layer's intermediate adapter was handed no aux to write"
+            _same(root(c.a["gelu_bwd_u"]), aux_of[l], f"layer {l} du: gelu_bwd_u = the aux the layer's intermediate adapter wrote")
+        if c.op not in ("lora_dense_fwd", "lora_dense_bwd"):
+            continue
+        assert l is not None, f"call {c.index} ({c.op}): A is no dense adapter of the model"
+        t, w = c.meta["target"], f"call {c.index} (layer {l} {st})"
+        g = calls[i - 1] if i else None
+        n += 1
+        if c.op == "lora_dense_fwd":
+            assert g is not None and g.op == "gemm_nt" and (g.meta["stage"], g.meta["layer"]) == (st[len("lora_"):], l), w + ": not directly behind its projection's GEMM"
+            _same(c.a["x"], g.a["A"], w + " x = the GEMM's A operand")
+            _same(c.a["y"], g.ret, w + " y = what the GEMM returned")
+            if int(c.a["mode"]) == DR.ADD:
+                assert st in ("lora_z1", "lora_z2"), w + ": ADD mode on the FFN-up seam"
+                assert g.a["resid"] is not None, w + ": the GEMM in front carried no residual"
+                assert _drop_of(g.a["drop"]) == _drop_of(c.a["drop"]), w + f": drop {_drop_of(c.a['drop'])} is not the GEMM's {_drop_of(g.a['drop'])}"
+                assert c.a["aux"] is None, w + ": aux in ADD mode"
+            else:
+                assert st == "lora_g", w + ": GELU mode outside the FFN-up seam"
+                assert not g.a["gelu"] and g.a["aux"] is None and g.a["resid"] is None and not _on(g.a["drop"]) and not _on(c.a["drop"]), \
+                    w + ": the GEMM in front of a GELU-mode adapter carried gelu / aux / resid / drop"
+                if c.a["aux"] is not None:
+                    aux_of[l] = c.a["aux"]
+            fad.setdefault(l, {})[t] = c
+            continue
+        assert g is not None and g.op in ("gemm_nt", "gemm_nt_splitk") and (g.meta["stage"], g.meta["layer"]) == (st[len("lora_"):], l), \
+            w + ": not directly behind its input-gradient GEMM"
+        _same(c.a["dx"], g.ret, w + " dx = what the GEMM returned")
+        _same(c.a["dy"], g.a["A"], w + " dy = the GEMM's A operand")
+        if st == "lora_du":
+            _same(c.a["gelu_u"], g.a["gelu_bwd_u"], w + " gelu_u = the GEMM's gelu_bwd_u")
+        else:
+            assert c.a["gelu_u"] is None, w + ": gelu_u outside the FFN-down seam"
+        f = fwd.get(l, {})
+        want = {"lora_du": lambda: f["g"].ret, "lora_dy1": lambda: f["ln1"].ret[0], "lora_dctx": lambda: f["attn_fwd"].ret[0]}[st]()
+        _same(root(c.a["x"]), want, w + " x = the layer's forward " + {"lora_du": "g", "lora_dy1": "ln1 output", "lora_dctx": "attention context"}[st])
+        on_gather = c.a["x"].region() in gathered
+        assert (c.a["h"] is None) == on_gather, w + (": h handed in with gathered operands" if on_gather else ": h = None on full rows")
+        if not on_gather:
+            ho = fad.get(l, {}).get(t)
+            assert ho is not None and ho.a["h_out"] is not None, w + ": the layer's forward adapter kept no h"
+            _same(c.a["h"], ho.a["h_out"], w + " h = what the layer's forward adapter wrote")
+            assert c.a["h"].shape[0] <= ho.a["h_out"].shape[0] and c.a["h"].shape[0] == c.a["dy"].shape[0], w + ": h is no leading-row view of h_out"
+        assert c.a["accumulate"] is True, w + ": accumulate is not True"
+        dl = model._lw[l].get("lora_dense")
+        assert dl is not None and t in dl["targets"], w + ": the layer has no such adapter"
+        for k, pk in (("gA", "pA"), ("gB", "pB")):
+            p = dl.get(pk, {}).get(t)
+            if p is not None:
+                assert (c.a[k] is not None) == bool(p.requires_grad), w + f": {k} handed in = {c.a[k] is not None}, requires_grad = {bool(p.requires_grad)}"
+            if c.a[k] is None:
+                continue
+            v = dl[k][t]
+            assert c.a[k].ptr == v.data_ptr() and c.a[k].shape == tuple(v.shape), w + f": {k} is not the layer's gradient view of the adapter"
+            if p is not None:
+                assert p.grad is not None and p.grad.data_ptr() == v.data_ptr(), w + f": {k} is not the .grad of its parameter"
+    return n
+
+
 def check_dataflow(calls, model):
     """All six checks of the module docstring; returns (forward / backward passes seen, dropout sites seen)."""
     names = annotate(calls, model)
@@ -1147,6 +1337,7 @@ def check_dataflow(calls, model):
     check_transposes(calls, names, model)
     sites = check_dropout_sites(calls)
     check_grad_views(calls, names, model)
+    check_dense_adapter_wiring(calls, model)
     return passes, sites
 
 
@@ -1170,12 +1361,13 @@ def _extent(r: Rec):
     return r.off, r.off + sum((n - 1) * st for n, st in zip(r.shape, r.stride)) + 1
 
 
-def check_frozen_writes(calls, names, plan, L, grads, offset, numel):
+def check_frozen_writes(calls, names, plan, L, grads, offset, numel, backward=True):
     """Exact: no recorded call writes into the part of the flat gradient buffer ``grads`` that belongs to a parameter the plan has
     frozen -- every region a call wrote (``post``, ``ret``) inside that buffer lies in trainable spans or in the padding between
     parameters -- and the weight-gradient problems written are exactly ``expected_wgrad_problems``.  ``grads``: the buffer (its storage
-    address and size are all that is used; a ``Rec`` will do), ``offset`` / ``numel``: the storage's maps.  Returns the number of write
-    regions inside the buffer."""
+    address and size are all that is used; a ``Rec`` will do), ``offset`` / ``numel``: the storage's maps.  The adapters' gradients count like
+    any other write: ``gA`` / ``gB`` of ``lora_qkv_bwd`` and of ``lora_dense_bwd``.  ``backward`` False (a forward under ``no_grad``): no
+    weight-gradient problem at all.  Returns the number of write regions inside the buffer."""
     g = grads if isinstance(grads, Rec) else Rec(grads, False)
     frozen = sorted((offset[n], offset[n] + numel[n], n) for n in (plan.frozen if plan is not None else ()) if numel[n] > 0)
     inside = 0
@@ -1195,15 +1387,15 @@ def check_frozen_writes(calls, names, plan, L, grads, offset, numel):
                 n = _name(names, W, {"g_" + k for k in _MODE_KEY.values()} | {"g_Wt", "g_word_pad"})
                 assert n is not None, f"call {c.index} ({c.op}): a weight-gradient problem writes no gradient view of the model"
                 wrote.add(n)
-    want = expected_wgrad_problems(plan, L)
+    want = expected_wgrad_problems(plan, L) if backward else set()
     assert wrote == want, f"weight-gradient problems written: unexpected {sorted(wrote - want)}, missing {sorted(want - wrote)}"
     return inside
 
 
-def check_dataflow_frozen(calls, model, plan, lora=None):
+def check_dataflow_frozen(calls, model, plan, lora=None, backward=True):
     """The dataflow checks for a step under a freeze.TrainablePlan and / or adapters (``lora`` = model._lora): the frozen form of check 1,
-    checks 2 (``check_producers``), ``check_kv_len``, 4 (``check_transposes``) and 5 (``check_dropout_sites``) unchanged, and
-    ``check_frozen_writes``.  ``_wiring`` and ``check_grad_views`` (checks 3 and 6) assume a full backward and are NOT part of it.
+    checks 2 (``check_producers``), ``check_kv_len``, 4 (``check_transposes``) and 5 (``check_dropout_sites``) unchanged,
+    ``check_dense_adapter_wiring`` and ``check_frozen_writes``.  ``backward`` False: a forward under ``no_grad``, no backward stage may run.  ``_wiring`` and ``check_grad_views`` (checks 3 and 6) assume a full backward and are NOT part of it.
     Returns (passes, dropout sites, write regions inside the gradient buffer)."""
     names = annotate(calls, model)
     L = len(model._lw)
@@ -1213,14 +1405,15 @@ def check_dataflow_frozen(calls, model, plan, lora=None):
             n += 1
         c.meta["pass"] = n
     stop = 0 if plan is None else plan.stop
-    passes = check_sequence(calls, L, stop, plan is not None and not plan.embedding_stage, tuple(lora["layers"]) if lora else ())
+    passes = check_sequence(calls, L, stop, plan is not None and not plan.embedding_stage, lora or (), backward)
     lens = next((c.a["layout"].lens for c in calls if c.op == "attn_fwd"), None)
     check_producers(calls, None if lens is None else torch.tensor([0] + lens[:-1]).cumsum(0))
     check_kv_len(calls)
     check_transposes(calls, names, model)
     sites = check_dropout_sites(calls)
+    check_dense_adapter_wiring(calls, model)
     f = model._flat
-    return passes, sites, check_frozen_writes(calls, names, plan, L, f.grads, f.offset, f.numel)
+    return passes, sites, check_frozen_writes(calls, names, plan, L, f.grads, f.offset, f.numel, backward)
 
 
 def check_accumulation(calls, names):

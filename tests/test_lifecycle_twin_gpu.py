@@ -1,6 +1,9 @@
 """The fine-tuning lifecycle of ONE long-lived model against fresh twins (tests/session_twin.py), bit for bit: parameters frozen and
 released again, adapters added on one rank and later on another, saved and loaded, merged so that no encoder layer is trainable, removed
--- with the batch shape changing at every item and the inference paths in between (``ST.freeze_script`` / ``ST.lora_script``).
+-- with the batch shape changing at every item and the inference paths in between (``ST.freeze_script`` / ``ST.lora_script``); and the same
+with adapters on the dense seams (``ST.dense_lora_script``: all six targets behind steps, two micro-batches onto their gradients, reload,
+merge, another rank without dense targets, then dense adapters alone on the top layer next to composite-path layers, ``predict`` through
+the [CLS]-only top layer on gathered rows).
 
 Deterministic mode, ``torch.equal`` throughout; every batch item of every script is compared and the count is asserted.  Two
 configurations: F = tests/test_freeze_gpu.py's (hidden 128, four layers, the generic LayerNorm kernels) and B of
@@ -20,7 +23,7 @@ from tests.test_step_stages_gpu import CFG as _CFG_AB
 pytestmark = pytest.mark.gpu
 
 CFG = {"F": CFG_F, "B": _CFG_AB["B"]}
-SCRIPTS = {"freeze": ST.freeze_script, "lora": ST.lora_script}
+SCRIPTS = {"freeze": ST.freeze_script, "lora": ST.lora_script, "dense": ST.dense_lora_script}
 _LONG = {}
 
 
@@ -64,16 +67,20 @@ def _long(cfg, name):
         results, snaps = ST.play(s, script)
         assert ST.leftovers(s.model) == []
         trains = [it for it in script if it[0] == "train"]
-        assert len(s.moves) == len(trains) == {"freeze": 7, "lora": 7}[name]
+        assert len(s.moves) == len(trains) == {"freeze": 7, "lora": 7, "dense": 8}[name]
         for k, (moved, frozen_moved) in enumerate(s.moves):
             assert moved and not frozen_moved, (k, len(moved), frozen_moved[:3])
+        if name == "dense":                                            # every step under adapters moved an adapter: trains 1, 2, 3 (all six
+            for k in (1, 2, 3, 5, 6):                                  # targets), 5 (key), 6 (intermediate + ffn_output on the top layer)
+                assert any(".lora_" in n for n in s.moves[k][0]), (k, s.moves[k][0][:3])
+            assert any(".dense.lora_B" in n for n in s.moves[2][0]) and any("intermediate.dense.lora_B" in n for n in s.moves[6][0])
         assert [r is None for r in results] == [it[0] in ST.MUTATIONS for it in script]
         _LONG[key] = (script, results, snaps)
     return _LONG[key]
 
 
 # ---------------------------------------------------------------------------------------------- 1. each script x each configuration
-@pytest.mark.parametrize("name", ["freeze", "lora"])
+@pytest.mark.parametrize("name", ["freeze", "lora", "dense"])
 @pytest.mark.parametrize("cfg", ["F", "B"])
 def test_a_long_lived_model_equals_fresh_twins_over_its_fine_tuning_lifecycle(cfg, name):
     """Every batch item of the script on the long-lived model -- losses, scores, the gradient buffer (frozen spans masked on the clone),
@@ -82,11 +89,11 @@ def test_a_long_lived_model_equals_fresh_twins_over_its_fine_tuning_lifecycle(cf
     optimizer.  Behind a mutation other than ``freeze`` the snapshot holds an unbound optimizer (m / v / ema None)."""
     script, results, snaps = _long(cfg, name)
     n = len(_batch_items(script))
-    assert n == {"freeze": 14, "lora": 13}[name]
+    assert n == {"freeze": 14, "lora": 13, "dense": 15}[name]
     behind_rebuild = [i for i in snaps if i and script[i - 1][0] in ST.MUTATIONS and script[i - 1][0] != "freeze"]
     assert behind_rebuild and all(snaps[i]["opt"]["m"] is None and snaps[i]["opt"]["ema"] is None and snaps[i]["opt"]["steps"] == 0 for i in behind_rebuild)
     kept = [i for i in snaps if i and script[i - 1][0] == "freeze"]
-    assert all(snaps[i]["opt"]["m"] is not None and snaps[i]["opt"]["steps"] > 0 for i in kept) and (kept or name == "lora")
+    assert all(snaps[i]["opt"]["m"] is not None and snaps[i]["opt"]["steps"] > 0 for i in kept) and (kept or name in ("lora", "dense"))
     compared = ST.check_against_twins(results, snaps, script, CFG[cfg], build)
     assert compared == n
     # the scripts' top layers, from the batches: sparse and dense each under "backward ends at the top layer" / under adapters
@@ -95,15 +102,24 @@ def test_a_long_lived_model_equals_fresh_twins_over_its_fine_tuning_lifecycle(cf
     facts = ST.lifecycle_facts(script, names, CFG[cfg]["layers"])
     under = facts["stop_is_top_layer_without_input_gradient"] if name == "freeze" else facts["adapters_on_frozen_base"] + facts["adapters_on_trainable_base"]
     assert {ST.top_layer_is_dense(script[i], CFG[cfg], "cuda") for i in under} == {False, True}
+    if name == "dense":
+        assert {ST.top_layer_is_dense(script[i], CFG[cfg], "cuda") for i in facts["dense_targets"]} == {False, True}
+        assert facts["ffn_up_adapter"] and facts["dense_only_layer"] and facts["merge"] and facts["reload"] and facts["no_encoder_layer_trainable"]
+        # the records the snapshots hold are the ones the names give: canonical target order, the twin's add_lora takes them as they are
+        states = ST.lifecycle_states(script, names, CFG[cfg]["layers"])
+        for i, sn in snaps.items():
+            want = states[i][1]
+            assert (sn["lora"] is None) == (want is None) and (want is None or {k: sn["lora"][k] for k in want} == want), (i, sn["lora"], want)
 
 
 # ---------------------------------------------------------------------------------------------- 2. composite C call against per-launch twins
-@pytest.mark.parametrize("name", ["freeze", "lora"])
+@pytest.mark.parametrize("name", ["freeze", "lora", "dense"])
 def test_the_composite_layer_path_equals_per_launch_twins_over_the_lifecycle(name):
     """DESIGN: the composite C call of a layer's backward body is bit-identical to the per-launch path.  The long-lived run at its default
     settings (composite) against twins forced to ``composite_layers = False``, over the changing shapes of a whole script instead of one:
     ``mmbert_layer_bwd`` with ``dx == NULL`` at the layer where backward ends, its cached argument block across storages, and the seam
-    to the adapter layers (which always take the per-launch body)."""
+    to the adapter layers (which always take the per-launch body) -- in the ``dense`` script the layers that dense adapters force onto
+    the per-launch body, alone on the top layer above composite layers, and back on the composite path behind ``remove_lora`` / ``merge_lora``."""
     script, results, snaps = _long("F", name)
     compared = ST.check_against_twins(results, snaps, script, CFG["F"], build, overrides={"composite_layers": False})
     assert compared == len(_batch_items(script))
@@ -205,7 +221,8 @@ def _unfreeze_behind_a_step(sess):
     sess.model.unfreeze()
 
 
-STALE = {"add_lora": lambda sess: sess.model.add_lora(r=8, targets=("key",), freeze_base=False, seed=5), "merge_lora": _lora_then("merge_lora"),
+STALE = {"add_lora": lambda sess: sess.model.add_lora(r=8, targets=("key",), freeze_base=False, seed=5),
+         "add_lora_dense": lambda sess: sess.model.add_lora(r=8, targets=("intermediate", "ffn_output"), freeze_base=False, seed=5), "merge_lora": _lora_then("merge_lora"),
          "remove_lora": _lora_then("remove_lora"), "unfreeze": _unfreeze_behind_a_step}
 
 
@@ -223,6 +240,8 @@ def test_the_optimizer_of_before_is_refused_and_writes_nothing(case):
     out[0].mean().backward()
     f = s.model._flat
     assert (f is old_flat) == (case == "unfreeze")
+    if case == "add_lora_dense":
+        assert any(".dense.lora_A" in n for n in f.order) and not any(".lora_" in n for n in old_flat.order)
     torch.cuda.synchronize()
     owned = dict(m=old._m, v=old._v, ema=old._ema, old_params=old_flat.params, old_half=old_flat.half, old_grads=old_flat.grads,
                  params=f.params, half=f.half, grads=f.grads, halfT=f.halfT)

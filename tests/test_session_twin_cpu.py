@@ -131,6 +131,8 @@ _FREEZE_FACTS = ("stop_rises", "stop_is_top_layer_without_input_gradient", "bias
                  "unfreeze_behind_steps", "unfreeze_without_a_step_since_the_freeze")
 _LORA_FACTS = ("stop_rises", "unfreeze_behind_steps", "no_encoder_layer_trainable", "adapters_on_frozen_base", "adapters_on_trainable_base",
                "adapters_on_a_subset_of_layers", "rank_changes", "targets_change", "merge", "remove", "reload")
+_DENSE_FACTS = ("dense_targets", "ffn_up_adapter", "dense_only_layer", "adapters_on_frozen_base", "adapters_on_trainable_base",
+                "adapters_on_a_subset_of_layers", "rank_changes", "targets_change", "merge", "remove", "reload", "no_encoder_layer_trainable")
 
 
 def _names(L):
@@ -147,10 +149,13 @@ def test_the_lifecycle_scripts_contain_every_transition_they_are_there_for(L):
     freezes through ``add_lora`` alone: each is held to its own list), and each the shape transitions it is to cross."""
     names = _names(L)
     fz, lo = ST.lifecycle_facts(ST.freeze_script(L), names, L), ST.lifecycle_facts(ST.lora_script(L), names, L)
-    assert set(fz) == set(lo) == set(ST.LIFECYCLE) == set(_FREEZE_FACTS) | set(_LORA_FACTS)
+    de = ST.lifecycle_facts(ST.dense_lora_script(L), names, L)
+    assert set(fz) == set(lo) == set(de) == set(ST.LIFECYCLE) == set(_FREEZE_FACTS) | set(_LORA_FACTS) | set(_DENSE_FACTS)
     assert all(fz[k] for k in _FREEZE_FACTS), {k: fz[k] for k in _FREEZE_FACTS}
     assert all(lo[k] for k in _LORA_FACTS), {k: lo[k] for k in _LORA_FACTS}
-    assert all(fz[k] or lo[k] for k in ST.LIFECYCLE)
+    assert all(de[k] for k in _DENSE_FACTS), {k: de[k] for k in _DENSE_FACTS}
+    assert all(fz[k] or lo[k] for k in ST.LIFECYCLE if k not in ("dense_targets", "ffn_up_adapter", "dense_only_layer"))
+    assert not any(fz[k] or lo[k] for k in ("dense_targets", "ffn_up_adapter", "dense_only_layer"))        # (the older scripts know no dense target)
     # where, as the scripts are written down in tests/session_twin.py
     assert fz["stop_rises"] == [2, 6] and fz["stop_is_top_layer_without_input_gradient"] == [6, 9, 10] and fz["bias_only_layer"] == [9, 10]
     assert fz["unfreeze_behind_steps"] == [12, 19] and fz["frozen_layer_between_trainable_ones"] == [15]
@@ -159,7 +164,8 @@ def test_the_lifecycle_scripts_contain_every_transition_they_are_there_for(L):
     assert lo["rank_changes"] == lo["targets_change"] == [14] and lo["adapters_on_trainable_base"] == lo["adapters_on_a_subset_of_layers"] == [15]
     assert lo["remove"] == [17]
     for script, under in ((ST.freeze_script(L), fz["stop_is_top_layer_without_input_gradient"]),
-                          (ST.lora_script(L), lo["adapters_on_frozen_base"] + lo["adapters_on_trainable_base"])):
+                          (ST.lora_script(L), lo["adapters_on_frozen_base"] + lo["adapters_on_trainable_base"]),
+                          (ST.dense_lora_script(L), de["dense_targets"])):
         tr = ST.transitions(script)
         for k in ("grows_past_everything", "shrinks_right_after_the_largest", "longer_than_256", "one_sample_labels_on_pair_rows"):
             assert tr[k], k
@@ -170,6 +176,51 @@ def test_the_lifecycle_scripts_contain_every_transition_they_are_there_for(L):
         kinds = {it[0] for it in script}
         assert set(ST.TRAINING) <= kinds and len(kinds & set(ST.KINDS)) >= 5
         assert len({it[2] for it in script if it[0] not in ST.MUTATIONS}) == len(shapes)
+
+
+@pytest.mark.parametrize("L", [3, 4])
+def test_the_dense_adapter_script_holds_what_it_is_there_for(L):
+    """``ST.dense_lora_script`` from the names alone: where each fact happens, as the script is written down; the adapter records in the
+    canonical order of ops.lora_split_targets with the dense targets' module paths; an ``accumulate`` + ``train`` pair under all six
+    targets; the one-sample shape at a ``DENSE_TOP_SEEDS`` seed; every inference kind while dense adapters are live; a targets change
+    from a set with dense targets to one without and back."""
+    from msa_amd import ops
+    names = _names(L)
+    script = ST.dense_lora_script(L)
+    assert ST.misplaced_mutations(script) == []
+    de = ST.lifecycle_facts(script, names, L)
+    assert de["adapters_on_frozen_base"] == [2, 3, 6, 9] and de["adapters_on_trainable_base"] == de["adapters_on_a_subset_of_layers"] == [16, 19]
+    assert de["dense_targets"] == de["ffn_up_adapter"] == [2, 3, 6, 9, 19] and de["dense_only_layer"] == [19]
+    assert de["rank_changes"] == de["targets_change"] == [15, 18] and de["reload"] == [8] and de["merge"] == [12] and de["remove"] == [17, 21]
+    assert de["no_encoder_layer_trainable"] == [13] and de["unfreeze_behind_steps"] == [14]
+    states = ST.lifecycle_states(script, names, L)
+    recs = [states[i][1] for i, it in enumerate(script) if it[0] == "add_lora"]
+    assert [r["targets"] for r in recs] == [ops.LORA_ALL_TARGETS, ("key",), ("intermediate", "ffn_output")]
+    assert [r["r"] for r in recs] == [8, 4, 16] and [r["layers"] for r in recs] == [tuple(range(L)), (0,), (L - 1,)]
+    has_dense = [any(t in ops.LORA_DENSE_TARGETS for t in r["targets"]) for r in recs]
+    assert has_dense == [True, False, True]                           # with dense targets -> without -> with
+    assert ST._lora_record(dict(targets=("ffn_output", "value", "attention_output")), L)["targets"] == ("value", "attention_output", "ffn_output")
+    assert ST.LORA_DENSE_PATHS == ops.LORA_DENSE_MODULES and ST.LORA_QKV == ops.LORA_TARGETS
+    with pytest.raises(ValueError):
+        ST._lora_record(dict(targets=("output",)), L)
+    # the flags name the adapters where add_lora puts them, and the base follows freeze_base
+    flags = states[2][0]
+    lora_names = sorted(n for n in flags if ".lora_" in n)
+    assert len(lora_names) == 2 * 6 * L and all(flags[n] for n in lora_names) and ST.base_frozen(flags)
+    for t, path in (("query", "attention.self.query"), ("attention_output", "attention.output.dense"), ("intermediate", "intermediate.dense"),
+                    ("ffn_output", "output.dense")):
+        assert ST.lora_module_path(t) == path and f"bert.encoder.layer.{L - 1}.{path}.lora_B" in flags
+    flags = states[19][0]
+    assert sorted(n for n in flags if ".lora_" in n) == sorted(f"bert.encoder.layer.{L - 1}.{p}.lora_{m}" for p in ("intermediate.dense", "output.dense") for m in "AB")
+    assert not ST.base_frozen(flags) and states[19][2] is None
+    # an accumulate + train pair under all six targets; the one-sample shape at a dense-top seed
+    assert script[2][0] == "accumulate" and script[3][0] == "train" and states[2][1]["targets"] == states[3][1]["targets"] == ops.LORA_ALL_TARGETS
+    assert script[3][1] == (1, 8, 8, 8) and script[3][2] in ST.DENSE_TOP_SEEDS and ST.top_layer_is_dense(script[3], _BATCH_CFG)
+    live = {it[0] for it, (_f, lora, _p) in zip(script, states) if it[0] in ST.KINDS and lora is not None and any(t in ops.LORA_DENSE_TARGETS for t in lora["targets"])}
+    assert live == set(ST.KINDS), sorted(set(ST.KINDS) - live)
+    # ``predict`` runs the [CLS]-only top layer: once under all six targets, once on a top layer with dense adapters and no Q/K/V ones
+    assert [states[i][1]["targets"] for i, it in enumerate(script) if it[0] == "predict"] == [ops.LORA_ALL_TARGETS, ("intermediate", "ffn_output")]
+    assert len([it for it in script if it[0] not in ST.MUTATIONS]) == 15 and len([it for it in script if it[0] == "train"]) == 8
 
 
 def test_the_lifecycle_facts_are_computed_not_assumed():
@@ -188,11 +239,16 @@ def test_the_lifecycle_facts_are_computed_not_assumed():
     assert not f["merge"] and not f["no_encoder_layer_trainable"]
     f = ST.lifecycle_facts(drop(ls, 13), names, L)                                   # no unfreeze in front of the second adapters: the base stays frozen
     assert not f["adapters_on_trainable_base"] and not f["unfreeze_behind_steps"] and f["adapters_on_a_subset_of_layers"]
+    ds = ST.dense_lora_script(L)
+    f = ST.lifecycle_facts(drop(ds, 18, 21), names, L)                               # no third adapter set: no layer with dense adapters alone
+    assert not f["dense_only_layer"] and f["dense_targets"] == f["ffn_up_adapter"] == [2, 3, 6, 9]
+    f = ST.lifecycle_facts([it if it[0] != "add_lora" or it[3]["seed"] != 81 else ST._mut("add_lora", **dict(it[3], targets=("query", "ffn_output"))) for it in ds], names, L)
+    assert f["dense_targets"] == [2, 3, 6, 9, 19] and f["ffn_up_adapter"] == f["dense_only_layer"] == [19]
 
 
 @pytest.mark.parametrize("L", [3, 4])
 def test_mutations_sit_only_at_optimizer_step_boundaries(L):
-    for script in (ST.freeze_script(L), ST.lora_script(L), ST.main_script(), ST.MODES_SCRIPT):
+    for script in (ST.freeze_script(L), ST.lora_script(L), ST.dense_lora_script(L), ST.main_script(), ST.MODES_SCRIPT):
         assert ST.misplaced_mutations(script) == []
         for kind, shape, _seed, options in script:
             assert (shape is None) == (kind in ST.MUTATIONS) and kind in ST.KINDS + ST.MUTATIONS

@@ -15,7 +15,11 @@ mutated chain's final gradients against the clean chain's, by ``compare_gradient
 For the two that exceed 4.5 % on their own the harness proves nothing new (the end-to-end test sees them as well); they stay in the list as
 checks of the recomputation itself.
 
-``gelu_bwd_ref``'s bound is validated here by its emulation (largest ratio 0.5)."""
+``gelu_bwd_ref``'s bound is validated here by its emulation (largest ratio 0.5).
+
+The adapter launches have chains of their own below: ``lora_chain`` (Q/K/V adapters, the grouped column sum) and ``dense_chain`` (the
+dense-seam adapters between the GEMMs they follow) -- the faithful chains pass, every mutation of tests/lora_ref.py / tests/lora_dense_ref.py
+applied to what the "kernels" computed fails the recomputation, every wiring change fails the exact check named for it."""
 import types
 
 import pytest
@@ -492,3 +496,243 @@ def test_the_frozen_form_of_the_sequence_check():
                     (fwd() + dense(2, (2,)) + dense(1) + dense(0), dict(lora_layers=(2,)))):        # the adapter forward is missing
         with pytest.raises(AssertionError):
             SS.check_sequence(calls_of(bad), L, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ the dense-seam adapter launches
+from tests import lora_dense_ref as DR                       # noqa: E402
+from tests.test_lora_dense_reference_cpu import MUTATIONS as DENSE_MUTATIONS     # noqa: E402
+
+DM, DRA, DRANK = 257, 249, 4                                 # (tests/test_lora_dense_reference_cpu.py's mutation case: 257 rows, (K, N) = (128, 512); backward on 249)
+DROWS = [0, 3, 17, 64, 65, 127, 128, 200, 248] + list(range(20, 48))            # the rows of the gathered launch (37: no multiple of 16)
+DENSE_TARGETS = ("intermediate", "ffn_output")               # (K, N) = (128, 512) and (512, 128): K != N both ways
+WIRING = ("triple", "gelu_u", "fresh_dx", "no_aux")
+
+
+def dense_chain(mutation=None, wiring=None):
+    """The FFN half of one encoder layer with dense-seam adapters as a recorded chain on the CPU, the adapters' outputs from
+    tests/lora_dense_ref.py's emulation, the launches around them from the other references' emulations: LayerNorm 1, the FFN-up GEMM
+    (bias only), ``lora_dense_fwd`` in GELU mode writing ``aux`` and h, the FFN-down GEMM with residual and a live dropout triple,
+    ``lora_dense_fwd`` in ADD mode with that triple; backward on the leading 249 rows: the ``du`` GEMM, ``lora_dense_bwd`` with ``gelu_u`` =
+    that ``aux``, ``dx`` in place and ``h`` a row slice; a gather, the split-K ``dy1`` GEMM on the gathered rows and ``lora_dense_bwd`` with
+    ``h=None`` -- the adapter gradients views of ONE flat buffer laid out by ``offset`` / ``numel`` (they hold an earlier micro-batch's
+    values: the launches accumulate).  ``mutation``: a tests/lora_dense_ref.py Mutation applied to what the adapter "kernels" computed;
+    ``wiring``: ``triple`` (the ADD-mode adapter gets another triple than its GEMM), ``gelu_u`` (another buffer than the du GEMM's),
+    ``fresh_dx`` (dx is a copy, not the GEMM's output), ``no_aux`` (the GELU-mode launch is handed no ``aux``: backward reads a buffer nobody
+    wrote).  Returns (calls, model stub, flat buffer, offset, numel)."""
+    assert wiring is None or wiring in WIRING
+    model = _params()
+    lw = model._lw[0]
+    g = torch.Generator().manual_seed(21)
+    s = 16.0 / DRANK
+    dims = {"intermediate": (H, I), "ffn_output": (I, H)}
+    names = [f"{t}.lora_{m}" for t in DENSE_TARGETS for m in ("A", "B")] + ["b2"]
+    numel = {f"{t}.lora_{m}": DRANK * (dims[t][0] if m == "A" else dims[t][1]) for t in DENSE_TARGETS for m in ("A", "B")}
+    numel["b2"] = H
+    offset, off = {}, 0
+    for n in names:
+        offset[n] = off
+        off = (off + numel[n] + 255) // 256 * 256
+    flat = torch.randn(off, generator=torch.Generator().manual_seed(9)) * 0.01
+    view = lambda n, shape: flat[offset[n]:offset[n] + numel[n]].view(shape)                 # noqa: E731
+    dl = dict(targets=DENSE_TARGETS, r=DRANK, scale=s, A={}, B={}, gA={}, gB={}, pA={}, pB={})
+    for k, t in enumerate(DENSE_TARGETS):
+        K, N = dims[t]
+        inp = DR.inputs(8, K, N, DRANK, "real", 6000 + k)
+        dl["A"][t], dl["B"][t] = inp["A"], inp["B"]
+        dl["gA"][t], dl["gB"][t] = view(f"{t}.lora_A", (DRANK, K)), view(f"{t}.lora_B", (N, DRANK))
+        dl["pA"][t] = types.SimpleNamespace(requires_grad=True, grad=dl["gA"][t])
+        dl["pB"][t] = types.SimpleNamespace(requires_grad=True, grad=dl["gB"][t])
+    lw["lora_dense"] = dl
+    calls = []
+
+    def emit(op, a, compute, writes=()):
+        c = SS.Call(op, {k: SS._snap(v) for k, v in a.items()})
+        ret = compute()
+        c.ret = SS._snap(ret)
+        c.post = {k: SS._snap(a[k]) for k in writes if a.get(k) is not None}
+        calls.append(c)
+        return ret
+
+    def nt(A_, B_, bias=None, resid=None, gelu_bwd_u=None, drop=None):
+        a = dict(A=A_, B=B_, out=None, bias=bias, gelu=False, aux=None, resid=resid, gelu_bwd_u=gelu_bwd_u, alpha=1.0, alpha_dev=None, drop=drop,
+                 out_f32=False)
+        keep = SS.flat_mask(A_.shape[0] * B_.shape[0], drop).view(A_.shape[0], B_.shape[0]) if drop else None
+        return emit("gemm_nt", a, lambda: _b16(G.nt(A_, B_, bias=bias, resid=resid, keep=keep, drop_scale=drop[2] if drop else 1.0,
+                                                     gelu_u=gelu_bwd_u, emu=True)["out"]))
+
+    def dense_fwd(t, x_, y_, mode, drop=None, aux=None, h_out=None):
+        a = dict(x=x_, y=y_, A=dl["A"][t], B=dl["B"][t], scale=s, mode=mode, drop=drop, aux=aux, h_out=h_out)
+
+        def compute():
+            e = DR.fwd(x_, y_, dl["A"][t], dl["B"][t], s, mode, drop=drop, emu=True, mutation=mutation)
+            y_.copy_(_b16(e["y"].val))
+            if aux is not None:
+                aux.copy_(_b16(e["aux"].val))
+            if h_out is not None:
+                h_out.copy_(_b16(e["h"].val))
+            return y_
+        return emit("lora_dense_fwd", a, compute, writes=("y", "aux", "h_out"))
+
+    def dense_bwd(t, dy, x_, h, dx, gelu_u=None):
+        gA, gB = dl["gA"][t], dl["gB"][t]
+        a = dict(dy=dy, x=x_, h=h, A=dl["A"][t], B=dl["B"][t], gA=gA, gB=gB, scale=s, dx=dx, gelu_u=gelu_u, accumulate=True, workspace=None)
+
+        def compute():
+            e = DR.bwd(dy, x_, h, dl["A"][t], dl["B"][t], s, dx=dx, gelu_u=gelu_u, gA0=gA.clone(), gB0=gB.clone(), accumulate=True, emu=True,
+                       mutation=mutation)
+            dx.copy_(_b16(e["dx"].val))
+            gA.copy_(e["dA"].val.float())
+            gB.copy_(e["dB"].val.float())
+            return dx
+        return emit("lora_dense_bwd", a, compute, writes=("dx", "gA", "gB"))
+
+    d_h2 = _drop(11, 2)
+    z1 = _b16(torch.randn(DM, H, generator=g))
+    # ---- forward
+    y1 = emit("ln_fwd", dict(x=z1, gamma=lw["ln1_g"], beta=lw["ln1_b"], eps=EPS, M=None, out=None, in_rows=None, out_rows=None, drop=None, stats=True,
+                             drop_row0=0), lambda: (lambda r: (_b16(r["y"]), r["mean"].to(f32), r["rstd"].to(f32)))(R.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], EPS, emu=True)))[0]
+    gg = nt(y1, lw["W1"], bias=lw["b1"])
+    u = torch.zeros(DM, I, dtype=bf)
+    h_i, h_f = torch.zeros(DM + 7, DRANK, dtype=bf), torch.zeros(DM + 7, DRANK, dtype=bf)
+    dense_fwd("intermediate", y1, gg, DR.GELU, aux=None if wiring == "no_aux" else u, h_out=h_i[:DM])
+    z2 = nt(gg, lw["W2"], bias=lw["b2"], resid=y1, drop=d_h2)
+    dense_fwd("ffn_output", gg, z2, DR.ADD, drop=_drop(11, 5) if wiring == "triple" else d_h2, h_out=h_f[:DM])
+    # ---- backward on the leading rows
+    dz2d = _b16(torch.randn(DRA, H, generator=g) * 0.05)
+    dz2 = _b16(torch.randn(len(DROWS), H, generator=g) * 0.05)
+    du = nt(dz2d, lw["W2T"], gelu_bwd_u=u[:DRA])
+    dense_bwd("ffn_output", dz2d, gg[:DRA], h_f[:DRA], du.clone() if wiring == "fresh_dx" else du, gelu_u=u.clone()[:DRA] if wiring == "gelu_u" else u[:DRA])
+    idx = torch.tensor(DROWS, dtype=torch.int32)
+    y1_c, du_c = emit("gather_rows", dict(srcs=[y1[:DRA], du], idx32=idx), lambda: [t[idx.long()].clone() for t in (y1[:DRA], du)])
+    dy1_c = emit("gemm_nt_splitk", dict(A=du_c, B=lw["W1T"], out=None, resid=dz2), lambda: _b16(G.splitk(du_c, lw["W1T"], resid=dz2, emu=True)["out"]))
+    dense_bwd("intermediate", du_c, y1_c, None, dy1_c)
+    for i, c in enumerate(calls):
+        c.index = i
+        c.meta["pass"] = 1
+    SS.annotate(calls, model)
+    return calls, model, flat, offset, numel
+
+
+def test_the_chain_through_the_dense_adapter_launches_passes():
+    """The faithful chain: every launch recomputed (measured on this chain: lora_dense_fwd 0.497, lora_dense_bwd 0.490 -- one bf16 rounding
+    of an output, half its bound), the producer check (backward read the h, the aux and the dx their producers left, bit for bit), the new
+    wiring check on all four adapter launches, check 5 with the ADD-mode adapter counted to its GEMM's site."""
+    calls, model, *_ = dense_chain()
+    assert [(c.meta["stage"], c.meta["layer"]) for c in calls] == [("ln1", 0), ("g", 0), ("lora_g", 0), ("z2", 0), ("lora_z2", 0), ("du", 0), ("lora_du", 0),
+                                                                   ("gather_rows2", None), ("dy1", 0), ("lora_dy1", 0)]
+    per = SS.recompute_all(calls)
+    assert {k: n for k, (n, _w) in per.items()} == {"ln_fwd": 1, "gemm_nt": 3, "gemm_nt_splitk": 1, "gather_rows": 1, "lora_dense_fwd": 2, "lora_dense_bwd": 2}
+    print({k: round(w, 3) for k, (_n, w) in per.items()})
+    assert all(w <= 1.0 for _n, w in per.values())
+    assert 0.2 < per["lora_dense_fwd"][1] <= 0.55 and 0.2 < per["lora_dense_bwd"][1] <= 0.55, per
+    SS.check_producers(calls)
+    assert SS.check_dense_adapter_wiring(calls, model) == 4
+    assert SS.check_dropout_sites(calls) == 1                   # (z2 and lora_z2: one site)
+    assert calls[9].a["h"] is None and calls[6].a["h"].shape[0] == DRA < calls[4].a["h_out"].shape[0]
+
+
+@pytest.mark.parametrize("name", list(DENSE_MUTATIONS))
+def test_each_dense_adapter_mutation_fails_the_recomputation(name):
+    """tests/lora_dense_ref.py's mutations (the delta not masked, the mask indexed by the pitch, drop_scale left out, GELU before the delta,
+    aux after GELU, gelu' missing or from the neighbouring row, s off by 2^-6, the last row block skipped, a fold slab skipped, accumulate
+    ignored, the contraction stopping at min(K, N) -- the chain holds K < N and K > N), each applied to what the chain's adapter launches
+    computed."""
+    make = DENSE_MUTATIONS[name][0]
+    mut = DR.mask_by_pitch(H + 8) if name.startswith("mask indexed") else make()          # (the ADD launch of the chain has N = 128)
+    calls, *_ = dense_chain(mut)
+    with pytest.raises(AssertionError, match="lora_dense_(fwd|bwd)"):
+        SS.recompute_all(calls)
+
+
+def test_each_wiring_change_of_the_dense_adapters_fails_its_check():
+    """The adapter's triple differs from its GEMM's (each launch still recomputes from its OWN triple: only check 5 sees it, and the wiring
+    check); ``gelu_u`` is another buffer than the du GEMM's; ``dx`` is a fresh buffer; the GELU-mode launch is handed no ``aux`` (every launch
+    still recomputes from what it read, and the producer check knows no writer of the buffer: only the wiring check names the mistake);
+    backward reads another h than forward wrote; gB lands in a frozen span."""
+    calls, model, *_ = dense_chain(wiring="triple")
+    assert all(w <= 1.0 for _n, w in SS.recompute_all(calls).values())
+    with pytest.raises(AssertionError, match=r"dropout site \(1, 0, 'z2'\): forward and backward carry different triples"):
+        SS.check_dropout_sites(calls)
+    with pytest.raises(AssertionError, match=r"layer 0 lora_z2\): drop .* is not the GEMM's"):
+        SS.check_dense_adapter_wiring(calls, model)
+    calls, model, *_ = dense_chain(wiring="gelu_u")
+    assert all(w <= 1.0 for _n, w in SS.recompute_all(calls).values())
+    SS.check_producers(calls)                                   # (the copy holds the same bits: only the address says it is another buffer)
+    with pytest.raises(AssertionError, match=r"layer 0 lora_du\) gelu_u = the GEMM's gelu_bwd_u"):
+        SS.check_dense_adapter_wiring(calls, model)
+    calls, model, *_ = dense_chain(wiring="fresh_dx")
+    with pytest.raises(AssertionError, match=r"layer 0 lora_du\) dx = what the GEMM returned"):
+        SS.check_dense_adapter_wiring(calls, model)
+    calls, model, *_ = dense_chain(wiring="no_aux")
+    assert all(w <= 1.0 for _n, w in SS.recompute_all(calls).values())
+    SS.check_producers(calls)                                   # (no recorded call ever wrote u: nothing to compare with)
+    with pytest.raises(AssertionError, match="layer 0 du: backward reads a pre-activation, yet the layer's intermediate adapter was handed no aux"):
+        SS.check_dense_adapter_wiring(calls, model)
+    calls, model, flat, offset, numel = dense_chain()
+    h = calls[6].a["h"]
+    h.t.view(torch.int16)[5, 3] += 1
+    h._cpu = None
+    with pytest.raises(AssertionError, match=r"lora_dense_bwd, lora_du\) operand h: 1 of"):
+        SS.check_producers(calls)
+    # gB in a frozen span
+    plan = lambda *frozen: types.SimpleNamespace(frozen=frozenset(frozen), layers={}, word_table=False)      # noqa: E731
+    names = SS.names_of(model)
+    wg = SS.synth("gemm_tn_grouped", dict(problems=[(torch.zeros(4, H, dtype=bf), torch.zeros(4, H, dtype=bf), model._w["g_Wt"], model._w["g_bt"])],
+                                          accumulate=True, alpha=1.0), post=dict(problems=[(model._w["g_Wt"], model._w["g_bt"])]))
+    wg.meta.update(stage="gemm_tn_grouped", layer=None)
+    calls, model, flat, offset, numel = dense_chain()
+    assert SS.check_frozen_writes(calls + [wg], names, plan("b2"), 1, flat, offset, numel) == 4              # gA and gB of two launches
+    with pytest.raises(AssertionError, match=r"lora_dense_bwd, stage lora_du layer 0\) writes elements \[\d+, \d+\) of the gradient buffer: the span of the frozen ffn_output.lora_B"):
+        SS.check_frozen_writes(calls + [wg], names, plan("ffn_output.lora_B"), 1, flat, offset, numel)
+    with pytest.raises(AssertionError, match="stage lora_dy1 layer 0.*the span of the frozen intermediate.lora_A"):
+        SS.check_frozen_writes(calls + [wg], names, plan("intermediate.lora_A"), 1, flat, offset, numel)
+
+
+def test_the_sequence_check_with_dense_adapter_stages():
+    """``check_sequence`` with an adapter record: on an adapted layer every present target's stage sits directly behind z1 / g / z2 in
+    forward and behind du / dy1 / dctx in backward -- for a subset of the targets, a subset of the layers, in the dense and in both
+    sparse top-layer forms; a missing forward stage, a missing backward stage, a swapped order, and an adapter launch on no layer fail."""
+    def calls_of(seq):
+        out = []
+        for st, l in seq:
+            c = SS.Call({"lora_z1": "lora_dense_fwd", "lora_dctx": "lora_dense_bwd"}.get(st, st), {})
+            c.meta.update(stage=st, layer=l)
+            out.append(c)
+        return out
+    L = 3
+    rec = lambda targets, layers: dict(r=4, alpha=8.0, targets=targets, layers=layers)          # noqa: E731
+    assert SS.adapter_stages(rec(("query", "ffn_output"), (1,))) == {1: (True, ("ffn_output",))}
+    assert SS.adapter_stages((0, 2)) == {0: (True, ()), 2: (True, ())} and SS.adapter_stages(None) == {}
+
+    def fwd(ad):
+        return [(s, l) for l in range(L) for s in SS._fwd_form(ad.get(l))]
+
+    def bwd(ad, l, form=SS.BWD_DENSE, dx=True):
+        f = SS._bwd_form(form, ad.get(l))
+        return [(s, l if s not in ("gather_rows8", "gather_rows1", "scatter_rows_zero", "attn_q_limit") else None) for s in f if dx or s != "dx"]
+    all6 = rec(("query", "key", "value", "attention_output", "intermediate", "ffn_output"), (0, 1, 2))
+    ad = SS.adapter_stages(all6)
+    assert SS._fwd_form(ad[0]) == ("qkv", "lora_fwd", "attn_fwd", "z1", "lora_z1", "ln1", "g", "lora_g", "z2", "lora_z2", "ln2")
+    assert SS._bwd_form(SS.BWD_DENSE, ad[0]) == ("ln2_bwd", "du", "lora_du", "dy1", "lora_dy1", "ln1_bwd", "dctx", "lora_dctx", "attn_bwd", "lora_bwd", "dx")
+    for form in (SS.BWD_DENSE,) + SS.BWD_TOP_SPARSE:
+        seq = fwd(ad) + bwd(ad, 2, form) + bwd(ad, 1) + bwd(ad, 0, dx=False)
+        assert SS.check_sequence(calls_of(seq), L, 0, True, all6) == {"fwd": 1, "bwd": 1}
+    # a subset of the targets on a subset of the layers, without Q/K/V adapters, next to plain layers
+    sub = rec(("intermediate", "ffn_output"), (2,))
+    ad2 = SS.adapter_stages(sub)
+    good = fwd(ad2) + bwd(ad2, 2, SS.BWD_TOP_SPARSE[0]) + bwd(ad2, 1) + bwd(ad2, 0)
+    assert SS._fwd_form(ad2[2]) == ("qkv", "attn_fwd", "z1", "ln1", "g", "lora_g", "z2", "lora_z2", "ln2") and SS._fwd_form(ad2.get(1)) == SS.FWD_LAYER
+    assert SS.check_sequence(calls_of(good), L, 0, False, sub) == {"fwd": 1, "bwd": 1}
+    assert SS.check_sequence(calls_of(fwd(ad2)), L, 0, False, sub, backward=False) == {"fwd": 1, "bwd": 0}
+    swap = lambda seq, a, b: [(b if s == a else a if s == b else s, l) for s, l in seq]        # noqa: E731
+    for bad in ([x for x in good if x[0] != "lora_g"],                                         # a missing forward stage
+                [x for x in good if x[0] != "lora_dy1"],                                       # a missing backward stage
+                swap(good, "lora_du", "du"),                                                   # the adapter in front of its GEMM
+                swap(good, "lora_du", "lora_dy1"),                                             # two adapters exchanged
+                good + [("lora_g", 2)]):                                                       # a stray adapter launch behind the step
+        with pytest.raises(AssertionError):
+            SS.check_sequence(calls_of(bad), L, 0, False, sub)
+    with pytest.raises(AssertionError, match="a forward pass without backward"):
+        SS.check_sequence(calls_of(fwd(ad2) + bwd(ad2, 2)), L, 0, False, sub, backward=False)
+    with pytest.raises(AssertionError, match="a dense adapter launch on no layer"):
+        SS.check_sequence(calls_of(good[:4] + [("lora_z1", None)] + good[4:]), L, 0, False, sub)
