@@ -194,6 +194,10 @@ class FlatParams:
         # the parameters the model's last forward saw with requires_grad == False (set_frozen): their .grad is None and stays None, nothing
         # reads their part of ``grads``, the optimizer does not step them
         self.frozen: frozenset = frozenset()
+        # the part of ``frozen`` that is there only because the model's last differentiated forward does not reach it (the label-only
+        # step: the MLM transform and prediction bias): trainable parameters whose gradient is None for this step, as torch leaves the
+        # gradient of a parameter outside the graph -- the optimizer skips them like frozen ones and steps them again once they are reached
+        self.unreached: frozenset = frozenset()
         self._reconciled_task = -1                  # the backward pass (autograd graph task) reconcile_in_backward() last ran in
         # the factor the optimizer applies to ``grads`` (1 / world under parallel.DataParallel, which sets it): the torch-semantics
         # clip (optim.clip_grad_norm_) measures the gradient the step will apply, the mean over ranks
@@ -250,16 +254,20 @@ class FlatParams:
         fz = self.frozen
         self.stale = set(self.lazy) if not fz else {i for i, (_, names) in self.lazy.items() if not all(n in fz for n in names)}
 
-    def set_frozen(self, names: frozenset):
-        """The set of frozen parameters as the model's forward has just read it.  Entering the set: ``.grad`` reads None from now on (no
-        lazy-zero or reconcile call attaches it again, and it is no caller's dropped gradient).  Leaving it: the parameter's part of
+    def set_frozen(self, names: frozenset, unreached: frozenset = frozenset()):
+        """The set of frozen parameters as the model's forward has just read it.  ``unreached``: trainable parameters that this forward's
+        backward does not reach (the label-only step) -- they join the set for as long as that holds and are remembered as such
+        (``self.unreached``; AdamW._follow_frozen reads it).  Entering the set: ``.grad`` reads None from now on (no lazy-zero or
+        reconcile call attaches it again, and it is no caller's dropped gradient).  Leaving it: the parameter's part of
         ``grads`` -- unspecified while frozen -- is zero-filled and attached again, like a dropped gradient.
         LIMIT: the storage holds ONE set, that of the latest forward that went ahead.  Which launches a backward makes follows the set
         its own forward saw (the record travels with the graph), but which ``.grad`` views exist follows this set: two forwards with
         different sets ahead of one backward leave ``.grad`` attached by the later one."""
+        self.unreached = frozenset(unreached) - frozenset(names)
+        names = frozenset(names) | self.unreached
         if names == self.frozen:
             return
-        was, self.frozen = self.frozen, frozenset(names)
+        was, self.frozen = self.frozen, names
         for n in self.frozen - was:
             self.named[n].grad = None
         back = [n for n in was - self.frozen if self.named[n].grad is None]

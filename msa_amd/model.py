@@ -1452,6 +1452,45 @@ class _MLMHeadFn(torch.autograd.Function):
         return ops.gemm_nt(dpre, w["WtT"])
 
 
+# the parameters only the MLM head reads (the word table is also the embeddings'): what a label-only step's backward does not reach
+_MLM_ONLY = ("cls.predictions.bias", "cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias",
+             "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias")
+
+
+class _ClsRowsFn(torch.autograd.Function):
+    """The [CLS] rows of the encoder output for the heads of a label-only step (forward() without masked_labels): what _MLMHeadFn hands
+    out as ``first``, without the MLM head.  Backward hands the trunk the rows' gradient in the compact form _MLMHeadFn uses -- an EMPTY
+    labelled-row list and the 3 B [CLS] rows (``trunk.compact``; _EncoderFn.run_backward then takes the sparse top-layer path) -- and
+    returns a stride-0 dummy for y; where the compact form does not apply (``sparse_top_layer_backward`` off, or 3 B rows are more than a
+    quarter of the backward's rows) it returns the dense [tokens, H] gradient, zero but for those rows."""
+
+    @staticmethod
+    def forward(ctx, y, top, first_rows, trunk, leave_rows):
+        """``leave_rows``: as in _MLMHeadFn.forward -- the level-launch heads read the rows from y themselves, ``first`` carries the edge."""
+        ctx.top, ctx.trunk, ctx.first_rows, ctx.M = top, trunk, first_rows, y.shape[0]
+        ctx.set_materialize_grads(False)
+        if leave_rows:
+            return torch.empty((first_rows.numel(), y.shape[1]), device=y.device, dtype=torch.float32)
+        return y.index_select(0, first_rows).float()
+
+    @staticmethod
+    def backward(ctx, dfirst):
+        if dfirst is None:
+            return None, None, None, None, None
+        top, t, first = ctx.top, ctx.trunk, ctx.first_rows
+        top._flat.reconcile_in_backward()
+        _join_heads(top)                                      # (nothing forks the heads' backward on this step; one a raised pass left is joined)
+        H = dfirst.shape[1]
+        if t is not None and getattr(top, "sparse_top_layer_backward", True):
+            ra = t.split.rows_a if t.split is not None else t.plan["layout"].tokens
+            if 4 * first.numel() <= ra:
+                t.compact = (first.new_empty(0, dtype=torch.int32), first, dfirst.to(torch.bfloat16))
+                return _zero_dummy(ctx.M, H, torch.bfloat16, dfirst.device), None, None, None, None
+        dy = torch.zeros((ctx.M, H), device=dfirst.device, dtype=torch.bfloat16)
+        dy.index_add_(0, first, dfirst.to(dy.dtype))
+        return dy, None, None, None, None
+
+
 # ================================================================================================
 # the reference's module API
 # ================================================================================================
@@ -1568,11 +1607,15 @@ class _GpuModelBase(nn.Module):
                 plan = _freeze.trainable_plan(dict(zip(f.named, key)), self.config.num_hidden_layers, f.offset, f.numel)
             d["_tplan"], d["_tplan_key"] = plan, key
 
-    def _apply_trainable(self):
-        """The frozen set of the record goes to the storage (FlatParams.set_frozen): from a forward that was not refused."""
+    def _apply_trainable(self, unreached=None):
+        """The frozen set of the record goes to the storage (FlatParams.set_frozen): from a forward that was not refused.  ``unreached``:
+        the trainable parameters this forward's backward does not reach (the label-only step; empty for every other differentiated
+        forward); None (a forward without autograd: no backward follows) leaves the storage's set as the last differentiated forward left it."""
         plan, f = self.__dict__.get("_tplan"), self._flat
-        if plan is not None or f.frozen:
-            f.set_frozen(plan.frozen if plan is not None else frozenset())
+        if unreached is None:
+            unreached = f.unreached
+        if plan is not None or f.frozen or unreached:
+            f.set_frozen(plan.frozen if plan is not None else frozenset(), unreached)
 
     def _trunk_anchor(self, dev):
         """The tensor that makes autograd call the trunk's backward: the embedding LayerNorm's weight, or -- when that is frozen -- a
@@ -1746,7 +1789,7 @@ class _GpuModelBase(nn.Module):
             labels.record_stream(torch.cuda.current_stream())
         return labels, None
 
-    def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None, predict=False, attention=None, freeze_ok=False):
+    def _encode(self, passes, labels=None, want_rows=False, rowset=False, packed=None, predict=False, attention=None, freeze_ok=False, label_only=False):
         """passes: list of dict(ids[B,T], tt[B,T]|None, mask, pair[B,P,D]|None, pair_mask|None).
         Returns (Y [tokens,H] bf16, plan, lens_per_pass, rows, trunk) -- ``rows`` = (labelled-row list, host words, event) when asked for;
         ``trunk`` = the _Trunk record of the call (forward() hands it to the MLM head: compact output gradient), None for ``predict``.
@@ -1762,7 +1805,10 @@ class _GpuModelBase(nn.Module):
         a train step are not touched and no trunk record is kept.  ``attention`` (with ``predict`` only) = (``"top"`` | ``"all"``, list):
         the list receives (layer index, fp32 [sequences, heads, longest sequence]) per probed layer -- the [CLS] queries' attention rows
         (ops.attn_probs_first).  ``predict="dense"`` (predict_tokens()): the same stateless inference call with EVERY layer run on every
-        row; Y is the [tokens, H] matrix in the caller's row order."""
+        row; Y is the [tokens, H] matrix in the caller's row order.
+        ``label_only`` (forward() without masked_labels): a train / eval step whose only readers of Y are the heads on the [CLS] rows --
+        no labelled-row list, the backward's valid-first packing from the unmasked lengths alone, and the MLM-only parameters
+        (_MLM_ONLY) are told to the storage as not reached by this step's backward."""
         bert = self._bert()
         dev = passes[0]["ids"].device
         self._ensure_ready(dev)
@@ -1775,7 +1821,8 @@ class _GpuModelBase(nn.Module):
                                           "call model.unfreeze() or use forward()")
             fz = None                      # (only parameters that are never differentiated carry the flag: nothing to honour on this path)
         if not predict:
-            self._apply_trainable()
+            gr = torch.is_grad_enabled()
+            self._apply_trainable((frozenset(n for n in _MLM_ONLY if n in self._flat.named) if label_only else frozenset()) if gr else None)
         if not predict:
             lnd = self.__dict__.get("_lnd")
             if lnd is not None and lnd.items and torch.is_grad_enabled():
@@ -1860,7 +1907,7 @@ class _GpuModelBase(nn.Module):
         if kv_len is not None:
             if infer:
                 pending = self._request_lengths(plan, kv_len, labels, True, (pair_info, B, T))
-            elif labels is not None and torch.is_grad_enabled() and getattr(self, "skip_padded_backward", True):
+            elif (labels is not None or label_only) and torch.is_grad_enabled() and getattr(self, "skip_padded_backward", True):
                 pending = (host[:nseq], None, ev)                     # the prologue's valid[]: unmasked length, extended to the last label
         # ---- embeddings + encoder: one autograd node (_TrunkFn)
         if packed is not None:
@@ -1918,7 +1965,8 @@ class _GpuModelBase(nn.Module):
         # when the caller is forward() / forward_fused() -- only they guarantee that nothing else is differentiated
         t.top_rows = (rows, plan["first"]) if (rows is not None and getattr(self, "sparse_top_layer_backward", True)) else None
         # the caller does not want the prediction scores (trainer.py never reads them): rows that nothing else reads are left out
-        drop = (not infer) and labels is not None and not getattr(self, "return_scores", True)
+        # (a label-only step returns no scores whatever ``return_scores`` says)
+        drop = (not infer) and (label_only or (labels is not None and not getattr(self, "return_scores", True)))
         # The valid-first packing needs the per-sequence lengths on the host.  With the prologue on the input stream (async_prologue)
         # they are there already: the packing is built FIRST and the embedding kernels store their rows in packed order.  With the
         # prologue on the compute stream the host would wait for the GPU to drain: the embedding kernels are queued first (they keep
@@ -3105,8 +3153,22 @@ class MMBertForPretraining(_GpuModelBase):
           (+1-2 % step time); None with ``return_scores = False``;
         * outputs[4], [5], [6] (ap_loss, label_loss, nce) are returned as VALUES by the fused heads path -- the one differentiable
           output is outputs[0], which is what trainer.py differentiates (REF:trainer.py:83); ``model.fused_heads = False``
-          (the eager heads) keeps them in the autograd graph like the reference."""
+          (the eager heads) keeps them in the autograd graph like the reference.
+
+        DECLARED EXTENSION, not in the reference: ``masked_labels=None`` is the LABEL-ONLY step (fine-tuning a head on unmasked text).
+        ``joint_loss = ap_loss + label_loss - beta * nce`` -- the heads' terms of REF :443 with no ``alpha`` term --, outputs[7], [9], [11]
+        are None, everything else and the second return value are as with labels; train and eval mode, with and without autograd.  The
+        MLM head does not run, forward or backward (no label staging, no transform / vocabulary GEMM / cross-entropy, no tied-decoder
+        weight gradient); the heads' [CLS]-row gradient enters the encoder's backward in compact form with an empty labelled-row list,
+        so the top layer's backward runs on the 3 B [CLS] rows (_last_layer_sparse).  The dropout seed sequence advances once, as always.
+        The parameters only the MLM head reads (``cls.predictions.transform.*``, ``cls.predictions.bias``) end such a backward with
+        ``.grad is None`` and the next ``AdamW.step()`` leaves them, their moments, copies and EMA alone, as torch treats a None
+        gradient (one difference: the fused step keeps one step count, so their bias correction does not lag when a standard step
+        updates them again); the word table is still reached through the embeddings.  ``model.fused_heads = False`` raises
+        NotImplementedError, as do ``forward_fused`` and ``parallel.DataParallel`` without labels."""
         self.outputs = ()
+        if masked_labels is None:
+            return self._forward_label_only(input_ids, token_type_ids, attention_mask, ap_label, sentiment)
         ncls = self._check_class_labels(sentiment)
         text_ids, visual, speech = input_ids[:3]
         ap_v, ap_s = ap_label
@@ -3142,6 +3204,28 @@ class MMBertForPretraining(_GpuModelBase):
             scores = tuple(self._scores_view(logits[b[k]:b[k + 1]], B, lens[k]) for k in range(3))
         self.outputs = (_scalar_loss(joint_loss), None, None, None, ap_loss, label_loss, nce,
                         scores[0], t_rel, scores[1], v_rel, scores[2], s_rel)
+        return self.outputs, logits_out
+
+    def _forward_label_only(self, input_ids, token_type_ids, attention_mask, ap_label, sentiment):
+        """forward() without masked_labels (see there): _encode without labels, _ClsRowsFn in the MLM head's place, the heads in-stream."""
+        if not self.fused_heads:
+            raise NotImplementedError("forward(masked_labels=None): fused_heads = False (the eager heads) is not supported by the label-only step")
+        if self.grad_hook is not None or self.head_grad_hook is not None or self.embed_ids_hook is not None:
+            raise NotImplementedError("forward(masked_labels=None): parallel.DataParallel is not supported by the label-only step")
+        self._check_class_labels(sentiment)
+        text_ids = input_ids[0]
+        ap_v, ap_s = ap_label
+        dev = text_ids.device
+        B = text_ids.shape[0]
+        passes = self._three_passes(input_ids, token_type_ids, attention_mask)
+        pk = self._pack_inputs(passes)
+        y, plan, lens, _rows, trunk = self._encode(passes, None, False, packed=None if pk is None else pk[:2], freeze_ok=True, label_only=True)
+        y = y.contiguous()
+        coop = self._heads_read_rows = self._coop_heads_apply(sentiment, B)
+        src = (y, plan["first"]) if coop else None
+        first = _ClsRowsFn.apply(y, self, plan["first"], trunk, coop)
+        joint_loss, ap_loss, label_loss, nce, logits_out, t_rel, v_rel, s_rel = self._run_heads(first, ap_v, ap_s, sentiment, dev, B, mlm=None, coop=coop, src=src)
+        self.outputs = (_scalar_loss(joint_loss), None, None, None, ap_loss, label_loss, nce, None, t_rel, None, v_rel, None, s_rel)
         return self.outputs, logits_out
 
     def predict(self, input_ids, token_type_ids, attention_mask, return_pooled=False, return_attention=None, return_probabilities=False):
@@ -3337,6 +3421,8 @@ class MMBertForPretraining(_GpuModelBase):
         Returns ((joint_loss, None, None, None, ap_loss, label_loss, nce, scores[B,S,V] | None, rel[B,2]), logits[B,1]).
         Checked against oracle.fused_forward (the same extension of the CPU restatement)."""
         self._refuse_lora("forward_fused")
+        if masked_labels is None:
+            raise NotImplementedError("forward_fused(masked_labels=None): the label-only step is forward()'s; forward_fused needs masked_labels")
         self._check_class_labels(sentiment)
         text_ids, visual, speech = input_ids
         am_t, am_v, am_s = attention_mask

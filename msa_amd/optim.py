@@ -158,6 +158,7 @@ class AdamW:
         LayerNorm's weight and bias; the q/k/v weights when H * H % 256 != 0) in different groups raise.  Listed parameters that the
         model's last forward saw frozen (flat.frozen) are skipped as torch skips ``grad is None``: their blocks stay "not owned"."""
         frozen = self._frozen = flat.frozen
+        self._unreached = flat.unreached     # (in ``frozen`` for the steps that do not reach them only: _follow_frozen lets them back)
         self._listed = frozenset(flat.name_at(p._mmb_flat[1]) for g in self.param_groups for p in g["params"])
         flags = flat.flags.clone().cpu()
         flags[flags != 2] = 3                # 3 = not owned by this optimizer -> treated as frozen below
@@ -195,11 +196,13 @@ class AdamW:
 
     def _follow_frozen(self):
         """The model's frozen set changed since the maps were built: rebuilt.  Freezing more parameters keeps their m and v; a parameter
-        of this optimizer that became trainable after the first step() raises."""
+        of this optimizer that became trainable after the first step() raises.  Parameters a label-only step does not reach
+        (flat.unreached: gradient None for that step) are skipped the same way -- p, m, v, the bf16 copies and the EMA keep their bits, no
+        weight decay, no moment decay -- and come back without raising: their m and v are the ones they had, under the shared step count."""
         flat = self._flat
         if flat.frozen == self._frozen:
             return
-        back = sorted(n for n in (self._frozen - flat.frozen) & self._listed if not any(n.startswith(fr) for fr in FROZEN))
+        back = sorted(n for n in ((self._frozen - self._unreached) - flat.frozen) & self._listed if not any(n.startswith(fr) for fr in FROZEN))
         if back and self._steps > 0:
             raise NotImplementedError(f"AdamW: {back[0]}" + (f" (and {len(back) - 1} more)" if len(back) > 1 else "") + " became trainable after this "
                                       "optimizer's first step(): the fused step keeps ONE step count for all parameters, so the parameter's "

@@ -114,10 +114,23 @@ def _stack(seq):
 
 def pack_step_inputs(batch, args, device, generator=None):
     """REF:trainer.py:42-64: MLM masking (re-drawn independently for text / twv / tws), label
-    duplication for the pair positions, tuple packing -- returns the model's keyword arguments."""
+    duplication for the pair positions, tuple packing -- returns the model's keyword arguments.
+    ``args.label_only`` (not a reference argument; ``default_args()`` has it False): the label-only step of
+    ``MMBertForPretraining.forward`` -- no MLM masking (nothing is drawn from ``generator`` or the device's mask seed), the ids as they
+    are, ``masked_labels=None``; train_epoch / eval_epoch / train and dataset.DeviceBatchBuilder.epoch pack through here."""
     text_batch, visual_batch, speech_batch, attention_batch = batch[:4]
     dev = torch.device(device)
     t0, v0, s0 = text_batch[0].to(dev), visual_batch[0].to(dev), speech_batch[0].to(dev)
+    if getattr(args, "label_only", False):
+        return dict(
+            input_ids=(t0, visual_batch[1].to(dev), speech_batch[1].to(dev), v0, s0),
+            token_type_ids=(text_batch[2].to(dev), visual_batch[3].to(dev), speech_batch[3].to(dev)),
+            attention_mask=(text_batch[3].to(dev), (attention_batch[0].to(dev), visual_batch[4].to(dev)),
+                            (attention_batch[1].to(dev), speech_batch[4].to(dev))),
+            masked_labels=None,
+            ap_label=(visual_batch[2].to(dev), speech_batch[2].to(dev)),
+            sentiment=text_batch[-1].to(dev),
+        )
     if args.mlm:
         text_inputs, text_labels = mask_tokens(t0.clone(), args, generator)
         twv_ids, v_labels = mask_tokens(v0.clone(), args, generator)
@@ -239,7 +252,7 @@ class _null:
 def default_args(**kw):
     """The reference's argparse defaults that the loop reads (REF:train.py:24-42)."""
     d = dict(train_batch_size=32, mlm=True, mlm_probability=0.15, gradient_accumulation_step=1, learning_rate=5e-4,
-             warmup_proportion=1.0, n_epochs=200, max_seq_length=40)
+             warmup_proportion=1.0, n_epochs=200, max_seq_length=40, label_only=False)
     d.update(kw)
     return types.SimpleNamespace(**d)
 
