@@ -22,7 +22,7 @@ from __future__ import annotations
 import json
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import contextlib
 
@@ -443,10 +443,32 @@ def _join_wgrads(top):
         torch.cuda.current_stream().wait_event(j[0])
 
 
+def _is_split(layout) -> bool:
+    """Whether ``layout`` is the valid-first packing (ops.SplitLayout: rows_a, inv, perm32) and not the plain one."""
+    return getattr(layout, "split", False)
+
+
+class _LayerSaved(NamedTuple):
+    """What one encoder layer's forward keeps for its backward: both forward forms build it by keyword, backward reads fields.  (A
+    NamedTuple: cheaper on the host than a __slots__ class -- built in 0.31 against 0.62 us, 18 reads 0.35 against 0.40 us.)"""
+    x: torch.Tensor; qkv: torch.Tensor; actx: torch.Tensor; lse: torch.Tensor       # layer input, QKV matrix, attention output and its LSE
+    z1: torch.Tensor; m1: torch.Tensor; r1: torch.Tensor; y1: torch.Tensor          # attention sublayer: pre-LN sum, LN mean / rstd, LN output
+    u: torch.Tensor; g: torch.Tensor; z2: torch.Tensor; m2: torch.Tensor; r2: torch.Tensor    # FFN: pre-activation, GELU output, pre-LN sum, LN mean / rstd
+    d_att: tuple; d_h1: tuple; d_h2: tuple                                          # the dropout triples: attention, behind Wo, behind W2
+    lora: Optional[tuple] = None       # Q/K/V adapters: (h, {target: (A takes a gradient, B takes one)})
+    dense: Optional[dict] = None       # dense-seam adapters: {target: (h, A takes a gradient, B takes one)}
+
+    def head(self, rows):
+        """The record with its tensor fields cut to their leading ``rows`` rows (the adapters' h is cut where it is used)."""
+        return self._make(t[:rows] if torch.is_tensor(t) else t for t in self)
+
+
 class _EncoderFn:
     """L x BertLayer (HF:374-416) over the packed token matrix: the forward / backward bodies that _TrunkFn runs between the
     embedding stage and the heads (plain functions: the whole trunk is ONE autograd node, so no [tokens, H] tensor crosses
-    autograd between its stages)."""
+    autograd between its stages).  A layer is spelled out once per direction and form: ``_layer_forward`` (attention, then
+    ``_forward_behind_attention``, which ``run_top_first`` shares on its gathered rows) and ``_composite_forward``; ``_layer_backward``
+    (``_backward_before_attention``, which ``_last_layer_sparse`` shares on its gathered rows, then attention) and ``_composite_backward``."""
 
     @staticmethod
     def run_forward(top, x, layout, key_bias, seed, kv_len, keep, y_out=None, y_rows=None, stop=None, train=None, probe=None, keep_from=0):
@@ -457,7 +479,7 @@ class _EncoderFn:
         ``keep_from``: the lowest layer whose backward will run (a frozen prefix below it, freeze.TrainablePlan.stop): the layers below keep
         nothing -- no pre-activation, no LayerNorm statistics, ``saved[i]`` is None -- and compute the same bits (dropout included)."""
         cfg = top.config
-        H, L = cfg.hidden_size, cfg.num_hidden_layers
+        L = cfg.num_hidden_layers
         nl = L if stop is None else stop
         train = top.training if train is None else train
         ph = cfg.hidden_dropout_prob if train else 0.0
@@ -467,62 +489,63 @@ class _EncoderFn:
         # One C call per layer (mmbert_layer_fwd: the same seven launches with the same arguments, bit-identical) unless somebody wrapped
         # the per-launch functions (bench.py's event timing, tests that spy on launches) or switched it off (model.composite_layers)
         composite = getattr(top, "composite_layers", True) and ops.launches_unwrapped() and top.debug_hidden is None
-        if composite:
-            AL = ops.attn_layout_struct(key_bias, layout, backward=False)
-            if kv_len is not None and not getattr(layout, "split", False):
-                AL.kv_len = kv_len.data_ptr()
-            I_, M_, dev = cfg.intermediate_size, x.shape[0], x.device
-            heads = layout.heads
-            bf, f32 = torch.bfloat16, torch.float32
-            tq = ops._tile_queue(dev)
-            for i in range(nl):
-                lw = top._lw[i]
-                keep = keep_all and i >= keep_from
-                if lw["lora"] is not None or lw.get("lora_dense") is not None:   # a layer with adapters takes the per-launch form (the composite call has no seam)
-                    x, s_i = _EncoderFn._layer_forward(top, i, x, layout, key_bias, seed, kv_len, keep, pa, ph, y_out, y_rows, probe)
-                    if keep_all:
-                        saved.append(s_i)
-                    continue
-                d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
-                last = i == L - 1 and y_out is not None
-                qkv, actx, z1, y1 = (torch.empty((M_, 3 * H), device=dev, dtype=bf), torch.empty((M_, H), device=dev, dtype=bf),
-                                     torch.empty((M_, H), device=dev, dtype=bf), torch.empty((M_, H), device=dev, dtype=bf))
-                g, z2 = torch.empty((M_, I_), device=dev, dtype=bf), torch.empty((M_, H), device=dev, dtype=bf)
-                lse = torch.empty((M_, heads), device=dev, dtype=f32)
-                u = torch.empty((M_, I_), device=dev, dtype=bf) if keep else None
-                if keep:
-                    m1, r1, m2, r2 = (torch.empty(M_, device=dev, dtype=f32) for _ in range(4))
-                else:
-                    m1 = r1 = m2 = r2 = None
-                y2 = y_out if last else torch.empty((M_, H), device=dev, dtype=bf)
-                a = lw.get("_fwd_args")
-                if a is None:                                        # the layer's constants, once
-                    a = lw["_fwd_args"] = ops._LayerFwd()
-                    for n in ("Wqkv", "Wo", "W1", "W2", "bqkv", "bo", "b1", "b2", "ln1_g", "ln1_b", "ln2_g", "ln2_b"):
-                        assert lw[n].is_contiguous()
-                        setattr(a, n, lw[n].data_ptr())
-                    a.H, a.I, a.ln_eps = H, I_, cfg.layer_norm_eps
-                a.x, a.ldx, a.rows = x.data_ptr(), x.stride(0), M_
-                a.qkv, a.actx, a.lse, a.z1, a.y1, a.g, a.z2 = qkv.data_ptr(), actx.data_ptr(), lse.data_ptr(), z1.data_ptr(), y1.data_ptr(), g.data_ptr(), z2.data_ptr()
-                a.u, a.m1, a.r1, a.m2, a.r2 = ops._ptr(u), ops._ptr(m1), ops._ptr(r1), ops._ptr(m2), ops._ptr(r2)
-                a.y2, a.ldy2, a.y2_rows = y2.data_ptr(), y2.stride(0), ops._ptr(y_rows) if last else None
-                a.tile_queue = tq
-                ops._set_drop(a.att, d_att); ops._set_drop(a.h1, d_h1); ops._set_drop(a.h2, d_h2)
-                ops.layer_fwd(AL, a)
-                if probe is not None:
-                    probe(i, qkv)
-                if keep_all:
-                    saved.append((x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2) if keep else None)
-                x = y2
-            return x, saved
+        cl = _EncoderFn._composite_layout(key_bias, layout, kv_len, x.device, backward=False) if composite else None
         for i in range(nl):
+            lw = top._lw[i]
             keep = keep_all and i >= keep_from
-            x, s_i = _EncoderFn._layer_forward(top, i, x, layout, key_bias, seed, kv_len, keep, pa, ph, y_out, y_rows, probe)
+            last = i == L - 1 and y_out is not None
+            drops = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
+            out, out_rows = (y_out, y_rows) if last else (None, None)
+            # (a layer with adapters takes the per-launch form: the composite call has no seam)
+            if composite and lw["lora"] is None and lw.get("lora_dense") is None:
+                x, s_i = _EncoderFn._composite_forward(top, i, x, cl, layout.heads, keep, drops, out, out_rows, probe)
+            else:
+                x, s_i = _EncoderFn._layer_forward(top, i, x, layout, key_bias, kv_len, keep, drops, out, out_rows, probe)
             if keep_all:
                 saved.append(s_i)
             if top.debug_hidden is not None:
-                top.debug_hidden.setdefault("_layers_packed", []).append(None if (i == L - 1 and y_out is not None) else x.detach())
+                top.debug_hidden.setdefault("_layers_packed", []).append(None if last else x.detach())
         return x, saved
+
+    @staticmethod
+    def _composite_layout(key_bias, layout, kv_len, dev, backward):
+        """(the attention layout struct, the tile queue) that every composite call of one direction of a pass shares."""
+        AL = ops.attn_layout_struct(key_bias, layout, backward=backward)
+        if kv_len is not None and not _is_split(layout):
+            AL.kv_len = kv_len.data_ptr()
+        return AL, ops._tile_queue(dev)
+
+    @staticmethod
+    def _composite_forward(top, i, x, cl, heads, keep, drops, out, out_rows, probe):
+        """One encoder layer from ONE C call (mmbert_layer_fwd): allocates the layer's buffers, fills the struct (the layer's constants
+        once: ``lw["_fwd_args"]``) and returns (output, what backward keeps or None), as _layer_forward does."""
+        cfg = top.config
+        H, I_, M_, dev = cfg.hidden_size, cfg.intermediate_size, x.shape[0], x.device
+        lw = top._lw[i]
+        d_att, d_h1, d_h2 = drops
+        new = lambda cols: torch.empty((M_, cols), device=dev, dtype=torch.bfloat16)
+        qkv, actx, z1, y1, g, z2 = new(3 * H), new(H), new(H), new(H), new(I_), new(H)
+        lse = torch.empty((M_, heads), device=dev, dtype=torch.float32)
+        u = new(I_) if keep else None
+        m1, r1, m2, r2 = (torch.empty(M_, device=dev, dtype=torch.float32) if keep else None for _ in range(4))
+        y2 = out if out is not None else new(H)
+        a = lw.get("_fwd_args")
+        if a is None:                                        # the layer's constants, once
+            a = lw["_fwd_args"] = ops._LayerFwd()
+            for n in ("Wqkv", "Wo", "W1", "W2", "bqkv", "bo", "b1", "b2", "ln1_g", "ln1_b", "ln2_g", "ln2_b"):
+                assert lw[n].is_contiguous()
+                setattr(a, n, lw[n].data_ptr())
+            a.H, a.I, a.ln_eps = H, I_, cfg.layer_norm_eps
+        a.x, a.ldx, a.rows = x.data_ptr(), x.stride(0), M_
+        a.qkv, a.actx, a.lse, a.z1, a.y1, a.g, a.z2 = qkv.data_ptr(), actx.data_ptr(), lse.data_ptr(), z1.data_ptr(), y1.data_ptr(), g.data_ptr(), z2.data_ptr()
+        a.u, a.m1, a.r1, a.m2, a.r2 = ops._ptr(u), ops._ptr(m1), ops._ptr(r1), ops._ptr(m2), ops._ptr(r2)
+        a.y2, a.ldy2, a.y2_rows, a.tile_queue = y2.data_ptr(), y2.stride(0), ops._ptr(out_rows), cl[1]
+        ops._set_drop(a.att, d_att); ops._set_drop(a.h1, d_h1); ops._set_drop(a.h2, d_h2)
+        ops.layer_fwd(cl[0], a)
+        if probe is not None:
+            probe(i, qkv)
+        return y2, _LayerSaved(x=x, qkv=qkv, actx=actx, lse=lse, z1=z1, m1=m1, r1=r1, y1=y1, u=u, g=g, z2=z2, m2=m2, r2=r2,
+                               d_att=d_att, d_h1=d_h1, d_h2=d_h2) if keep else None
 
     @staticmethod
     def _lora_forward(lo, x, qkv, keep):
@@ -567,22 +590,30 @@ class _EncoderFn:
                            dl["gB"][t] if fb else None, dl["scale"], dx=dx, gelu_u=gelu_u, accumulate=True)
 
     @staticmethod
-    def _layer_forward(top, i, x, layout, key_bias, seed, kv_len, keep, pa, ph, y_out, y_rows, probe):
-        """One encoder layer, one call per launch.  Returns (output, what backward keeps or None)."""
-        cfg = top.config
-        H, L = cfg.hidden_size, cfg.num_hidden_layers
+    def _layer_forward(top, i, x, layout, key_bias, kv_len, keep, drops, out, out_rows, probe):
+        """One encoder layer, one call per launch.  ``drops``: its dropout triples (attention, behind Wo, behind W2); ``out`` /
+        ``out_rows``: run_forward's y_out / y_rows on the last layer.  Returns (output, what backward keeps or None)."""
         lw = top._lw[i]
-        d_att, d_h1, d_h2 = (ops.make_drop(pa, seed, 8 * i), ops.make_drop(ph, seed, 8 * i + 1), ops.make_drop(ph, seed, 8 * i + 2))
+        d_att, d_h1, d_h2 = drops
         qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
         ls = _EncoderFn._lora_forward(lw["lora"], x, qkv, keep) if lw["lora"] is not None else None
-        actx, lse = ops.attn_fwd(qkv, key_bias, layout, H, drop=d_att, kv_len=kv_len)
+        actx, lse = ops.attn_fwd(qkv, key_bias, layout, top.config.hidden_size, drop=d_att, kv_len=kv_len)
         if probe is not None:
             probe(i, qkv)
+        y2, kept = _EncoderFn._forward_behind_attention(top, lw, actx, x, keep, d_h1, d_h2, out, out_rows)
+        return y2, _LayerSaved(x=x, qkv=qkv, actx=actx, lse=lse, d_att=d_att, d_h1=d_h1, d_h2=d_h2, lora=ls, **kept) if keep else None
+
+    @staticmethod
+    def _forward_behind_attention(top, lw, actx, xr, keep, d_h1=None, d_h2=None, out=None, out_rows=None):
+        """Everything behind the attention of a layer, one call per launch, each dense-seam adapter directly behind its projection's GEMM.
+        ``actx`` / ``xr`` (the residual): all rows of the layer, or the gathered rows of run_top_first; ``out`` / ``out_rows``: where the last
+        LayerNorm writes.  Returns (output, the _LayerSaved fields it produced or None when nothing is kept)."""
+        cfg = top.config
         dl, ds = lw.get("lora_dense"), {}
-        z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=x, drop=d_h1)
+        z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=xr, drop=d_h1)
         ds["attention_output"] = _EncoderFn._dense_forward(dl, "attention_output", actx, z1, keep, drop=d_h1)
         y1, m1, r1 = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=keep)
-        u = torch.empty((x.shape[0], cfg.intermediate_size), device=x.device, dtype=torch.bfloat16) if keep else None
+        u = torch.empty((xr.shape[0], cfg.intermediate_size), device=xr.device, dtype=torch.bfloat16) if keep else None
         if dl is not None and "intermediate" in dl["targets"]:
             # GELU is not linear: the GEMM leaves bf16(v) (bias only), the adapter launch adds its delta, stores the pre-activation and applies GELU
             g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"])
@@ -591,17 +622,9 @@ class _EncoderFn:
             g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True, aux=u)
         z2 = ops.gemm_nt(g, lw["W2"], bias=lw["b2"], resid=y1, drop=d_h2)
         ds["ffn_output"] = _EncoderFn._dense_forward(dl, "ffn_output", g, z2, keep, drop=d_h2)
-        last = i == L - 1 and y_out is not None
-        y2, m2, r2 = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=keep,
-                                out=y_out if last else None, out_rows=y_rows if last else None)
-        s_i = None
-        if keep:
-            s_i = (x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2)
-            if ls is not None or dl is not None:
-                s_i = s_i + (ls,)                                # (a 17th entry on layers with adapters only; None without Q / K / V adapters)
-            if dl is not None:
-                s_i = s_i + ({t: v for t, v in ds.items() if v is not None},)   # (an 18th with dense adapters: {target: (h, flags)})
-        return y2, s_i
+        y2, m2, r2 = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=keep, out=out, out_rows=out_rows)
+        return y2, dict(z1=z1, m1=m1, r1=r1, y1=y1, u=u, g=g, z2=z2, m2=m2, r2=r2,
+                        dense=None if dl is None else {t: v for t, v in ds.items() if v is not None}) if keep else None
 
     @staticmethod
     def run_top_first(top, x, layout, key_bias, kv_len, q_rows, probe=None):
@@ -623,19 +646,8 @@ class _EncoderFn:
             probe(cfg.num_hidden_layers - 1, qkv)
         del qkv
         xr = ops.gather_rows([x], q_rows)[0]
-        dl = lw.get("lora_dense")                                 # (the dense adapters on the gathered rows; no dropout here: c = 1)
-        z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=xr)
-        _EncoderFn._dense_forward(dl, "attention_output", actx, z1, False)
-        y1, _, _ = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=False)
-        if dl is not None and "intermediate" in dl["targets"]:
-            g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"])
-            _EncoderFn._dense_forward(dl, "intermediate", y1, g, False, mode=ops.LORA_DENSE_GELU)
-        else:
-            g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True)
-        z2 = ops.gemm_nt(g, lw["W2"], bias=lw["b2"], resid=y1)
-        _EncoderFn._dense_forward(dl, "ffn_output", g, z2, False)
-        y2, _, _ = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=False)
-        return y2
+        # (the dense adapters too run on the gathered rows; nothing is kept and no dropout here: c = 1)
+        return _EncoderFn._forward_behind_attention(top, lw, actx, xr, False)[0]
 
     @staticmethod
     def run_backward(top, layout, key_bias, kv_len, saved, dy, dy_rows, top_rows, compact=None, lnd=None, fz=None):
@@ -664,8 +676,8 @@ class _EncoderFn:
             for i in reversed(range(L)):
                 top._layer_grads_done(i)
             return None
-        M_all = saved[stop][0].shape[0]
-        ra = layout.rows_a if getattr(layout, "split", False) else M_all
+        M_all = saved[stop].x.shape[0]
+        ra = layout.rows_a if _is_split(layout) else M_all
         if dy is not None and dy_rows is None and ra < dy.shape[0]:
             dy = dy[:ra]
         # LayerNorm' leaves its gamma / beta partial sums in a workspace; ONE reduce launch folds all layers' sums into the gradients at
@@ -681,43 +693,35 @@ class _EncoderFn:
         if dw is None and _DEFER_ENV:
             dw = _DEFER_ENV != "0"
         if dw is None:
-            dw = _auto_defer_wgrads(H, top.config.intermediate_size, L, x_dev=saved[stop][0].device, rows=ra)
+            dw = _auto_defer_wgrads(H, top.config.intermediate_size, L, x_dev=saved[stop].x.device, rows=ra)
         defer_wgrads, deferred = (top.grad_hook is None and bool(dw)), []
         composite_bwd = getattr(top, "composite_layers", True) and ops.launches_unwrapped()
-        AL = tq = None
+        cl = None
         for i in reversed(range(stop, L)):
             lw = top._lw[i]
-            modes = None if fz is None else fz.layers[i]
             skip_dx = no_dx and i == stop
-            saved_i = saved[i]
+            s = saved[i]
             saved[i] = None
             if ra < M_all:
-                saved_i = tuple(t[:ra] if torch.is_tensor(t) else t for t in saved_i)
-            x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i[:16]
-            lora_s = saved_i[16] if len(saved_i) > 16 else None          # (h, gradient flags) of a layer with adapters
-            dense_s = saved_i[17] if len(saved_i) > 17 else None         # {dense target: (h, gradient flags)}
-            dl = lw.get("lora_dense")
-            g2g, g2b, g1g, g1b = _ln_grads(lw, fz, i)
+                s = s.head(ra)
             if i == L - 1 and (top_rows is not None or compact is not None):
-                R = None
-                R32 = None
+                R = R32 = None
                 if compact is not None:
                     rows_l, rows_f, dy_c = compact                # labelled rows (int32 / int64), [CLS] rows (int64), their gradients stacked
                     # (with the list's stamped inverse: the two gradients that go back to full height below do so in one launch)
                     rinv = top.__dict__.get("_row_inverse")
                     if rinv is None or rinv.table.numel() < M_all or rinv.table.device != rows_f.device:
                         rinv = top.__dict__["_row_inverse"] = ops.RowInverse(M_all, rows_f.device)
-                    R, R32 = ops.compact_rows(rows_l, rows_f, layout.inv if getattr(layout, "split", False) else None, inverse=rinv)
+                    R, R32 = ops.compact_rows(rows_l, rows_f, layout.inv if _is_split(layout) else None, inverse=rinv)
                 elif top_rows is not None:
                     Ro = _EncoderFn._sparse_rows(top_rows, None, ra)          # rows in the caller's order
                     if Ro is not None:
-                        R = layout.inv.index_select(0, Ro) if getattr(layout, "split", False) else Ro
+                        R = layout.inv.index_select(0, Ro) if _is_split(layout) else Ro
                         src_rows = Ro if dy_rows is not None else R            # dy is in the caller's order iff it comes with a map
                         (dy_c,) = ops.gather_rows([dy], src_rows.int())
                 if R is not None:
-                    dy = _EncoderFn._last_layer_sparse(top, lw, layout, key_bias, kv_len, saved_i, dy_c, R, H, ra, R32, lnd,
-                                                       rinv if compact is not None else None, deferred if defer_wgrads else None, modes, skip_dx,
-                                                       (g2g, g2b, g1g, g1b))
+                    dy = _EncoderFn._last_layer_sparse(top, i, layout, key_bias, kv_len, s, dy_c, R, R32, lnd, rinv if compact is not None else None,
+                                                       deferred if defer_wgrads else None, fz, skip_dx)
                     if top.grad_hook is not None:
                         lnd.flush()
                     dy_rows = None
@@ -725,81 +729,21 @@ class _EncoderFn:
                     continue
                 if compact is not None:
                     raise RuntimeError("compact output gradient without the sparse top-layer path")
-            if composite_bwd and lora_s is None and dense_s is None:
-                # the seven launches of the dense backward body from ONE C call (mmbert_layer_bwd: same kernels, same arguments, bit-identical)
-                dev, bf = z2.device, torch.bfloat16
-                I_ = top.config.intermediate_size
-                if AL is None:
-                    AL = ops.attn_layout_struct(key_bias, layout, backward=True)
-                    if kv_len is not None and not getattr(layout, "split", False):
-                        AL.kv_len = kv_len.data_ptr()
-                    tq = ops._tile_queue(dev)
-                dz2, dz1, dy1, dctx = (torch.empty((ra, H), device=dev, dtype=bf) for _ in range(4))
-                dx_ = None if skip_dx else torch.empty((ra, H), device=dev, dtype=bf)
-                dz2d = torch.empty((ra, H), device=dev, dtype=bf) if d_h2[1] else None
-                dz1d = torch.empty((ra, H), device=dev, dtype=bf) if d_h1[1] else None
-                du, dqkv = torch.empty((ra, I_), device=dev, dtype=bf), torch.empty((ra, 3 * H), device=dev, dtype=bf)
-                delta = torch.empty((ra, layout.heads), device=dev, dtype=torch.float32)
-                lnd.reserve(2, ra, H, dev)                           # (both slots are taken before their launches: no flush in between)
-                ws2 = lnd.slot(ra, H, dev, g2g, g2b, None)
-                ws1 = lnd.slot(ra, H, dev, g1g, g1b, None)
-                b = lw.get("_bwd_args")
-                if b is None:
-                    b = lw["_bwd_args"] = ops._LayerBwd()
-                    for n in ("W2T", "W1T", "WoT", "WqkvT", "ln2_g", "ln1_g", "g_ln2_g", "g_ln2_b", "g_ln1_g", "g_ln1_b"):
-                        assert lw[n].is_contiguous()
-                        setattr(b, n, lw[n].data_ptr())
-                    b.H, b.I = H, I_
-                b.dy, b.lddy, b.dy_rows, b.rows = dy.data_ptr(), dy.stride(0), ops._ptr(dy_rows), ra
-                b.z2, b.m2, b.r2, b.ln2_ws, b.z1, b.m1, b.r1, b.ln1_ws = z2.data_ptr(), m2.data_ptr(), r2.data_ptr(), ws2, z1.data_ptr(), m1.data_ptr(), r1.data_ptr(), ws1
-                b.u, b.qkv, b.actx, b.lse = u.data_ptr(), qkv.data_ptr(), actx.data_ptr(), lse.data_ptr()
-                b.dz2, b.dz2d, b.du, b.dy1, b.dz1, b.dz1d = dz2.data_ptr(), ops._ptr(dz2d), du.data_ptr(), dy1.data_ptr(), dz1.data_ptr(), ops._ptr(dz1d)
-                b.dctx, b.dqkv, b.delta, b.dx, b.tile_queue = dctx.data_ptr(), dqkv.data_ptr(), delta.data_ptr(), ops._ptr(dx_), tq
-                ops._set_drop(b.att, d_att); ops._set_drop(b.h1, d_h1); ops._set_drop(b.h2, d_h2)
-                ops.layer_bwd(AL, b)
-                dy_rows = None
-                dy = dx_
-                if dz2d is None:
-                    dz2d = dz2
-                if dz1d is None:
-                    dz1d = dz1
+            ln_grads = _ln_grads(lw, fz, i)
+            if composite_bwd and s.lora is None and s.dense is None:
+                if cl is None:
+                    cl = _EncoderFn._composite_layout(key_bias, layout, kv_len, s.z2.device, backward=True)
+                dy, grads = _EncoderFn._composite_backward(top, i, s, cl, layout.heads, dy, dy_rows, lnd, ln_grads, skip_dx)
             else:
-              # --- output sublayer: y2 = LN(dropout(g.W2^T + b2) + y1)      (b2 / bo gradients = column sums of dz2d / dz1d: they ride
-              # on the weight-gradient launch below, like b1 and bqkv, on an all-ones MFMA operand)
-              dz2d = torch.empty((ra, H), device=z2.device, dtype=torch.bfloat16) if d_h2[1] else None
-              dz2 = ops.ln_bwd(dy, z2, m2, r2, lw["ln2_g"], g2g, g2b, dx2=dz2d, pre_drop=d_h2, deferred=lnd, dy_rows=dy_rows)
-              dy_rows = None
-              if dz2d is None:
-                  dz2d = dz2
-              du = ops.gemm_nt(dz2d, lw["W2T"], gelu_bwd_u=u)
-              # (the dense adapters update the input gradients in place, each directly behind the GEMM that wrote it: the buffers are fresh
-              # and nothing launched earlier reads them; the weight-gradient problems below read the final du)
-              _EncoderFn._dense_backward(dl, dense_s, "ffn_output", dz2d, g, du, gelu_u=u)
-              dy1 = ops.gemm_nt(du, lw["W1T"], resid=dz2)
-              _EncoderFn._dense_backward(dl, dense_s, "intermediate", du, y1, dy1)
-              # --- attention sublayer: y1 = LN(dropout(ctx.Wo^T + bo) + x)
-              dz1d = torch.empty((ra, H), device=z2.device, dtype=torch.bfloat16) if d_h1[1] else None
-              dz1 = ops.ln_bwd(dy1, z1, m1, r1, lw["ln1_g"], g1g, g1b, dx2=dz1d, pre_drop=d_h1, deferred=lnd)
-              if dz1d is None:
-                  dz1d = dz1
-              dctx = ops.gemm_nt(dz1d, lw["WoT"])
-              _EncoderFn._dense_backward(dl, dense_s, "attention_output", dz1d, actx, dctx)
-              dqkv = ops.attn_bwd(qkv, actx, dctx, lse, key_bias, layout, H, drop=d_att, kv_len=kv_len)
-              dres = dz1
-              if lora_s is not None:
-                  # (a buffer of its own: dz1 can be dz1d, which the Wo weight gradient below still reads)
-                  dres = _EncoderFn._lora_backward(top, lw["lora"], lora_s, dqkv, x, None if skip_dx else dz1)
-              dy = None if skip_dx else ops.gemm_nt(dqkv, lw["WqkvT"], resid=dres)
+                dy, grads = _EncoderFn._layer_backward(top, i, s, layout, key_bias, kv_len, dy, dy_rows, lnd, ln_grads, skip_dx)
+            dy_rows = None
             # --- all four weight gradients (+ their bias gradients) of the layer in ONE launch.  (They are off the critical path of backward;
             # a side stream for them was measured a loss in rounds 1, 3 and 4 -- the chip's power envelope is shared -- and is gone.)
-            probs = [(du, y1, lw["g_W1"], lw["g_b1"]), (dz2d, g, lw["g_W2"], lw["g_b2"]),
-                     (dqkv, x, lw["g_Wqkv"], lw["g_bqkv"]), (dz1d, actx, lw["g_Wo"], lw["g_bo"])]
-            if modes is not None:
-                # frozen weights: their problems leave the launch; a trainable bias of a frozen weight gets its column sum from ONE grouped
-                # launch per layer (the bias gradients are zero-filled by the optimizer: always added)
-                probs, sums = _trainable_probs(list(zip(("w1", "w2", "qkv", "o"), probs)), modes)
-                if sums:
-                    ops.colsum_grouped(sums, accumulate=True)
+            # Frozen weights: their problems leave the launch; a trainable bias of a frozen weight gets its column sum from ONE grouped
+            # launch per layer (the bias gradients are zero-filled by the optimizer: always added)
+            probs, sums = _trainable_probs(_EncoderFn._wgrad_problems(lw, s, *grads), None if fz is None else fz.layers[i])
+            if sums:
+                ops.colsum_grouped(sums, accumulate=True)
             if defer_wgrads:
                 # One GPU (no gradient hook): nothing needs this layer's weight gradients before the optimizer, so ALL dense layers'
                 # weight gradients can go out as ONE call at the end of backward, in whole rounds of 256 tiles (11 layers = 1188
@@ -812,21 +756,18 @@ class _EncoderFn:
                 deferred.extend(probs)
                 top._layer_grads_done(i)
                 continue
-            if pair_wgrads:
-                # Two layers per launch: a layer's 108 tiles leave the chip half empty, so a single layer splits the token axis in two
-                # (fp32 slabs + a reduce launch, 12 us and 85 MB per layer); two layers' 216 tiles fill it in one round unsplit.  The
-                # upper layer of a pair just keeps its operands alive for one more layer (fresh buffers from the caching allocator)
-                if held is None and i > stop:
-                    held = (i, probs)
-                    continue
-                if held is not None:
-                    _wgrad(top, held[1] + probs)
-                    if top.grad_hook is not None:
-                        lnd.flush()
-                    top._layer_grads_done(held[0])
-                    held = None
-                else:
-                    _wgrad(top, probs)
+            # pair_wgrads: two layers per launch: a layer's 108 tiles leave the chip half empty, so a single layer splits the token axis in
+            # two (fp32 slabs + a reduce launch, 12 us and 85 MB per layer); two layers' 216 tiles fill it in one round unsplit.  The
+            # upper layer of a pair just keeps its operands alive for one more layer (fresh buffers from the caching allocator)
+            if pair_wgrads and held is None and i > stop:
+                held = (i, probs)
+                continue
+            if held is not None:
+                _wgrad(top, held[1] + probs)
+                if top.grad_hook is not None:
+                    lnd.flush()
+                top._layer_grads_done(held[0])
+                held = None
             else:
                 _wgrad(top, probs)
             if top.grad_hook is not None:
@@ -851,87 +792,145 @@ class _EncoderFn:
         if 4 * r > ra or int(host[1]) != 0:                       # a labelled [CLS] row would be gathered twice: dense backward
             return None
         R = torch.cat((idx[:n].long(), first))
-        if layout is not None and getattr(layout, "split", False):
+        if layout is not None and _is_split(layout):
             R = layout.inv.index_select(0, R)
         return R
 
     @staticmethod
-    def _last_layer_sparse(top, lw, layout, key_bias, kv_len, saved_i, dy_c, R, H, ra, R32=None, lnd=None, rinv=None, deferred=None, modes=None,
-                           skip_dx=False, ln_grads=None):
-        """Backward of the top encoder layer when only the rows R of its output carry a gradient: the output sublayer (LayerNorm',
-        FFN-down and FFN-up input gradients, their weight gradients), LayerNorm' and the output projection of the attention
+    def _composite_backward(top, i, s, cl, heads, dy, dy_rows, lnd, ln_grads, skip_dx):
+        """One encoder layer's backward from ONE C call (mmbert_layer_bwd: the launches of _layer_backward with the same arguments,
+        bit-identical): allocates the gradients, fills the struct (the layer's constants once: ``lw["_bwd_args"]``) and returns what
+        _layer_backward returns."""
+        H, I_ = top.config.hidden_size, top.config.intermediate_size
+        lw = top._lw[i]
+        g2g, g2b, g1g, g1b = ln_grads
+        ra, dev = s.z2.shape[0], s.z2.device
+        new = lambda cols: torch.empty((ra, cols), device=dev, dtype=torch.bfloat16)
+        dz2, dz1, dy1, dctx = new(H), new(H), new(H), new(H)
+        dx = None if skip_dx else new(H)
+        dz2d, dz1d = new(H) if s.d_h2[1] else None, new(H) if s.d_h1[1] else None
+        du, dqkv = new(I_), new(3 * H)
+        delta = torch.empty((ra, heads), device=dev, dtype=torch.float32)
+        lnd.reserve(2, ra, H, dev)                           # (both slots are taken before their launches: no flush in between)
+        ws2 = lnd.slot(ra, H, dev, g2g, g2b, None)
+        ws1 = lnd.slot(ra, H, dev, g1g, g1b, None)
+        b = lw.get("_bwd_args")
+        if b is None:
+            b = lw["_bwd_args"] = ops._LayerBwd()
+            for n in ("W2T", "W1T", "WoT", "WqkvT", "ln2_g", "ln1_g", "g_ln2_g", "g_ln2_b", "g_ln1_g", "g_ln1_b"):
+                assert lw[n].is_contiguous()
+                setattr(b, n, lw[n].data_ptr())
+            b.H, b.I = H, I_
+        b.dy, b.lddy, b.dy_rows, b.rows = dy.data_ptr(), dy.stride(0), ops._ptr(dy_rows), ra
+        b.z2, b.m2, b.r2, b.ln2_ws, b.z1, b.m1, b.r1, b.ln1_ws = s.z2.data_ptr(), s.m2.data_ptr(), s.r2.data_ptr(), ws2, s.z1.data_ptr(), s.m1.data_ptr(), s.r1.data_ptr(), ws1
+        b.u, b.qkv, b.actx, b.lse = s.u.data_ptr(), s.qkv.data_ptr(), s.actx.data_ptr(), s.lse.data_ptr()
+        b.dz2, b.dz2d, b.du, b.dy1, b.dz1, b.dz1d = dz2.data_ptr(), ops._ptr(dz2d), du.data_ptr(), dy1.data_ptr(), dz1.data_ptr(), ops._ptr(dz1d)
+        b.dctx, b.dqkv, b.delta, b.dx, b.tile_queue = dctx.data_ptr(), dqkv.data_ptr(), delta.data_ptr(), ops._ptr(dx), cl[1]
+        ops._set_drop(b.att, s.d_att); ops._set_drop(b.h1, s.d_h1); ops._set_drop(b.h2, s.d_h2)
+        ops.layer_bwd(cl[0], b)
+        return dx, (du, dz2 if dz2d is None else dz2d, dqkv, dz1 if dz1d is None else dz1d)
+
+    @staticmethod
+    def _layer_backward(top, i, s, layout, key_bias, kv_len, dy, dy_rows, lnd, ln_grads, skip_dx):
+        """One encoder layer's backward, one call per launch: _backward_before_attention, attention, the Q/K/V adapters, the input
+        gradient (not with ``skip_dx``).  Returns (dx or None, (du, dz2d, dqkv, dz1d): the gradients _wgrad_problems takes)."""
+        lw = top._lw[i]
+        _dz2, dz2d, du, _dy1, dz1, dz1d, dctx = _EncoderFn._backward_before_attention(lw, s, dy, lnd, ln_grads, dy_rows=dy_rows)
+        dqkv = ops.attn_bwd(s.qkv, s.actx, dctx, s.lse, key_bias, layout, top.config.hidden_size, drop=s.d_att, kv_len=kv_len)
+        dres = dz1
+        if s.lora is not None:
+            # (a buffer of its own: dz1 can be dz1d, which the Wo weight gradient still reads)
+            dres = _EncoderFn._lora_backward(top, lw["lora"], s.lora, dqkv, s.x, None if skip_dx else dz1)
+        dx = None if skip_dx else ops.gemm_nt(dqkv, lw["WqkvT"], resid=dres)
+        return dx, (du, dz2d, dqkv, dz1d)
+
+    @staticmethod
+    def _backward_before_attention(lw, s, dy, lnd, ln_grads, dy_rows=None, rows=None):
+        """The backward of everything behind a layer's attention, one call per launch, on the operands of ``s``: all rows of the layer
+        (``dy_rows``: the map the first LayerNorm' reads ``dy`` through), or -- ``rows`` = their int32 list -- the gathered rows of
+        _last_layer_sparse: ``s`` then holds the gathered m / r / u / y1 / g / actx, both LayerNorm' read z and the dropout masks of the
+        ORIGINAL rows through the list, the adapters recompute h from the gathered operands (the same bits as the saved rows, instead of
+        widening the gather) and the W1 input gradient of at most 1024 rows is a split-K launch (K = 4H, 18 output tiles: 50 -> 15 us at
+        the headline shape).  Returns dz2, dz2d, du, dy1, dz1, dz1d, dctx (dz?d: in front of the sublayer's dropout; dz? itself without one)."""
+        g2g, g2b, g1g, g1b = ln_grads
+        dl, full = lw.get("lora_dense"), rows is None
+        n, H = s.m2.shape[0], s.z2.shape[1]
+        # --- output sublayer: y2 = LN(dropout(g.W2^T + b2) + y1)
+        dz2d = torch.empty((n, H), device=s.z2.device, dtype=torch.bfloat16) if s.d_h2[1] else None
+        dz2 = ops.ln_bwd(dy, s.z2, s.m2, s.r2, lw["ln2_g"], g2g, g2b, dx2=dz2d, pre_drop=s.d_h2, deferred=lnd, dy_rows=dy_rows,
+                         x_rows=rows, drop_rows=rows)
+        if dz2d is None:
+            dz2d = dz2
+        du = ops.gemm_nt(dz2d, lw["W2T"], gelu_bwd_u=s.u)
+        # (the dense adapters update the input gradients in place, each directly behind the GEMM that wrote it: the buffers are fresh
+        # and nothing launched earlier reads them; the weight-gradient problems read the final du)
+        _EncoderFn._dense_backward(dl, s.dense, "ffn_output", dz2d, s.g, du, gelu_u=s.u, saved_h=full)
+        dy1 = ops.gemm_nt(du, lw["W1T"], resid=dz2) if full or n > 1024 else ops.gemm_nt_splitk(du, lw["W1T"], resid=dz2)
+        _EncoderFn._dense_backward(dl, s.dense, "intermediate", du, s.y1, dy1, saved_h=full)
+        # --- attention sublayer: y1 = LN(dropout(ctx.Wo^T + bo) + x)
+        dz1d = torch.empty((n, H), device=s.z2.device, dtype=torch.bfloat16) if s.d_h1[1] else None
+        dz1 = ops.ln_bwd(dy1, s.z1, s.m1, s.r1, lw["ln1_g"], g1g, g1b, dx2=dz1d, pre_drop=s.d_h1, deferred=lnd, x_rows=rows, drop_rows=rows)
+        if dz1d is None:
+            dz1d = dz1
+        dctx = ops.gemm_nt(dz1d, lw["WoT"])
+        _EncoderFn._dense_backward(dl, s.dense, "attention_output", dz1d, s.actx, dctx, saved_h=full)
+        return dz2, dz2d, du, dy1, dz1, dz1d, dctx
+
+    @staticmethod
+    def _wgrad_problems(lw, s, du, dz2d, dqkv, dz1d):
+        """The layer's four weight-gradient problems, keyed for _trainable_probs: (dY, X, gW, gb) with X from ``s`` (on the sparse top layer
+        the gathered record, whose x is still every row) -- the bias gradients are column sums of dY on the launch's all-ones MFMA operand."""
+        return [("w1", (du, s.y1, lw["g_W1"], lw["g_b1"])), ("w2", (dz2d, s.g, lw["g_W2"], lw["g_b2"])),
+                ("qkv", (dqkv, s.x, lw["g_Wqkv"], lw["g_bqkv"])), ("o", (dz1d, s.actx, lw["g_Wo"], lw["g_bo"]))]
+
+    @staticmethod
+    def _last_layer_sparse(top, i, layout, key_bias, kv_len, s, dy_c, R, R32, lnd, rinv, deferred, fz, skip_dx):
+        """Backward of the top encoder layer ``i`` when only the rows R of its output carry a gradient ``dy_c``: the output sublayer
+        (LayerNorm', FFN-down and FFN-up input gradients, their weight gradients), LayerNorm' and the output projection of the attention
         sublayer run on those rows only (gathered operands, the dropout masks of the ORIGINAL rows); attention's backward is
-        dense again (every unmasked key receives a gradient), as is everything below.  ``modes`` / ``skip_dx``: as in run_backward (the
-        layer's frozen weights; no input gradient when the layer is where backward ends); ``ln_grads``: _ln_grads of the layer."""
-        cfg = top.config
-        g2g, g2b, g1g, g1b = ln_grads if ln_grads is not None else _ln_grads(lw, None, cfg.num_hidden_layers - 1)
-        x, qkv, actx, lse, z1, m1, r1, y1, u, g, z2, m2, r2, d_att, d_h1, d_h2 = saved_i[:16]
-        lora_s = saved_i[16] if len(saved_i) > 16 else None
-        dense_s = saved_i[17] if len(saved_i) > 17 else None
-        dl = lw.get("lora_dense")
+        dense again (every unmasked key receives a gradient), as is everything below.  ``s``: the layer's record, cut to the backward's rows;
+        ``R32`` / ``rinv``: R as int32 and its stamped inverse where the caller has them; ``deferred`` / ``fz`` / ``skip_dx``: run_backward's."""
+        lw = top._lw[i]
+        ln_grads = _ln_grads(lw, fz, i)
+        ra, H = s.x.shape[0], top.config.hidden_size
         if R32 is None:
             R32 = R.int()
         # the rows R of every saved activation this path reads, in ONE launch (9 index_select launches before)
-        m2_c, r2_c, u_c, m1_c, r1_c, y1_c, g_c, actx_c = ops.gather_rows([m2, r2, u, m1, r1, y1, g, actx], R32)
-        dy = dy_c
-        dz2d_c = torch.empty_like(dy_c) if d_h2[1] else None
-        dz2_c = ops.ln_bwd(dy_c, z2, m2_c, r2_c, lw["ln2_g"], g2g, g2b, x_rows=R32, dx2=dz2d_c, pre_drop=d_h2,
-                           drop_rows=R32, deferred=lnd)
-        if dz2d_c is None:
-            dz2d_c = dz2_c
-        du_c = ops.gemm_nt(dz2d_c, lw["W2T"], gelu_bwd_u=u_c)
-        # (dense adapters on the gathered rows; h is recomputed from them -- the same bits as the saved rows -- instead of widening the gather)
-        _EncoderFn._dense_backward(dl, dense_s, "ffn_output", dz2d_c, g_c, du_c, gelu_u=u_c, saved_h=False)
-        # K = 4H with a few hundred rows: 18 output tiles -> split-K (50 -> 15 us at the headline shape)
-        dy1_c = ops.gemm_nt_splitk(du_c, lw["W1T"], resid=dz2_c) if du_c.shape[0] <= 1024 else ops.gemm_nt(du_c, lw["W1T"], resid=dz2_c)
-        _EncoderFn._dense_backward(dl, dense_s, "intermediate", du_c, y1_c, dy1_c, saved_h=False)
-        dz1d_c = torch.empty_like(dy_c) if d_h1[1] else None
-        dz1_c = ops.ln_bwd(dy1_c, z1, m1_c, r1_c, lw["ln1_g"], g1g, g1b, x_rows=R32, dx2=dz1d_c, pre_drop=d_h1,
-                           drop_rows=R32, deferred=lnd)
-        if dz1d_c is None:
-            dz1d_c = dz1_c
-        dctx_c = ops.gemm_nt(dz1d_c, lw["WoT"])
-        _EncoderFn._dense_backward(dl, dense_s, "attention_output", dz1d_c, actx_c, dctx_c, saved_h=False)
+        m2_c, r2_c, u_c, m1_c, r1_c, y1_c, g_c, actx_c = ops.gather_rows([s.m2, s.r2, s.u, s.m1, s.r1, s.y1, s.g, s.actx], R32)
+        sc = s._replace(m2=m2_c, r2=r2_c, u=u_c, m1=m1_c, r1=r1_c, y1=y1_c, g=g_c, actx=actx_c)
+        _dz2_c, dz2d_c, du_c, _dy1_c, dz1_c, dz1d_c, dctx_c = _EncoderFn._backward_before_attention(lw, sc, dy_c, lnd, ln_grads, rows=R32)
         if rinv is not None:                                      # both full-height gradients in ONE launch (zero fill + index_copy_, twice, before)
             dctx, dz1 = ops.scatter_rows_zero([dctx_c, dz1_c], rinv, ra)
         else:
-            dctx = torch.zeros((ra, H), device=dy.device, dtype=torch.bfloat16)
+            dctx = torch.zeros((ra, H), device=dy_c.device, dtype=torch.bfloat16)
             dctx.index_copy_(0, R, dctx_c)
         # only the rows R of this layer's attention output have a gradient: the query loops of its backward stop at the last of them
         # in every sequence (the labelled text rows and [CLS] sit in a sequence's first rows: one 64-row query tile instead of ~7).
         # Exact: a query row with dO = 0 has delta = 0 and dS = 0 (round 4; model.top_layer_query_limit = False switches it off)
         qlim = ops.attn_q_limit(R32, layout) if getattr(top, "top_layer_query_limit", True) else None
-        dqkv = ops.attn_bwd(qkv, actx, dctx, lse, key_bias, layout, H, drop=d_att, kv_len=kv_len, q_limit=qlim)
+        dqkv = ops.attn_bwd(s.qkv, s.actx, dctx, s.lse, key_bias, layout, H, drop=s.d_att, kv_len=kv_len, q_limit=qlim)
         if rinv is None:
-            dz1 = torch.zeros((ra, H), device=dy.device, dtype=torch.bfloat16)
+            dz1 = torch.zeros((ra, H), device=dy_c.device, dtype=torch.bfloat16)
             dz1.index_copy_(0, R, dz1_c)
-        if lora_s is not None:
-            dz1 = _EncoderFn._lora_backward(top, lw["lora"], lora_s, dqkv, x, None if skip_dx else dz1)
+        if s.lora is not None:
+            dz1 = _EncoderFn._lora_backward(top, lw["lora"], s.lora, dqkv, s.x, None if skip_dx else dz1)
         out = None if skip_dx else ops.gemm_nt(dqkv, lw["WqkvT"], resid=dz1)
         # (bias gradients b1 / b2 / bo: column sums of the bf16 gradients on the ones-operand MFMA, as in the dense layers)
-        few = [(du_c, y1_c, lw["g_W1"], lw["g_b1"]), (dz2d_c, g_c, lw["g_W2"], lw["g_b2"]), (dz1d_c, actx_c, lw["g_Wo"], lw["g_bo"])]
-        if modes is not None:
-            few, sums = _trainable_probs(list(zip(("w1", "w2", "o"), few)), modes)
-            wide, sums_w = _trainable_probs([("qkv", (dqkv, x, lw["g_Wqkv"], lw["g_bqkv"]))], modes)
-            if sums + sums_w:
-                ops.colsum_grouped(sums + sums_w, accumulate=True)
-            if deferred is not None and getattr(top, "late_wgrads", True):
-                deferred.extend(wide)
-                for q in few:
-                    _late_wgrad(top, q, True)
-            else:
-                _wgrad(top, few)
-                _wgrad(top, wide)
-            return out
+        keyed = _EncoderFn._wgrad_problems(lw, sc, du_c, dz2d_c, dqkv, dz1d_c)
+        modes = None if fz is None else fz.layers[i]
+        few, sums = _trainable_probs(keyed[:2] + keyed[3:], modes)      # w1, w2, o: the gathered rows
+        wide, sums_w = _trainable_probs(keyed[2:3], modes)              # qkv: all rows of the backward
+        if sums + sums_w:
+            ops.colsum_grouped(sums + sums_w, accumulate=True)
         if deferred is not None and getattr(top, "late_wgrads", True):
-            # the deferred multi-layer call takes them: the QKV gradient (all rows of the backward) as one more of its problems -- it was a
-            # launch of 27 tiles with the token axis split 8 ways + a reduce launch --, the three few-row ones behind its tiles
-            deferred.append((dqkv, x, lw["g_Wqkv"], lw["g_bqkv"]))
+            # the deferred multi-layer call takes them: the QKV gradient as one more of its problems -- it was a launch of 27 tiles with
+            # the token axis split 8 ways + a reduce launch --, the three few-row ones behind its tiles
+            deferred.extend(wide)
             for q in few:
                 _late_wgrad(top, q, True)
         else:
             _wgrad(top, few)
-            _wgrad(top, [(dqkv, x, lw["g_Wqkv"], lw["g_bqkv"])])
+            _wgrad(top, wide)
         return out
 
 

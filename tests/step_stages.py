@@ -104,9 +104,9 @@ ACCUMULATES = {"gemm_tn": ("bias_out",), "embed_scatter": ("gword", "gtype", "gp
                "lora_dense_fwd": ("y",), "lora_dense_bwd": ("dx", "gA", "gB")}    # (gA / gB of both adapter backwards: when ``accumulate``)
 
 # ---- the op sequence of the trunk (check 1): stage names, see ``_stage``
-FWD_LAYER = ("qkv", "attn_fwd", "z1", "ln1", "g", "z2", "ln2")                                  # model._EncoderFn.run_forward, per-launch body
-BWD_DENSE = ("ln2_bwd", "du", "dy1", "ln1_bwd", "dctx", "attn_bwd", "dx")                        # ... run_backward, dense body
-BWD_TOP_SPARSE = (                                                                              # ... _last_layer_sparse
+FWD_LAYER = ("qkv", "attn_fwd", "z1", "ln1", "g", "z2", "ln2")            # model._EncoderFn._layer_forward (z1 .. ln2: _forward_behind_attention)
+BWD_DENSE = ("ln2_bwd", "du", "dy1", "ln1_bwd", "dctx", "attn_bwd", "dx")  # ... _layer_backward (ln2_bwd .. dctx: _backward_before_attention)
+BWD_TOP_SPARSE = (                                                        # ... _last_layer_sparse (the same body on the gathered rows)
     ("gather_rows8", "ln2_bwd", "du", "dy1", "ln1_bwd", "dctx", "scatter_rows_zero", "attn_q_limit", "attn_bwd", "dx"),    # compact hand-over
     ("gather_rows1", "gather_rows8", "ln2_bwd", "du", "dy1", "ln1_bwd", "dctx", "attn_q_limit", "attn_bwd", "dx"))         # dense dy, gathered
 # (gather_rows<n>: n tensors gathered in the launch -- 8 saved activations of the top layer, 1 = the output gradient; the MLM head's own

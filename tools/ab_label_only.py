@@ -9,7 +9,7 @@ of the forward pass) and the label-only step on the same batches without their l
 ``--warmup``), min / max / spread, the peak of allocated memory during one step ABOVE what is allocated when the step starts (all models
 of the configuration warmed up and resident), and the native calls per step.
 
-    python tools/ab_label_only.py [--steps 12] [--warmup 4] [--rounds 5]
+    python tools/ab_label_only.py [--steps 12] [--warmup 4] [--rounds 5] [--only add_lora]
 """
 import argparse
 import os
@@ -27,6 +27,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=12)
 ap.add_argument("--warmup", type=int, default=4)
 ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--only", default=None, help="only the configurations whose name contains this (e.g. add_lora)")
 a = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -88,6 +89,8 @@ def leg(built, batches, steps, warmup, count=False):
 print(f"train step at the headline shape (batch 16, text 50, pair 500, 12 layers, H 768); {a.rounds} rounds of {a.steps} steps per "
       "route, alternating; ms per step")
 for cname, prepare in configs:
+    if a.only and a.only not in cname:
+        continue
     built = {r: make(prepare, r) for r in pools}
     for r in pools:                                          # every model's storage and optimizer state exist before anything is measured
         leg(built[r], pools[r], 1, 1)
