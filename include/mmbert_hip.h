@@ -553,7 +553,8 @@ int mmbert_adamw_grouped(mmbert_stream_t stream, float* p, float* g, float* m, f
  * refresh, fused zero_grad) that also folds the new p into ema: for every block with (flags & 3) != 2, ema += omd * (p_new - ema),
  * omd = 1 - ema_decay formed in double and rounded to fp32 once.  Frozen blocks leave ema alone.  group_of_block == NULL: every block
  * is group 0.  The writes to p, m, v, g and the bf16 copy are bit-identical to the kernel that would run without the average
- * (mmbert_adamw / _devscale / _grouped).  +8 B/parameter, no extra launch, no sync.  Returns -1 under mmbert_adamw_grouped's
+ * (mmbert_adamw / _devscale / _grouped) -- by construction: the four kernels share one update body whose rounding is fixed in the
+ * source.  +8 B/parameter, no extra launch, no sync.  Returns -1 under mmbert_adamw_grouped's
  * conditions, for ema == NULL and for an ema_decay outside [0, 1). */
 int mmbert_adamw_ema(mmbert_stream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags,
                      const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale,

@@ -1559,184 +1559,143 @@ __global__ __launch_bounds__(256) void vocab_topk_kernel(const void* __restrict_
 // mode 0 = transformers-2.8 AdamW (decay after the update), 1 = torch.optim.AdamW.
 // Also writes the bf16 working copy and (optionally) zeroes the gradient: zero_grad fused.
 // --------------------------------------------------------------------------------------------
-// The scalar coefficients arrive ready-made (mmbert_adamw forms them in double): omb1 / omb2 = 1 - beta1 / 1 - beta2; step_size =
-// lr sqrt(bc2) / bc1 (mode 0) or lr / bc1 (mode 1); rsbc2 = 1 / sqrt(bc2) (mode 1); lrwd = lr * wd.
+// The eight scalar coefficients of one hyper-parameter set, ready-made (adamw_coefs forms them in double and rounds once): omb1 / omb2 =
+// 1 - beta1 / 1 - beta2; step_size = lr sqrt(bc2) / bc1 (mode 0) or lr / bc1 (mode 1); rsbc2 = 1 / sqrt(bc2) (mode 1); lrwd = lr * wd.
+struct AdamWCoefs { float beta1, beta2, omb1, omb2, eps, step_size, rsbc2, lrwd; };
+
+// One element of the update, with the rounding fixed in the source.  The library is built with -ffast-math: which multiply of
+// beta1 m + omb1 gr is fused into the FMA, and how the division and the square root are expanded, is then the compiler's choice, and it
+// made another one when the plain expressions of the four kernels were moved into one shared body: every stored bit of a training
+// trajectory moved.  So each FMA is named with its operand roles, the square root and the reciprocal are the hardware approximations
+// (v_sqrt_f32, v_rcp_f32) by name, and contraction and reassociation are off here: every kernel below computes this dataflow and no other.
+__device__ __forceinline__ void adamw_element(float& p, float g, float& m, float& v, const AdamWCoefs& c, float decay, float gscale, int mode) {
+#pragma clang fp contract(off)
+#pragma clang fp reassociate(off)
+    const float gr = g * gscale;
+    if (mode == 1) p = p * (1.0f - decay);
+    m = __builtin_fmaf(c.omb1, gr, c.beta1 * m);
+    v = __builtin_fmaf(c.omb2, gr * gr, c.beta2 * v);
+    const float rt = __builtin_amdgcn_sqrtf(v), upd = c.step_size * m;
+    if (mode == 0) {
+        p = __builtin_fmaf(-upd, __builtin_amdgcn_rcpf(rt + c.eps), p);
+        p = __builtin_fmaf(-p, decay, p);
+    } else {
+        p = __builtin_fmaf(-upd, __builtin_amdgcn_rcpf(__builtin_fmaf(c.rsbc2, rt, c.eps)), p);
+    }
+}
+
+// ema += omd (p - ema), one element: a subtract, then one FMA onto e (the form e + omd (p - e) keeps updates that are small against e
+// at decay 0.9999).  Pinned like adamw_element.
+__device__ __forceinline__ float ema_element(float e, float p, float omd) {
+#pragma clang fp contract(off)
+#pragma clang fp reassociate(off)
+    return __builtin_fmaf(p - e, omd, e);
+}
+
+// The lane's first element (four per lane, 256 lanes per workgroup); n % 256 == 0, so a lane is wholly inside or wholly outside.
+__device__ __forceinline__ size_t adamw_lane_element() { return ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; }
+
+// The body of every AdamW kernel, for the lane whose elements start at i < n: the flag byte, the live / frozen split, the update of
+// p, m, v (and of ema, when EMA), the fused zero_grad, the bf16 refresh.  coefs() yields the block's AdamWCoefs and is called for live
+// blocks only: the kernels differ in where it reads them, in where gscale comes from and in EMA, and in nothing else.
+template <bool EMA, class Coefs>
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                             float* __restrict__ ema, bf16_t* __restrict__ pb, const uint8_t* __restrict__ flags, size_t i,
+                                             Coefs coefs, float gscale, float omd, int mode, int zero_grad) {
+    const uint8_t fb = flags[i >> 8];
+    const uint8_t f = fb & 3;
+    float4 P = *(float4*)(p + i);
+    if (f != 2) {
+        const AdamWCoefs c = coefs();
+        float4 G = *(float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i), E;
+        if (EMA) E = *(float4*)(ema + i);
+        float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w}, ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
+        const float decay = (f == 1) ? c.lrwd : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) adamw_element(pa[r], ga[r], ma[r], va[r], c, decay, gscale, mode);
+        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
+        *(float4*)(p + i) = P;
+        *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
+        *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
+        if (EMA)
+            *(float4*)(ema + i) = make_float4(ema_element(E.x, P.x, omd), ema_element(E.y, P.y, omd), ema_element(E.z, P.z, omd),
+                                              ema_element(E.w, P.w, omd));
+    }
+    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+}
+
+// One hyper-parameter set, its coefficients in the kernel's scalar arguments; the gradient scale from the host.
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                     bf16_t* __restrict__ pb, const uint8_t* __restrict__ flags, size_t n,
                                                     float beta1, float beta2, float omb1, float omb2, float eps, float step_size, float rsbc2, float lrwd,
                                                     float gscale, int mode, int zero_grad) {
-    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t i = adamw_lane_element();
     if (i >= n) return;
-    const uint8_t fb = flags[i >> 8];
-    const uint8_t f = fb & 3;
-    float4 P = *(float4*)(p + i);
-    if (f != 2) {
-        float4 G = *(float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i);
-        float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w}, ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
-        const float decay = (f == 1) ? lrwd : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float gr = ga[r] * gscale;
-            if (mode == 1) pa[r] *= (1.0f - decay);
-            ma[r] = beta1 * ma[r] + omb1 * gr;
-            va[r] = beta2 * va[r] + omb2 * gr * gr;
-            if (mode == 0) {
-                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) + eps);
-                pa[r] -= decay * pa[r];
-            } else {
-                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) * rsbc2 + eps);
-            }
-        }
-        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
-        *(float4*)(p + i) = P;
-        *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
-        *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
-    }
-    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+    adamw_update<false>(p, g, m, v, nullptr, pb, flags, i, [&] { return AdamWCoefs{beta1, beta2, omb1, omb2, eps, step_size, rsbc2, lrwd}; },
+                        gscale, 0.f, mode, zero_grad);
 }
 
 // adamw_kernel with the gradient scale read from the DEVICE scalar *coef (the clip coefficient of mmbert_grad_norm with the 1/world
-// average folded in; one scalar load per wave) in place of the host gscale.  Otherwise line for line adamw_kernel: a shared inline body
-// or a template changed adamw_kernel's register allocation and schedule (or its name in the traces), so the measured kernel stays as it was.
+// average folded in; one scalar load per wave) in place of the host gscale.  A kernel of its own, like the two below, for its name in
+// the traces and so that adamw_kernel's arguments stay as they are; the arithmetic is adamw_update's in all of them.
 __global__ __launch_bounds__(256) void adamw_devscale_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                              bf16_t* __restrict__ pb, const uint8_t* __restrict__ flags, size_t n,
                                                              float beta1, float beta2, float omb1, float omb2, float eps, float step_size, float rsbc2,
                                                              float lrwd, const float* __restrict__ coef, int mode, int zero_grad) {
-    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t i = adamw_lane_element();
     if (i >= n) return;
-    const float gscale = *coef;
-    const uint8_t fb = flags[i >> 8];
-    const uint8_t f = fb & 3;
-    float4 P = *(float4*)(p + i);
-    if (f != 2) {
-        float4 G = *(float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i);
-        float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w}, ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
-        const float decay = (f == 1) ? lrwd : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float gr = ga[r] * gscale;
-            if (mode == 1) pa[r] *= (1.0f - decay);
-            ma[r] = beta1 * ma[r] + omb1 * gr;
-            va[r] = beta2 * va[r] + omb2 * gr * gr;
-            if (mode == 0) {
-                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) + eps);
-                pa[r] -= decay * pa[r];
-            } else {
-                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) * rsbc2 + eps);
-            }
-        }
-        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
-        *(float4*)(p + i) = P;
-        *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
-        *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
-    }
-    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+    adamw_update<false>(p, g, m, v, nullptr, pb, flags, i, [&] { return AdamWCoefs{beta1, beta2, omb1, omb2, eps, step_size, rsbc2, lrwd}; },
+                        *coef, 0.f, mode, zero_grad);
 }
 
 // Per-parameter-group AdamW (torch / transformers param groups with their own lr, betas, eps, weight_decay).  group_of_block[i / 256]
 // names each 256-element block's group, at the granularity of flags; slot[group] picks one of the de-duplicated coefficient sets that
-// mmbert_adamw_grouped formed in double and rounded to fp32 once.  The whole table travels BY VALUE in the kernel arguments: no device
+// adamw_fill_slots formed in double and rounded to fp32 once.  The whole table travels BY VALUE in the kernel arguments: no device
 // allocation, no copy per step (the host runs a step ahead), nothing to sync, graph-capturable.  One wave = 64 lanes x 4 floats = one
 // block, so the group is wave-uniform: readfirstlane makes that provable and the slot word and the 8 coefficients come in as scalar
-// loads from the argument segment, once per wave.  The element loop is adamw_kernel's (same traffic + 1 byte per block).
+// loads from the argument segment, once per wave.  The update is adamw_kernel's (same traffic + 1 byte per block).
 #define ADAMW_MAX_GROUPS 255             // == MMBERT_ADAMW_MAX_GROUPS (include/mmbert_hip.h)
 #define ADAMW_MAX_SLOTS 64               // == MMBERT_ADAMW_MAX_SLOTS
 struct AdamWSlots {
-    float c[ADAMW_MAX_SLOTS][8];         // beta1, beta2, 1 - beta1, 1 - beta2, eps, step_size, 1 / sqrt(bc2), lr * wd
+    AdamWCoefs c[ADAMW_MAX_SLOTS];
     uint32_t slot4[64];                  // group k -> slot in byte k & 3 of word k >> 2 (a word: one scalar load; 256 entries = every
                                          // value of a group byte, so a stray index reads slot 0, never past the table)
 };
 static_assert(sizeof(AdamWSlots) == 2304, "AdamWSlots layout");
 static_assert(sizeof(AdamWSlots) + 128 <= 4096, "adamw_grouped_kernel's arguments must fit the 4 KiB kernel-argument segment");
 
+__device__ __forceinline__ AdamWCoefs adamw_slot_coefs(const AdamWSlots& a, int grp) {
+    return a.c[(a.slot4[grp >> 2] >> ((grp & 3) * 8)) & 255u];
+}
+
 template <bool DEVSCALE>
 __global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                             bf16_t* __restrict__ pb, const uint8_t* __restrict__ flags,
                                                             const uint8_t* __restrict__ group_of_block, size_t n, const AdamWSlots a,
                                                             float host_gscale, const float* __restrict__ coef, int mode, int zero_grad) {
-    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t i = adamw_lane_element();
     if (i >= n) return;
     const float gscale = DEVSCALE ? *coef : host_gscale;
-    const uint8_t fb = flags[i >> 8];
-    const uint8_t f = fb & 3;
     const int grp = __builtin_amdgcn_readfirstlane((int)group_of_block[i >> 8]);
-    float4 P = *(float4*)(p + i);
-    if (f != 2) {
-        const float* c = a.c[(a.slot4[grp >> 2] >> ((grp & 3) * 8)) & 255u];
-        const float beta1 = c[0], beta2 = c[1], omb1 = c[2], omb2 = c[3], eps = c[4], step_size = c[5], rsbc2 = c[6], lrwd = c[7];
-        float4 G = *(float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i);
-        float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w}, ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
-        const float decay = (f == 1) ? lrwd : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float gr = ga[r] * gscale;
-            if (mode == 1) pa[r] *= (1.0f - decay);
-            ma[r] = beta1 * ma[r] + omb1 * gr;
-            va[r] = beta2 * va[r] + omb2 * gr * gr;
-            if (mode == 0) {
-                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) + eps);
-                pa[r] -= decay * pa[r];
-            } else {
-                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) * rsbc2 + eps);
-            }
-        }
-        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
-        *(float4*)(p + i) = P;
-        *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
-        *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
-    }
-    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+    adamw_update<false>(p, g, m, v, nullptr, pb, flags, i, [&] { return adamw_slot_coefs(a, grp); }, gscale, 0.f, mode, zero_grad);
 }
 
 // adamw_grouped_kernel plus an exponential moving average of the weights: once a live block's new p is formed (it is in registers),
-// ema += omd * (p - ema) with omd = 1 - decay (mmbert_adamw_ema forms it in double and rounds once; the form e + omd (p - e) keeps
-// updates that are small against e at decay 0.9999).  Frozen blocks (flag 2) leave ema alone.  group_of_block == NULL: every block is
-// group 0 (one hyper-parameter set: the table then holds mmbert_adamw's coefficients in slot 0).  The update of p, m, v, g and the bf16
-// copy is adamw_kernel's line for line -- a kernel of its own for the reason given above adamw_devscale_kernel -- so that turning the
-// average on moves no bit of a training trajectory.  New traffic: one float4 load and one store of ema per lane (36 B/parameter).
+// ema += omd * (p - ema) with omd = 1 - decay (mmbert_adamw_ema forms it in double and rounds once).  Frozen blocks (flag 2) leave ema
+// alone.  group_of_block == NULL: every block is group 0 (one hyper-parameter set: the table then holds mmbert_adamw's coefficients in
+// slot 0).  The update of p, m, v, g and the bf16 copy is adamw_update's, the one body of all four kernels, so turning the average on
+// moves no bit of a training trajectory -- by construction.  New traffic: one float4 load and one store of ema per lane (36 B/parameter).
 template <bool DEVSCALE>
 __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                         float* __restrict__ ema, bf16_t* __restrict__ pb, const uint8_t* __restrict__ flags,
                                                         const uint8_t* __restrict__ group_of_block, size_t n, const AdamWSlots a,
                                                         float host_gscale, const float* __restrict__ coef, float omd, int mode, int zero_grad) {
-    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t i = adamw_lane_element();
     if (i >= n) return;
     const float gscale = DEVSCALE ? *coef : host_gscale;
-    const uint8_t fb = flags[i >> 8];
-    const uint8_t f = fb & 3;
     const int grp = group_of_block ? __builtin_amdgcn_readfirstlane((int)group_of_block[i >> 8]) : 0;
-    float4 P = *(float4*)(p + i);
-    if (f != 2) {
-        const float* c = a.c[(a.slot4[grp >> 2] >> ((grp & 3) * 8)) & 255u];
-        const float beta1 = c[0], beta2 = c[1], omb1 = c[2], omb2 = c[3], eps = c[4], step_size = c[5], rsbc2 = c[6], lrwd = c[7];
-        float4 G = *(float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i);
-        const float4 E = *(float4*)(ema + i);
-        float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w}, ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
-        const float decay = (f == 1) ? lrwd : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float gr = ga[r] * gscale;
-            if (mode == 1) pa[r] *= (1.0f - decay);
-            ma[r] = beta1 * ma[r] + omb1 * gr;
-            va[r] = beta2 * va[r] + omb2 * gr * gr;
-            if (mode == 0) {
-                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) + eps);
-                pa[r] -= decay * pa[r];
-            } else {
-                pa[r] -= step_size * ma[r] / (sqrtf(va[r]) * rsbc2 + eps);
-            }
-        }
-        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
-        *(float4*)(p + i) = P;
-        *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
-        *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
-        *(float4*)(ema + i) = make_float4(E.x + omd * (P.x - E.x), E.y + omd * (P.y - E.y), E.z + omd * (P.z - E.z), E.w + omd * (P.w - E.w));
-    }
-    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+    adamw_update<true>(p, g, m, v, ema, pb, flags, i, [&] { return adamw_slot_coefs(a, grp); }, gscale, omd, mode, zero_grad);
 }
 
 // p <-> ema, and the bf16 working copy of the new p (mmbert_cast_f32_bf16's rounding), in one pass: 16 B/parameter + 2 for the copy, no
@@ -2648,16 +2607,45 @@ int mmbert_active_rows(hipStream_t stream, const int64_t* labels, int M, int V, 
     return 0;
 }
 
+// The coefficients of one (lr, beta1, beta2, eps, weight_decay) at a step: every derived value in double, rounded to fp32 once (the
+// reference's optimizer computes them as Python floats).
+static AdamWCoefs adamw_coefs(double lr, double beta1, double beta2, double eps, double wd, int step, int mode) {
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double step_size = mode == 0 ? lr * sqrt(bc2) / bc1 : lr / bc1;
+    return {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size, (float)(1.0 / sqrt(bc2)),
+            (float)(lr * wd)};
+}
+
+// hyper[5 k ..] = (lr, beta1, beta2, eps, weight_decay) of group k -> the table of distinct combinations, in first-seen order, and
+// every group's slot in it.  -1: no hyper, ngroups outside 1 .. ADAMW_MAX_GROUPS, or more than ADAMW_MAX_SLOTS distinct combinations.
+static int adamw_fill_slots(AdamWSlots& a, const double* hyper, int ngroups, int step, int mode) {
+    if (!hyper || ngroups < 1 || ngroups > ADAMW_MAX_GROUPS) return -1;
+    memset(&a, 0, sizeof(a));
+    const double* key[ADAMW_MAX_SLOTS];  // the first group of each slot
+    int nslot = 0;
+    for (int k = 0; k < ngroups; ++k) {
+        const double* h = hyper + 5 * k;
+        int s = 0;
+        while (s < nslot && !(key[s][0] == h[0] && key[s][1] == h[1] && key[s][2] == h[2] && key[s][3] == h[3] && key[s][4] == h[4])) ++s;
+        if (s == nslot) {
+            if (nslot == ADAMW_MAX_SLOTS) return -1;
+            key[nslot++] = h;
+            a.c[s] = adamw_coefs(h[0], h[1], h[2], h[3], h[4], step, mode);
+        }
+        a.slot4[k >> 2] |= (uint32_t)s << ((k & 3) * 8);
+    }
+    return 0;
+}
+
+static dim3 adamw_grid(size_t n) { return dim3((unsigned)((n / 4 + 255) / 256)); }
+
 int mmbert_adamw(hipStream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags, size_t n,
                  double lr, double beta1, double beta2, double eps, double wd, int step, double gscale, int mode, int zero_grad) {
     if (n == 0) return 0;
     if (n & 255) return -1;
-    // every derived coefficient in double, rounded to fp32 once (the reference's optimizer computes them as Python floats)
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = mode == 0 ? lr * sqrt(bc2) / bc1 : lr / bc1;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, n,
-                       (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size, (float)(1.0 / sqrt(bc2)),
-                       (float)(lr * wd), (float)gscale, mode, zero_grad);
+    const AdamWCoefs c = adamw_coefs(lr, beta1, beta2, eps, wd, step, mode);
+    hipLaunchKernelGGL(adamw_kernel, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, n,
+                       c.beta1, c.beta2, c.omb1, c.omb2, c.eps, c.step_size, c.rsbc2, c.lrwd, (float)gscale, mode, zero_grad);
     MMB_CHECK_LAUNCH();
     return 0;
 }
@@ -2666,11 +2654,9 @@ int mmbert_adamw_devscale(hipStream_t stream, float* p, float* g, float* m, floa
                           double lr, double beta1, double beta2, double eps, double wd, int step, const float* coef, int mode, int zero_grad) {
     if (n == 0) return 0;
     if ((n & 255) || !coef) return -1;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = mode == 0 ? lr * sqrt(bc2) / bc1 : lr / bc1;
-    hipLaunchKernelGGL(adamw_devscale_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, n,
-                       (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size, (float)(1.0 / sqrt(bc2)),
-                       (float)(lr * wd), coef, mode, zero_grad);
+    const AdamWCoefs c = adamw_coefs(lr, beta1, beta2, eps, wd, step, mode);
+    hipLaunchKernelGGL(adamw_devscale_kernel, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, n,
+                       c.beta1, c.beta2, c.omb1, c.omb2, c.eps, c.step_size, c.rsbc2, c.lrwd, coef, mode, zero_grad);
     MMB_CHECK_LAUNCH();
     return 0;
 }
@@ -2679,80 +2665,34 @@ int mmbert_adamw_grouped(hipStream_t stream, float* p, float* g, float* m, float
                          const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale, const float* coef,
                          int mode, int zero_grad) {
     if (n == 0) return 0;
-    if ((n & 255) || !hyper || ngroups < 1 || ngroups > ADAMW_MAX_GROUPS) return -1;
     AdamWSlots a;
-    memset(&a, 0, sizeof(a));
-    double key[ADAMW_MAX_SLOTS][5];      // (lr, beta1, beta2, eps, weight_decay) of each slot, in first-seen order
-    int nslot = 0;
-    for (int k = 0; k < ngroups; ++k) {
-        const double* h = hyper + 5 * k;
-        int s = 0;
-        while (s < nslot && !(key[s][0] == h[0] && key[s][1] == h[1] && key[s][2] == h[2] && key[s][3] == h[3] && key[s][4] == h[4])) ++s;
-        if (s == nslot) {
-            if (nslot == ADAMW_MAX_SLOTS) return -1;
-            for (int j = 0; j < 5; ++j) key[s][j] = h[j];
-            ++nslot;
-        }
-        a.slot4[k >> 2] |= (uint32_t)s << ((k & 3) * 8);
-    }
-    for (int s = 0; s < nslot; ++s) {    // mmbert_adamw's coefficients, slot by slot: formed in double, rounded to fp32 once
-        const double lr = key[s][0], beta1 = key[s][1], beta2 = key[s][2], eps = key[s][3], wd = key[s][4];
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const double step_size = mode == 0 ? lr * sqrt(bc2) / bc1 : lr / bc1;
-        const float c[8] = {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size,
-                            (float)(1.0 / sqrt(bc2)), (float)(lr * wd)};
-        for (int j = 0; j < 8; ++j) a.c[s][j] = c[j];
-    }
-    const dim3 grid((unsigned)((n / 4 + 255) / 256));
+    if ((n & 255) || adamw_fill_slots(a, hyper, ngroups, step, mode) != 0) return -1;
     if (coef)
-        hipLaunchKernelGGL(adamw_grouped_kernel<true>, grid, dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, group_of_block, n, a,
-                           1.0f, coef, mode, zero_grad);
+        hipLaunchKernelGGL(adamw_grouped_kernel<true>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, group_of_block, n,
+                           a, 1.0f, coef, mode, zero_grad);
     else
-        hipLaunchKernelGGL(adamw_grouped_kernel<false>, grid, dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, group_of_block, n, a,
-                           (float)gscale, (const float*)nullptr, mode, zero_grad);
+        hipLaunchKernelGGL(adamw_grouped_kernel<false>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, flags, group_of_block, n,
+                           a, (float)gscale, (const float*)nullptr, mode, zero_grad);
     MMB_CHECK_LAUNCH();
     return 0;
 }
 
-// mmbert_adamw_grouped with the weight EMA fused in.  The slot table is built exactly as there (that entry point stays as it is: the
-// tests hold the two to bit-identity); 1 - ema_decay in double, rounded to fp32 once like the other coefficients.
+// mmbert_adamw_grouped with the weight EMA fused in: the same slot table; 1 - ema_decay in double, rounded to fp32 once like the other
+// coefficients.
 int mmbert_adamw_ema(hipStream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags,
                      const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale, const float* coef,
                      int mode, int zero_grad, float* ema, double ema_decay) {
     if (n == 0) return 0;
-    if ((n & 255) || !hyper || ngroups < 1 || ngroups > ADAMW_MAX_GROUPS) return -1;
-    if (!ema || !(ema_decay >= 0.0 && ema_decay < 1.0)) return -1;
     AdamWSlots a;
-    memset(&a, 0, sizeof(a));
-    double key[ADAMW_MAX_SLOTS][5];
-    int nslot = 0;
-    for (int k = 0; k < ngroups; ++k) {
-        const double* h = hyper + 5 * k;
-        int s = 0;
-        while (s < nslot && !(key[s][0] == h[0] && key[s][1] == h[1] && key[s][2] == h[2] && key[s][3] == h[3] && key[s][4] == h[4])) ++s;
-        if (s == nslot) {
-            if (nslot == ADAMW_MAX_SLOTS) return -1;
-            for (int j = 0; j < 5; ++j) key[s][j] = h[j];
-            ++nslot;
-        }
-        a.slot4[k >> 2] |= (uint32_t)s << ((k & 3) * 8);
-    }
-    for (int s = 0; s < nslot; ++s) {
-        const double lr = key[s][0], beta1 = key[s][1], beta2 = key[s][2], eps = key[s][3], wd = key[s][4];
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const double step_size = mode == 0 ? lr * sqrt(bc2) / bc1 : lr / bc1;
-        const float c[8] = {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size,
-                            (float)(1.0 / sqrt(bc2)), (float)(lr * wd)};
-        for (int j = 0; j < 8; ++j) a.c[s][j] = c[j];
-    }
+    if ((n & 255) || adamw_fill_slots(a, hyper, ngroups, step, mode) != 0) return -1;
+    if (!ema || !(ema_decay >= 0.0 && ema_decay < 1.0)) return -1;
     const float omd = (float)(1.0 - ema_decay);
-    const dim3 grid((unsigned)((n / 4 + 255) / 256));
     if (coef)
-        hipLaunchKernelGGL(adamw_ema_kernel<true>, grid, dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)p_bf16, flags, group_of_block, n, a,
-                           1.0f, coef, omd, mode, zero_grad);
+        hipLaunchKernelGGL(adamw_ema_kernel<true>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)p_bf16, flags, group_of_block, n,
+                           a, 1.0f, coef, omd, mode, zero_grad);
     else
-        hipLaunchKernelGGL(adamw_ema_kernel<false>, grid, dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)p_bf16, flags, group_of_block, n, a,
-                           (float)gscale, (const float*)nullptr, omd, mode, zero_grad);
+        hipLaunchKernelGGL(adamw_ema_kernel<false>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)p_bf16, flags, group_of_block, n,
+                           a, (float)gscale, (const float*)nullptr, omd, mode, zero_grad);
     MMB_CHECK_LAUNCH();
     return 0;
 }

@@ -1038,14 +1038,20 @@ def adamw_devscale(p, g, m, v, p_bf16, flags, coef, *, lr, beta1=0.9, beta2=0.99
 ADAMW_MAX_GROUPS, ADAMW_MAX_SLOTS = 255, 64      # MMBERT_ADAMW_MAX_GROUPS / _SLOTS (include/mmbert_hip.h)
 
 
+def _hyper_array(hyper):
+    """(the C array of doubles, the group count) of a host sequence of (lr, beta1, beta2, eps, weight_decay) per group"""
+    hyper = [tuple(float(x) for x in h) for h in hyper]
+    assert all(len(h) == 5 for h in hyper)
+    return (ctypes.c_double * (5 * max(1, len(hyper))))(*[x for h in hyper for x in h]), len(hyper)
+
+
 def adamw_grouped(p, g, m, v, p_bf16, flags, group_of_block, hyper, *, step=1, gscale=1.0, coef=None, mode=0, zero_grad=True):
     """ops.adamw with per-group hyper-parameters (mmbert_adamw_grouped): ``group_of_block`` device uint8 [n / 256], ``hyper`` a host
     sequence of (lr, beta1, beta2, eps, weight_decay) per group; ``coef`` (device fp32 scalar) replaces ``gscale`` when given."""
-    hyper = [tuple(float(x) for x in h) for h in hyper]
-    assert all(len(h) == 5 for h in hyper) and group_of_block.dtype == torch.uint8 and group_of_block.numel() * 256 >= p.numel()
-    arr = (ctypes.c_double * (5 * max(1, len(hyper))))(*[x for h in hyper for x in h])
+    assert group_of_block.dtype == torch.uint8 and group_of_block.numel() * 256 >= p.numel()
+    arr, ngroups = _hyper_array(hyper)
     _lib.check(_lib.load().mmbert_adamw_grouped(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16),
-                                                flags.data_ptr(), group_of_block.data_ptr(), p.numel(), arr, len(hyper), int(step),
+                                                flags.data_ptr(), group_of_block.data_ptr(), p.numel(), arr, ngroups, int(step),
                                                 float(gscale), None if coef is None else coef.data_ptr(), int(mode),
                                                 1 if zero_grad else 0), "mmbert_adamw_grouped")
 
@@ -1053,13 +1059,11 @@ def adamw_grouped(p, g, m, v, p_bf16, flags, group_of_block, hyper, *, step=1, g
 def adamw_ema(p, g, m, v, p_bf16, flags, group_of_block, hyper, ema, *, ema_decay, step=1, gscale=1.0, coef=None, mode=0, zero_grad=True):
     """ops.adamw_grouped that also folds the new ``p`` of every live block into the fp32 ``ema``: ema += (1 - ema_decay) (p - ema)
     (mmbert_adamw_ema).  ``group_of_block`` None: every block is group 0 (``hyper`` then holds one tuple)."""
-    hyper = [tuple(float(x) for x in h) for h in hyper]
-    assert all(len(h) == 5 for h in hyper)
     assert group_of_block is None or (group_of_block.dtype == torch.uint8 and group_of_block.numel() * 256 >= p.numel())
     assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == p.numel())
-    arr = (ctypes.c_double * (5 * max(1, len(hyper))))(*[x for h in hyper for x in h])
+    arr, ngroups = _hyper_array(hyper)
     _lib.check(_lib.load().mmbert_adamw_ema(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16),
-                                            flags.data_ptr(), _ptr(group_of_block), p.numel(), arr, len(hyper), int(step), float(gscale),
+                                            flags.data_ptr(), _ptr(group_of_block), p.numel(), arr, ngroups, int(step), float(gscale),
                                             None if coef is None else coef.data_ptr(), int(mode), 1 if zero_grad else 0, _ptr(ema),
                                             float(ema_decay)), "mmbert_adamw_ema")
 
