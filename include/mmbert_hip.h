@@ -668,6 +668,38 @@ int mmbert_lora_dense_bwd(mmbert_stream_t stream, const void* dy, int lddy, cons
                           const void* A, const void* B, float scale, void* dx, int lddx, const void* gelu_u, int ldu, float* gA, float* gB,
                           int accumulate, void* workspace);
 
+/* ---- LoRA dropout: dropout of the adapters' INPUT, fused into the adapter launches (a declared extension) ----
+ * The four entry points above plus the input-dropout triple (in_stream, in_thr16, in_scale) of the seam input x; the functions above are
+ * these with in_thr16 = 0.  Only the low-rank branch sees the mask: the projection's own GEMM read the undropped x.  With Kp the 0/1 keep
+ * matrix, c = in_scale (the caller passes 1 / (1 - in_thr16 / 65536)) and s = scale:
+ *   fwd   h  = c * (Kp . x) A^T                  y  += s * h B^T       (the epilogues as above: the GEMM's own output mask / GELU)
+ *   bwd   g  = c * dy B                          dx += s * Kp . (g A)  [* gelu'(u)]
+ *         dA = [dA +] s * g^T (Kp . x)           dB  = [dB +] s * dy^T h   (h as forward wrote it, or recomputed under the same mask)
+ * Mask: element (m, k) of x, of LOGICAL width K (H for q / k / v; never the row pitch), is kept iff the generator's keep rule holds for
+ *   stream in_stream, the 64-bit element index row(m) * K + k and the threshold in_thr16 (drop probability in_thr16 / 65536; the pair
+ *   counter wraps mod 2^32 like every mask of this library).  row(m) = m, or rows[m] when mmbert_lora_dense_bwd_drop gets `rows` (int32,
+ *   device, M entries, 4-byte aligned; may be NULL): backward on gathered rows draws the mask of the rows' own site rows.  The q / k / v
+ *   adapters of a call read the same x and SHARE its mask (one mask per seam input, not per adapted projection).
+ * Roundings: a dropped element of an x fragment is set to +0 -- a select, not a product, so a NaN in a dropped element does not travel;
+ *   c is ONE fp32 multiply on the fp32 accumulator of h and of g, before their bf16 rounding, so the stored h / g carry c and dA, dB, dx
+ *   take no further factor; an element of dx / dres_out that the mask dropped keeps the BITS of dx / dres_in.
+ * in_thr16 == 0: every output has the bits of the function without _drop (in_scale and rows are checked, not read).  Argument checks,
+ *   workspaces, launch counts and return codes are those of the functions above, plus -1 for in_thr16 > 65535, an in_scale that is not
+ *   finite and > 0, or a misaligned rows. */
+int mmbert_lora_qkv_fwd_drop(mmbert_stream_t stream, const void* x, int ldx, void* qkv, int ldq, int M, int H, int r, int targets,
+                             const void* const* A, const void* const* B, float scale, void* h_out, int ldh,
+                             unsigned in_stream, unsigned in_thr16, float in_scale);
+int mmbert_lora_qkv_bwd_drop(mmbert_stream_t stream, const void* dqkv, int lddq, const void* x, int ldx, const void* h, int ldh, int M, int H, int r,
+                             int targets, const void* const* A, const void* const* B, float scale, const void* dres_in, int lddi,
+                             void* dres_out, int lddo, float* const* gA, float* const* gB, int accumulate, void* workspace,
+                             unsigned in_stream, unsigned in_thr16, float in_scale);
+int mmbert_lora_dense_fwd_drop(mmbert_stream_t stream, const void* x, int ldx, void* y, int ldy, int M, int K, int N, int r, const void* A, const void* B,
+                               float scale, int mode, unsigned drop_stream, unsigned drop_thr16, float drop_scale, void* aux, int ldaux,
+                               void* h_out, int ldh, unsigned in_stream, unsigned in_thr16, float in_scale);
+int mmbert_lora_dense_bwd_drop(mmbert_stream_t stream, const void* dy, int lddy, const void* x, int ldx, const void* h, int ldh, int M, int K, int N, int r,
+                               const void* A, const void* B, float scale, void* dx, int lddx, const void* gelu_u, int ldu, float* gA, float* gB,
+                               int accumulate, void* workspace, unsigned in_stream, unsigned in_thr16, float in_scale, const int* rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,11 @@ SIGNATURES = {
     "mmbert_lora_dense_fwd": (I, [P, P, I, P, I, I, I, I, I, P, P, F, I, U32, U32, F, P, I, P, I]),
     "mmbert_lora_dense_bwd_workspace": (SZ, [I, I, I, I]),
     "mmbert_lora_dense_bwd": (I, [P, P, I, P, I, P, I, I, I, I, I, P, P, F, P, I, P, I, P, P, I, P]),
+    # the same with the adapter-input dropout triple behind the old lists (dense_bwd: and the int32 row list)
+    "mmbert_lora_qkv_fwd_drop": (I, [P, P, I, P, I, I, I, I, I, P, P, F, P, I, U32, U32, F]),
+    "mmbert_lora_qkv_bwd_drop": (I, [P, P, I, P, I, P, I, I, I, I, I, P, P, F, P, I, P, I, P, P, I, P, U32, U32, F]),
+    "mmbert_lora_dense_fwd_drop": (I, [P, P, I, P, I, I, I, I, I, P, P, F, I, U32, U32, F, P, I, P, I, U32, U32, F]),
+    "mmbert_lora_dense_bwd_drop": (I, [P, P, I, P, I, P, I, I, I, I, I, P, P, F, P, I, P, I, P, P, I, P, U32, U32, F, P]),
 }
 
 _lib = None

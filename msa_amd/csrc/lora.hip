@@ -25,18 +25,23 @@
 #define LORA_SLAB 128         // token rows per partial sum of the weight gradients
 #define LORA_LDS_MAX 163840   // 160 KiB per CU (gfx950)
 
+// the input dropout of a seam (the comment block below); rows (dense backward only): local row i is site row rows[i]
+struct LoraInDrop { uint32_t stream, thr_pk; float c; int pad; const int32_t* rows; };
 struct LoraTarget { const bf16_t* A; const bf16_t* B; int third; int pad; };
 struct LoraFwdArgs {
     LoraTarget t[3]; int nt, M, H, r, ldx, ldq, ldh; float s;
     const bf16_t* x; bf16_t* qkv; bf16_t* h;
+    LoraInDrop in;
 };
 struct LoraBwdArgs {
     LoraTarget t[3]; int nt, M, H, r, ldx, lddq, lddi, lddo, recompute; float s;
     const bf16_t* x; const bf16_t* dqkv; const bf16_t* dres_in; bf16_t* dres_out;
     bf16_t* gbuf; bf16_t* hbuf;            // [M, nt * r] each (workspace)
+    LoraInDrop in;
 };
-struct LoraStream { const bf16_t* src; const bf16_t* coef; float* out; int lds, ldc, colmajor, acc; };   // colmajor: out is [H, r] (dB), else [r, H] (dA)
-struct LoraWArgs { LoraStream st[6]; int ns, M, H, r, nslab; float s; float* part; };
+// colmajor: out is [H, r] (dB), else [r, H] (dA), whose src is the seam input: the only streams the input mask applies to
+struct LoraStream { const bf16_t* src; const bf16_t* coef; float* out; int lds, ldc, colmajor, acc; };
+struct LoraWArgs { LoraStream st[6]; int ns, M, H, r, nslab; float s; float* part; LoraInDrop in; };
 
 
 __device__ __forceinline__ bf16x8 lora_zero8() { bf16x8 z; for (int j = 0; j < 8; ++j) z[j] = (bf16_t)0.0f; return z; }
@@ -50,6 +55,38 @@ __device__ __forceinline__ bf16x4 lora_round4(f32x4 a) {
     bf16x4 o;
     o[0] = f2bf(a[0]); o[1] = f2bf(a[1]); o[2] = f2bf(a[2]); o[3] = f2bf(a[3]);
     return o;
+}
+
+// ---- input dropout of the low-rank branch (the *_drop entry points).  Element (m, k) of a seam input of LOGICAL width K
+// (never the row pitch) is kept iff mmb_keep(stream, (uint64) row(m) * K + k, thr16); the base product sees the undropped x.  Every load of
+// x is a 16-byte fragment of 8 consecutive columns at a column that is a multiple of 8 and K % 64 == 0, so the fragment is four whole
+// element pairs: four hash words, decided on the packed halves.  The roundings:
+//   * a dropped element of the fragment becomes +0 -- a SELECT (an AND on the bits), not a product: a NaN in a dropped element stays put;
+//   * c = 1 / (1 - thr16 / 65536) is ONE fp32 multiply on the MFMA accumulator of h and of g, before their bf16 rounding: the stored h / g
+//     carry c, and dA = s g^T (Kp . x), dB = s dy^T h, dx += s Kp . (g A) need no further factor;
+//   * where the mask dropped an element of dx / dres_out, the element keeps the BITS of dx_old / dres_in;
+//   * thr16 == 0 runs the DROP = false instantiation of every kernel: the bits of the entry points without dropout (c is not read).
+typedef __attribute__((ext_vector_type(4))) uint32_t lora_u32x4;
+// the pair index of element (row, 0) of a seam of logical width K (row * K is even); pair indices wrap mod 2^32 as mmb_keep's do
+__device__ __forceinline__ uint32_t lora_row_pair(const int32_t* rows, int m, int K) {
+    const uint32_t row = rows ? (uint32_t)rows[m] : (uint32_t)m;
+    return (uint32_t)(((uint64_t)row * (uint64_t)K) >> 1);
+}
+// 0xFFFF in the halves of the four words whose elements are DROPPED: the 8 elements from pair index pair0
+__device__ __forceinline__ lora_u32x4 lora_drop_bits8(uint32_t stream, uint32_t pair0, uint32_t thr_pk) {
+    lora_u32x4 d;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) d[q] = mmb_drop_mask2(mmb_pair_bits(stream, pair0 + q), thr_pk);
+    return d;
+}
+// the fragment with its dropped elements set to +0
+__device__ __forceinline__ bf16x8 lora_drop8(bf16x8 v, uint32_t stream, uint32_t pair0, uint32_t thr_pk) {
+    return __builtin_bit_cast(bf16x8, __builtin_bit_cast(lora_u32x4, v) & ~lora_drop_bits8(stream, pair0, thr_pk));
+}
+// `o` where the mask kept the element, the bits of `old` where it dropped it
+__device__ __forceinline__ bf16x8 lora_keep_old8(bf16x8 o, bf16x8 old, uint32_t stream, uint32_t pair0, uint32_t thr_pk) {
+    const lora_u32x4 d = lora_drop_bits8(stream, pair0, thr_pk);
+    return __builtin_bit_cast(bf16x8, (__builtin_bit_cast(lora_u32x4, o) & ~d) | (__builtin_bit_cast(lora_u32x4, old) & d));
 }
 
 // T[ti][k][0 .. H) = W_ti[k][0 .. H) for k < r, zeros for r <= k < 16 (W = A: [r, H] row-major).  Row pitch HP = H + 8 elements.
@@ -118,6 +155,25 @@ __device__ __forceinline__ f32x4 lora_contract_h(const bf16_t* T, const bf16_t* 
     }
     return acc;
 }
+// the same for the nt targets at once under the input mask: the targets read the same x and share its mask (one mask per seam INPUT), so
+// the masked fragment is formed ONCE per K step; each accumulator takes the k blocks in lora_contract_h's order, then c (rowpair:
+// lora_row_pair of this lane's row)
+__device__ __forceinline__ void lora_contract_h_drop(const bf16_t* T, const bf16_t* xrow, int H, int nt, int lane, const LoraInDrop& d, uint32_t rowpair, f32x4 acc[3]) {
+    const int i = lane & 15, g = lane >> 4;
+    const bf16_t* tr = T + (size_t)i * (H + 8) + 8 * g;
+    const bf16_t* xr = xrow + 8 * g;
+    const uint32_t p0 = rowpair + 4 * g;
+#pragma unroll
+    for (int ti = 0; ti < 3; ++ti) acc[ti] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < H; k0 += 32) {
+        const bf16x8 xf = lora_drop8(*(const bf16x8*)(xr + k0), d.stream, p0 + (uint32_t)(k0 >> 1), d.thr_pk);
+#pragma unroll
+        for (int ti = 0; ti < 3; ++ti)
+            if (ti < nt) acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)(tr + (size_t)ti * 16 * (H + 8) + k0), xf, acc[ti], 0, 0, 0);
+    }
+#pragma unroll
+    for (int ti = 0; ti < 3; ++ti) acc[ti] *= d.c;
+}
 
 // the two MFMAs of one 32-column block: d[sub][reg] = sum_k U[c0 + 8 g + 4 sub + reg][k] v[m][k]  (token m = lane & 15, g = lane >> 4)
 __device__ __forceinline__ void lora_expand32(const bf16_t* U, int c0, bf16x8 vf, int lane, f32x4& d0, f32x4& d1) {
@@ -128,6 +184,7 @@ __device__ __forceinline__ void lora_expand32(const bf16_t* U, int c0, bf16x8 vf
     d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u1, vf, d1, 0, 0, 0);
 }
 
+template <bool DROP>
 __global__ __launch_bounds__(256) void lora_qkv_fwd_kernel(const LoraFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* T = (bf16_t*)smem;
@@ -143,10 +200,13 @@ __global__ __launch_bounds__(256) void lora_qkv_fwd_kernel(const LoraFwdArgs a) 
     for (int ti = 0; ti < 3; ++ti) hf[ti] = lora_zero8();
     if (wave_live) {
         const bf16_t* xrow = a.x + (size_t)mr * a.ldx;
+        f32x4 hacc[3];
+        if constexpr (DROP) lora_contract_h_drop(T, xrow, H, nt, lane, a.in, lora_row_pair(nullptr, mr, H), hacc);
 #pragma unroll
         for (int ti = 0; ti < 3; ++ti) {
             if (ti < nt) {
-                const bf16x4 hb = lora_round4(lora_contract_h(T + (size_t)ti * 16 * (H + 8), xrow, H, lane));
+                if constexpr (!DROP) hacc[ti] = lora_contract_h(T + (size_t)ti * 16 * (H + 8), xrow, H, lane);
+                const bf16x4 hb = lora_round4(hacc[ti]);
                 hf[ti] = lora_low4(hb);
                 if (a.h && live && 4 * g < r) *(bf16x4*)(a.h + (size_t)m * a.ldh + ti * r + 4 * g) = hb;
             }
@@ -175,6 +235,7 @@ __global__ __launch_bounds__(256) void lora_qkv_fwd_kernel(const LoraFwdArgs a) 
 }
 
 // backward launch 1: g (and h, when it is recomputed) into the workspace, and the input-gradient part
+template <bool DROP>
 __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* T = (bf16_t*)smem;
@@ -190,10 +251,13 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
         __syncthreads();
         if (wave_live) {
             const bf16_t* xrow = a.x + (size_t)mr * a.ldx;
+            f32x4 hacc[3];
+            if constexpr (DROP) lora_contract_h_drop(T, xrow, H, nt, lane, a.in, lora_row_pair(nullptr, mr, H), hacc);
 #pragma unroll
             for (int ti = 0; ti < 3; ++ti) {
                 if (ti < nt) {
-                    const bf16x4 hb = lora_round4(lora_contract_h(T + (size_t)ti * 16 * (H + 8), xrow, H, lane));
+                    if constexpr (!DROP) hacc[ti] = lora_contract_h(T + (size_t)ti * 16 * (H + 8), xrow, H, lane);
+                    const bf16x4 hb = lora_round4(hacc[ti]);
                     if (live && 4 * g < r) *(bf16x4*)(a.hbuf + (size_t)m * ldw + ti * r + 4 * g) = hb;
                 }
             }
@@ -209,7 +273,9 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
         for (int ti = 0; ti < 3; ++ti) {
             if (ti < nt) {
                 const bf16_t* drow = a.dqkv + (size_t)mr * a.lddq + (size_t)a.t[ti].third * H;
-                const bf16x4 gb = lora_round4(lora_contract_h(T + (size_t)ti * 16 * (H + 8), drow, H, lane));
+                f32x4 gacc = lora_contract_h(T + (size_t)ti * 16 * (H + 8), drow, H, lane);
+                if constexpr (DROP) gacc *= a.in.c;                  // g carries c: dA and the input gradient need no further factor
+                const bf16x4 gb = lora_round4(gacc);
                 gf[ti] = lora_low4(gb);
                 if (live && 4 * g < r) *(bf16x4*)(a.gbuf + (size_t)m * ldw + ti * r + 4 * g) = gb;
             }
@@ -222,6 +288,7 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
     if (!wave_live) return;
     const bf16_t* din = a.dres_in + (size_t)mr * a.lddi + 8 * g;
     bf16_t* dout = a.dres_out + (size_t)mr * a.lddo + 8 * g;
+    const uint32_t p0 = DROP ? lora_row_pair(nullptr, mr, H) + 4 * g : 0u;
 
     for (int c0 = 0; c0 < H; c0 += 32) {
         const bf16x8 old = *(const bf16x8*)(din + c0);
@@ -232,17 +299,20 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
         bf16x8 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { o[j] = f2bf(fmaf(a.s, d0[j], bf2f(old[j]))); o[4 + j] = f2bf(fmaf(a.s, d1[j], bf2f(old[4 + j]))); }
+        if constexpr (DROP) o = lora_keep_old8(o, old, a.in.stream, p0 + (uint32_t)(c0 >> 1), a.in.thr_pk);
         if (live) *(bf16x8*)(dout + c0) = o;
     }
 }
 
 // backward launch 2: part[stream][slab][k, c] = sum over the slab's tokens m of coef[m][k] * src[m][c]  (fp32; not yet scaled by s).
 // A lane owns 8 columns and all R rank entries; the workgroup's row lanes take interleaved tokens and are added in row-lane order.
-template <int R>
+// DROP: the dA streams (src = x, the seam input) read x under the input mask; the dB streams read dqkv and the h forward wrote, as they are.
+template <int R, bool DROP>
 __global__ __launch_bounds__(256) void lora_qkv_bwd_w_kernel(const LoraWArgs a) {
     __shared__ __attribute__((aligned(16))) float red[256 * 8];
     const LoraStream& st = a.st[blockIdx.y];
     const int H = a.H, CH = H >> 3;
+    const bool masked = DROP && !st.colmajor;                        // (uniform over the workgroup)
     const int CHW = CH < 256 ? CH : 256, RL = 256 / CHW;
     const int cc = threadIdx.x % CHW, rl = threadIdx.x / CHW;
     const int mbeg = blockIdx.x * LORA_SLAB, mend = min(a.M, mbeg + LORA_SLAB);
@@ -264,6 +334,8 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_w_kernel(const LoraWArgs a) 
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     v[u] = *(const bf16x8*)(src + (size_t)(m + u * RL) * st.lds);
+                    if constexpr (DROP)
+                        if (masked) v[u] = lora_drop8(v[u], a.in.stream, lora_row_pair(nullptr, m + u * RL, H) + 4 * c, a.in.thr_pk);
 #pragma unroll
                     for (int q = 0; q < R / 4; ++q) w[u][q] = *(const bf16x4*)(st.coef + (size_t)(m + u * RL) * st.ldc + 4 * q);
                 }
@@ -277,7 +349,9 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_w_kernel(const LoraWArgs a) 
                     }
             }
             for (; m < mend; m += RL) {
-                const bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
+                bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
+                if constexpr (DROP)
+                    if (masked) v = lora_drop8(v, a.in.stream, lora_row_pair(nullptr, m, H) + 4 * c, a.in.thr_pk);
 #pragma unroll
                 for (int k = 0; k < R; ++k) {
                     const float wk = bf2f(st.coef[(size_t)m * st.ldc + k]);
@@ -364,11 +438,50 @@ static int lora_targets(LoraTarget* t, int targets, const void* const* A, const 
     return nt;
 }
 
-extern "C" {
+// the input-dropout triple of the *_drop entry points: thr16 <= 65535, scale finite and > 0 (thr16 == 0: the triple is otherwise unused)
+static inline bool lora_in_drop_ok(unsigned thr16, float scale) { return thr16 <= 65535u && scale > 0.0f && scale < INFINITY; }
+static inline LoraInDrop lora_in_drop(unsigned in_stream, unsigned thr16, float scale, const int32_t* rows) {
+    LoraInDrop d = {};
+    d.stream = in_stream; d.thr_pk = mmb_thr_packed(thr16); d.c = scale; d.rows = rows;
+    return d;
+}
 
-int mmbert_lora_qkv_fwd(hipStream_t stream, const void* x, int ldx, void* qkv, int ldq, int M, int H, int r, int targets,
-                        const void* const* A, const void* const* B, float scale, void* h_out, int ldh) {
-    if (!lora_shape_ok(M, H, r, targets)) return -1;
+template <bool DROP>
+static int lora_qkv_fwd_launch(hipStream_t stream, const LoraFwdArgs& a, size_t lds) {
+    if (lds > 65536) {
+        static std::atomic<unsigned long long> done{0};
+        const int e = mmb_allow_lds((const void*)lora_qkv_fwd_kernel<DROP>, (int)lds, done);
+        if (e) return e;
+    }
+    hipLaunchKernelGGL(lora_qkv_fwd_kernel<DROP>, dim3((a.M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+template <bool DROP>
+static int lora_qkv_bwd_g_launch(hipStream_t stream, const LoraBwdArgs& a, size_t lds) {
+    if (lds > 65536) {
+        static std::atomic<unsigned long long> done{0};
+        const int e = mmb_allow_lds((const void*)lora_qkv_bwd_g_kernel<DROP>, (int)lds, done);
+        if (e) return e;
+    }
+    hipLaunchKernelGGL(lora_qkv_bwd_g_kernel<DROP>, dim3((a.M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+template <bool DROP>
+static int lora_qkv_bwd_w_launch(hipStream_t stream, dim3 grid, const LoraWArgs& w) {
+    if (w.r == 4) hipLaunchKernelGGL((lora_qkv_bwd_w_kernel<4, DROP>), grid, dim3(256), 0, stream, w);
+    else if (w.r == 8) hipLaunchKernelGGL((lora_qkv_bwd_w_kernel<8, DROP>), grid, dim3(256), 0, stream, w);
+    else hipLaunchKernelGGL((lora_qkv_bwd_w_kernel<16, DROP>), grid, dim3(256), 0, stream, w);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+static int lora_qkv_fwd_impl(hipStream_t stream, const void* x, int ldx, void* qkv, int ldq, int M, int H, int r, int targets,
+                             const void* const* A, const void* const* B, float scale, void* h_out, int ldh,
+                             unsigned in_stream, unsigned in_thr16, float in_scale) {
+    if (!lora_shape_ok(M, H, r, targets) || !lora_in_drop_ok(in_thr16, in_scale)) return -1;
     if (M == 0) return 0;
     LoraFwdArgs a = {};
     a.nt = lora_targets(a.t, targets, A, B);
@@ -377,16 +490,23 @@ int mmbert_lora_qkv_fwd(hipStream_t stream, const void* x, int ldx, void* qkv, i
     if (h_out && (!lora_al8(h_out) || ldh < a.nt * r || (ldh & 3))) return -1;
     const size_t lds = lora_lds_bytes(a.nt, H);
     if (lds > LORA_LDS_MAX) return -2;
-    if (lds > 65536) {
-        static std::atomic<unsigned long long> done{0};
-        const int e = mmb_allow_lds((const void*)lora_qkv_fwd_kernel, (int)lds, done);
-        if (e) return e;
-    }
     a.M = M; a.H = H; a.r = r; a.ldx = ldx; a.ldq = ldq; a.ldh = ldh; a.s = scale;
     a.x = (const bf16_t*)x; a.qkv = (bf16_t*)qkv; a.h = (bf16_t*)h_out;
-    hipLaunchKernelGGL(lora_qkv_fwd_kernel, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
-    MMB_CHECK_LAUNCH();
-    return 0;
+    a.in = lora_in_drop(in_stream, in_thr16, in_scale, nullptr);
+    return in_thr16 ? lora_qkv_fwd_launch<true>(stream, a, lds) : lora_qkv_fwd_launch<false>(stream, a, lds);
+}
+
+extern "C" {
+
+int mmbert_lora_qkv_fwd(hipStream_t stream, const void* x, int ldx, void* qkv, int ldq, int M, int H, int r, int targets,
+                        const void* const* A, const void* const* B, float scale, void* h_out, int ldh) {
+    return lora_qkv_fwd_impl(stream, x, ldx, qkv, ldq, M, H, r, targets, A, B, scale, h_out, ldh, 0u, 0u, 1.0f);
+}
+
+int mmbert_lora_qkv_fwd_drop(hipStream_t stream, const void* x, int ldx, void* qkv, int ldq, int M, int H, int r, int targets,
+                             const void* const* A, const void* const* B, float scale, void* h_out, int ldh,
+                             unsigned in_stream, unsigned in_thr16, float in_scale) {
+    return lora_qkv_fwd_impl(stream, x, ldx, qkv, ldq, M, H, r, targets, A, B, scale, h_out, ldh, in_stream, in_thr16, in_scale);
 }
 
 // [partial sums: 2 nt streams x slabs x r H floats][g: M x nt r bf16][h, when backward recomputes it: the same]; 0 for M == 0 or a bad shape
@@ -399,10 +519,11 @@ size_t mmbert_lora_qkv_bwd_workspace(int M, int H, int r, int targets) {
     return part + 2 * gb;
 }
 
-int mmbert_lora_qkv_bwd(hipStream_t stream, const void* dqkv, int lddq, const void* x, int ldx, const void* h, int ldh, int M, int H, int r,
-                        int targets, const void* const* A, const void* const* B, float scale, const void* dres_in, int lddi,
-                        void* dres_out, int lddo, float* const* gA, float* const* gB, int accumulate, void* workspace) {
-    if (!lora_shape_ok(M, H, r, targets)) return -1;
+static int lora_qkv_bwd_impl(hipStream_t stream, const void* dqkv, int lddq, const void* x, int ldx, const void* h, int ldh, int M, int H, int r,
+                             int targets, const void* const* A, const void* const* B, float scale, const void* dres_in, int lddi,
+                             void* dres_out, int lddo, float* const* gA, float* const* gB, int accumulate, void* workspace,
+                             unsigned in_stream, unsigned in_thr16, float in_scale) {
+    if (!lora_shape_ok(M, H, r, targets) || !lora_in_drop_ok(in_thr16, in_scale)) return -1;
     if (M == 0) return 0;
     LoraBwdArgs a = {};
     a.nt = lora_targets(a.t, targets, A, B);
@@ -414,11 +535,6 @@ int mmbert_lora_qkv_bwd(hipStream_t stream, const void* dqkv, int lddq, const vo
     if (!workspace || !lora_al16(workspace)) return -3;
     const size_t lds = lora_lds_bytes(nt, H);
     if (lds > LORA_LDS_MAX) return -2;
-    if (lds > 65536) {
-        static std::atomic<unsigned long long> done{0};
-        const int e = mmb_allow_lds((const void*)lora_qkv_bwd_g_kernel, (int)lds, done);
-        if (e) return e;
-    }
     const int nslab = (M + LORA_SLAB - 1) / LORA_SLAB;
     const size_t part = (size_t)2 * nt * nslab * (size_t)r * H * sizeof(float);
     const size_t gb = lora_up16((size_t)M * nt * r * sizeof(bf16_t));
@@ -447,18 +563,32 @@ int mmbert_lora_qkv_bwd(hipStream_t stream, const void* dqkv, int lddq, const vo
     }
     a.recompute = need_h ? 1 : 0;
     if (!dres_out && w.ns == 0) return 0;                            // nothing asked for
-    hipLaunchKernelGGL(lora_qkv_bwd_g_kernel, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
-    MMB_CHECK_LAUNCH();
+    a.in = w.in = lora_in_drop(in_stream, in_thr16, in_scale, nullptr);
+    int e = in_thr16 ? lora_qkv_bwd_g_launch<true>(stream, a, lds) : lora_qkv_bwd_g_launch<false>(stream, a, lds);
+    if (e) return e;
     if (w.ns == 0) return 0;
     w.M = M; w.H = H; w.r = r; w.nslab = nslab; w.s = scale; w.part = (float*)workspace;
     const dim3 grid(nslab, w.ns);
-    if (r == 4) hipLaunchKernelGGL(lora_qkv_bwd_w_kernel<4>, grid, dim3(256), 0, stream, w);
-    else if (r == 8) hipLaunchKernelGGL(lora_qkv_bwd_w_kernel<8>, grid, dim3(256), 0, stream, w);
-    else hipLaunchKernelGGL(lora_qkv_bwd_w_kernel<16>, grid, dim3(256), 0, stream, w);
-    MMB_CHECK_LAUNCH();
+    e = in_thr16 ? lora_qkv_bwd_w_launch<true>(stream, grid, w) : lora_qkv_bwd_w_launch<false>(stream, grid, w);
+    if (e) return e;
     hipLaunchKernelGGL(lora_qkv_fold_kernel, dim3((unsigned)(((size_t)r * H / 4 + 255) / 256), w.ns), dim3(256), 0, stream, w);
     MMB_CHECK_LAUNCH();
     return 0;
+}
+
+int mmbert_lora_qkv_bwd(hipStream_t stream, const void* dqkv, int lddq, const void* x, int ldx, const void* h, int ldh, int M, int H, int r,
+                        int targets, const void* const* A, const void* const* B, float scale, const void* dres_in, int lddi,
+                        void* dres_out, int lddo, float* const* gA, float* const* gB, int accumulate, void* workspace) {
+    return lora_qkv_bwd_impl(stream, dqkv, lddq, x, ldx, h, ldh, M, H, r, targets, A, B, scale, dres_in, lddi, dres_out, lddo, gA, gB, accumulate,
+                             workspace, 0u, 0u, 1.0f);
+}
+
+int mmbert_lora_qkv_bwd_drop(hipStream_t stream, const void* dqkv, int lddq, const void* x, int ldx, const void* h, int ldh, int M, int H, int r,
+                             int targets, const void* const* A, const void* const* B, float scale, const void* dres_in, int lddi,
+                             void* dres_out, int lddo, float* const* gA, float* const* gB, int accumulate, void* workspace,
+                             unsigned in_stream, unsigned in_thr16, float in_scale) {
+    return lora_qkv_bwd_impl(stream, dqkv, lddq, x, ldx, h, ldh, M, H, r, targets, A, B, scale, dres_in, lddi, dres_out, lddo, gA, gB, accumulate,
+                             workspace, in_stream, in_thr16, in_scale);
 }
 
 }  // extern "C"
@@ -484,13 +614,15 @@ struct LoraDenseFwdArgs {
     int M, K, N, r, ldx, ldy, ldaux, ldh, gelu;
     float s, sc;                                           // sc = s * drop_scale (ONE fp32 product, formed on the host)
     uint32_t dstream, thr16, thr_pk;
+    LoraInDrop in;                                         // the dropout of the adapter's INPUT x (the triple above: the GEMM's, on y)
 };
 struct LoraDenseBwdArgs {
     const bf16_t* dy; const bf16_t* x; const bf16_t* A; const bf16_t* B; const bf16_t* u; bf16_t* dx; bf16_t* gbuf; bf16_t* hbuf;
     int M, K, N, r, lddy, ldx, lddx, ldu, recompute; float s;
+    LoraInDrop in;
 };
 struct LoraDStream { const bf16_t* src; const bf16_t* coef; float* out; size_t part_off; int lds, ldc, colmajor, acc, W, pad; };
-struct LoraDWArgs { LoraDStream st[2]; int ns, M, r, nslab; float s; float* part; };
+struct LoraDWArgs { LoraDStream st[2]; int ns, M, r, nslab; float s; float* part; LoraInDrop in; };
 
 // T[k][0 .. w) = A[k][k0 .. k0 + w) for k < r, zeros for r <= k < 16 (A: [r, K] row-major); row pitch LORA_DPITCH
 __device__ __forceinline__ void lora_stage_rows_chunk(bf16_t* T, const bf16_t* A, int K, int k0, int w, int r) {
@@ -540,30 +672,38 @@ __device__ __forceinline__ void lora_stage_pad16_t_chunk(bf16_t* U, const bf16_t
     }
 }
 // acc[n][m] += sum_k T[n][k] X[m][k0 + k] over the chunk's w columns (xrow already points at column k0 of this lane's row)
-__device__ __forceinline__ void lora_contract_chunk(f32x4& acc, const bf16_t* T, const bf16_t* xrow, int w, int lane) {
+// DROP: X is read under the input mask; p0 = the pair index of this lane's first fragment of the chunk (row pair + (k0 + 8 g) / 2)
+template <bool DROP>
+__device__ __forceinline__ void lora_contract_chunk(f32x4& acc, const bf16_t* T, const bf16_t* xrow, int w, int lane, const LoraInDrop& d, uint32_t p0) {
     const int i = lane & 15, g = lane >> 4;
     const bf16_t* tr = T + (size_t)i * LORA_DPITCH + 8 * g;
     const bf16_t* xr = xrow + 8 * g;
     for (int k = 0; k < w; k += 32) {
-        const bf16x8 xf = *(const bf16x8*)(xr + k);
+        bf16x8 xf = *(const bf16x8*)(xr + k);
+        if constexpr (DROP) xf = lora_drop8(xf, d.stream, p0 + (uint32_t)(k >> 1), d.thr_pk);
         const bf16x8 tf = *(const bf16x8*)(tr + k);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, xf, acc, 0, 0, 0);
     }
 }
-// h = x . A^T of the wave's 16 rows over all of K, chunk by chunk (every thread of the workgroup calls it: it synchronises)
-__device__ __forceinline__ f32x4 lora_dense_contract(bf16_t* T, const bf16_t* W, bool rows_form, const bf16_t* xrow, int K, int r, bool wave_live, int lane) {
+// h = x . A^T of the wave's 16 rows over all of K, chunk by chunk (every thread of the workgroup calls it: it synchronises).  DROP: x under
+// the input mask (rowpair: lora_row_pair of this lane's row) and c on the finished accumulator
+template <bool DROP>
+__device__ __forceinline__ f32x4 lora_dense_contract(bf16_t* T, const bf16_t* W, bool rows_form, const bf16_t* xrow, int K, int r, bool wave_live, int lane,
+                                                     const LoraInDrop& d, uint32_t rowpair) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < K; k0 += LORA_DCHUNK) {
         const int w = min(LORA_DCHUNK, K - k0);
         if (rows_form) lora_stage_rows_chunk(T, W, K, k0, w, r);
         else lora_stage_cols_t_chunk(T, W, k0, w, r);
         __syncthreads();
-        if (wave_live) lora_contract_chunk(acc, T, xrow + k0, w, lane);
+        if (wave_live) lora_contract_chunk<DROP>(acc, T, xrow + k0, w, lane, d, rowpair + (uint32_t)((k0 + 8 * (lane >> 4)) >> 1));
         __syncthreads();
     }
+    if constexpr (DROP) acc *= d.c;
     return acc;
 }
 
+template <bool DROP>
 __global__ __launch_bounds__(256) void lora_dense_fwd_kernel(const LoraDenseFwdArgs a) {
     __shared__ __attribute__((aligned(16))) bf16_t T[LORA_DTILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
@@ -572,7 +712,8 @@ __global__ __launch_bounds__(256) void lora_dense_fwd_kernel(const LoraDenseFwdA
     const bool live = m < a.M;
     const bool wave_live = blockIdx.x * LORA_ROWS + wave * 16 < a.M;
     const int mr = live ? m : a.M - 1;                              // rows past M read row M - 1 and store nothing
-    const bf16x4 hb = lora_round4(lora_dense_contract(T, a.A, true, a.x + (size_t)mr * a.ldx, K, r, wave_live, lane));
+    const bf16x4 hb = lora_round4(lora_dense_contract<DROP>(T, a.A, true, a.x + (size_t)mr * a.ldx, K, r, wave_live, lane, a.in,
+                                                            DROP ? lora_row_pair(nullptr, mr, K) : 0u));
     const bf16x8 hf = lora_low4(hb);
     if (a.h && live && 4 * g < r) *(bf16x4*)(a.h + (size_t)m * a.ldh + 4 * g) = hb;
     bf16_t* yrow = a.y + (size_t)mr * a.ldy + 8 * g;
@@ -622,6 +763,7 @@ __global__ __launch_bounds__(256) void lora_dense_fwd_kernel(const LoraDenseFwdA
 }
 
 // backward launch 1: g (and h, when it is recomputed) into the workspace, and the in-place update of the input gradient
+template <bool DROP>
 __global__ __launch_bounds__(256) void lora_dense_bwd_g_kernel(const LoraDenseBwdArgs a) {
     __shared__ __attribute__((aligned(16))) bf16_t T[LORA_DTILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
@@ -630,11 +772,14 @@ __global__ __launch_bounds__(256) void lora_dense_bwd_g_kernel(const LoraDenseBw
     const bool live = m < a.M;
     const bool wave_live = blockIdx.x * LORA_ROWS + wave * 16 < a.M;
     const int mr = live ? m : a.M - 1;
+    const uint32_t rowpair = DROP ? lora_row_pair(a.in.rows, mr, K) : 0u;   // the mask of the SITE row: rows[mr] on gathered operands
     if (a.recompute) {                                               // h = bf16(x . A^T), as forward formed it
-        const bf16x4 hb = lora_round4(lora_dense_contract(T, a.A, true, a.x + (size_t)mr * a.ldx, K, r, wave_live, lane));
+        const bf16x4 hb = lora_round4(lora_dense_contract<DROP>(T, a.A, true, a.x + (size_t)mr * a.ldx, K, r, wave_live, lane, a.in, rowpair));
         if (live && 4 * g < r) *(bf16x4*)(a.hbuf + (size_t)m * r + 4 * g) = hb;
     }
-    const bf16x4 gb = lora_round4(lora_dense_contract(T, a.B, false, a.dy + (size_t)mr * a.lddy, N, r, wave_live, lane));
+    f32x4 gacc = lora_dense_contract<false>(T, a.B, false, a.dy + (size_t)mr * a.lddy, N, r, wave_live, lane, a.in, 0u);
+    if constexpr (DROP) gacc *= a.in.c;                              // g carries c: dA and the input gradient need no further factor
+    const bf16x4 gb = lora_round4(gacc);
     const bf16x8 gf = lora_low4(gb);
     if (live && 4 * g < r) *(bf16x4*)(a.gbuf + (size_t)m * r + 4 * g) = gb;
     if (!a.dx) return;                                               // (uniform over the grid)
@@ -660,6 +805,7 @@ __global__ __launch_bounds__(256) void lora_dense_bwd_g_kernel(const LoraDenseBw
                 bf16x8 o;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = f2bf(fmaf(a.s, q[j], bf2f(old[j])));
+                if constexpr (DROP) o = lora_keep_old8(o, old, a.in.stream, rowpair + (uint32_t)((k0 + c0 + 8 * g) >> 1), a.in.thr_pk);
                 if (live) *(bf16x8*)(drow + k0 + c0) = o;
             }
         }
@@ -670,11 +816,14 @@ __global__ __launch_bounds__(256) void lora_dense_bwd_g_kernel(const LoraDenseBw
 // backward launch 2: part[stream][slab][k, c] = sum over the slab's tokens m of coef[m][k] * src[m][c] (fp32; not yet scaled by s); the FMA form
 // of lora_qkv_bwd_w_kernel with a width per stream and the column axis over blockIdx.z (128 lanes x 8 columns per workgroup: an I-wide
 // stream runs on 3 (bert-base) or 4 (bert-large) workgroups per slab with two row lanes each)
-template <int R>
+// DROP: the dA stream (src = x, width K) reads x under the input mask of the SITE rows (rows[m] on gathered operands); the dB stream reads
+// dy and h as they are.
+template <int R, bool DROP>
 __global__ __launch_bounds__(256) void lora_dense_bwd_w_kernel(const LoraDWArgs a) {
     __shared__ __attribute__((aligned(16))) float red[256 * 8];
     const LoraDStream& st = a.st[blockIdx.y];
     const int W = st.W, CH = W >> 3;
+    const bool masked = DROP && !st.colmajor;                        // (uniform over the workgroup)
     const int CHW = CH < 128 ? CH : 128, RL = 256 / CHW;
     const int cb = blockIdx.z * CHW;
     if (cb >= CH) return;                                            // (uniform over the workgroup: the narrower stream has fewer column blocks)
@@ -697,6 +846,8 @@ __global__ __launch_bounds__(256) void lora_dense_bwd_w_kernel(const LoraDWArgs 
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 v[u] = *(const bf16x8*)(src + (size_t)(m + u * RL) * st.lds);
+                if constexpr (DROP)
+                    if (masked) v[u] = lora_drop8(v[u], a.in.stream, lora_row_pair(a.in.rows, m + u * RL, W) + 4 * c, a.in.thr_pk);
 #pragma unroll
                 for (int q = 0; q < R / 4; ++q) w[u][q] = *(const bf16x4*)(st.coef + (size_t)(m + u * RL) * st.ldc + 4 * q);
             }
@@ -710,7 +861,9 @@ __global__ __launch_bounds__(256) void lora_dense_bwd_w_kernel(const LoraDWArgs 
                 }
         }
         for (; m < mend; m += RL) {
-            const bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
+            bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
+            if constexpr (DROP)
+                if (masked) v = lora_drop8(v, a.in.stream, lora_row_pair(a.in.rows, m, W) + 4 * c, a.in.thr_pk);
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const float wk = bf2f(st.coef[(size_t)m * st.ldc + k]);
@@ -782,12 +935,22 @@ static inline bool lora_dense_shape_ok(int M, int K, int N, int r) {
 // what ONE workgroup stages at a time; constant in K and N (the chunking), so the -2 of the convention cannot occur for these kernels
 static inline size_t lora_dense_lds_bytes() { return (size_t)LORA_DTILE * sizeof(bf16_t); }
 
+template <bool DROP>
+static int lora_dense_bwd_w_launch(hipStream_t stream, dim3 grid, const LoraDWArgs& w) {
+    if (w.r == 4) hipLaunchKernelGGL((lora_dense_bwd_w_kernel<4, DROP>), grid, dim3(256), 0, stream, w);
+    else if (w.r == 8) hipLaunchKernelGGL((lora_dense_bwd_w_kernel<8, DROP>), grid, dim3(256), 0, stream, w);
+    else hipLaunchKernelGGL((lora_dense_bwd_w_kernel<16, DROP>), grid, dim3(256), 0, stream, w);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" {
 
-int mmbert_lora_dense_fwd(hipStream_t stream, const void* x, int ldx, void* y, int ldy, int M, int K, int N, int r, const void* A, const void* B,
-                          float scale, int mode, unsigned drop_stream, unsigned drop_thr16, float drop_scale, void* aux, int ldaux,
-                          void* h_out, int ldh) {
+static int lora_dense_fwd_impl(hipStream_t stream, const void* x, int ldx, void* y, int ldy, int M, int K, int N, int r, const void* A, const void* B,
+                               float scale, int mode, unsigned drop_stream, unsigned drop_thr16, float drop_scale, void* aux, int ldaux,
+                               void* h_out, int ldh, unsigned in_stream, unsigned in_thr16, float in_scale) {
     if (!lora_dense_shape_ok(M, K, N, r) || (mode != MMBERT_LORA_DENSE_ADD && mode != MMBERT_LORA_DENSE_GELU)) return -1;
+    if (!lora_in_drop_ok(in_thr16, in_scale)) return -1;
     if (M == 0) return 0;
     if (!x || !y || !A || !B || !lora_al16(x) || !lora_al16(y) || !lora_al16(A) || !lora_al16(B)) return -1;
     if (ldx < K || (ldx & 7) || ldy < N || (ldy & 7) || drop_thr16 > 65535u) return -1;
@@ -799,9 +962,25 @@ int mmbert_lora_dense_fwd(hipStream_t stream, const void* x, int ldx, void* y, i
     a.M = M; a.K = K; a.N = N; a.r = r; a.ldx = ldx; a.ldy = ldy; a.ldaux = ldaux; a.ldh = ldh; a.gelu = mode == MMBERT_LORA_DENSE_GELU;
     a.s = scale; a.sc = scale * drop_scale;
     a.dstream = drop_stream; a.thr16 = a.gelu ? 0u : drop_thr16; a.thr_pk = mmb_thr_packed(drop_thr16);
-    hipLaunchKernelGGL(lora_dense_fwd_kernel, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
+    a.in = lora_in_drop(in_stream, in_thr16, in_scale, nullptr);
+    if (in_thr16) hipLaunchKernelGGL(lora_dense_fwd_kernel<true>, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(lora_dense_fwd_kernel<false>, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
     MMB_CHECK_LAUNCH();
     return 0;
+}
+
+int mmbert_lora_dense_fwd(hipStream_t stream, const void* x, int ldx, void* y, int ldy, int M, int K, int N, int r, const void* A, const void* B,
+                          float scale, int mode, unsigned drop_stream, unsigned drop_thr16, float drop_scale, void* aux, int ldaux,
+                          void* h_out, int ldh) {
+    return lora_dense_fwd_impl(stream, x, ldx, y, ldy, M, K, N, r, A, B, scale, mode, drop_stream, drop_thr16, drop_scale, aux, ldaux, h_out, ldh,
+                               0u, 0u, 1.0f);
+}
+
+int mmbert_lora_dense_fwd_drop(hipStream_t stream, const void* x, int ldx, void* y, int ldy, int M, int K, int N, int r, const void* A, const void* B,
+                               float scale, int mode, unsigned drop_stream, unsigned drop_thr16, float drop_scale, void* aux, int ldaux,
+                               void* h_out, int ldh, unsigned in_stream, unsigned in_thr16, float in_scale) {
+    return lora_dense_fwd_impl(stream, x, ldx, y, ldy, M, K, N, r, A, B, scale, mode, drop_stream, drop_thr16, drop_scale, aux, ldaux, h_out, ldh,
+                               in_stream, in_thr16, in_scale);
 }
 
 // [partial sums: slabs x r (K + N) floats][g: M x r bf16][h, when backward recomputes it: the same]; 0 for M == 0 or a bad shape
@@ -813,10 +992,10 @@ size_t mmbert_lora_dense_bwd_workspace(int M, int K, int N, int r) {
     return part + 2 * gb;
 }
 
-int mmbert_lora_dense_bwd(hipStream_t stream, const void* dy, int lddy, const void* x, int ldx, const void* h, int ldh, int M, int K, int N, int r,
-                          const void* A, const void* B, float scale, void* dx, int lddx, const void* gelu_u, int ldu, float* gA, float* gB,
-                          int accumulate, void* workspace) {
-    if (!lora_dense_shape_ok(M, K, N, r)) return -1;
+static int lora_dense_bwd_impl(hipStream_t stream, const void* dy, int lddy, const void* x, int ldx, const void* h, int ldh, int M, int K, int N, int r,
+                               const void* A, const void* B, float scale, void* dx, int lddx, const void* gelu_u, int ldu, float* gA, float* gB,
+                               int accumulate, void* workspace, unsigned in_stream, unsigned in_thr16, float in_scale, const int32_t* rows) {
+    if (!lora_dense_shape_ok(M, K, N, r) || !lora_in_drop_ok(in_thr16, in_scale) || ((uintptr_t)rows & 3)) return -1;
     if (M == 0) return 0;
     if (!dy || !x || !A || !B || !lora_al16(dy) || !lora_al16(x) || !lora_al16(A) || !lora_al16(B)) return -1;
     if (lddy < N || (lddy & 7) || ldx < K || (ldx & 7)) return -1;
@@ -850,18 +1029,32 @@ int mmbert_lora_dense_bwd(hipStream_t stream, const void* dy, int lddy, const vo
         else { s.coef = a.hbuf; s.ldc = r; }
         if (N > wmax) wmax = N;
     }
-    hipLaunchKernelGGL(lora_dense_bwd_g_kernel, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
+    a.in = w.in = lora_in_drop(in_stream, in_thr16, in_scale, rows);
+    if (in_thr16) hipLaunchKernelGGL(lora_dense_bwd_g_kernel<true>, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(lora_dense_bwd_g_kernel<false>, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
     MMB_CHECK_LAUNCH();
     if (w.ns == 0) return 0;
     w.M = M; w.r = r; w.nslab = nslab; w.s = scale; w.part = (float*)workspace;
     const dim3 grid(nslab, w.ns, (wmax / 8 + 127) / 128);
-    if (r == 4) hipLaunchKernelGGL(lora_dense_bwd_w_kernel<4>, grid, dim3(256), 0, stream, w);
-    else if (r == 8) hipLaunchKernelGGL(lora_dense_bwd_w_kernel<8>, grid, dim3(256), 0, stream, w);
-    else hipLaunchKernelGGL(lora_dense_bwd_w_kernel<16>, grid, dim3(256), 0, stream, w);
-    MMB_CHECK_LAUNCH();
+    const int e = in_thr16 ? lora_dense_bwd_w_launch<true>(stream, grid, w) : lora_dense_bwd_w_launch<false>(stream, grid, w);
+    if (e) return e;
     hipLaunchKernelGGL(lora_dense_fold_kernel, dim3((unsigned)(((size_t)r * wmax / 4 + 255) / 256), w.ns), dim3(256), 0, stream, w);
     MMB_CHECK_LAUNCH();
     return 0;
+}
+
+int mmbert_lora_dense_bwd(hipStream_t stream, const void* dy, int lddy, const void* x, int ldx, const void* h, int ldh, int M, int K, int N, int r,
+                          const void* A, const void* B, float scale, void* dx, int lddx, const void* gelu_u, int ldu, float* gA, float* gB,
+                          int accumulate, void* workspace) {
+    return lora_dense_bwd_impl(stream, dy, lddy, x, ldx, h, ldh, M, K, N, r, A, B, scale, dx, lddx, gelu_u, ldu, gA, gB, accumulate, workspace,
+                               0u, 0u, 1.0f, nullptr);
+}
+
+int mmbert_lora_dense_bwd_drop(hipStream_t stream, const void* dy, int lddy, const void* x, int ldx, const void* h, int ldh, int M, int K, int N, int r,
+                               const void* A, const void* B, float scale, void* dx, int lddx, const void* gelu_u, int ldu, float* gA, float* gB,
+                               int accumulate, void* workspace, unsigned in_stream, unsigned in_thr16, float in_scale, const int* rows) {
+    return lora_dense_bwd_impl(stream, dy, lddy, x, ldx, h, ldh, M, K, N, r, A, B, scale, dx, lddx, gelu_u, ldu, gA, gB, accumulate, workspace,
+                               in_stream, in_thr16, in_scale, (const int32_t*)rows);
 }
 
 }  // extern "C"

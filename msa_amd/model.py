@@ -455,8 +455,9 @@ class _LayerSaved(NamedTuple):
     z1: torch.Tensor; m1: torch.Tensor; r1: torch.Tensor; y1: torch.Tensor          # attention sublayer: pre-LN sum, LN mean / rstd, LN output
     u: torch.Tensor; g: torch.Tensor; z2: torch.Tensor; m2: torch.Tensor; r2: torch.Tensor    # FFN: pre-activation, GELU output, pre-LN sum, LN mean / rstd
     d_att: tuple; d_h1: tuple; d_h2: tuple                                          # the dropout triples: attention, behind Wo, behind W2
-    lora: Optional[tuple] = None       # Q/K/V adapters: (h, {target: (A takes a gradient, B takes one)})
-    dense: Optional[dict] = None       # dense-seam adapters: {target: (h, A takes a gradient, B takes one)}
+    # (the adapters' input-dropout triples travel HERE, never on the model: each forward's backward regenerates its own masks)
+    lora: Optional[tuple] = None       # Q/K/V adapters: (h, {target: (A takes a gradient, B takes one)}, input-dropout triple or None)
+    dense: Optional[dict] = None       # dense-seam adapters: {target: (h, A takes a gradient, B takes one, input-dropout triple or None)}
 
     def head(self, rows):
         """The record with its tensor fields cut to their leading ``rows`` rows (the adapters' h is cut where it is used)."""
@@ -484,6 +485,7 @@ class _EncoderFn:
         train = top.training if train is None else train
         ph = cfg.hidden_dropout_prob if train else 0.0
         pa = cfg.attention_probs_dropout_prob if train else 0.0
+        pl = getattr(top, "lora_dropout", 0.0) if train else 0.0      # the adapters' input dropout, from the step's one seed
         keep_all = keep
         saved = []
         # One C call per layer (mmbert_layer_fwd: the same seven launches with the same arguments, bit-identical) unless somebody wrapped
@@ -500,7 +502,8 @@ class _EncoderFn:
             if composite and lw["lora"] is None and lw.get("lora_dense") is None:
                 x, s_i = _EncoderFn._composite_forward(top, i, x, cl, layout.heads, keep, drops, out, out_rows, probe)
             else:
-                x, s_i = _EncoderFn._layer_forward(top, i, x, layout, key_bias, kv_len, keep, drops, out, out_rows, probe)
+                in_drops = ops.lora_in_drops(pl, seed, i, _EncoderFn._lora_seams(lw)) if pl > 0.0 else None
+                x, s_i = _EncoderFn._layer_forward(top, i, x, layout, key_bias, kv_len, keep, drops, out, out_rows, probe, in_drops)
             if keep_all:
                 saved.append(s_i)
             if top.debug_hidden is not None:
@@ -548,80 +551,99 @@ class _EncoderFn:
                                d_att=d_att, d_h1=d_h1, d_h2=d_h2) if keep else None
 
     @staticmethod
-    def _lora_forward(lo, x, qkv, keep):
-        """The adapters' update of ``qkv`` in place (ops.lora_qkv_fwd), directly behind the QKV product.  Returns what the layer's backward
-        needs (None when nothing is kept): the rank-r activations h and, per target, whether A / B take a gradient."""
+    def _lora_seams(lw):
+        """The seam inputs of a layer that feed an adapter (keys of ops.LORA_DROP_SITES), once per flat storage."""
+        seams = lw.get("_lora_seams")
+        if seams is None:
+            dl = lw.get("lora_dense")
+            seams = lw["_lora_seams"] = (("qkv",) if lw["lora"] is not None else ()) + (tuple(dl["targets"]) if dl is not None else ())
+        return seams
+
+    @staticmethod
+    def _lora_forward(lo, x, qkv, keep, in_drop=None):
+        """The adapters' update of ``qkv`` in place (ops.lora_qkv_fwd), directly behind the QKV product.  ``in_drop``: the dropout triple of
+        the adapters' input (None: none, and the call of a model without adapter dropout).  Returns what the layer's backward needs (None
+        when nothing is kept): the rank-r activations h, per target whether A / B take a gradient, and ``in_drop``."""
         h = torch.empty((x.shape[0], len(lo["targets"]) * lo["r"]), device=x.device, dtype=torch.bfloat16) if keep else None
-        ops.lora_qkv_fwd(x, qkv, lo["A"], lo["B"], lo["targets"], lo["scale"], h_out=h)
+        kw = {} if in_drop is None else {"in_drop": in_drop}
+        ops.lora_qkv_fwd(x, qkv, lo["A"], lo["B"], lo["targets"], lo["scale"], h_out=h, **kw)
         if not keep:
             return None
-        return (h, {t: (lo["pA"][t].requires_grad, lo["pB"][t].requires_grad) for t in lo["targets"]})
+        return (h, {t: (lo["pA"][t].requires_grad, lo["pB"][t].requires_grad) for t in lo["targets"]}, in_drop)
 
     @staticmethod
     def _lora_backward(top, lo, ls, dqkv, x, dres):
         """The adapters' backward directly behind the attention backward (ops.lora_qkv_bwd): their gradients (added: the optimizer zero-fills
         them) and, with ``dres`` (the residual gradient the input-gradient GEMM adds), the NEW tensor that takes its place there."""
-        h, flags = ls
+        h, flags, in_drop = ls
         gA = {t: lo["gA"][t] for t in lo["targets"] if flags[t][0]}
         gB = {t: lo["gB"][t] for t in lo["targets"] if flags[t][1]}
         if dres is None and not gA and not gB:
             return None
-        return ops.lora_qkv_bwd(dqkv, x, h[:dqkv.shape[0]], lo["A"], lo["B"], gA, gB, lo["targets"], lo["scale"], dres=dres, accumulate=True)
+        kw = {} if in_drop is None else {"in_drop": in_drop}
+        return ops.lora_qkv_bwd(dqkv, x, h[:dqkv.shape[0]], lo["A"], lo["B"], gA, gB, lo["targets"], lo["scale"], dres=dres, accumulate=True, **kw)
 
     @staticmethod
-    def _dense_forward(dl, t, x, y, keep, mode=ops.LORA_DENSE_ADD, drop=None, aux=None):
+    def _dense_forward(dl, t, x, y, keep, mode=ops.LORA_DENSE_ADD, drop=None, aux=None, in_drops=None):
         """The adapter of the dense target ``t`` (when the layer has one), in place on ``y`` directly behind the projection's own GEMM
-        (ops.lora_dense_fwd; ``drop``: the triple that GEMM got).  Returns what backward needs, or None: (h, A takes a gradient, B takes one)."""
+        (ops.lora_dense_fwd; ``drop``: the triple that GEMM got; ``in_drops``: the layer's adapter-input triples, ops.lora_in_drops, or
+        None).  Returns what backward needs, or None: (h, A takes a gradient, B takes one, the input-dropout triple or None)."""
         if dl is None or t not in dl["targets"]:
             return None
         h = torch.empty((x.shape[0], dl["r"]), device=x.device, dtype=torch.bfloat16) if keep else None
-        ops.lora_dense_fwd(x, y, dl["A"][t], dl["B"][t], dl["scale"], mode=mode, drop=drop, aux=aux, h_out=h)
-        return (h, dl["pA"][t].requires_grad, dl["pB"][t].requires_grad) if keep else None
+        in_drop = None if in_drops is None else in_drops[t]
+        kw = {} if in_drop is None else {"in_drop": in_drop}
+        ops.lora_dense_fwd(x, y, dl["A"][t], dl["B"][t], dl["scale"], mode=mode, drop=drop, aux=aux, h_out=h, **kw)
+        return (h, dl["pA"][t].requires_grad, dl["pB"][t].requires_grad, in_drop) if keep else None
 
     @staticmethod
-    def _dense_backward(dl, ds, t, dy, x, dx, gelu_u=None, saved_h=True):
+    def _dense_backward(dl, ds, t, dy, x, dx, gelu_u=None, saved_h=True, rows=None):
         """The backward of the dense target ``t`` (when the layer has one) directly behind the input-gradient GEMM of its projection: its
         gradients (added: the optimizer zero-fills them) and the update of ``dx`` in place (ops.lora_dense_bwd).  ``saved_h`` False: the
-        operands are gathered rows, h is recomputed from them (the same bits)."""
+        operands are gathered rows, h is recomputed from them (the same bits); ``rows``: their int32 list -- under the adapter's input
+        dropout row i draws the mask of the ORIGINAL row rows[i]."""
         if dl is None or ds is None or t not in ds:
             return
-        h, fa, fb = ds[t]
+        h, fa, fb, in_drop = ds[t]
+        kw = {} if in_drop is None else ({"in_drop": in_drop} if rows is None else {"in_drop": in_drop, "rows": rows})
         ops.lora_dense_bwd(dy, x, h[:dy.shape[0]] if saved_h else None, dl["A"][t], dl["B"][t], dl["gA"][t] if fa else None,
-                           dl["gB"][t] if fb else None, dl["scale"], dx=dx, gelu_u=gelu_u, accumulate=True)
+                           dl["gB"][t] if fb else None, dl["scale"], dx=dx, gelu_u=gelu_u, accumulate=True, **kw)
 
     @staticmethod
-    def _layer_forward(top, i, x, layout, key_bias, kv_len, keep, drops, out, out_rows, probe):
+    def _layer_forward(top, i, x, layout, key_bias, kv_len, keep, drops, out, out_rows, probe, in_drops=None):
         """One encoder layer, one call per launch.  ``drops``: its dropout triples (attention, behind Wo, behind W2); ``out`` /
-        ``out_rows``: run_forward's y_out / y_rows on the last layer.  Returns (output, what backward keeps or None)."""
+        ``out_rows``: run_forward's y_out / y_rows on the last layer; ``in_drops``: the adapters' input-dropout triples (ops.lora_in_drops)
+        or None.  Returns (output, what backward keeps or None)."""
         lw = top._lw[i]
         d_att, d_h1, d_h2 = drops
         qkv = ops.gemm_nt(x, lw["Wqkv"], bias=lw["bqkv"])
-        ls = _EncoderFn._lora_forward(lw["lora"], x, qkv, keep) if lw["lora"] is not None else None
+        ls = _EncoderFn._lora_forward(lw["lora"], x, qkv, keep, None if in_drops is None else in_drops["qkv"]) if lw["lora"] is not None else None
         actx, lse = ops.attn_fwd(qkv, key_bias, layout, top.config.hidden_size, drop=d_att, kv_len=kv_len)
         if probe is not None:
             probe(i, qkv)
-        y2, kept = _EncoderFn._forward_behind_attention(top, lw, actx, x, keep, d_h1, d_h2, out, out_rows)
+        y2, kept = _EncoderFn._forward_behind_attention(top, lw, actx, x, keep, d_h1, d_h2, out, out_rows, in_drops)
         return y2, _LayerSaved(x=x, qkv=qkv, actx=actx, lse=lse, d_att=d_att, d_h1=d_h1, d_h2=d_h2, lora=ls, **kept) if keep else None
 
     @staticmethod
-    def _forward_behind_attention(top, lw, actx, xr, keep, d_h1=None, d_h2=None, out=None, out_rows=None):
+    def _forward_behind_attention(top, lw, actx, xr, keep, d_h1=None, d_h2=None, out=None, out_rows=None, in_drops=None):
         """Everything behind the attention of a layer, one call per launch, each dense-seam adapter directly behind its projection's GEMM.
         ``actx`` / ``xr`` (the residual): all rows of the layer, or the gathered rows of run_top_first; ``out`` / ``out_rows``: where the last
-        LayerNorm writes.  Returns (output, the _LayerSaved fields it produced or None when nothing is kept)."""
+        LayerNorm writes; ``in_drops``: the adapters' input-dropout triples or None.  Returns (output, the _LayerSaved fields it produced or None
+        when nothing is kept)."""
         cfg = top.config
         dl, ds = lw.get("lora_dense"), {}
         z1 = ops.gemm_nt(actx, lw["Wo"], bias=lw["bo"], resid=xr, drop=d_h1)
-        ds["attention_output"] = _EncoderFn._dense_forward(dl, "attention_output", actx, z1, keep, drop=d_h1)
+        ds["attention_output"] = _EncoderFn._dense_forward(dl, "attention_output", actx, z1, keep, drop=d_h1, in_drops=in_drops)
         y1, m1, r1 = ops.ln_fwd(z1, lw["ln1_g"], lw["ln1_b"], cfg.layer_norm_eps, stats=keep)
         u = torch.empty((xr.shape[0], cfg.intermediate_size), device=xr.device, dtype=torch.bfloat16) if keep else None
         if dl is not None and "intermediate" in dl["targets"]:
             # GELU is not linear: the GEMM leaves bf16(v) (bias only), the adapter launch adds its delta, stores the pre-activation and applies GELU
             g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"])
-            ds["intermediate"] = _EncoderFn._dense_forward(dl, "intermediate", y1, g, keep, mode=ops.LORA_DENSE_GELU, aux=u)
+            ds["intermediate"] = _EncoderFn._dense_forward(dl, "intermediate", y1, g, keep, mode=ops.LORA_DENSE_GELU, aux=u, in_drops=in_drops)
         else:
             g = ops.gemm_nt(y1, lw["W1"], bias=lw["b1"], gelu=True, aux=u)
         z2 = ops.gemm_nt(g, lw["W2"], bias=lw["b2"], resid=y1, drop=d_h2)
-        ds["ffn_output"] = _EncoderFn._dense_forward(dl, "ffn_output", g, z2, keep, drop=d_h2)
+        ds["ffn_output"] = _EncoderFn._dense_forward(dl, "ffn_output", g, z2, keep, drop=d_h2, in_drops=in_drops)
         y2, m2, r2 = ops.ln_fwd(z2, lw["ln2_g"], lw["ln2_b"], cfg.layer_norm_eps, stats=keep, out=out, out_rows=out_rows)
         return y2, dict(z1=z1, m1=m1, r1=r1, y1=y1, u=u, g=g, z2=z2, m2=m2, r2=r2,
                         dense=None if dl is None else {t: v for t, v in ds.items() if v is not None}) if keep else None
@@ -864,16 +886,16 @@ class _EncoderFn:
         du = ops.gemm_nt(dz2d, lw["W2T"], gelu_bwd_u=s.u)
         # (the dense adapters update the input gradients in place, each directly behind the GEMM that wrote it: the buffers are fresh
         # and nothing launched earlier reads them; the weight-gradient problems read the final du)
-        _EncoderFn._dense_backward(dl, s.dense, "ffn_output", dz2d, s.g, du, gelu_u=s.u, saved_h=full)
+        _EncoderFn._dense_backward(dl, s.dense, "ffn_output", dz2d, s.g, du, gelu_u=s.u, saved_h=full, rows=rows)
         dy1 = ops.gemm_nt(du, lw["W1T"], resid=dz2) if full or n > 1024 else ops.gemm_nt_splitk(du, lw["W1T"], resid=dz2)
-        _EncoderFn._dense_backward(dl, s.dense, "intermediate", du, s.y1, dy1, saved_h=full)
+        _EncoderFn._dense_backward(dl, s.dense, "intermediate", du, s.y1, dy1, saved_h=full, rows=rows)
         # --- attention sublayer: y1 = LN(dropout(ctx.Wo^T + bo) + x)
         dz1d = torch.empty((n, H), device=s.z2.device, dtype=torch.bfloat16) if s.d_h1[1] else None
         dz1 = ops.ln_bwd(dy1, s.z1, s.m1, s.r1, lw["ln1_g"], g1g, g1b, dx2=dz1d, pre_drop=s.d_h1, deferred=lnd, x_rows=rows, drop_rows=rows)
         if dz1d is None:
             dz1d = dz1
         dctx = ops.gemm_nt(dz1d, lw["WoT"])
-        _EncoderFn._dense_backward(dl, s.dense, "attention_output", dz1d, s.actx, dctx, saved_h=full)
+        _EncoderFn._dense_backward(dl, s.dense, "attention_output", dz1d, s.actx, dctx, saved_h=full, rows=rows)
         return dz2, dz2d, du, dy1, dz1, dz1d, dctx
 
     @staticmethod
@@ -2531,6 +2553,7 @@ class MMBertForPretraining(_GpuModelBase):
         self.cpc_zt, self.cpc_zv, self.cpc_za = (CPC(H, H, 1, "Tanh") for _ in range(3))
         self._init_runtime()
         self._lora = None                                            # add_lora: {"r", "alpha", "targets", "layers"}
+        self.lora_dropout = 0.0                                      # add_lora / set_lora_dropout: a training setting, not part of _lora
         self.return_scores = True
         # dtype of the returned prediction-score tensors (outputs[7], [9], [11]): zero-copy [B, S, vocab] views of the logits the
         # vocabulary GEMM writes.  DEVIATION from the reference (fp32 scores): the default stores bf16, the compute dtype of the path;
@@ -2815,7 +2838,21 @@ class MMBertForPretraining(_GpuModelBase):
             return []
         return [(i, t, self._lora_linear(i, t)) for i in lc["layers"] for t in lc["targets"]]
 
-    def add_lora(self, r=8, alpha=16.0, targets=("query", "value"), layers=None, freeze_base=True, seed=None):
+    @staticmethod
+    def _lora_dropout_value(p, what):
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) < 1.0:      # (a NaN fails the comparison)
+            raise ValueError(f"{what}: dropout must be a number with 0 <= dropout < 1, got {p!r}")
+        return float(p)
+
+    def set_lora_dropout(self, p):
+        """The dropout probability of the adapters' input (see ``add_lora``), 0 <= p < 1; takes effect at the next ``forward`` and leaves the
+        flat storage and the optimizer as they are.  ValueError without adapters."""
+        if not getattr(self, "_lora", None):
+            raise ValueError("set_lora_dropout: the model has no adapters")
+        self.lora_dropout = self._lora_dropout_value(p, "set_lora_dropout")
+        return self
+
+    def add_lora(self, r=8, alpha=16.0, targets=("query", "value"), layers=None, freeze_base=True, seed=None, dropout=0.0):
         """DECLARED EXTENSION: low-rank adapters on a layer's dense projections.  For every layer of ``layers`` (None: all) and every name of
         ``targets`` (a non-empty subset of query / key / value / attention_output / intermediate / ffn_output, or "all-linear" for all six)
         registers ``lora_A`` [r, K] (kaiming-uniform, a = sqrt 5: bound 1 / sqrt(K), K the projection's own fan-in) and ``lora_B`` [N, r]
@@ -2823,6 +2860,10 @@ class MMBertForPretraining(_GpuModelBase):
         ``intermediate.dense`` (H -> I), ``output.dense`` (I -> H); the projection then computes x W^T + b + (alpha / r) (x A^T) B^T.  The As
         are drawn from ONE generator seeded by ``seed``, in this order: first query / key / value for every layer in ascending order (so a
         seed gives those the As it always gave), then attention_output / intermediate / ffn_output for every layer in ascending order.
+        ``dropout`` (0 <= p < 1; ``model.lora_dropout``, changed by ``set_lora_dropout``): in train mode the low-rank branch reads
+        dropout_p(x) -- (alpha / r) (dropout_p(x) A^T) B^T -- while the base product keeps the undropped x; eval mode, every ``predict*`` and
+        ``merge_lora`` never drop.  Declared difference from peft: ONE mask per seam input, so the query / key / value adapters of a layer,
+        which read the same x, share its mask.
         r in {4, 8, 16}; the dense targets need intermediate_size % 64 == 0.  ``freeze_base``: ``requires_grad_(False)`` on every ``bert.embeddings.*``,
         ``bert.jointEmbeddings.*`` and ``bert.encoder.*`` parameter but the adapters (pooler and heads keep their flags).  The flat storage
         is dropped (rebuilt on the next use): call it BEFORE the optimizer is built, like ``set_num_labels``.  Invalid arguments, or
@@ -2842,6 +2883,7 @@ class MMBertForPretraining(_GpuModelBase):
         alpha = float(alpha)
         if not math.isfinite(alpha):
             raise ValueError(f"add_lora: alpha must be finite, got {alpha!r}")
+        dropout = self._lora_dropout_value(dropout, "add_lora")
         idx = list(range(L)) if layers is None else list(layers)
         if not idx or any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < L for i in idx) or len(set(idx)) != len(idx):
             raise ValueError(f"add_lora: layers must be distinct indices in 0 .. {L - 1} (None: all), got {layers!r}")
@@ -2857,6 +2899,7 @@ class MMBertForPretraining(_GpuModelBase):
                     lin.lora_A = nn.Parameter(A.to(device=w.device, dtype=w.dtype))
                     lin.lora_B = nn.Parameter(torch.zeros((N, r), device=w.device, dtype=w.dtype))
         self._lora = dict(r=r, alpha=alpha, targets=names, layers=tuple(sorted(idx)))
+        self.lora_dropout = dropout
         if freeze_base:
             for n, p in self.named_parameters():
                 if n.startswith(self._LORA_BASE) and ".lora_" not in n:
@@ -2866,11 +2909,12 @@ class MMBertForPretraining(_GpuModelBase):
 
     def remove_lora(self):
         """Drops the adapters without merging them (``requires_grad`` flags stay as they are; ``unfreeze()`` resets them) and the flat
-        storage with them: an optimizer built before is stale."""
+        storage with them: an optimizer built before is stale.  ``lora_dropout`` returns to 0."""
         for _, _, lin in self._lora_linears():
             del lin.lora_A
             del lin.lora_B
         self._lora = None
+        self.lora_dropout = 0.0
         self._flat = None
         return self
 
@@ -2887,7 +2931,8 @@ class MMBertForPretraining(_GpuModelBase):
         return self.remove_lora()
 
     def lora_state_dict(self):
-        """The adapter tensors by their state-dict names (clones) and {"r", "alpha", "targets", "layers"}: the per-task file."""
+        """The adapter tensors by their state-dict names (clones) and {"r", "alpha", "targets", "layers"}: the per-task file.  (The adapter
+        dropout is a training setting and is not written: the file's non-tensor keys are exactly these four.)"""
         lc = getattr(self, "_lora", None)
         if not lc:
             raise ValueError("lora_state_dict: the model has no adapters")
@@ -2900,11 +2945,13 @@ class MMBertForPretraining(_GpuModelBase):
     def load_lora_state_dict(self, sd, freeze_base=True):
         """Loads what ``lora_state_dict`` returned: creates the adapters when the model has none (``add_lora`` with the file's r, alpha,
         targets and layers, and ``freeze_base``), raises ValueError when existing ones differ in any of the four or a tensor is missing or
-        has another shape, copies the values and calls ``parameters_changed()``."""
+        has another shape, copies the values and calls ``parameters_changed()``.  An optional plain float ``sd["dropout"]`` is the adapter
+        dropout ``add_lora`` gets when the adapters are created here (absent: 0); it never enters the comparison -- a training setting, not a
+        property of the weights -- and existing adapters keep theirs."""
         meta = dict(r=int(sd["r"]), alpha=float(sd["alpha"]), targets=tuple(t for t in ops.LORA_ALL_TARGETS if t in tuple(sd["targets"])),
                     layers=tuple(sorted(int(i) for i in sd["layers"])))
         if not getattr(self, "_lora", None):
-            self.add_lora(meta["r"], meta["alpha"], meta["targets"], meta["layers"], freeze_base=freeze_base)
+            self.add_lora(meta["r"], meta["alpha"], meta["targets"], meta["layers"], freeze_base=freeze_base, dropout=float(sd.get("dropout", 0.0)))
         if self._lora != meta:
             raise ValueError(f"load_lora_state_dict: the model's adapters {self._lora} differ from the file's {meta}")
         todo = []

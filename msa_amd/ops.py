@@ -1584,16 +1584,21 @@ def _pitch(t) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
-def lora_qkv_fwd(x, qkv, A, B, targets, scale, h_out=None):
+def lora_qkv_fwd(x, qkv, A, B, targets, scale, h_out=None, in_drop: Drop = None):
     """In place on ``qkv`` [M, 3H] bf16: for every target t, qkv_t += scale * bf16(x @ A[t]^T) @ B[t]^T (see mmbert_lora_qkv_fwd).
-    ``A`` / ``B``: {target name: bf16 tensor}; ``h_out`` [M, len(targets) * r] bf16 receives the rank-r activations.  Returns qkv."""
+    ``A`` / ``B``: {target name: bf16 tensor}; ``h_out`` [M, len(targets) * r] bf16 receives the rank-r activations.  ``in_drop``: the
+    dropout triple of the adapters' input (one mask of x for all targets, mmbert_lora_qkv_fwd_drop); None: today's call.  Returns qkv."""
     M, H = x.shape
     assert x.dtype == torch.bfloat16 and qkv.dtype == torch.bfloat16 and qkv.shape == (M, 3 * H) and (M == 0 or (x.stride(1) == 1 and qkv.stride(1) == 1))
     mask, r, names, pa, pb = _lora_operands(A, B, targets, H, "lora_qkv_fwd")
     if h_out is not None:
         assert h_out.dtype == torch.bfloat16 and h_out.shape == (M, len(names) * r) and (M == 0 or h_out.stride(1) == 1)
-    _lib.check(_lib.load().mmbert_lora_qkv_fwd(_stream(), x.data_ptr(), _pitch(x), qkv.data_ptr(), _pitch(qkv), M, H, r, mask, pa, pb, float(scale),
-                                               _ptr(h_out), _pitch(h_out) if h_out is not None else 0), "mmbert_lora_qkv_fwd")
+    args = (_stream(), x.data_ptr(), _pitch(x), qkv.data_ptr(), _pitch(qkv), M, H, r, mask, pa, pb, float(scale),
+            _ptr(h_out), _pitch(h_out) if h_out is not None else 0)
+    if in_drop is None:
+        _lib.check(_lib.load().mmbert_lora_qkv_fwd(*args), "mmbert_lora_qkv_fwd")
+    else:
+        _lib.check(_lib.load().mmbert_lora_qkv_fwd_drop(*args, *in_drop), "mmbert_lora_qkv_fwd_drop")
     return qkv
 
 
@@ -1601,11 +1606,12 @@ def lora_qkv_bwd_workspace(M: int, H: int, r: int, targets) -> int:
     return int(_lib.load().mmbert_lora_qkv_bwd_workspace(int(M), int(H), int(r), lora_mask(targets)))
 
 
-def lora_qkv_bwd(dqkv, x, h, A, B, gA, gB, targets, scale, dres=None, accumulate=True, workspace=None):
+def lora_qkv_bwd(dqkv, x, h, A, B, gA, gB, targets, scale, dres=None, accumulate=True, workspace=None, in_drop: Drop = None):
     """The adapters' backward from ``dqkv`` [M, 3H] bf16 (see mmbert_lora_qkv_bwd): gA[t] [r, H] (+)= scale * g_t^T @ x and
     gB[t] [H, r] (+)= scale * dqkv_t^T @ h_t (fp32; a missing name or None: not computed; ``gA`` / ``gB`` may be None), g_t = bf16(dqkv_t @ B[t]).
     ``h``: forward's h_out, or None (recomputed from x and A).  ``dres`` [M, H] bf16: returns a NEW tensor bf16(dres + scale * sum_t g_t @ A[t])
-    (``dres`` itself is not written); None: no input-gradient part, returns None.  ``workspace``: a caller's buffer (tests)."""
+    (``dres`` itself is not written); None: no input-gradient part, returns None.  ``workspace``: a caller's buffer (tests).  ``in_drop``: the
+    triple forward got (mmbert_lora_qkv_bwd_drop: the same mask again, bit for bit); None: today's call."""
     lib = _lib.load()
     M, H = x.shape
     assert dqkv.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and dqkv.shape == (M, 3 * H) and (M == 0 or (x.stride(1) == 1 and dqkv.stride(1) == 1))
@@ -1625,9 +1631,13 @@ def lora_qkv_bwd(dqkv, x, h, A, B, gA, gB, targets, scale, dres=None, accumulate
                 dst[LORA_TARGETS.index(t)] = g.data_ptr()
     if workspace is None:
         workspace = _ws_f32((lib.mmbert_lora_qkv_bwd_workspace(M, H, r, mask) + 3) // 4, x.device)
-    _lib.check(lib.mmbert_lora_qkv_bwd(_stream(), dqkv.data_ptr(), _pitch(dqkv), x.data_ptr(), _pitch(x), _ptr(h), _pitch(h) if h is not None else 0,
-                                       M, H, r, mask, pa, pb, float(scale), _ptr(dres), _pitch(dres) if dres is not None else 0,
-                                       _ptr(out), H, _Ptr3(*ga), _Ptr3(*gb), 1 if accumulate else 0, workspace.data_ptr()), "mmbert_lora_qkv_bwd")
+    args = (_stream(), dqkv.data_ptr(), _pitch(dqkv), x.data_ptr(), _pitch(x), _ptr(h), _pitch(h) if h is not None else 0,
+            M, H, r, mask, pa, pb, float(scale), _ptr(dres), _pitch(dres) if dres is not None else 0,
+            _ptr(out), H, _Ptr3(*ga), _Ptr3(*gb), 1 if accumulate else 0, workspace.data_ptr())
+    if in_drop is None:
+        _lib.check(lib.mmbert_lora_qkv_bwd(*args), "mmbert_lora_qkv_bwd")
+    else:
+        _lib.check(lib.mmbert_lora_qkv_bwd_drop(*args, *in_drop), "mmbert_lora_qkv_bwd_drop")
     return out
 
 
@@ -1637,6 +1647,17 @@ LORA_DENSE_TARGETS = ("attention_output", "intermediate", "ffn_output")
 LORA_ALL_TARGETS = LORA_TARGETS + LORA_DENSE_TARGETS          # the canonical order (model._lora["targets"], the seeded draws of A)
 LORA_DENSE_MODULES = {"attention_output": "attention.output.dense", "intermediate": "intermediate.dense", "ffn_output": "output.dense"}
 LORA_DENSE_ADD, LORA_DENSE_GELU = 0, 1
+
+
+# adapter-input dropout (mmbert_lora_*_drop): the site offsets of a layer's four seam inputs -- layer i draws site 8 * i + offset, beside
+# its attention / hidden dropout sites 8 * i + {0, 1, 2}; the q / k / v adapters read the same x and share its mask; 8 * i + 7 stays free
+LORA_DROP_SITES = {"qkv": 3, "attention_output": 4, "intermediate": 5, "ffn_output": 6}
+
+
+def lora_in_drops(p: float, seed: int, layer: int, seams=None):
+    """{seam: (stream, thr16, scale)} of the adapter-input dropout of encoder layer ``layer`` under the step's ``seed`` (the seams and their
+    sites: LORA_DROP_SITES); ``seams``: only these (the ones a layer has adapters on: a stream is one C call)."""
+    return {k: make_drop(p, seed, 8 * layer + off) for k, off in LORA_DROP_SITES.items() if seams is None or k in seams}
 
 
 def lora_dense_dims(target: str, H: int, I: int):
@@ -1667,19 +1688,24 @@ def _lora_dense_check(x, y, A, B, what):
     return M, K, N, r
 
 
-def lora_dense_fwd(x, y, A, B, scale, mode=LORA_DENSE_ADD, drop: Drop = None, aux=None, h_out=None):
+def lora_dense_fwd(x, y, A, B, scale, mode=LORA_DENSE_ADD, drop: Drop = None, aux=None, h_out=None, in_drop: Drop = None):
     """In place on ``y`` [M, N] bf16, what the projection's own gemm_nt left (see mmbert_lora_dense_fwd), with p = bf16(x @ A^T) @ B^T:
     LORA_DENSE_ADD: y += scale * c * p, c = the dropout scale where the GEMM's ``drop`` (the same triple) kept the element, 0 where it dropped;
-    LORA_DENSE_GELU: w = y + scale * p, ``aux`` [M, N] bf16 (optional) = w, y = gelu(w).  ``h_out`` [M, r] bf16 receives x @ A^T.  Returns y."""
+    LORA_DENSE_GELU: w = y + scale * p, ``aux`` [M, N] bf16 (optional) = w, y = gelu(w).  ``h_out`` [M, r] bf16 receives x @ A^T.  ``in_drop``: the
+    dropout triple of the adapter's input x (mmbert_lora_dense_fwd_drop; ``drop`` is the GEMM's, on y); None: today's call.  Returns y."""
     M, K, N, r = _lora_dense_check(x, y, A, B, "lora_dense_fwd")
     if aux is not None:
         assert aux.dtype == torch.bfloat16 and aux.shape == (M, N) and (M == 0 or aux.stride(1) == 1)
     if h_out is not None:
         assert h_out.dtype == torch.bfloat16 and h_out.shape == (M, r) and (M == 0 or h_out.stride(1) == 1)
     ds, dt, dsc = drop or NO_DROP
-    _lib.check(_lib.load().mmbert_lora_dense_fwd(_stream(), x.data_ptr(), _pitch(x), y.data_ptr(), _pitch(y), M, K, N, r, A.data_ptr(), B.data_ptr(),
-                                                 float(scale), int(mode), ds, dt, dsc, _ptr(aux), _pitch(aux) if aux is not None else 0,
-                                                 _ptr(h_out), _pitch(h_out) if h_out is not None else 0), "mmbert_lora_dense_fwd")
+    args = (_stream(), x.data_ptr(), _pitch(x), y.data_ptr(), _pitch(y), M, K, N, r, A.data_ptr(), B.data_ptr(),
+            float(scale), int(mode), ds, dt, dsc, _ptr(aux), _pitch(aux) if aux is not None else 0,
+            _ptr(h_out), _pitch(h_out) if h_out is not None else 0)
+    if in_drop is None:
+        _lib.check(_lib.load().mmbert_lora_dense_fwd(*args), "mmbert_lora_dense_fwd")
+    else:
+        _lib.check(_lib.load().mmbert_lora_dense_fwd_drop(*args, *in_drop), "mmbert_lora_dense_fwd_drop")
     return y
 
 
@@ -1687,11 +1713,13 @@ def lora_dense_bwd_workspace(M: int, K: int, N: int, r: int) -> int:
     return int(_lib.load().mmbert_lora_dense_bwd_workspace(int(M), int(K), int(N), int(r)))
 
 
-def lora_dense_bwd(dy, x, h, A, B, gA, gB, scale, dx=None, gelu_u=None, accumulate=True, workspace=None):
+def lora_dense_bwd(dy, x, h, A, B, gA, gB, scale, dx=None, gelu_u=None, accumulate=True, workspace=None, in_drop: Drop = None, rows=None):
     """One dense adapter's backward from ``dy`` [M, N] bf16, the gradient of the projection's output before its dropout (see
     mmbert_lora_dense_bwd): gA [r, K] (+)= scale * g^T @ x, gB [N, r] (+)= scale * dy^T @ h (fp32; None: not computed), g = bf16(dy @ B);
     ``dx`` [M, K] bf16 is updated IN PLACE, dx += scale * (g @ A) (* gelu'(``gelu_u``) when given); None: no input-gradient part.  ``h``:
-    forward's h_out, or None (recomputed from x and A).  ``workspace``: a caller's buffer (tests).  Returns dx."""
+    forward's h_out, or None (recomputed from x and A).  ``workspace``: a caller's buffer (tests).  ``in_drop``: the triple forward got
+    (mmbert_lora_dense_bwd_drop); ``rows`` [M] int32: the operands are gathered rows and row i draws the mask of site row rows[i] (None: the
+    identity).  With neither: today's call.  Returns dx."""
     lib = _lib.load()
     M, K, N, r = _lora_dense_check(x, dy, A, B, "lora_dense_bwd")
     if h is not None:
@@ -1704,10 +1732,15 @@ def lora_dense_bwd(dy, x, h, A, B, gA, gB, scale, dx=None, gelu_u=None, accumula
             assert g.dtype == torch.float32 and tuple(g.shape) == shape and g.is_contiguous()
     if workspace is None:
         workspace = _ws_f32((lib.mmbert_lora_dense_bwd_workspace(M, K, N, r) + 3) // 4, x.device)
-    _lib.check(lib.mmbert_lora_dense_bwd(_stream(), dy.data_ptr(), _pitch(dy), x.data_ptr(), _pitch(x), _ptr(h), _pitch(h) if h is not None else 0,
-                                         M, K, N, r, A.data_ptr(), B.data_ptr(), float(scale), _ptr(dx), _pitch(dx) if dx is not None else 0,
-                                         _ptr(gelu_u), _pitch(gelu_u) if gelu_u is not None else 0, _ptr(gA), _ptr(gB), 1 if accumulate else 0,
-                                         workspace.data_ptr()), "mmbert_lora_dense_bwd")
+    args = (_stream(), dy.data_ptr(), _pitch(dy), x.data_ptr(), _pitch(x), _ptr(h), _pitch(h) if h is not None else 0,
+            M, K, N, r, A.data_ptr(), B.data_ptr(), float(scale), _ptr(dx), _pitch(dx) if dx is not None else 0,
+            _ptr(gelu_u), _pitch(gelu_u) if gelu_u is not None else 0, _ptr(gA), _ptr(gB), 1 if accumulate else 0, workspace.data_ptr())
+    if in_drop is None and rows is None:
+        _lib.check(lib.mmbert_lora_dense_bwd(*args), "mmbert_lora_dense_bwd")
+    else:
+        if rows is not None:
+            assert rows.dtype == torch.int32 and rows.shape == (M,) and rows.is_contiguous() and rows.device == x.device
+        _lib.check(lib.mmbert_lora_dense_bwd_drop(*args, *(in_drop or NO_DROP), _ptr(rows)), "mmbert_lora_dense_bwd_drop")
     return dx
 
 

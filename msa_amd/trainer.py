@@ -326,7 +326,8 @@ def apply_freeze(model, args):
 def apply_lora(model, args):
     """``model.add_lora`` from the optional ``args.lora_rank`` (4, 8 or 16), ``args.lora_alpha`` (default 2 x rank), ``args.lora_targets``
     (default query + value; any of query / key / value / attention_output / intermediate / ffn_output, or "all-linear"),
-    ``args.lora_layers`` (default all), ``args.lora_freeze_base`` (default True) and ``args.lora_seed``.
+    ``args.lora_layers`` (default all), ``args.lora_freeze_base`` (default True), ``args.lora_seed`` and ``args.lora_dropout`` (default 0:
+    the dropout of the adapters' input in train mode).
     ``default_args()`` has none of them: without ``lora_rank`` (or with None) nothing happens.  Call it before the optimizer is built
     (``build_optimizer`` does, for a model that has no adapters yet).  Returns whether adapters were added."""
     r = getattr(args, "lora_rank", None)
@@ -334,7 +335,7 @@ def apply_lora(model, args):
         return False
     model.add_lora(r=r, alpha=getattr(args, "lora_alpha", None) or 2.0 * r, targets=getattr(args, "lora_targets", None) or ("query", "value"),
                    layers=getattr(args, "lora_layers", None), freeze_base=bool(getattr(args, "lora_freeze_base", True)),
-                   seed=getattr(args, "lora_seed", None))
+                   seed=getattr(args, "lora_seed", None), dropout=getattr(args, "lora_dropout", None) or 0.0)
     return True
 
 
