@@ -563,6 +563,37 @@ int mmbert_adamw_ema(mmbert_stream_t stream, float* p, float* g, float* m, float
  * temporary; twice restores everything bitwise.  n % 256 == 0. */
 int mmbert_ema_swap(mmbert_stream_t stream, float* p, float* ema, void* p_bf16, size_t n);
 
+/* ---- optimizer: flat LAMB (You et al. 2020, Algorithm 2 with bias correction; apex FusedLAMB's defaults) ----
+ * Over the buffers, flags, group_of_block (NULL: every block is group 0) and hyper table of mmbert_adamw_grouped, with g' = gscale g (host
+ * gscale when coef == NULL, else the device scalar coef[0]) and t = step >= 1:
+ *   m = beta1 m + (1 - beta1) g'      v = beta2 v + (1 - beta2) g'^2          (bit-identical to what mmbert_adamw_grouped writes)
+ *   u = (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps) + wd p          (wd: the block's group's weight_decay if flagged "decay", else 0)
+ *   p = p - lr r_T u                                                          (r_T: the trust ratio of the element's TRUST UNIT T)
+ * A trust unit is a parameter tensor.  units[4 T ..] = (b0, b1, adapt, 0): blocks b0 <= b < b1 are those that may hold elements of T.
+ * r_T = ||p_T|| / ||u_T|| (both over T's elements, p before the step) when adapt != 0 and both norms are > 0, else 1; then
+ * min(r_T, max_trust) when max_trust > 0 (0: no cap).  ratios[3 T ..] = (r_T, ||p_T||, ||u_T||) in fp32, written for every T < nunits.
+ * Which elements belong to which unit -- device int32 maps, read by the kernels only:
+ *   unit_of_block[b] >= 0: block b is PURE, all 256 elements (padding included: p = g = 0 adds nothing) are in that unit;
+ *   unit_of_block[b] = -(k + 1): block b is MIXED, record k of `mixed`: eight ints (q0, u0, q1, u1, q2, u2, q3, u3).  The block's 64
+ *     aligned quads (4 floats) q_e <= q < q_(e+1) belong to unit u_e; q0 = 0, the q ascend, an unused entry has q = 64; u_e = -1 is
+ *     "no unit" (ratio 1, nothing measured).  So every unit boundary inside a block is a multiple of 4 elements;
+ *   blocks with (flags & 3) == 2 are frozen: p, m, v keep their bits, they belong to no unit and their map entry is not read.
+ * Indices outside their tables are clamped into them (never read past), they are not diagnosed.
+ * Three launches on stream, no atomics, no host read, no allocation: (1) moments + per-wave sums of p^2 and u^2 (fp32) into workspace
+ * (>= MMBERT_LAMB_WORKSPACE(n / 256, nmixed) bytes, caller-owned, no other use during the call; pure block b owns slot b, entry e of
+ * record k slot n / 256 + 4 k + e); (2) one workgroup per unit folds its slots in a fixed order in double: the bits depend on the data
+ * alone, deterministic mode or not; (3) u again from the stored m, v through the same device function, p, the bf16 copy (p_bf16 may be
+ * NULL), g = 0 unless flags & 4 or zero_grad == 0 (frozen blocks too, as mmbert_adamw), and with ema != NULL ema += (1 - ema_decay)
+ * (p_new - ema) on live blocks as mmbert_adamw_ema.  g is read by launch 1 only.  46 B/parameter (24 + 22).
+ * Returns -1, nothing launched or written: n % 256 != 0; step < 1; hyper / ngroups / distinct tuples as mmbert_adamw_grouped; p, g, m, v,
+ * flags, unit_of_block, units, ratios or workspace NULL; nunits < 1; nmixed < 0, or > 0 with mixed NULL; workspace_bytes too small;
+ * max_trust < 0 or NaN; ema != NULL with ema_decay outside [0, 1).  n == 0 returns 0. */
+#define MMBERT_LAMB_WORKSPACE(nblk, nmixed) (8 * ((size_t)(nblk) + 4 * (size_t)(nmixed)))
+int mmbert_lamb(mmbert_stream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags,
+                const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale, const float* coef,
+                int zero_grad, const int32_t* unit_of_block, const int32_t* mixed, int nmixed, const int32_t* units, int nunits,
+                double max_trust, void* workspace, size_t workspace_bytes, float* ratios, float* ema, double ema_decay);
+
 /* ---- global gradient-norm clipping (torch.nn.utils.clip_grad_norm_) ----
  * segs: device int64 array of nseg pairs (offset, length) in elements of g[0..n): the elements the norm covers, any offsets and lengths
  * (0 <= offset, offset + length <= n; parameters pack inside 256-element blocks).  g 16-byte aligned.  Two launches, no float atomics:

@@ -100,6 +100,7 @@ SIGNATURES = {
     "mmbert_adamw_devscale": (I, [P, P, P, P, P, P, P, SZ, D, D, D, D, D, I, P, I, I]),
     "mmbert_adamw_grouped": (I, [P, P, P, P, P, P, P, P, SZ, P, I, I, D, P, I, I]),
     "mmbert_adamw_ema": (I, [P, P, P, P, P, P, P, P, SZ, P, I, I, D, P, I, I, P, D]),
+    "mmbert_lamb": (I, [P, P, P, P, P, P, P, P, SZ, P, I, I, D, P, I, P, P, I, P, I, D, P, SZ, P, P, D]),
     "mmbert_ema_swap": (I, [P, P, P, P, SZ]),
     "mmbert_grad_norm": (I, [P, P, SZ, P, I, D, D, D, P, P]),
     "mmbert_grad_scale": (I, [P, P, SZ, P, I, P]),

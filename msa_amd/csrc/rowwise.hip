@@ -1710,6 +1710,206 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, fl
 }
 
 // --------------------------------------------------------------------------------------------
+// Flat LAMB (You et al., Algorithm 2 with bias correction; apex FusedLAMB's defaults) over the buffers, flags and groups of the AdamW
+// kernels: the Adam moments, then per parameter tensor (a TRUST UNIT) r = ||p|| / ||u|| of u = mhat / (sqrt(vhat) + eps) + wd p, then
+// p -= lr r u.  Three launches, no atomics, nothing read back:
+//   1. lamb_moments_kernel  p, g, m, v -> m, v; sum p^2 and sum u^2 of every wave's block into its slot(s) of the partials slab
+//   2. lamb_fold_kernel     one workgroup per unit: its slots in a fixed order, in double -> (r, ||p||, ||u||)
+//   3. lamb_apply_kernel    p, m, v -> u again through lamb_u (the bits that were measured are the bits applied), p, bf16, zero_grad, ema
+// Units follow the tensors, not the blocks (flat.FlatParams packs a LayerNorm's weight and bias or the q / k / v biases into one block):
+// unit_of_block[b] >= 0 is the unit of a PURE block (slot b of the slab); -(k + 1) names record k of `mixed`, eight ints
+// (q0, u0, q1, u1, q2, u2, q3, u3): lanes q_e <= lane < q_(e+1) of the wave (a lane holds one aligned float4: a quad) belong to unit
+// u_e; q0 = 0, ascending, an unused entry has q = 64; u_e = -1 is "no unit" (ratio 1, nothing measured).  Entry e of record k owns
+// slot nblk + 4 k + e.  Stray indices are clamped into their tables: nothing is read or written past them.
+// --------------------------------------------------------------------------------------------
+struct LambCoefs { float beta1, beta2, omb1, omb2, eps, rbc1, rbc2, lr, wd; };   // rbc = 1 / (1 - beta^step), in double, rounded once
+struct LambSlots {
+    LambCoefs c[ADAMW_MAX_SLOTS];
+    uint32_t slot4[64];                  // as AdamWSlots::slot4
+};
+static_assert(sizeof(LambSlots) + 160 <= 4096, "the LAMB kernels' arguments must fit the 4 KiB kernel-argument segment");
+
+__device__ __forceinline__ LambCoefs lamb_slot_coefs(const LambSlots& a, int grp) {
+    return a.c[(a.slot4[grp >> 2] >> ((grp & 3) * 8)) & 255u];
+}
+
+// adamw_element's two moment lines, FMA for FMA under the same pragmas: m and v get the bits mmbert_adamw_grouped writes.
+__device__ __forceinline__ void lamb_moments_element(float g, float& m, float& v, const LambCoefs& c, float gscale) {
+#pragma clang fp contract(off)
+#pragma clang fp reassociate(off)
+    const float gr = g * gscale;
+    m = __builtin_fmaf(c.omb1, gr, c.beta1 * m);
+    v = __builtin_fmaf(c.omb2, gr * gr, c.beta2 * v);
+}
+
+// u of one element, pinned like adamw_element (v_sqrt_f32, v_rcp_f32 by name): launches 1 and 3 both call this on the same p, m, v.
+__device__ __forceinline__ float lamb_u(float p, float m, float v, const LambCoefs& c, float wd) {
+#pragma clang fp contract(off)
+#pragma clang fp reassociate(off)
+    const float den = __builtin_amdgcn_sqrtf(v * c.rbc2) + c.eps;
+    return __builtin_fmaf(wd, p, (m * c.rbc1) * __builtin_amdgcn_rcpf(den));
+}
+
+__device__ __forceinline__ float lamb_wave_sum(float a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);          // xor butterfly: a fixed order, the same sum in every lane
+    return a;
+}
+
+// The mixed-block record of map entry e < 0, clamped into the table.
+__device__ __forceinline__ const int* lamb_record(const int* __restrict__ mixed, int nmixed, int e, int& k) {
+    k = min(max(-e - 1, 0), nmixed - 1);
+    return mixed + 8 * (size_t)k;
+}
+
+template <bool DEVSCALE>
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const uint8_t* __restrict__ flags,
+                                                           const uint8_t* __restrict__ group_of_block, const int* __restrict__ unit_of_block,
+                                                           const int* __restrict__ mixed, int nmixed, size_t n, const LambSlots a,
+                                                           float host_gscale, const float* __restrict__ coef, float2* __restrict__ part) {
+    const size_t i = adamw_lane_element();
+    if (i >= n) return;
+    const size_t b = i >> 8, nblk = n >> 8;
+    const uint8_t f = flags[b] & 3;
+    if (f == 2) return;                                                   // frozen: in no unit, nothing stored
+    const float gscale = DEVSCALE ? *coef : host_gscale;
+    const int grp = group_of_block ? __builtin_amdgcn_readfirstlane((int)group_of_block[b]) : 0;
+    const LambCoefs c = lamb_slot_coefs(a, grp);
+    const float wd = (f == 1) ? c.wd : 0.f;
+    const float4 P = *(const float4*)(p + i), G = *(const float4*)(g + i), Mm = *(float4*)(m + i), Vv = *(float4*)(v + i);
+    const float pa[4] = {P.x, P.y, P.z, P.w}, ga[4] = {G.x, G.y, G.z, G.w};
+    float ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
+    float sp = 0.f, su = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        lamb_moments_element(ga[r], ma[r], va[r], c, gscale);
+        const float u = lamb_u(pa[r], ma[r], va[r], c, wd);
+        sp = fmaf(pa[r], pa[r], sp);
+        su = fmaf(u, u, su);
+    }
+    *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
+    *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
+    const int lane = threadIdx.x & 63;
+    const int e = __builtin_amdgcn_readfirstlane(unit_of_block[b]);
+    if (e >= 0) {
+        const float tp = lamb_wave_sum(sp), tu = lamb_wave_sum(su);
+        if (lane == 0) part[b] = make_float2(tp, tu);
+    } else if (nmixed > 0) {
+        int k;
+        const int* rec = lamb_record(mixed, nmixed, e, k);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int q0 = rec[2 * s], q1 = s < 3 ? rec[2 * s + 2] : 64, unit = rec[2 * s + 1];
+            if (q0 >= 64 || unit < 0) continue;                           // (wave-uniform: the record is read with scalar loads)
+            const bool mine = lane >= q0 && lane < q1;
+            const float tp = lamb_wave_sum(mine ? sp : 0.f), tu = lamb_wave_sum(mine ? su : 0.f);
+            if (lane == 0) part[nblk + 4 * (size_t)k + s] = make_float2(tp, tu);
+        }
+    }
+}
+
+// units[4 T ..] = (first block, one past the last block, adapt, 0) of unit T: the blocks that can hold a part of it.  ratios[3 T ..] =
+// (r, ||p||, ||u||): r = ||p|| / ||u|| when adapt != 0 and both are > 0, else 1; then min(r, max_trust) when max_trust > 0.  Every thread
+// adds its blocks' slots in ascending order, the threads are then added in a fixed tree: the bits depend on the data alone.
+#define LAMB_FOLD_THREADS 1024
+#define LAMB_FOLD_UNROLL 8
+__global__ __launch_bounds__(LAMB_FOLD_THREADS) void lamb_fold_kernel(const float2* __restrict__ part, const uint8_t* __restrict__ flags,
+                                                                      const int* __restrict__ unit_of_block, const int* __restrict__ mixed,
+                                                                      int nmixed, const int* __restrict__ units, int nblk, float max_trust,
+                                                                      float* __restrict__ ratios) {
+    __shared__ double red[2][LAMB_FOLD_THREADS / 64];
+    const int T = blockIdx.x;
+    const int b0 = min(max(units[4 * T], 0), nblk), b1 = min(max(units[4 * T + 1], b0), nblk), adapt = units[4 * T + 2];
+    double sp = 0.0, su = 0.0;
+    for (int base = b0 + (int)threadIdx.x; base < b1; base += LAMB_FOLD_UNROLL * LAMB_FOLD_THREADS) {
+        int e[LAMB_FOLD_UNROLL];
+        uint8_t fl[LAMB_FOLD_UNROLL];
+        float2 x[LAMB_FOLD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < LAMB_FOLD_UNROLL; ++u) {                      // issued together (the word table's unit has 90k blocks); the
+            const int b = min(base + u * LAMB_FOLD_THREADS, b1 - 1);      // pure slot is read before it is known to be one: b < nblk
+            e[u] = unit_of_block[b]; fl[u] = flags[b]; x[u] = part[b];
+        }
+#pragma unroll
+        for (int u = 0; u < LAMB_FOLD_UNROLL; ++u) {
+            if (base + u * LAMB_FOLD_THREADS >= b1 || (fl[u] & 3) == 2) continue;
+            if (e[u] >= 0) {
+                if (e[u] == T) { sp += (double)x[u].x; su += (double)x[u].y; }
+            } else if (nmixed > 0) {
+                int k;
+                const int* rec = lamb_record(mixed, nmixed, e[u], k);
+                for (int s = 0; s < 4; ++s)
+                    if (rec[2 * s] < 64 && rec[2 * s + 1] == T) {
+                        const float2 y = part[(size_t)nblk + 4 * (size_t)k + s];
+                        sp += (double)y.x; su += (double)y.y;
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); su += __shfl_xor(su, o, 64); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sp; red[1][threadIdx.x >> 6] = su; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sp = red[0][0]; su = red[1][0];
+        for (int w = 1; w < LAMB_FOLD_THREADS / 64; ++w) { sp += red[0][w]; su += red[1][w]; }
+        const double np = sqrt(sp), nu = sqrt(su);
+        float r = (adapt && np > 0.0 && nu > 0.0) ? (float)(np / nu) : 1.f;
+        if (max_trust > 0.f && r > max_trust) r = max_trust;
+        ratios[3 * T] = r; ratios[3 * T + 1] = (float)np; ratios[3 * T + 2] = (float)nu;
+    }
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, float* __restrict__ g, const float* __restrict__ m,
+                                                         const float* __restrict__ v, float* __restrict__ ema, bf16_t* __restrict__ pb,
+                                                         const uint8_t* __restrict__ flags, const uint8_t* __restrict__ group_of_block,
+                                                         const int* __restrict__ unit_of_block, const int* __restrict__ mixed, int nmixed,
+                                                         const float* __restrict__ ratios, int nunits, size_t n, const LambSlots a,
+                                                         float omd, int zero_grad) {
+    const size_t i = adamw_lane_element();
+    if (i >= n) return;
+    const size_t b = i >> 8;
+    const uint8_t fb = flags[b];
+    const uint8_t f = fb & 3;
+    float4 P = *(float4*)(p + i);
+    if (f != 2) {
+        const int grp = group_of_block ? __builtin_amdgcn_readfirstlane((int)group_of_block[b]) : 0;
+        const LambCoefs c = lamb_slot_coefs(a, grp);
+        const float wd = (f == 1) ? c.wd : 0.f;
+        const float4 Mm = *(const float4*)(m + i), Vv = *(const float4*)(v + i);
+        float4 E;
+        if (EMA) E = *(float4*)(ema + i);
+        const int e = __builtin_amdgcn_readfirstlane(unit_of_block[b]);
+        float r = 1.f;
+        if (e >= 0) {
+            r = ratios[3 * (size_t)min(e, nunits - 1)];                   // wave-uniform: one scalar load
+        } else if (nmixed > 0) {
+            int k;
+            const int* rec = lamb_record(mixed, nmixed, e, k);
+            const int lane = threadIdx.x & 63;
+            int unit = rec[1];
+#pragma unroll
+            for (int s = 1; s < 4; ++s) unit = (lane >= rec[2 * s]) ? rec[2 * s + 1] : unit;
+            if (unit >= 0) r = ratios[3 * (size_t)min(unit, nunits - 1)];
+        }
+        float pa[4] = {P.x, P.y, P.z, P.w};
+        const float ma[4] = {Mm.x, Mm.y, Mm.z, Mm.w}, va[4] = {Vv.x, Vv.y, Vv.z, Vv.w};
+        const float step = c.lr * r;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pa[q] = __builtin_fmaf(-step, lamb_u(pa[q], ma[q], va[q], c, wd), pa[q]);
+        P = make_float4(pa[0], pa[1], pa[2], pa[3]);
+        *(float4*)(p + i) = P;
+        if (EMA)
+            *(float4*)(ema + i) = make_float4(ema_element(E.x, P.x, omd), ema_element(E.y, P.y, omd), ema_element(E.z, P.z, omd),
+                                              ema_element(E.w, P.w, omd));
+    }
+    if (zero_grad && !(fb & 4)) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pb) { bf16x4 o = {f2bf(P.x), f2bf(P.y), f2bf(P.z), f2bf(P.w)}; *(bf16x4*)(pb + i) = o; }
+}
+
+// --------------------------------------------------------------------------------------------
 // Global gradient norm over a list of element segments of a flat fp32 buffer (torch.nn.utils.clip_grad_norm_: the reference
 // never clips; BERT's recipe and HF Trainer clip at 1.0).  segs[2 s], segs[2 s + 1] = offset, length of
 // segment s in elements -- any offset, any length: parameters pack inside 256-element blocks (flat.py ALIGN).
@@ -2617,8 +2817,10 @@ static AdamWCoefs adamw_coefs(double lr, double beta1, double beta2, double eps,
 }
 
 // hyper[5 k ..] = (lr, beta1, beta2, eps, weight_decay) of group k -> the table of distinct combinations, in first-seen order, and
-// every group's slot in it.  -1: no hyper, ngroups outside 1 .. ADAMW_MAX_GROUPS, or more than ADAMW_MAX_SLOTS distinct combinations.
-static int adamw_fill_slots(AdamWSlots& a, const double* hyper, int ngroups, int step, int mode) {
+// every group's slot in it; coefs(h) forms one combination's coefficients (AdamWSlots and LambSlots share the layout of the slot words).
+// -1: no hyper, ngroups outside 1 .. ADAMW_MAX_GROUPS, or more than ADAMW_MAX_SLOTS distinct combinations.
+extern "C++" template <class Slots, class Coefs>
+static int fill_slots(Slots& a, const double* hyper, int ngroups, Coefs coefs) {
     if (!hyper || ngroups < 1 || ngroups > ADAMW_MAX_GROUPS) return -1;
     memset(&a, 0, sizeof(a));
     const double* key[ADAMW_MAX_SLOTS];  // the first group of each slot
@@ -2630,11 +2832,15 @@ static int adamw_fill_slots(AdamWSlots& a, const double* hyper, int ngroups, int
         if (s == nslot) {
             if (nslot == ADAMW_MAX_SLOTS) return -1;
             key[nslot++] = h;
-            a.c[s] = adamw_coefs(h[0], h[1], h[2], h[3], h[4], step, mode);
+            a.c[s] = coefs(h);
         }
         a.slot4[k >> 2] |= (uint32_t)s << ((k & 3) * 8);
     }
     return 0;
+}
+
+static int adamw_fill_slots(AdamWSlots& a, const double* hyper, int ngroups, int step, int mode) {
+    return fill_slots(a, hyper, ngroups, [&](const double* h) { return adamw_coefs(h[0], h[1], h[2], h[3], h[4], step, mode); });
 }
 
 static dim3 adamw_grid(size_t n) { return dim3((unsigned)((n / 4 + 255) / 256)); }
@@ -2693,6 +2899,46 @@ int mmbert_adamw_ema(hipStream_t stream, float* p, float* g, float* m, float* v,
     else
         hipLaunchKernelGGL(adamw_ema_kernel<false>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)p_bf16, flags, group_of_block, n,
                            a, (float)gscale, (const float*)nullptr, omd, mode, zero_grad);
+    MMB_CHECK_LAUNCH();
+    return 0;
+}
+
+// hyper as in adamw_fill_slots (the same de-duplication, the same limits) -> the LAMB coefficients of every slot, in double, rounded once
+static int lamb_fill_slots(LambSlots& a, const double* hyper, int ngroups, int step) {
+    return fill_slots(a, hyper, ngroups, [&](const double* h) {
+        return LambCoefs{(float)h[1], (float)h[2], (float)(1.0 - h[1]), (float)(1.0 - h[2]), (float)h[3],
+                         (float)(1.0 / (1.0 - pow(h[1], (double)step))), (float)(1.0 / (1.0 - pow(h[2], (double)step))), (float)h[0], (float)h[4]};
+    });
+}
+
+int mmbert_lamb(hipStream_t stream, float* p, float* g, float* m, float* v, void* p_bf16, const uint8_t* flags,
+                const uint8_t* group_of_block, size_t n, const double* hyper, int ngroups, int step, double gscale, const float* coef,
+                int zero_grad, const int32_t* unit_of_block, const int32_t* mixed, int nmixed, const int32_t* units, int nunits,
+                double max_trust, void* workspace, size_t workspace_bytes, float* ratios, float* ema, double ema_decay) {
+    if (n == 0) return 0;
+    LambSlots a;
+    if ((n & 255) || (n >> 8) > (size_t)INT32_MAX || step < 1 || lamb_fill_slots(a, hyper, ngroups, step) != 0) return -1;
+    if (!p || !g || !m || !v || !flags || !unit_of_block || !units || nunits < 1 || nmixed < 0 || (nmixed > 0 && !mixed) || !ratios) return -1;
+    if (!workspace || workspace_bytes < 8 * ((n >> 8) + 4 * (size_t)nmixed) /* == MMBERT_LAMB_WORKSPACE */ || !(max_trust >= 0.0)) return -1;
+    if (ema && !(ema_decay >= 0.0 && ema_decay < 1.0)) return -1;
+    float2* part = (float2*)workspace;
+    const int nblk = (int)(n >> 8);
+    if (coef)
+        hipLaunchKernelGGL(lamb_moments_kernel<true>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, flags, group_of_block, unit_of_block, mixed,
+                           nmixed, n, a, 1.0f, coef, part);
+    else
+        hipLaunchKernelGGL(lamb_moments_kernel<false>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, flags, group_of_block, unit_of_block, mixed,
+                           nmixed, n, a, (float)gscale, (const float*)nullptr, part);
+    MMB_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lamb_fold_kernel, dim3(nunits), dim3(LAMB_FOLD_THREADS), 0, stream, (const float2*)part, flags, unit_of_block, mixed, nmixed,
+                       units, nblk, (float)max_trust, ratios);
+    MMB_CHECK_LAUNCH();
+    if (ema)
+        hipLaunchKernelGGL(lamb_apply_kernel<true>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)p_bf16, flags, group_of_block,
+                           unit_of_block, mixed, nmixed, ratios, nunits, n, a, (float)(1.0 - ema_decay), zero_grad);
+    else
+        hipLaunchKernelGGL(lamb_apply_kernel<false>, adamw_grid(n), dim3(256), 0, stream, p, g, m, v, (float*)nullptr, (bf16_t*)p_bf16, flags,
+                           group_of_block, unit_of_block, mixed, nmixed, ratios, nunits, n, a, 0.f, zero_grad);
     MMB_CHECK_LAUNCH();
     return 0;
 }

@@ -1068,6 +1068,43 @@ def adamw_ema(p, g, m, v, p_bf16, flags, group_of_block, hyper, ema, *, ema_deca
                                             float(ema_decay)), "mmbert_adamw_ema")
 
 
+def lamb_workspace_bytes(nblk, nmixed):
+    """MMBERT_LAMB_WORKSPACE (include/mmbert_hip.h): one (sum p^2, sum u^2) fp32 pair per block and per mixed-record entry"""
+    return 8 * (int(nblk) + 4 * int(nmixed))
+
+
+def lamb(p, g, m, v, p_bf16, flags, group_of_block, hyper, unit_of_block, mixed, units, *, step=1, gscale=1.0, coef=None, zero_grad=True,
+         max_trust=None, ratios=None, workspace=None, ema=None, ema_decay=0.0):
+    """One LAMB step over flat buffers (mmbert_lamb: three launches, no sync): ``flags`` / ``group_of_block`` / ``hyper`` / ``coef`` as
+    ops.adamw_grouped; ``unit_of_block`` device int32 [n / 256], ``mixed`` device int32 [nmixed, 8] or None, ``units`` device int32
+    [nunits, 4] of (first block, end block, adapt, 0) -- the encoding of the header.  Returns ``ratios``: device fp32 [nunits, 3] of
+    (trust ratio, ||p||, ||u||).  ``workspace``: >= lamb_workspace_bytes(n / 256, nmixed) bytes (allocated here when None)."""
+    assert group_of_block is None or (group_of_block.dtype == torch.uint8 and group_of_block.numel() * 256 >= p.numel())
+    assert unit_of_block.dtype == torch.int32 and unit_of_block.is_contiguous() and unit_of_block.numel() * 256 >= p.numel()
+    assert units.dtype == torch.int32 and units.is_contiguous() and units.dim() == 2 and units.shape[1] == 4
+    nmixed = 0
+    if mixed is not None:
+        assert mixed.dtype == torch.int32 and mixed.is_contiguous() and mixed.dim() == 2 and mixed.shape[1] == 8
+        nmixed = mixed.shape[0]
+    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == p.numel())
+    nunits = units.shape[0]
+    if ratios is None:
+        ratios = torch.empty(max(nunits, 1), 3, dtype=torch.float32, device=p.device)
+    assert ratios.dtype == torch.float32 and ratios.is_contiguous() and ratios.numel() >= 3 * nunits
+    need = lamb_workspace_bytes(p.numel() // 256, nmixed)
+    if workspace is None:
+        workspace = torch.empty(max(need // 4, 2), dtype=torch.float32, device=p.device)
+    arr, ngroups = _hyper_array(hyper)
+    _lib.check(_lib.load().mmbert_lamb(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16), flags.data_ptr(),
+                                       _ptr(group_of_block), p.numel(), arr, ngroups, int(step), float(gscale),
+                                       None if coef is None else coef.data_ptr(), 1 if zero_grad else 0, unit_of_block.data_ptr(),
+                                       _ptr(mixed) if nmixed else None, nmixed, units.data_ptr(), nunits,
+                                       0.0 if max_trust is None else float(max_trust), workspace.data_ptr(),
+                                       workspace.numel() * workspace.element_size(), ratios.data_ptr(), _ptr(ema), float(ema_decay)),
+               "mmbert_lamb")
+    return ratios
+
+
 def ema_swap(p, ema, p_bf16=None):
     """p <-> ema in place, ``p_bf16`` (may be None) = bf16 of the new ``p`` (mmbert_ema_swap): one launch, no temporary."""
     assert p.dtype == torch.float32 and ema.dtype == torch.float32 and p.is_contiguous() and ema.is_contiguous() and p.numel() == ema.numel()

@@ -5,6 +5,9 @@ bf16 working-copy refresh and zero_grad in a single pass over 28 B/parameter.
 ``mode="hf"`` (default) is transformers-2.8 ``optimization.AdamW`` -- the class the reference
 imports (eps 1e-6, bias correction, decay applied after the update); ``mode="torch"`` is
 ``torch.optim.AdamW``, the optimizer the golden fixture G8 was generated with.
+
+``LAMB`` is the layer-wise adaptive alternative for large global batches on the same binding (mmbert_lamb: three launches, a trust ratio
+per parameter tensor).
 """
 from __future__ import annotations
 
@@ -53,6 +56,8 @@ def ema_decay_at(decay, updates, warmup=False):
 
 
 class AdamW:
+    kind = "adamw"                          # state_dict()["optimizer"]: load_state_dict refuses another kind's state
+
     def __init__(self, params: Union[Iterable[torch.nn.Parameter], List[dict]], lr=1e-3, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, correct_bias=True, mode="hf"):
         params = list(params)
@@ -321,13 +326,7 @@ class AdamW:
         if tuple(h[4] > 0 for h in hyper) != self._decay:
             self._build_maps(self._flat)     # a group's weight_decay turned on or off since the flags were built
             self._build_flags()
-        act = [hyper[i] for i in self._active] or hyper[:1]
-        wds = {h[4] for h in act if h[4] > 0}
-        grouped = any(h[:4] != act[0][:4] for h in act) or len(wds) > 1
-        if grouped:
-            adamw_slots(hyper)               # (the limits: raise before anything is launched)
-        lr, beta1, beta2, eps, _ = act[0]
-        wd = wds.pop() if wds else 0.0
+        launch = self._plan(hyper)           # (the limits: raise before anything is launched)
         flat = self._flat
         self._steps += 1
         flat.join_side_writers()             # (left by a backward that raised: nothing may still add into the gradients the kernel reads and zeroes)
@@ -336,6 +335,27 @@ class AdamW:
         flat.settle()                        # a lazy gradient no backward has written since the last step counts as zero
         flat.attach_lazy()
         clip, self._clip = self._clip, None
+        launch(clip)
+        flat.refresh_transposes(side=True)
+        flat.mark_synced()
+        flat.grads_dirty = False
+        if self.lazy_zero:
+            flat.drop_lazy()
+
+    def _plan(self, hyper):
+        """Which kernel this step's update is, from the groups' hyper-parameters: checks the limits and returns the function of the clip
+        scalars (or None) that launches it, once step() has settled the gradients.  The part of step() a subclass replaces (LAMB)."""
+        act = [hyper[i] for i in self._active] or hyper[:1]
+        wds = {h[4] for h in act if h[4] > 0}
+        grouped = any(h[:4] != act[0][:4] for h in act) or len(wds) > 1
+        if grouped:
+            adamw_slots(hyper)
+        lr, beta1, beta2, eps, _ = act[0]
+        wd = wds.pop() if wds else 0.0
+        return lambda clip: self._launch(hyper, grouped, lr, beta1, beta2, eps, wd, clip)
+
+    def _launch(self, hyper, grouped, lr, beta1, beta2, eps, wd, clip):
+        flat = self._flat
         if self._ema is not None:            # the same update with the weight average folded in: one kernel for the three routes below
             ops.adamw_ema(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, self._group_of_block if grouped else None,
                           hyper if grouped else [(lr, beta1, beta2, eps, wd)], self._ema,
@@ -352,11 +372,6 @@ class AdamW:
         else:                                # clip_grad_norm_ ran: its coefficient (x grad_scale) from the device
             ops.adamw_devscale(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, clip[2:3], lr=lr, beta1=beta1,
                                beta2=beta2, eps=eps, wd=wd, step=self._steps, mode=self.mode, zero_grad=True)
-        flat.refresh_transposes(side=True)
-        flat.mark_synced()
-        flat.grads_dirty = False
-        if self.lazy_zero:
-            flat.drop_lazy()
 
     def zero_grad(self, set_to_none: bool = False):
         self._clip = None                    # a clip coefficient no step() applied belongs to the gradients dropped here
@@ -384,12 +399,15 @@ class AdamW:
 
     def state_dict(self):
         self._refuse_swapped("state_dict()")
-        return dict(steps=self._steps, m=None if self._flat is None else self._m, v=None if self._flat is None else self._v,
+        return dict(optimizer=self.kind, steps=self._steps, m=None if self._flat is None else self._m, v=None if self._flat is None else self._v,
                     lrs=[g["lr"] for g in self.param_groups], ema=self._ema, ema_decay=self._ema_decay, ema_warmup=self._ema_warmup,
                     ema_updates=self.ema_updates)
 
     def load_state_dict(self, sd):
         self._refuse_swapped("load_state_dict()")
+        if sd.get("optimizer", self.kind) != self.kind:      # (a dict from before the key existed is an AdamW's or the caller's business)
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the state is a {sd['optimizer']!r} optimizer's, this one is {self.kind!r}: "
+                             "m and v mean the same, the step they were taken with does not")
         if self._flat is None:
             self._bind()
         if sd.get("ema_decay") is not None:  # (a dict without the ema keys, or saved with the EMA off, leaves the EMA as it is)
@@ -403,6 +421,123 @@ class AdamW:
             self._v.copy_(sd["v"])
         for g, lr in zip(self.param_groups, sd["lrs"]):
             g["lr"] = lr
+
+
+LAMB_MIXED_ENTRIES = 4                     # (first quad, unit) pairs of one mixed-block record (include/mmbert_hip.h, mmbert_lamb)
+
+
+def lamb_unit_maps(spans, nblk, others=()):
+    """mmbert_lamb's maps of trust units onto 256-element blocks, on the host (numpy int32): ``spans[T]`` = (offset, length) in elements
+    of unit T, disjoint; ``others``: spans of tensors that are in no unit (not stepped) but may share a block with one.  Returns
+    (unit_of_block [nblk], mixed [nmixed, 8], ranges [nunits, 2]).  A block that one unit has to itself from its first element (whatever
+    follows the unit's end is padding) is pure: its entry is the unit.  Any other block that holds a unit gets -(k + 1) and record k:
+    (first quad, unit) pairs in ascending order, -1 for a stretch of ``others``, padding joined to the stretch before it, unused pairs
+    (64, -1).  Record 0 is "no unit" alone: every block without a unit names it (frozen blocks are not looked up at all).  A unit that starts
+    inside a block off a multiple of 4 elements raises ValueError, more than LAMB_MIXED_ENTRIES stretches in one block NotImplementedError."""
+    import numpy as np
+    pieces, whole = {}, []
+    for unit, (off, length) in [(t, s) for t, s in enumerate(spans)] + [(-1, s) for s in others]:
+        off, length = int(off), int(length)
+        if length <= 0:
+            continue
+        if off < 0 or off + length > nblk * 256:
+            raise ValueError(f"lamb_unit_maps: span ({off}, {length}) outside the {nblk} blocks")
+        first, start, end = off // 256, off % 256, off + length
+        if start % 4:
+            raise ValueError(f"lamb_unit_maps: span ({off}, {length}) starts inside block {first} at element {start}, not a multiple of 4")
+        lo, hi = first + (1 if start else 0), end // 256       # the blocks [lo, hi) are the span's from their first to their last element
+        if hi > lo:
+            whole.append((lo, hi, unit))
+        if start:
+            pieces.setdefault(first, []).append((start // 4, unit))
+        if end % 256 and (hi > first or not start):
+            pieces.setdefault(hi, []).append((0, unit))
+    records = [[0, -1] + [64, -1] * (LAMB_MIXED_ENTRIES - 1)]                     # record 0: "no unit", shared
+    unit_of_block = np.full(nblk, -1, dtype=np.int32)
+    taken = np.zeros(nblk, dtype=bool)
+    for lo, hi, unit in whole:
+        if taken[lo:hi].any():
+            raise ValueError(f"lamb_unit_maps: overlapping spans in blocks {lo} .. {hi - 1}")
+        taken[lo:hi] = True
+        unit_of_block[lo:hi] = unit                                                # (-1 for ``others``: record 0)
+    for b in sorted(pieces):
+        ps = sorted(pieces[b])
+        if taken[b] or any(a[0] == c[0] for a, c in zip(ps, ps[1:])):
+            raise ValueError(f"lamb_unit_maps: overlapping spans in block {b}")
+        if ps[0][0] > 0:
+            ps.insert(0, (0, -1))
+        ps = [x for j, x in enumerate(ps) if j == 0 or x[1] >= 0 or ps[j - 1][1] >= 0]         # neighbouring "no unit" stretches are one
+        if len(ps) == 1 and ps[0][1] >= 0:
+            unit_of_block[b] = ps[0][1]
+        elif any(u >= 0 for _, u in ps):
+            if len(ps) > LAMB_MIXED_ENTRIES:
+                raise NotImplementedError(f"LAMB: block {b} of the flat buffer holds {len(ps)} stretches of different tensors, the fused step "
+                                          f"takes {LAMB_MIXED_ENTRIES}")
+            unit_of_block[b] = -(len(records) + 1)
+            records.append([x for q in ps for x in q] + [64, -1] * (LAMB_MIXED_ENTRIES - len(ps)))
+    mixed = np.asarray(records, dtype=np.int32).reshape(-1, 2 * LAMB_MIXED_ENTRIES)
+    ranges = np.asarray([(o // 256, (o + k + 255) // 256) if k > 0 else (0, 0) for o, k in spans], dtype=np.int32).reshape(-1, 2)
+    return unit_of_block, mixed, ranges
+
+
+class LAMB(AdamW):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning", Algorithm 2 with bias correction; apex ``FusedLAMB``'s defaults) on
+    AdamW's binding to the flat storage: the same flags, lazy zero, frozen and unreached parameters, per-group hyper-parameters,
+    ``clip_grad_norm_`` / ``grad_scale``, EMA, ``zero_grad`` and schedulers.  Per element ``u = mhat / (sqrt(vhat) + eps) + wd p``; per
+    parameter tensor ``r = ||p|| / ||u||`` (1 when either norm is 0, and for tensors of a group with weight_decay 0 unless
+    ``always_adapt``), capped at ``max_trust`` when given; ``p -= lr r u``.  One step is mmbert_lamb's three launches, no host sync."""
+    kind = "lamb"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, always_adapt=False, max_trust=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if max_trust is not None and not float(max_trust) > 0.0:
+            raise ValueError(f"LAMB: max_trust must be > 0 or None, got {max_trust}")
+        self.always_adapt, self.max_trust = bool(always_adapt), None if max_trust is None else float(max_trust)
+        self._ratios_valid = False
+
+    def _build_maps(self, flat):
+        """AdamW's per-block maps, then the trust units: one per stepped parameter, in the order of ``self._names``."""
+        super()._build_maps(flat)
+        names = self._names
+        group_of = {flat.name_at(p._mmb_flat[1]): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+        live = (self._base_flags != 2).tolist()
+        stepped = set(names)
+        others = [(flat.offset[n], flat.numel[n]) for n in flat.order if n not in stepped and flat.numel[n] > 0
+                  and any(live[flat.offset[n] // 256:(flat.offset[n] + flat.numel[n] - 1) // 256 + 1])]
+        unit_of_block, mixed, ranges = lamb_unit_maps([(flat.offset[n], flat.numel[n]) for n in names], flat.total // 256, others)
+        units = torch.zeros(max(len(names), 1), 4, dtype=torch.int32)
+        for t, n in enumerate(names):
+            units[t, 0], units[t, 1] = int(ranges[t][0]), int(ranges[t][1])
+            units[t, 2] = 1 if (self.always_adapt or self.param_groups[group_of[n]]["weight_decay"] > 0) else 0
+        dev = flat.device
+        self._unit_of_block = torch.from_numpy(unit_of_block).to(dev)
+        self._mixed = torch.from_numpy(mixed).to(dev)
+        self._units = units.to(dev)
+        self._ratios = torch.zeros(units.shape[0], 3, dtype=torch.float32, device=dev)
+        self._lamb_ws = torch.empty(max(ops.lamb_workspace_bytes(flat.total // 256, len(mixed)) // 4, 2), dtype=torch.float32, device=dev)
+        self._ratios_valid = False
+
+    def _plan(self, hyper):
+        adamw_slots(hyper)                   # (mmbert_lamb's limits are the grouped AdamW's)
+        return lambda clip: self._launch_lamb(hyper, clip)
+
+    def _launch_lamb(self, hyper, clip):
+        flat, ema = self._flat, self._ema
+        ops.lamb(flat.params, flat.grads, self._m, self._v, flat.half, self._flags, self._group_of_block, hyper, self._unit_of_block,
+                 self._mixed, self._units, step=self._steps, gscale=self.grad_scale, coef=None if clip is None else clip[2:3],
+                 zero_grad=True, max_trust=self.max_trust, ratios=self._ratios, workspace=self._lamb_ws, ema=ema,
+                 ema_decay=0.0 if ema is None else ema_decay_at(self._ema_decay, self.ema_updates, self._ema_warmup))
+        if ema is not None:
+            self.ema_updates += 1
+        self._ratios_valid = True
+
+    def trust_ratios(self):
+        """{parameter name: (trust ratio, ||p||, ||u||)} of the last ``step()`` as Python floats, for the parameters that step updated
+        (frozen and unreached ones are absent); {} before the first step.  Reads the device: the one call here that syncs."""
+        if self._flat is None or not self._ratios_valid:
+            return {}
+        rows = self._ratios.cpu().tolist()
+        return {n: tuple(rows[t]) for t, n in enumerate(self._names)}
 
 
 _NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight")               # REF:train.py:78 (trainer.build_optimizer)

@@ -347,7 +347,9 @@ def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
     ``args.ema_decay`` / ``args.ema_warmup`` (optional, likewise): an exponential moving average of the weights, kept inside the
     optimizer step (``AdamW.ema``); ``train`` then validates, tests and saves under the averaged weights.
     Frozen parameters (``requires_grad == False``: apply_freeze, model.freeze) are in no group.
-    ``args.lora_rank`` (optional, likewise): ``apply_lora`` runs first when the model has no adapters yet, so the groups hold them."""
+    ``args.lora_rank`` (optional, likewise): ``apply_lora`` runs first when the model has no adapters yet, so the groups hold them.
+    ``args.optimizer = "lamb"`` (optional, likewise) with ``args.lamb_always_adapt`` / ``args.lamb_max_trust``: ``optim.LAMB`` over the
+    same groups (``mode`` does not apply: LAMB has one definition)."""
     from .optim import AdamW, get_linear_schedule_with_warmup, layerwise_param_groups
     if not getattr(model, "_lora", None):
         apply_lora(model, args)
@@ -359,7 +361,15 @@ def build_optimizer(model, args, num_train_optimization_steps, mode="hf"):
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         groups = [{"params": [p for n, p in named if not any(nd in n for nd in no_decay)], "weight_decay": 0.01},
                   {"params": [p for n, p in named if any(nd in n for nd in no_decay)], "weight_decay": 0.0}]
-    opt = AdamW(groups, lr=args.learning_rate, mode=mode)
+    kind = getattr(args, "optimizer", None)                                  # (not a reference argument: absent = AdamW)
+    if kind is None or kind == "adamw":
+        opt = AdamW(groups, lr=args.learning_rate, mode=mode)
+    elif kind == "lamb":
+        from .optim import LAMB
+        opt = LAMB(groups, lr=args.learning_rate, always_adapt=bool(getattr(args, "lamb_always_adapt", False)),
+                   max_trust=getattr(args, "lamb_max_trust", None))
+    else:
+        raise ValueError(f"build_optimizer: args.optimizer must be 'adamw' or 'lamb', got {kind!r}")
     if getattr(args, "ema_decay", None) is not None:
         opt.ema(args.ema_decay, warmup=bool(getattr(args, "ema_warmup", False)))
     sched = get_linear_schedule_with_warmup(opt, num_warmup_steps=num_train_optimization_steps,
