@@ -18,6 +18,14 @@
 // The token-axis contraction (dA, dB) has no MFMA form without a transpose of the two big streams (x and dqkv are row-major in the token:
 // a fragment would need four tokens of one column in a lane); it runs as fp32 FMAs on 16-byte loads -- r FMAs per loaded element, below
 // the memory time of the pass -- a lane owns 8 columns x r rank entries.
+//
+// The dense seams (the second half of the file) run the same scheme.  SHARED by the two families: the staging helpers and the contraction
+// over a staged tile (the tile's row pitch is an argument), lora_expand32, the eight-column update, the input mask, and backward launches 2
+// and 3 with their records and launch helper -- the token sums and the fold know streams of a width each, not seams.  SEPARATE: the forward
+// and `g` kernels.  The Q | K | V ones stage whole [16, H] tiles of up to three targets (dynamic LDS, row pitch H + 8 elements) and read x
+// ONCE for all of them (67.0 us for q + k + v against 3 x 27.7 us as three single-target calls, profiles/lora_dropout_ab.txt); the dense
+// ones stage one target in column chunks of a static tile (row pitch LORA_DPITCH) and carry their epilogues.
+#include <type_traits>
 #include "common.h"
 #include "../../include/mmbert_hip.h"
 
@@ -39,9 +47,11 @@ struct LoraBwdArgs {
     bf16_t* gbuf; bf16_t* hbuf;            // [M, nt * r] each (workspace)
     LoraInDrop in;
 };
-// colmajor: out is [H, r] (dB), else [r, H] (dA), whose src is the seam input: the only streams the input mask applies to
-struct LoraStream { const bf16_t* src; const bf16_t* coef; float* out; int lds, ldc, colmajor, acc; };
-struct LoraWArgs { LoraStream st[6]; int ns, M, H, r, nslab; float s; float* part; LoraInDrop in; };
+// One weight-gradient stream of width W (both seam families).  colmajor: out is [W, r] (dB), else [r, W] (dA), whose src is the seam input:
+// the only streams the input mask applies to.  part_off: where the stream's [nslab][r W] partial sums start in the workspace (floats)
+struct LoraStream { const bf16_t* src; const bf16_t* coef; float* out; size_t part_off; int lds, ldc, colmajor, acc, W, pad; };
+// col_lanes: the cap on column lanes (of 8 columns) per workgroup -- it fixes the row-lane count, i.e. the order of the fp32 token sums
+struct LoraWArgs { LoraStream st[6]; int ns, M, r, nslab, col_lanes; float s; float* part; LoraInDrop in; };
 
 
 __device__ __forceinline__ bf16x8 lora_zero8() { bf16x8 z; for (int j = 0; j < 8; ++j) z[j] = (bf16_t)0.0f; return z; }
@@ -89,75 +99,74 @@ __device__ __forceinline__ bf16x8 lora_keep_old8(bf16x8 o, bf16x8 old, uint32_t 
     return __builtin_bit_cast(bf16x8, (__builtin_bit_cast(lora_u32x4, o) & ~d) | (__builtin_bit_cast(lora_u32x4, old) & d));
 }
 
-// T[ti][k][0 .. H) = W_ti[k][0 .. H) for k < r, zeros for r <= k < 16 (W = A: [r, H] row-major).  Row pitch HP = H + 8 elements.
-__device__ __forceinline__ void lora_stage_rows(bf16_t* T, const LoraTarget* t, int nt, int H, int r) {
-    const int CH = H >> 3, HP = H + 8, total = nt * 16 * CH;
+// The staging helpers (every thread of the workgroup calls them).  The Q | K | V kernels call them once per target over all of H into that
+// target's tile (pitch H + 8); the dense kernels per column chunk into the one static tile (pitch LORA_DPITCH, a constant once inlined).
+// T[k][0 .. w) = A[k][c0 .. c0 + w) for k < r, zeros for r <= k < 16 (A: [r, ld] row-major); T's row pitch is `pitch` elements
+__device__ __forceinline__ void lora_stage_rows(bf16_t* T, const bf16_t* A, int ld, int c0, int w, int r, int pitch) {
+    const int CH = w >> 3, total = 16 * CH;
     for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const int ti = idx / (16 * CH), rem = idx - ti * 16 * CH, k = rem / CH, c = rem - k * CH;
+        const int k = idx / CH, c = idx - k * CH;
         bf16x8 v = lora_zero8();
-        if (k < r) v = *(const bf16x8*)(t[ti].A + (size_t)k * H + 8 * c);
-        *(bf16x8*)(T + (size_t)(ti * 16 + k) * HP + 8 * c) = v;
+        if (k < r) v = *(const bf16x8*)(A + (size_t)k * ld + c0 + 8 * c);
+        *(bf16x8*)(T + (size_t)k * pitch + 8 * c) = v;
     }
 }
-// T[ti][k][c] = B_ti[c][k] for k < r, zeros above (B: [H, r] row-major): the transposed tile for the contraction over H in backward
-__device__ __forceinline__ void lora_stage_cols_t(bf16_t* T, const LoraTarget* t, int nt, int H, int r) {
-    const int HP = H + 8, total = nt * H;
-    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const int ti = idx / H, c = idx - ti * H;
-        const bf16_t* src = t[ti].B + (size_t)c * r;
-        bf16_t* dst = T + (size_t)(ti * 16) * HP + c;
+// T[k][c] = B[c0 + c][k] for k < r, zeros above (B: [N, r] row-major), c < w: the transposed tile for the contraction over N in backward
+__device__ __forceinline__ void lora_stage_cols_t(bf16_t* T, const bf16_t* B, int c0, int w, int r, int pitch) {
+    for (int c = threadIdx.x; c < w; c += blockDim.x) {
+        const bf16_t* src = B + (size_t)(c0 + c) * r;
+        bf16_t* dst = T + c;
         for (int k0 = 0; k0 < r; k0 += 4) {
             const bf16x4 v = *(const bf16x4*)(src + k0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) dst[(size_t)(k0 + j) * HP] = v[j];
+            for (int j = 0; j < 4; ++j) dst[(size_t)(k0 + j) * pitch] = v[j];
         }
-        for (int k = r; k < 16; ++k) dst[(size_t)k * HP] = (bf16_t)0.0f;
+        for (int k = r; k < 16; ++k) dst[(size_t)k * pitch] = (bf16_t)0.0f;
     }
 }
-// U[ti][c][k] = W[c][k] for k < r, zeros for r <= k < 16, from a [H, r] row-major matrix (B), 16 elements per column c
-__device__ __forceinline__ void lora_stage_pad16(bf16_t* U, const LoraTarget* t, int nt, int H, int r) {
-    const int total = nt * H;
-    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const int ti = idx / H, c = idx - ti * H;
-        const bf16_t* src = t[ti].B + (size_t)c * r;
+// U[c][k] = B[c0 + c][k] for k < r, zeros for r <= k < 16: 16 elements per column c < w
+__device__ __forceinline__ void lora_stage_pad16(bf16_t* U, const bf16_t* B, int c0, int w, int r) {
+    for (int c = threadIdx.x; c < w; c += blockDim.x) {
+        const bf16_t* src = B + (size_t)(c0 + c) * r;
         bf16x8 lo = lora_zero8(), hi = lora_zero8();
         if (r == 16) { lo = *(const bf16x8*)src; hi = *(const bf16x8*)(src + 8); }
         else if (r == 8) lo = *(const bf16x8*)src;
         else lo = lora_low4(*(const bf16x4*)src);
-        bf16_t* dst = U + (size_t)idx * 16;
+        bf16_t* dst = U + (size_t)c * 16;
         *(bf16x8*)dst = lo; *(bf16x8*)(dst + 8) = hi;
     }
 }
-// U[ti][c][k] = A_ti[k][c] for k < r, zeros above (A: [r, H] row-major): the transposed form, for the input gradient
-__device__ __forceinline__ void lora_stage_pad16_t(bf16_t* U, const LoraTarget* t, int nt, int H, int r) {
-    const int CH = H >> 3, total = nt * 16 * CH;
+// U[c][k] = A[k][c0 + c] for k < r, zeros above (A: [r, ld] row-major), c < w: the transposed form, for the input gradient
+__device__ __forceinline__ void lora_stage_pad16_t(bf16_t* U, const bf16_t* A, int ld, int c0, int w, int r) {
+    const int CH = w >> 3, total = 16 * CH;
     for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const int ti = idx / (16 * CH), rem = idx - ti * 16 * CH, k = rem / CH, c = rem - k * CH;
+        const int k = idx / CH, c = idx - k * CH;
         bf16x8 v = lora_zero8();
-        if (k < r) v = *(const bf16x8*)(t[ti].A + (size_t)k * H + 8 * c);
-        bf16_t* dst = U + ((size_t)ti * H + 8 * c) * 16 + k;
+        if (k < r) v = *(const bf16x8*)(A + (size_t)k * ld + c0 + 8 * c);
+        bf16_t* dst = U + (size_t)(8 * c) * 16 + k;
 #pragma unroll
         for (int j = 0; j < 8; ++j) dst[j * 16] = v[j];
     }
 }
 
-// acc[n][m] += sum_k T[n][k] X[m][k] over k < H: T = a padded tile in LDS (pitch H + 8), X = the wave's 16 rows (row `xrow` of this lane)
-__device__ __forceinline__ f32x4 lora_contract_h(const bf16_t* T, const bf16_t* xrow, int H, int lane) {
+// acc[n][m] += sum_k T[n][k] X[m][k] over k < w, in 32-wide blocks in ascending k: T = a staged tile of row pitch `pitch`, X = the wave's 16
+// rows (xrow: this lane's row, at the tile's first column).  DROP: X is read under the input mask; p0 = the pair index of this lane's first
+// fragment (row pair + (first column + 8 g) / 2)
+template <bool DROP>
+__device__ __forceinline__ void lora_contract_chunk(f32x4& acc, const bf16_t* T, const bf16_t* xrow, int w, int pitch, int lane, const LoraInDrop& d, uint32_t p0) {
     const int i = lane & 15, g = lane >> 4;
-    const bf16_t* tr = T + (size_t)i * (H + 8) + 8 * g;
+    const bf16_t* tr = T + (size_t)i * pitch + 8 * g;
     const bf16_t* xr = xrow + 8 * g;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-
-    for (int k0 = 0; k0 < H; k0 += 32) {
-        const bf16x8 xf = *(const bf16x8*)(xr + k0);
-        const bf16x8 tf = *(const bf16x8*)(tr + k0);
+    for (int k = 0; k < w; k += 32) {
+        bf16x8 xf = *(const bf16x8*)(xr + k);
+        if constexpr (DROP) xf = lora_drop8(xf, d.stream, p0 + (uint32_t)(k >> 1), d.thr_pk);
+        const bf16x8 tf = *(const bf16x8*)(tr + k);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, xf, acc, 0, 0, 0);
     }
-    return acc;
 }
 // the same for the nt targets at once under the input mask: the targets read the same x and share its mask (one mask per seam INPUT), so
-// the masked fragment is formed ONCE per K step; each accumulator takes the k blocks in lora_contract_h's order, then c (rowpair:
-// lora_row_pair of this lane's row)
+// the masked fragment is formed ONCE per K step; each accumulator takes the k blocks in lora_contract_chunk's order, then c (rowpair:
+// lora_row_pair of this lane's row; the tiles at pitch H + 8)
 __device__ __forceinline__ void lora_contract_h_drop(const bf16_t* T, const bf16_t* xrow, int H, int nt, int lane, const LoraInDrop& d, uint32_t rowpair, f32x4 acc[3]) {
     const int i = lane & 15, g = lane >> 4;
     const bf16_t* tr = T + (size_t)i * (H + 8) + 8 * g;
@@ -183,18 +192,25 @@ __device__ __forceinline__ void lora_expand32(const bf16_t* U, int c0, bf16x8 vf
     d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u0, vf, d0, 0, 0, 0);
     d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u1, vf, d1, 0, 0, 0);
 }
+// the update of the eight columns lora_expand32 left in this lane: o[j] = bf16(fma(s, d[j], float(old[j])))
+__device__ __forceinline__ bf16x8 lora_update8(float s, f32x4 d0, f32x4 d1, bf16x8 old) {
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { o[j] = f2bf(fmaf(s, d0[j], bf2f(old[j]))); o[4 + j] = f2bf(fmaf(s, d1[j], bf2f(old[4 + j]))); }
+    return o;
+}
 
 template <bool DROP>
 __global__ __launch_bounds__(256) void lora_qkv_fwd_kernel(const LoraFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* T = (bf16_t*)smem;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
-    const int H = a.H, r = a.r, nt = a.nt;
+    const int H = a.H, HP = H + 8, r = a.r, nt = a.nt;
     const int m = blockIdx.x * LORA_ROWS + wave * 16 + (lane & 15);
     const bool live = m < a.M;
     const bool wave_live = blockIdx.x * LORA_ROWS + wave * 16 < a.M;
     const int mr = live ? m : a.M - 1;                              // rows past M read row M - 1 and store nothing
-    lora_stage_rows(T, a.t, nt, H, r);
+    for (int ti = 0; ti < nt; ++ti) lora_stage_rows(T + (size_t)ti * 16 * HP, a.t[ti].A, H, 0, H, r, HP);
     __syncthreads();
     bf16x8 hf[3];
     for (int ti = 0; ti < 3; ++ti) hf[ti] = lora_zero8();
@@ -205,7 +221,10 @@ __global__ __launch_bounds__(256) void lora_qkv_fwd_kernel(const LoraFwdArgs a) 
 #pragma unroll
         for (int ti = 0; ti < 3; ++ti) {
             if (ti < nt) {
-                if constexpr (!DROP) hacc[ti] = lora_contract_h(T + (size_t)ti * 16 * (H + 8), xrow, H, lane);
+                if constexpr (!DROP) {
+                    hacc[ti] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    lora_contract_chunk<false>(hacc[ti], T + (size_t)ti * 16 * HP, xrow, H, HP, lane, a.in, 0u);
+                }
                 const bf16x4 hb = lora_round4(hacc[ti]);
                 hf[ti] = lora_low4(hb);
                 if (a.h && live && 4 * g < r) *(bf16x4*)(a.h + (size_t)m * a.ldh + ti * r + 4 * g) = hb;
@@ -213,7 +232,7 @@ __global__ __launch_bounds__(256) void lora_qkv_fwd_kernel(const LoraFwdArgs a) 
         }
     }
     __syncthreads();
-    lora_stage_pad16(T, a.t, nt, H, r);
+    for (int ti = 0; ti < nt; ++ti) lora_stage_pad16(T + (size_t)ti * H * 16, a.t[ti].B, 0, H, r);
     __syncthreads();
     if (!wave_live) return;
 #pragma unroll
@@ -226,9 +245,7 @@ __global__ __launch_bounds__(256) void lora_qkv_fwd_kernel(const LoraFwdArgs a) 
             const bf16x8 old = *(const bf16x8*)(q + c0);
             f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
             lora_expand32(U, c0, hf[ti], lane, d0, d1);
-            bf16x8 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { o[j] = f2bf(fmaf(a.s, d0[j], bf2f(old[j]))); o[4 + j] = f2bf(fmaf(a.s, d1[j], bf2f(old[4 + j]))); }
+            const bf16x8 o = lora_update8(a.s, d0, d1, old);
             if (live) *(bf16x8*)(q + c0) = o;
         }
     }
@@ -240,14 +257,14 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* T = (bf16_t*)smem;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
-    const int H = a.H, r = a.r, nt = a.nt;
+    const int H = a.H, HP = H + 8, r = a.r, nt = a.nt;
     const int m = blockIdx.x * LORA_ROWS + wave * 16 + (lane & 15);
     const bool live = m < a.M;
     const bool wave_live = blockIdx.x * LORA_ROWS + wave * 16 < a.M;
     const int mr = live ? m : a.M - 1;
     const int ldw = nt * r;
     if (a.recompute) {                                               // h = bf16(x . A^T), as forward formed it
-        lora_stage_rows(T, a.t, nt, H, r);
+        for (int ti = 0; ti < nt; ++ti) lora_stage_rows(T + (size_t)ti * 16 * HP, a.t[ti].A, H, 0, H, r, HP);
         __syncthreads();
         if (wave_live) {
             const bf16_t* xrow = a.x + (size_t)mr * a.ldx;
@@ -256,7 +273,10 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
 #pragma unroll
             for (int ti = 0; ti < 3; ++ti) {
                 if (ti < nt) {
-                    if constexpr (!DROP) hacc[ti] = lora_contract_h(T + (size_t)ti * 16 * (H + 8), xrow, H, lane);
+                    if constexpr (!DROP) {
+                        hacc[ti] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                        lora_contract_chunk<false>(hacc[ti], T + (size_t)ti * 16 * HP, xrow, H, HP, lane, a.in, 0u);
+                    }
                     const bf16x4 hb = lora_round4(hacc[ti]);
                     if (live && 4 * g < r) *(bf16x4*)(a.hbuf + (size_t)m * ldw + ti * r + 4 * g) = hb;
                 }
@@ -264,7 +284,7 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
         }
         __syncthreads();
     }
-    lora_stage_cols_t(T, a.t, nt, H, r);
+    for (int ti = 0; ti < nt; ++ti) lora_stage_cols_t(T + (size_t)ti * 16 * HP, a.t[ti].B, 0, H, r, HP);
     __syncthreads();
     bf16x8 gf[3];
     for (int ti = 0; ti < 3; ++ti) gf[ti] = lora_zero8();
@@ -273,7 +293,8 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
         for (int ti = 0; ti < 3; ++ti) {
             if (ti < nt) {
                 const bf16_t* drow = a.dqkv + (size_t)mr * a.lddq + (size_t)a.t[ti].third * H;
-                f32x4 gacc = lora_contract_h(T + (size_t)ti * 16 * (H + 8), drow, H, lane);
+                f32x4 gacc = {0.f, 0.f, 0.f, 0.f};
+                lora_contract_chunk<false>(gacc, T + (size_t)ti * 16 * HP, drow, H, HP, lane, a.in, 0u);
                 if constexpr (DROP) gacc *= a.in.c;                  // g carries c: dA and the input gradient need no further factor
                 const bf16x4 gb = lora_round4(gacc);
                 gf[ti] = lora_low4(gb);
@@ -283,7 +304,7 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
     }
     if (!a.dres_out) return;                                         // (uniform over the grid)
     __syncthreads();
-    lora_stage_pad16_t(T, a.t, nt, H, r);
+    for (int ti = 0; ti < nt; ++ti) lora_stage_pad16_t(T + (size_t)ti * H * 16, a.t[ti].A, H, 0, H, r);
     __syncthreads();
     if (!wave_live) return;
     const bf16_t* din = a.dres_in + (size_t)mr * a.lddi + 8 * g;
@@ -296,109 +317,119 @@ __global__ __launch_bounds__(256) void lora_qkv_bwd_g_kernel(const LoraBwdArgs a
 #pragma unroll
         for (int ti = 0; ti < 3; ++ti)
             if (ti < nt) lora_expand32(T + (size_t)ti * H * 16, c0, gf[ti], lane, d0, d1);
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { o[j] = f2bf(fmaf(a.s, d0[j], bf2f(old[j]))); o[4 + j] = f2bf(fmaf(a.s, d1[j], bf2f(old[4 + j]))); }
+        bf16x8 o = lora_update8(a.s, d0, d1, old);
         if constexpr (DROP) o = lora_keep_old8(o, old, a.in.stream, p0 + (uint32_t)(c0 >> 1), a.in.thr_pk);
         if (live) *(bf16x8*)(dout + c0) = o;
     }
 }
 
-// backward launch 2: part[stream][slab][k, c] = sum over the slab's tokens m of coef[m][k] * src[m][c]  (fp32; not yet scaled by s).
-// A lane owns 8 columns and all R rank entries; the workgroup's row lanes take interleaved tokens and are added in row-lane order.
-// DROP: the dA streams (src = x, the seam input) read x under the input mask; the dB streams read dqkv and the h forward wrote, as they are.
+// backward launch 2, both seam families: part[stream][slab][k, c] = sum over the slab's tokens m of coef[m][k] * src[m][c]  (fp32; not yet
+// scaled by s).  A lane owns 8 columns and all R rank entries; the column axis runs over blockIdx.z in blocks of CHW = min(W / 8, col_lanes)
+// column lanes, and the workgroup's 256 / CHW row lanes take interleaved tokens and are added in row-lane order.  col_lanes is the caller's:
+// 256 from the Q | K | V entry points (one workgroup per slab and stream up to H = 2048), 128 from the dense ones (an I-wide stream runs on 3
+// (bert-base) or 4 (bert-large) workgroups per slab with two row lanes each).
+// DROP: the dA streams (src = x, the seam input) read x under the input mask of the SITE rows (in.rows[m] on gathered operands, m itself when
+// it is null); the dB streams read dy / dqkv and h as they are.
 template <int R, bool DROP>
-__global__ __launch_bounds__(256) void lora_qkv_bwd_w_kernel(const LoraWArgs a) {
+__global__ __launch_bounds__(256) void lora_bwd_w_kernel(const LoraWArgs a) {
     __shared__ __attribute__((aligned(16))) float red[256 * 8];
     const LoraStream& st = a.st[blockIdx.y];
-    const int H = a.H, CH = H >> 3;
+    const int W = st.W, CH = W >> 3;
     const bool masked = DROP && !st.colmajor;                        // (uniform over the workgroup)
-    const int CHW = CH < 256 ? CH : 256, RL = 256 / CHW;
+    const int CHW = min(CH, a.col_lanes), RL = 256 / CHW;
+    const int cb = blockIdx.z * CHW;
+    if (cb >= CH) return;                                            // (uniform over the workgroup: the narrower stream has fewer column blocks)
     const int cc = threadIdx.x % CHW, rl = threadIdx.x / CHW;
     const int mbeg = blockIdx.x * LORA_SLAB, mend = min(a.M, mbeg + LORA_SLAB);
-    float* part = a.part + ((size_t)blockIdx.y * a.nslab + blockIdx.x) * (size_t)(R * H);
-    for (int cb = 0; cb < CH; cb += CHW) {                           // (one round for H <= 2048)
-        const int c = cb + cc;
-        const bool act = rl < RL && c < CH;
-        float acc[R][8];
+    float* part = a.part + st.part_off + (size_t)blockIdx.x * (size_t)(R * W);
+    const int c = cb + cc;
+    const bool act = rl < RL && c < CH;
+    float acc[R][8];
 #pragma unroll
-        for (int k = 0; k < R; ++k)
+    for (int k = 0; k < R; ++k)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
-        if (act) {
-            const bf16_t* src = st.src + 8 * c;
-            int m = mbeg + rl;
-            for (; m + 3 * RL < mend; m += 4 * RL) {                  // four independent 16-byte loads in flight
-                bf16x8 v[4];
-                bf16x4 w[4][R / 4];
+        for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
+    // The token sums of this lane.  gather: the mask of row m is that of site row in.rows[m]; else that of row m.  Two loops, chosen outside
+    // them: with the row list's null test inside the loop the four loads of a round no longer go out together, which cost the Q | K | V
+    // seam (never a row list) 2 us of 77 at 18 400 rows (profiles/lora_kernels_ab.txt)
+    auto sums = [&](auto gather) {
+        const int32_t* rows = decltype(gather)::value ? a.in.rows : nullptr;
+        const bf16_t* src = st.src + 8 * c;
+        int m = mbeg + rl;
+        for (; m + 3 * RL < mend; m += 4 * RL) {                      // four independent 16-byte loads in flight
+            bf16x8 v[4];
+            bf16x4 w[4][R / 4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    v[u] = *(const bf16x8*)(src + (size_t)(m + u * RL) * st.lds);
-                    if constexpr (DROP)
-                        if (masked) v[u] = lora_drop8(v[u], a.in.stream, lora_row_pair(nullptr, m + u * RL, H) + 4 * c, a.in.thr_pk);
-#pragma unroll
-                    for (int q = 0; q < R / 4; ++q) w[u][q] = *(const bf16x4*)(st.coef + (size_t)(m + u * RL) * st.ldc + 4 * q);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int k = 0; k < R; ++k) {
-                        const float wk = bf2f(w[u][k >> 2][k & 3]);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[u][j]), acc[k][j]);
-                    }
-            }
-            for (; m < mend; m += RL) {
-                bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
+            for (int u = 0; u < 4; ++u) {
+                v[u] = *(const bf16x8*)(src + (size_t)(m + u * RL) * st.lds);
                 if constexpr (DROP)
-                    if (masked) v = lora_drop8(v, a.in.stream, lora_row_pair(nullptr, m, H) + 4 * c, a.in.thr_pk);
+                    if (masked) v[u] = lora_drop8(v[u], a.in.stream, lora_row_pair(rows, m + u * RL, W) + 4 * c, a.in.thr_pk);
+#pragma unroll
+                for (int q = 0; q < R / 4; ++q) w[u][q] = *(const bf16x4*)(st.coef + (size_t)(m + u * RL) * st.ldc + 4 * q);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
 #pragma unroll
                 for (int k = 0; k < R; ++k) {
-                    const float wk = bf2f(st.coef[(size_t)m * st.ldc + k]);
+                    const float wk = bf2f(w[u][k >> 2][k & 3]);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[j]), acc[k][j]);
+                    for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[u][j]), acc[k][j]);
                 }
+        }
+        for (; m < mend; m += RL) {
+            bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
+            if constexpr (DROP)
+                if (masked) v = lora_drop8(v, a.in.stream, lora_row_pair(rows, m, W) + 4 * c, a.in.thr_pk);
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                const float wk = bf2f(st.coef[(size_t)m * st.ldc + k]);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[j]), acc[k][j]);
             }
         }
+    };
+    if (act) {
+        if (DROP && masked && a.in.rows) sums(std::true_type{});
+        else sums(std::false_type{});
+    }
 #pragma unroll
-        for (int k = 0; k < R; ++k) {                                // row lanes 1 .. RL-1 are added onto row lane 0, in order
-            if (act && rl > 0) {
-                *(float4*)(red + (size_t)threadIdx.x * 8) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
-                *(float4*)(red + (size_t)threadIdx.x * 8 + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
-            }
-            __syncthreads();
-            if (act && rl == 0) {
-                for (int q = 1; q < RL; ++q)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[k][j] += red[(size_t)(q * CHW + cc) * 8 + j];
-            }
-            __syncthreads();
+    for (int k = 0; k < R; ++k) {                                    // row lanes 1 .. RL-1 are added onto row lane 0, in order
+        if (act && rl > 0) {
+            *(float4*)(red + (size_t)threadIdx.x * 8) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+            *(float4*)(red + (size_t)threadIdx.x * 8 + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
         }
+        __syncthreads();
         if (act && rl == 0) {
-            if (st.colmajor) {                                       // [H, R]: R consecutive floats per column
+            for (int q = 1; q < RL; ++q)
 #pragma unroll
-                for (int j = 0; j < 8; ++j)
+                for (int j = 0; j < 8; ++j) acc[k][j] += red[(size_t)(q * CHW + cc) * 8 + j];
+        }
+        __syncthreads();
+    }
+    if (act && rl == 0) {
+        if (st.colmajor) {                                           // [W, R]: R consecutive floats per column
 #pragma unroll
-                    for (int k = 0; k < R; k += 4)
-                        *(float4*)(part + (size_t)(8 * c + j) * R + k) = make_float4(acc[k][j], acc[k + 1][j], acc[k + 2][j], acc[k + 3][j]);
-            } else {                                                 // [R, H]
+            for (int j = 0; j < 8; ++j)
 #pragma unroll
-                for (int k = 0; k < R; ++k) {
-                    *(float4*)(part + (size_t)k * H + 8 * c) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
-                    *(float4*)(part + (size_t)k * H + 8 * c + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
-                }
+                for (int k = 0; k < R; k += 4)
+                    *(float4*)(part + (size_t)(8 * c + j) * R + k) = make_float4(acc[k][j], acc[k + 1][j], acc[k + 2][j], acc[k + 3][j]);
+        } else {                                                     // [R, W]
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                *(float4*)(part + (size_t)k * W + 8 * c) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+                *(float4*)(part + (size_t)k * W + 8 * c + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
             }
         }
     }
 }
 
 // backward launch 3: out[e] = (acc ? out[e] : 0) + s * (slab 0 + slab 1 + ... in ascending order); a lane owns 4 consecutive elements
-__global__ __launch_bounds__(256) void lora_qkv_fold_kernel(const LoraWArgs a) {
+__global__ __launch_bounds__(256) void lora_fold_kernel(const LoraWArgs a) {
     const LoraStream& st = a.st[blockIdx.y];
-    const size_t n = (size_t)a.r * a.H;
+    const size_t n = (size_t)a.r * st.W;
     const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (e >= n) return;
-    const float* p = a.part + (size_t)blockIdx.y * a.nslab * n + e;
+    const float* p = a.part + st.part_off + e;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     int q = 0;
     for (; q + 4 <= a.nslab; q += 4) {                               // loads four slabs ahead, adds in order
@@ -446,34 +477,27 @@ static inline LoraInDrop lora_in_drop(unsigned in_stream, unsigned thr16, float 
     return d;
 }
 
-template <bool DROP>
-static int lora_qkv_fwd_launch(hipStream_t stream, const LoraFwdArgs& a, size_t lds) {
+// launch 1 of either direction: one workgroup per LORA_ROWS token rows; more than 64 KiB of dynamic LDS needs the kernel's one-time opt-in
+template <auto KERNEL, typename Args>
+static int lora_rows_launch(hipStream_t stream, const Args& a, size_t lds) {
     if (lds > 65536) {
         static std::atomic<unsigned long long> done{0};
-        const int e = mmb_allow_lds((const void*)lora_qkv_fwd_kernel<DROP>, (int)lds, done);
+        const int e = mmb_allow_lds((const void*)KERNEL, (int)lds, done);
         if (e) return e;
     }
-    hipLaunchKernelGGL(lora_qkv_fwd_kernel<DROP>, dim3((a.M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(KERNEL, dim3((a.M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
     MMB_CHECK_LAUNCH();
     return 0;
 }
-
+// backward launches 2 and 3 over the streams of w; wmax = the widest of them
 template <bool DROP>
-static int lora_qkv_bwd_g_launch(hipStream_t stream, const LoraBwdArgs& a, size_t lds) {
-    if (lds > 65536) {
-        static std::atomic<unsigned long long> done{0};
-        const int e = mmb_allow_lds((const void*)lora_qkv_bwd_g_kernel<DROP>, (int)lds, done);
-        if (e) return e;
-    }
-    hipLaunchKernelGGL(lora_qkv_bwd_g_kernel<DROP>, dim3((a.M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), lds, stream, a);
+static int lora_bwd_w_launch(hipStream_t stream, const LoraWArgs& w, int wmax) {
+    const dim3 grid(w.nslab, w.ns, (wmax / 8 + w.col_lanes - 1) / w.col_lanes);
+    if (w.r == 4) hipLaunchKernelGGL((lora_bwd_w_kernel<4, DROP>), grid, dim3(256), 0, stream, w);
+    else if (w.r == 8) hipLaunchKernelGGL((lora_bwd_w_kernel<8, DROP>), grid, dim3(256), 0, stream, w);
+    else hipLaunchKernelGGL((lora_bwd_w_kernel<16, DROP>), grid, dim3(256), 0, stream, w);
     MMB_CHECK_LAUNCH();
-    return 0;
-}
-template <bool DROP>
-static int lora_qkv_bwd_w_launch(hipStream_t stream, dim3 grid, const LoraWArgs& w) {
-    if (w.r == 4) hipLaunchKernelGGL((lora_qkv_bwd_w_kernel<4, DROP>), grid, dim3(256), 0, stream, w);
-    else if (w.r == 8) hipLaunchKernelGGL((lora_qkv_bwd_w_kernel<8, DROP>), grid, dim3(256), 0, stream, w);
-    else hipLaunchKernelGGL((lora_qkv_bwd_w_kernel<16, DROP>), grid, dim3(256), 0, stream, w);
+    hipLaunchKernelGGL(lora_fold_kernel, dim3((unsigned)(((size_t)w.r * wmax / 4 + 255) / 256), w.ns), dim3(256), 0, stream, w);
     MMB_CHECK_LAUNCH();
     return 0;
 }
@@ -493,7 +517,7 @@ static int lora_qkv_fwd_impl(hipStream_t stream, const void* x, int ldx, void* q
     a.M = M; a.H = H; a.r = r; a.ldx = ldx; a.ldq = ldq; a.ldh = ldh; a.s = scale;
     a.x = (const bf16_t*)x; a.qkv = (bf16_t*)qkv; a.h = (bf16_t*)h_out;
     a.in = lora_in_drop(in_stream, in_thr16, in_scale, nullptr);
-    return in_thr16 ? lora_qkv_fwd_launch<true>(stream, a, lds) : lora_qkv_fwd_launch<false>(stream, a, lds);
+    return in_thr16 ? lora_rows_launch<lora_qkv_fwd_kernel<true>>(stream, a, lds) : lora_rows_launch<lora_qkv_fwd_kernel<false>>(stream, a, lds);
 }
 
 extern "C" {
@@ -551,12 +575,12 @@ static int lora_qkv_bwd_impl(hipStream_t stream, const void* dqkv, int lddq, con
         if (ga) {
             if (!lora_al16(ga)) return -1;
             LoraStream& s = w.st[w.ns++];
-            s.src = a.x; s.lds = ldx; s.coef = a.gbuf + ti * r; s.ldc = nt * r; s.out = ga; s.colmajor = 0; s.acc = accumulate ? 1 : 0;
+            s.src = a.x; s.lds = ldx; s.coef = a.gbuf + ti * r; s.ldc = nt * r; s.out = ga; s.colmajor = 0;
         }
         if (gb_) {
             if (!lora_al16(gb_)) return -1;
             LoraStream& s = w.st[w.ns++];
-            s.src = a.dqkv + (size_t)k * H; s.lds = lddq; s.out = gb_; s.colmajor = 1; s.acc = accumulate ? 1 : 0;
+            s.src = a.dqkv + (size_t)k * H; s.lds = lddq; s.out = gb_; s.colmajor = 1;
             if (h) { s.coef = (const bf16_t*)h + ti * r; s.ldc = ldh; }
             else { s.coef = a.hbuf + ti * r; s.ldc = nt * r; need_h = true; }
         }
@@ -564,16 +588,13 @@ static int lora_qkv_bwd_impl(hipStream_t stream, const void* dqkv, int lddq, con
     a.recompute = need_h ? 1 : 0;
     if (!dres_out && w.ns == 0) return 0;                            // nothing asked for
     a.in = w.in = lora_in_drop(in_stream, in_thr16, in_scale, nullptr);
-    int e = in_thr16 ? lora_qkv_bwd_g_launch<true>(stream, a, lds) : lora_qkv_bwd_g_launch<false>(stream, a, lds);
-    if (e) return e;
-    if (w.ns == 0) return 0;
-    w.M = M; w.H = H; w.r = r; w.nslab = nslab; w.s = scale; w.part = (float*)workspace;
-    const dim3 grid(nslab, w.ns);
-    e = in_thr16 ? lora_qkv_bwd_w_launch<true>(stream, grid, w) : lora_qkv_bwd_w_launch<false>(stream, grid, w);
-    if (e) return e;
-    hipLaunchKernelGGL(lora_qkv_fold_kernel, dim3((unsigned)(((size_t)r * H / 4 + 255) / 256), w.ns), dim3(256), 0, stream, w);
-    MMB_CHECK_LAUNCH();
-    return 0;
+    const int e = in_thr16 ? lora_rows_launch<lora_qkv_bwd_g_kernel<true>>(stream, a, lds) : lora_rows_launch<lora_qkv_bwd_g_kernel<false>>(stream, a, lds);
+    if (e || w.ns == 0) return e;
+    for (int i = 0; i < w.ns; ++i) {                                 // every stream is H wide: stream i's partial sums follow stream i - 1's
+        w.st[i].W = H; w.st[i].part_off = (size_t)i * nslab * (size_t)r * H; w.st[i].acc = accumulate ? 1 : 0;
+    }
+    w.M = M; w.r = r; w.nslab = nslab; w.col_lanes = 256; w.s = scale; w.part = (float*)workspace;
+    return in_thr16 ? lora_bwd_w_launch<true>(stream, w, H) : lora_bwd_w_launch<false>(stream, w, H);
 }
 
 int mmbert_lora_qkv_bwd(hipStream_t stream, const void* dqkv, int lddq, const void* x, int ldx, const void* h, int ldh, int M, int H, int r,
@@ -595,16 +616,16 @@ int mmbert_lora_qkv_bwd_drop(hipStream_t stream, const void* dqkv, int lddq, con
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // Adapters on the three remaining dense seams of an encoder layer (attention.output.dense, intermediate.dense, output.dense; DESIGN.md
-// S3.15): y [M, N] behind the projection's own GEMM, x [M, K] its input, A [r, K], B [N, r], K != N in general.  The fragment scheme is the
-// one above, unchanged in its arithmetic; what differs:
+// S3.15): y [M, N] behind the projection's own GEMM, x [M, K] its input, A [r, K], B [N, r], K != N in general.  The fragment scheme, the
+// helpers and backward launches 2 and 3 are the ones above (one stream of width K for dA, one of width N for dB, col_lanes = 128); these
+// forward and `g` kernels differ from the Q | K | V ones in:
 //   * A and B are staged in column CHUNKS of LORA_DCHUNK (768) columns into ONE static 24.8 KB tile, so the LDS footprint does not grow
 //     with the FFN width and several workgroups share a CU.  The fp32 accumulator of a contraction lives across the chunks: k ascends in
-//     32-wide blocks exactly as in lora_contract_h, chunking changes no rounding.
+//     32-wide blocks exactly as over one whole tile, chunking changes no rounding.
 //   * the epilogue of the forward update: ADD  y = bf16(fma(s * c, p, float(y))), c = drop_scale on the elements the GEMM's dropout kept
 //     (same stream, threshold, flat index m * N + n) and the element untouched where it dropped;  GELU  w = fma(s, p, float(y)),
 //     aux = bf16(w), y = bf16(gelu(w)).
 //   * the input gradient is updated IN PLACE, optionally times gelu'(float(u)).
-//   * the token sums take one stream of width K (dA) and one of width N (dB); the column axis is split over blockIdx.z in chunks of 1024.
 #define LORA_DCHUNK 768
 #define LORA_DPITCH (LORA_DCHUNK + 8)
 #define LORA_DTILE (16 * LORA_DPITCH)                      // elements; >= LORA_DCHUNK * 16 (the [columns, 16] form)
@@ -621,70 +642,7 @@ struct LoraDenseBwdArgs {
     int M, K, N, r, lddy, ldx, lddx, ldu, recompute; float s;
     LoraInDrop in;
 };
-struct LoraDStream { const bf16_t* src; const bf16_t* coef; float* out; size_t part_off; int lds, ldc, colmajor, acc, W, pad; };
-struct LoraDWArgs { LoraDStream st[2]; int ns, M, r, nslab; float s; float* part; LoraInDrop in; };
 
-// T[k][0 .. w) = A[k][k0 .. k0 + w) for k < r, zeros for r <= k < 16 (A: [r, K] row-major); row pitch LORA_DPITCH
-__device__ __forceinline__ void lora_stage_rows_chunk(bf16_t* T, const bf16_t* A, int K, int k0, int w, int r) {
-    const int CH = w >> 3, total = 16 * CH;
-    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const int k = idx / CH, c = idx - k * CH;
-        bf16x8 v = lora_zero8();
-        if (k < r) v = *(const bf16x8*)(A + (size_t)k * K + k0 + 8 * c);
-        *(bf16x8*)(T + (size_t)k * LORA_DPITCH + 8 * c) = v;
-    }
-}
-// T[k][c] = B[n0 + c][k] for k < r, zeros above (B: [N, r] row-major), c < w: the transposed tile for the contraction over N in backward
-__device__ __forceinline__ void lora_stage_cols_t_chunk(bf16_t* T, const bf16_t* B, int n0, int w, int r) {
-    for (int c = threadIdx.x; c < w; c += blockDim.x) {
-        const bf16_t* src = B + (size_t)(n0 + c) * r;
-        bf16_t* dst = T + c;
-        for (int k0 = 0; k0 < r; k0 += 4) {
-            const bf16x4 v = *(const bf16x4*)(src + k0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dst[(size_t)(k0 + j) * LORA_DPITCH] = v[j];
-        }
-        for (int k = r; k < 16; ++k) dst[(size_t)k * LORA_DPITCH] = (bf16_t)0.0f;
-    }
-}
-// U[c][k] = B[n0 + c][k] for k < r, zeros for r <= k < 16: 16 elements per column c < w
-__device__ __forceinline__ void lora_stage_pad16_chunk(bf16_t* U, const bf16_t* B, int n0, int w, int r) {
-    for (int c = threadIdx.x; c < w; c += blockDim.x) {
-        const bf16_t* src = B + (size_t)(n0 + c) * r;
-        bf16x8 lo = lora_zero8(), hi = lora_zero8();
-        if (r == 16) { lo = *(const bf16x8*)src; hi = *(const bf16x8*)(src + 8); }
-        else if (r == 8) lo = *(const bf16x8*)src;
-        else lo = lora_low4(*(const bf16x4*)src);
-        bf16_t* dst = U + (size_t)c * 16;
-        *(bf16x8*)dst = lo; *(bf16x8*)(dst + 8) = hi;
-    }
-}
-// U[c][k] = A[k][k0 + c] for k < r, zeros above (A: [r, K] row-major), c < w: the transposed form, for the input gradient
-__device__ __forceinline__ void lora_stage_pad16_t_chunk(bf16_t* U, const bf16_t* A, int K, int k0, int w, int r) {
-    const int CH = w >> 3, total = 16 * CH;
-    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const int k = idx / CH, c = idx - k * CH;
-        bf16x8 v = lora_zero8();
-        if (k < r) v = *(const bf16x8*)(A + (size_t)k * K + k0 + 8 * c);
-        bf16_t* dst = U + (size_t)(8 * c) * 16 + k;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dst[j * 16] = v[j];
-    }
-}
-// acc[n][m] += sum_k T[n][k] X[m][k0 + k] over the chunk's w columns (xrow already points at column k0 of this lane's row)
-// DROP: X is read under the input mask; p0 = the pair index of this lane's first fragment of the chunk (row pair + (k0 + 8 g) / 2)
-template <bool DROP>
-__device__ __forceinline__ void lora_contract_chunk(f32x4& acc, const bf16_t* T, const bf16_t* xrow, int w, int lane, const LoraInDrop& d, uint32_t p0) {
-    const int i = lane & 15, g = lane >> 4;
-    const bf16_t* tr = T + (size_t)i * LORA_DPITCH + 8 * g;
-    const bf16_t* xr = xrow + 8 * g;
-    for (int k = 0; k < w; k += 32) {
-        bf16x8 xf = *(const bf16x8*)(xr + k);
-        if constexpr (DROP) xf = lora_drop8(xf, d.stream, p0 + (uint32_t)(k >> 1), d.thr_pk);
-        const bf16x8 tf = *(const bf16x8*)(tr + k);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, xf, acc, 0, 0, 0);
-    }
-}
 // h = x . A^T of the wave's 16 rows over all of K, chunk by chunk (every thread of the workgroup calls it: it synchronises).  DROP: x under
 // the input mask (rowpair: lora_row_pair of this lane's row) and c on the finished accumulator
 template <bool DROP>
@@ -693,10 +651,10 @@ __device__ __forceinline__ f32x4 lora_dense_contract(bf16_t* T, const bf16_t* W,
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < K; k0 += LORA_DCHUNK) {
         const int w = min(LORA_DCHUNK, K - k0);
-        if (rows_form) lora_stage_rows_chunk(T, W, K, k0, w, r);
-        else lora_stage_cols_t_chunk(T, W, k0, w, r);
+        if (rows_form) lora_stage_rows(T, W, K, k0, w, r, LORA_DPITCH);
+        else lora_stage_cols_t(T, W, k0, w, r, LORA_DPITCH);
         __syncthreads();
-        if (wave_live) lora_contract_chunk<DROP>(acc, T, xrow + k0, w, lane, d, rowpair + (uint32_t)((k0 + 8 * (lane >> 4)) >> 1));
+        if (wave_live) lora_contract_chunk<DROP>(acc, T, xrow + k0, w, LORA_DPITCH, lane, d, rowpair + (uint32_t)((k0 + 8 * (lane >> 4)) >> 1));
         __syncthreads();
     }
     if constexpr (DROP) acc *= d.c;
@@ -721,7 +679,7 @@ __global__ __launch_bounds__(256) void lora_dense_fwd_kernel(const LoraDenseFwdA
     const uint64_t flat = (uint64_t)mr * (uint64_t)N + (uint64_t)(8 * g);   // the GEMM's dropout index: LOGICAL column count, not the pitch
     for (int n0 = 0; n0 < N; n0 += LORA_DCHUNK) {
         const int w = min(LORA_DCHUNK, N - n0);
-        lora_stage_pad16_chunk(T, a.B, n0, w, r);
+        lora_stage_pad16(T, a.B, n0, w, r);
         __syncthreads();
         if (wave_live) {
             for (int c0 = 0; c0 < w; c0 += 32) {
@@ -742,8 +700,7 @@ __global__ __launch_bounds__(256) void lora_dense_fwd_kernel(const LoraDenseFwdA
                     }
                     if (arow && live) *(bf16x8*)(arow + n0 + c0) = uo;
                 } else if (a.thr16 == 0) {                          // no dropout: c = drop_scale everywhere
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) o[j] = f2bf(fmaf(a.sc, p[j], bf2f(old[j])));
+                    o = lora_update8(a.sc, d0, d1, old);
                 } else {
                     const uint32_t pair0 = (uint32_t)((flat + (uint64_t)(n0 + c0)) >> 1);
 #pragma unroll
@@ -787,24 +744,19 @@ __global__ __launch_bounds__(256) void lora_dense_bwd_g_kernel(const LoraDenseBw
     const bf16_t* urow = a.u ? a.u + (size_t)mr * a.ldu + 8 * g : nullptr;
     for (int k0 = 0; k0 < K; k0 += LORA_DCHUNK) {
         const int w = min(LORA_DCHUNK, K - k0);
-        lora_stage_pad16_t_chunk(T, a.A, K, k0, w, r);
+        lora_stage_pad16_t(T, a.A, K, k0, w, r);
         __syncthreads();
         if (wave_live) {
             for (int c0 = 0; c0 < w; c0 += 32) {
                 const bf16x8 old = *(const bf16x8*)(drow + k0 + c0);
                 f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
                 lora_expand32(T, c0, gf, lane, d0, d1);
-                float q[8];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { q[j] = d0[j]; q[4 + j] = d1[j]; }
                 if (urow) {                                          // the FFN-down seam: the base input gradient carries the same gelu' factor
                     const bf16x8 uv = *(const bf16x8*)(urow + k0 + c0);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) q[j] *= gelu_erf_grad(bf2f(uv[j]));
+                    for (int j = 0; j < 4; ++j) { d0[j] *= gelu_erf_grad(bf2f(uv[j])); d1[j] *= gelu_erf_grad(bf2f(uv[4 + j])); }
                 }
-                bf16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = f2bf(fmaf(a.s, q[j], bf2f(old[j])));
+                bf16x8 o = lora_update8(a.s, d0, d1, old);
                 if constexpr (DROP) o = lora_keep_old8(o, old, a.in.stream, rowpair + (uint32_t)((k0 + c0 + 8 * g) >> 1), a.in.thr_pk);
                 if (live) *(bf16x8*)(drow + k0 + c0) = o;
             }
@@ -813,136 +765,11 @@ __global__ __launch_bounds__(256) void lora_dense_bwd_g_kernel(const LoraDenseBw
     }
 }
 
-// backward launch 2: part[stream][slab][k, c] = sum over the slab's tokens m of coef[m][k] * src[m][c] (fp32; not yet scaled by s); the FMA form
-// of lora_qkv_bwd_w_kernel with a width per stream and the column axis over blockIdx.z (128 lanes x 8 columns per workgroup: an I-wide
-// stream runs on 3 (bert-base) or 4 (bert-large) workgroups per slab with two row lanes each)
-// DROP: the dA stream (src = x, width K) reads x under the input mask of the SITE rows (rows[m] on gathered operands); the dB stream reads
-// dy and h as they are.
-template <int R, bool DROP>
-__global__ __launch_bounds__(256) void lora_dense_bwd_w_kernel(const LoraDWArgs a) {
-    __shared__ __attribute__((aligned(16))) float red[256 * 8];
-    const LoraDStream& st = a.st[blockIdx.y];
-    const int W = st.W, CH = W >> 3;
-    const bool masked = DROP && !st.colmajor;                        // (uniform over the workgroup)
-    const int CHW = CH < 128 ? CH : 128, RL = 256 / CHW;
-    const int cb = blockIdx.z * CHW;
-    if (cb >= CH) return;                                            // (uniform over the workgroup: the narrower stream has fewer column blocks)
-    const int cc = threadIdx.x % CHW, rl = threadIdx.x / CHW;
-    const int mbeg = blockIdx.x * LORA_SLAB, mend = min(a.M, mbeg + LORA_SLAB);
-    float* part = a.part + st.part_off + (size_t)blockIdx.x * (size_t)(R * W);
-    const int c = cb + cc;
-    const bool act = rl < RL && c < CH;
-    float acc[R][8];
-#pragma unroll
-    for (int k = 0; k < R; ++k)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
-    if (act) {
-        const bf16_t* src = st.src + 8 * c;
-        int m = mbeg + rl;
-        for (; m + 3 * RL < mend; m += 4 * RL) {                      // four independent 16-byte loads in flight
-            bf16x8 v[4];
-            bf16x4 w[4][R / 4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                v[u] = *(const bf16x8*)(src + (size_t)(m + u * RL) * st.lds);
-                if constexpr (DROP)
-                    if (masked) v[u] = lora_drop8(v[u], a.in.stream, lora_row_pair(a.in.rows, m + u * RL, W) + 4 * c, a.in.thr_pk);
-#pragma unroll
-                for (int q = 0; q < R / 4; ++q) w[u][q] = *(const bf16x4*)(st.coef + (size_t)(m + u * RL) * st.ldc + 4 * q);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int k = 0; k < R; ++k) {
-                    const float wk = bf2f(w[u][k >> 2][k & 3]);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[u][j]), acc[k][j]);
-                }
-        }
-        for (; m < mend; m += RL) {
-            bf16x8 v = *(const bf16x8*)(src + (size_t)m * st.lds);
-            if constexpr (DROP)
-                if (masked) v = lora_drop8(v, a.in.stream, lora_row_pair(a.in.rows, m, W) + 4 * c, a.in.thr_pk);
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const float wk = bf2f(st.coef[(size_t)m * st.ldc + k]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(wk, bf2f(v[j]), acc[k][j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < R; ++k) {                                    // row lanes 1 .. RL-1 are added onto row lane 0, in order
-        if (act && rl > 0) {
-            *(float4*)(red + (size_t)threadIdx.x * 8) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
-            *(float4*)(red + (size_t)threadIdx.x * 8 + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
-        }
-        __syncthreads();
-        if (act && rl == 0) {
-            for (int q = 1; q < RL; ++q)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[k][j] += red[(size_t)(q * CHW + cc) * 8 + j];
-        }
-        __syncthreads();
-    }
-    if (act && rl == 0) {
-        if (st.colmajor) {                                           // [W, R]: R consecutive floats per column
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int k = 0; k < R; k += 4)
-                    *(float4*)(part + (size_t)(8 * c + j) * R + k) = make_float4(acc[k][j], acc[k + 1][j], acc[k + 2][j], acc[k + 3][j]);
-        } else {                                                     // [R, W]
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                *(float4*)(part + (size_t)k * W + 8 * c) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
-                *(float4*)(part + (size_t)k * W + 8 * c + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
-            }
-        }
-    }
-}
-
-// backward launch 3: out[e] = (acc ? out[e] : 0) + s * (slab 0 + slab 1 + ... in ascending order); a lane owns 4 consecutive elements
-__global__ __launch_bounds__(256) void lora_dense_fold_kernel(const LoraDWArgs a) {
-    const LoraDStream& st = a.st[blockIdx.y];
-    const size_t n = (size_t)a.r * st.W;
-    const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (e >= n) return;
-    const float* p = a.part + st.part_off + e;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    int q = 0;
-    for (; q + 4 <= a.nslab; q += 4) {                               // loads four slabs ahead, adds in order
-        float4 t[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) t[u] = *(const float4*)(p + (size_t)(q + u) * n);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { s.x += t[u].x; s.y += t[u].y; s.z += t[u].z; s.w += t[u].w; }
-    }
-    for (; q < a.nslab; ++q) {
-        const float4 t = *(const float4*)(p + (size_t)q * n);
-        s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
-    }
-    float4* o = (float4*)(st.out + e);
-    float4 v = make_float4(a.s * s.x, a.s * s.y, a.s * s.z, a.s * s.w);
-    if (st.acc) { const float4 w = *o; v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w; }
-    *o = v;
-}
-
 static inline bool lora_dense_shape_ok(int M, int K, int N, int r) {
     return M >= 0 && K > 0 && N > 0 && (K & 63) == 0 && (N & 63) == 0 && (r == 4 || r == 8 || r == 16);
 }
 // what ONE workgroup stages at a time; constant in K and N (the chunking), so the -2 of the convention cannot occur for these kernels
 static inline size_t lora_dense_lds_bytes() { return (size_t)LORA_DTILE * sizeof(bf16_t); }
-
-template <bool DROP>
-static int lora_dense_bwd_w_launch(hipStream_t stream, dim3 grid, const LoraDWArgs& w) {
-    if (w.r == 4) hipLaunchKernelGGL((lora_dense_bwd_w_kernel<4, DROP>), grid, dim3(256), 0, stream, w);
-    else if (w.r == 8) hipLaunchKernelGGL((lora_dense_bwd_w_kernel<8, DROP>), grid, dim3(256), 0, stream, w);
-    else hipLaunchKernelGGL((lora_dense_bwd_w_kernel<16, DROP>), grid, dim3(256), 0, stream, w);
-    MMB_CHECK_LAUNCH();
-    return 0;
-}
 
 extern "C" {
 
@@ -963,10 +790,7 @@ static int lora_dense_fwd_impl(hipStream_t stream, const void* x, int ldx, void*
     a.s = scale; a.sc = scale * drop_scale;
     a.dstream = drop_stream; a.thr16 = a.gelu ? 0u : drop_thr16; a.thr_pk = mmb_thr_packed(drop_thr16);
     a.in = lora_in_drop(in_stream, in_thr16, in_scale, nullptr);
-    if (in_thr16) hipLaunchKernelGGL(lora_dense_fwd_kernel<true>, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(lora_dense_fwd_kernel<false>, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
-    MMB_CHECK_LAUNCH();
-    return 0;
+    return in_thr16 ? lora_rows_launch<lora_dense_fwd_kernel<true>>(stream, a, 0) : lora_rows_launch<lora_dense_fwd_kernel<false>>(stream, a, 0);
 }
 
 int mmbert_lora_dense_fwd(hipStream_t stream, const void* x, int ldx, void* y, int ldy, int M, int K, int N, int r, const void* A, const void* B,
@@ -1015,32 +839,25 @@ static int lora_dense_bwd_impl(hipStream_t stream, const void* dy, int lddy, con
     a.M = M; a.K = K; a.N = N; a.r = r; a.lddy = lddy; a.ldx = ldx; a.lddx = lddx; a.ldu = ldu; a.s = scale;
     a.recompute = (gB && !h) ? 1 : 0;
     // the weight-gradient streams that run: dA needs g and x (width K), dB needs dy and h (width N)
-    LoraDWArgs w = {};
+    LoraWArgs w = {};
     int wmax = 0;
     if (gA) {
-        LoraDStream& s = w.st[w.ns++];
+        LoraStream& s = w.st[w.ns++];
         s.src = a.x; s.lds = ldx; s.coef = a.gbuf; s.ldc = r; s.out = gA; s.colmajor = 0; s.acc = accumulate ? 1 : 0; s.W = K; s.part_off = 0;
         wmax = K;
     }
     if (gB) {
-        LoraDStream& s = w.st[w.ns++];
+        LoraStream& s = w.st[w.ns++];
         s.src = a.dy; s.lds = lddy; s.out = gB; s.colmajor = 1; s.acc = accumulate ? 1 : 0; s.W = N; s.part_off = (size_t)nslab * (size_t)r * (size_t)K;
         if (h) { s.coef = (const bf16_t*)h; s.ldc = ldh; }
         else { s.coef = a.hbuf; s.ldc = r; }
         if (N > wmax) wmax = N;
     }
     a.in = w.in = lora_in_drop(in_stream, in_thr16, in_scale, rows);
-    if (in_thr16) hipLaunchKernelGGL(lora_dense_bwd_g_kernel<true>, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(lora_dense_bwd_g_kernel<false>, dim3((M + LORA_ROWS - 1) / LORA_ROWS), dim3(256), 0, stream, a);
-    MMB_CHECK_LAUNCH();
-    if (w.ns == 0) return 0;
-    w.M = M; w.r = r; w.nslab = nslab; w.s = scale; w.part = (float*)workspace;
-    const dim3 grid(nslab, w.ns, (wmax / 8 + 127) / 128);
-    const int e = in_thr16 ? lora_dense_bwd_w_launch<true>(stream, grid, w) : lora_dense_bwd_w_launch<false>(stream, grid, w);
-    if (e) return e;
-    hipLaunchKernelGGL(lora_dense_fold_kernel, dim3((unsigned)(((size_t)r * wmax / 4 + 255) / 256), w.ns), dim3(256), 0, stream, w);
-    MMB_CHECK_LAUNCH();
-    return 0;
+    const int e = in_thr16 ? lora_rows_launch<lora_dense_bwd_g_kernel<true>>(stream, a, 0) : lora_rows_launch<lora_dense_bwd_g_kernel<false>>(stream, a, 0);
+    if (e || w.ns == 0) return e;
+    w.M = M; w.r = r; w.nslab = nslab; w.col_lanes = 128; w.s = scale; w.part = (float*)workspace;
+    return in_thr16 ? lora_bwd_w_launch<true>(stream, w, wmax) : lora_bwd_w_launch<false>(stream, w, wmax);
 }
 
 int mmbert_lora_dense_bwd(hipStream_t stream, const void* dy, int lddy, const void* x, int ldx, const void* h, int ldh, int M, int K, int N, int r,
