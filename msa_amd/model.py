@@ -25,6 +25,7 @@ import os
 from typing import NamedTuple, Optional
 
 import contextlib
+import weakref
 
 import torch
 import torch.nn as nn
@@ -2239,6 +2240,37 @@ class _HeadsStepFn(torch.autograd.Function):
         a.Wat, a.bat, a.Wc1, a.bc1, a.Wc2, a.bc2 = (t.data_ptr() for t in (at.weight, at.bias, c1.weight, c1.bias, c2.weight, c2.bias))
         for m in range(3):
             a.vw[m], a.vb[m], a.Wq[m], a.bq[m] = vs3[m].weight.data_ptr(), vs3[m].bias.data_ptr(), qs[m].weight.data_ptr(), qs[m].bias.data_ptr()
+        a._top = top                                            # (a plain attribute of the record, for ``tensors``)
+
+    @staticmethod
+    def tensors(a):
+        """{field name: the tensor the record's address points at} of a train step's record, for a launch recorder (tests/step_stages.py):
+        made on demand from what _set_params / _setup / forward / backward hung onto the record -- the model, their operand tuples, weak
+        references to the tensors autograd hands on (the loss would close a reference cycle through the node's ctx; a second owner of
+        dfirst would make AccumulateGrad copy it instead of taking it).  Fields that point nowhere are left out."""
+        top = a._top
+        pool, al, sr, at = top.bert.pooler.dense, top.cls.align, top.cls.seq_relationship, top.attn
+        vs3, c1, c2 = (top.vt, top.vv, top.vs), top.classifier1_1, top.classifier1_2
+        qs = (top.cpc_zt.net, top.cpc_zv.net, top.cpc_za.net)
+        par = dict(Wp=pool.weight, bp=pool.bias, Wal=al.weight, bal=al.bias, Wsr=sr.weight, bsr=sr.bias, Wat=at.weight, bat=at.bias,
+                   Wc1=c1.weight, bc1=c1.bias, Wc2=c2.weight, bc2=c2.bias)
+        for m in range(3):
+            par.update({f"vw{m}": vs3[m].weight, f"vb{m}": vs3[m].bias, f"Wq{m}": qs[m].weight, f"bq{m}": qs[m].bias})
+        t = dict(par)
+        src, first, ap, sent, pred, cw, loss, aux, out5, logits, t_rel, rel, ws = a._fwd
+        multi = bool(a.multi_label)
+        t.update(y=None if src is None else src[0], first_rows=None if src is None else src[1], first=first if src is None else None,
+                 ap=ap[0] if isinstance(ap, tuple) else ap, ap2=ap[1] if isinstance(ap, tuple) else None,
+                 **{"multi_target" if multi else "sent_cls" if a.ncls else "sent": sent}, pred=pred, cls_weight=cw,
+                 pos_weight=getattr(top, "pos_weight", None) if multi else None, threshold=getattr(top, "thresholds", None) if multi else None,
+                 loss=loss(), aux=aux, out5=out5, logits=logits, t_rel=t_rel, rel=rel, ws=ws, mlm=getattr(a, "_mlm", None))
+        if getattr(a, "_bwd", None) is not None:
+            d1, dfirst, dmlm, scratch = a._bwd
+            dmlm = None if dmlm is None else dmlm()
+            if scratch is not None and a.dmlm == scratch.data_ptr():
+                dmlm = scratch
+            t.update(dloss=d1, dfirst=dfirst(), dmlm=dmlm, **{"g" + k: _gv(p) for k, p in par.items() if k not in ("Wsr", "bsr")})
+        return {k: v for k, v in t.items() if v is not None}
 
     @staticmethod
     def predict(top, y, B):
@@ -2333,6 +2365,7 @@ class _HeadsStepFn(torch.autograd.Function):
             a.cls_weight = cw.data_ptr()
         a.loss, a.aux, a.out5, a.logits, a.t_rel, a.rel, a.ws = (t.data_ptr() for t in (loss, aux, out5, logits, t_rel, rel, ws))
         a.sync = ops.heads_step_sync(dev).data_ptr()
+        a._fwd = (src, first, ap, sent, pred, cw, weakref.ref(loss), aux, out5, logits, t_rel, rel, ws)      # (for ``tensors``)
         return a, (loss, aux, logits, t_rel, rel), (ap, sent, ws, pred, out5)     # (the class weights are the model's buffer; only level 7 reads them)
 
     @staticmethod
@@ -2367,6 +2400,7 @@ class _HeadsStepFn(torch.autograd.Function):
         if mlm is not None:
             mlm = mlm.detach().float().contiguous()
             a.mlm, a.nmlm = mlm.data_ptr(), mlm.numel()
+            a._mlm = mlm
             keep.append(mlm)
         ops.heads_step_fwd(a, 1 if ev is None else 7, 7)
         loss, aux, logits, t_rel, rel = outs
@@ -2399,6 +2433,7 @@ class _HeadsStepFn(torch.autograd.Function):
                                                       _gv(qs[m].bias).data_ptr())
         assert _gv(at.weight).is_contiguous() and _gv(c2.weight).is_contiguous() and _gv(c2.weight).shape == c2.weight.shape
         a.sync = ops.heads_step_sync(dev).data_ptr()
+        a._bwd = (d1, weakref.ref(dfirst), None if dmlm is None else weakref.ref(dmlm), None)                 # (for ``tensors``)
         if ctx.side and dmlm is not None and getattr(top, "heads_side_stream", True):
             # round 6: the six levels on a side stream, beside the MLM head's sparse backward (which needs nothing of the heads' but the
             # gradient of its per-pass losses: one tiny launch here) -- two chains of small dependent launches that leave the chip empty,
@@ -2407,6 +2442,7 @@ class _HeadsStepFn(torch.autograd.Function):
             ops.heads_step_dmlm(a)
             scratch = torch.empty_like(dmlm)
             a.dmlm = scratch.data_ptr()                            # (level 6 writes the same values: into its own words)
+            a._bwd = a._bwd[:3] + (scratch,)
             s = ops.side_stream("heads", dev)
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):

@@ -67,8 +67,34 @@ unchanged, and one more exact check,
 weight-gradient problems written are exactly the weights whose mode is "full", the MLM transform and -- iff ``word_table`` -- the tied
 table.  Checks 3 and 6 (``_wiring``, ``check_grad_views``) assume a full backward and are not extended to it.
 
-Not covered: the fused pretraining / classification heads (``heads_step_*``) and the step prologue.  tests/test_heads_gpu.py and
-tests/test_layout_gpu.py hold them to references at the operands the model passes; the recorder takes their outputs as given inputs.
+The seam between the last encoder LayerNorm of the forward pass and the first launch of the encoder's backward is recorded too.  The
+level-launch heads take addresses in a ``_HeadsStepMl`` record: model._HeadsStepFn hangs its operand tuples onto the record as plain
+attributes (no launch, no argument changes), ``_HeadsStepFn.tensors(a)`` makes {field: tensor} of them and the recorder clones those -- before the call on the stream it is
+issued on (the side stream for the prelaunched and the backward levels), after it what the levels write -- with the record's scalar
+fields (``HEAD_SCALARS``, ``lo``, ``hi``).  A frozen head parameter's gradient view (computed and dropped: model._gv) is left out of what
+the call wrote.  The prologue's ``ret`` holds its named views and every word of the ``prologue_sizes`` extent of both buffers.
+
+    heads_step_fwd (judged once level 7 has run) / heads_step_dmlm /     heads_ref, heads_cls_ref (``ncls``), heads_multilabel_ref (``multi_label``),
+        heads_step_bwd (``heads_case``: first = the recorded rows            loss_options_ref (an option on): that reference's ``expected`` /
+        ``first_rows`` of ``y``, the recorded parameters, prior = the        ``check_all``; ``pred`` exactly
+        gradient views as the backward call found them)
+    prologue (both ``rowset`` settings, every output word)               layout_ref.prologue_ref, exact
+    active_rows / compact_rows / pack_i64                                layout_ref.active_rows_ref / compact_ref / pack_ref, exact
+
+The heads' references hold where fp32 and float64 take the same side of every kink (``heads_expected``): the ratios reached are kept in
+``call.meta["precondition"]`` and ``preconditions(calls)`` asserts them.
+
+ 8. ``check_seam`` (its docstring names every check): the heads' ``y`` / ``first_rows`` against the top layer's ``ln2`` and the layout, what
+    levels 1 - 6 wrote against what level 7 found, ``mlm`` against ``ce_fwd``'s losses, ``ce_bwd``'s ``gscale`` against ``heads_step_dmlm``, the
+    row list handed to ``compact_rows``, the heads' 22 gradient operands against the parameters' ``.grad``, every attention call's key
+    bias / ``kv_len`` and the MLM head's row list against the step's prologue, alternating prologue buffer sets -- and the [CLS] rows of
+    the output gradient the top layer's backward reads, written by an unrecorded ATen copy / ``index_add_``: ``check_seam`` states what the
+    whole matrix must hold (compact: the last MLM product's rows, then the RNE bf16 of the recorded ``dfirst``; dense: torch's bf16
+    ``index_add_`` onto what the MLM head left) and ``check_producers`` compares every row with it.  Part of ``check_dataflow`` and
+    ``check_dataflow_frozen`` (where ``check_frozen_writes`` sees the heads' writes like any other).
+
+Still not covered: the 19-launch and the eager heads (``coop_heads = False``: no recorded ``dfirst``, the [CLS] rows of the dense output
+gradient may then differ from the shadow, no other row), ``forward_fused``, the optimizer launches, ``predict*``'s heads (``heads_predict``).
 """
 from __future__ import annotations
 
@@ -91,17 +117,35 @@ from tests import rowwise_ref as R
 
 SPIED = ("gemm_nt", "gemm_nt_splitk", "gemm_tn", "gemm_tn_grouped", "attn_fwd", "attn_bwd", "attn_q_limit", "ln_fwd", "ln_bwd", "gelu_bwd",
          "embed_gather", "embed_scatter", "pair_proj_fwd", "pair_proj_bwd", "ce_fwd", "ce_bwd", "gather_rows", "scatter_rows_zero",
-         "lora_qkv_fwd", "lora_qkv_bwd", "lora_dense_fwd", "lora_dense_bwd", "colsum_grouped")
+         "lora_qkv_fwd", "lora_qkv_bwd", "lora_dense_fwd", "lora_dense_bwd", "colsum_grouped",
+         "prologue", "active_rows", "compact_rows", "pack_i64")
+# the level-launch heads: their operands are addresses in a ``_HeadsStepMl`` record; model._HeadsStepFn.tensors(a) gives the tensors behind
+# them (field name -> tensor), which is what ``heads_spy`` clones
+HEADS = ("heads_step_fwd", "heads_step_bwd", "heads_step_dmlm")
+HEAD_SCALARS = ("B", "H", "tanh_lo", "ncls", "nmlm", "alpha", "beta", "ldy", "loss_kind", "huber_delta", "label_smoothing", "multi_label")
+# record field -> parameter name (heads_ref.PARAMS / FWD_ONLY); its gradient view is the field "g" + name
+HEAD_PARAM = {"Wp": "bert.pooler.dense.weight", "bp": "bert.pooler.dense.bias", "Wal": "cls.align.weight", "bal": "cls.align.bias",
+              "Wsr": "cls.seq_relationship.weight", "bsr": "cls.seq_relationship.bias", "Wat": "attn.weight", "bat": "attn.bias",
+              "Wc1": "classifier1_1.weight", "bc1": "classifier1_1.bias", "Wc2": "classifier1_2.weight", "bc2": "classifier1_2.bias"}
+for _m, (_g, _q) in enumerate(zip(("vt", "vv", "vs"), ("cpc_zt.net", "cpc_zv.net", "cpc_za.net"))):
+    HEAD_PARAM.update({f"vw{_m}": _g + ".weight", f"vb{_m}": _g + ".bias", f"Wq{_m}": _q + ".weight", f"bq{_m}": _q + ".bias"})
+HEAD_GRADS = {"g" + k: v for k, v in HEAD_PARAM.items() if k not in ("Wsr", "bsr")}
+HEAD_FWD_FINAL = ("logits", "t_rel", "rel")                     # final after levels 1 - 6 (with the workspace's P / T views)
+HEAD_FWD_OUT = HEAD_FWD_FINAL + ("ws", "pred", "loss", "aux", "out5")
 # operands an op writes (cloned again after the call); ACCUMULATES: of those, the ones whose previous value the op reads
 WRITES = {"gemm_nt": ("out", "aux"), "gemm_nt_splitk": ("out",), "gemm_tn": ("W", "bias_out"), "gemm_tn_grouped": ("problems",),
           "attn_fwd": ("ctx", "lse"), "attn_bwd": ("dqkv",), "ln_fwd": ("out", "stats"), "ln_bwd": ("dx", "dx2", "dgamma", "dbeta", "dbias2"),
           "gelu_bwd": ("du",), "embed_gather": ("out",), "embed_scatter": ("gword", "gtype", "gpos"), "pair_proj_fwd": ("out",),
           "pair_proj_bwd": ("dW", "db"), "ce_bwd": ("dlogits",), "lora_qkv_fwd": ("qkv", "h_out"), "lora_qkv_bwd": ("gA", "gB"),
-          "lora_dense_fwd": ("y", "aux", "h_out"), "lora_dense_bwd": ("dx", "gA", "gB"), "colsum_grouped": ("problems",)}
+          "lora_dense_fwd": ("y", "aux", "h_out"), "lora_dense_bwd": ("dx", "gA", "gB"), "colsum_grouped": ("problems",),
+          "prologue": ("bufs",), "heads_step_fwd": HEAD_FWD_OUT, "heads_step_dmlm": ("dmlm",),
+          "heads_step_bwd": ("dfirst", "dmlm", "ws") + tuple(HEAD_GRADS)}
 ACCUMULATES = {"gemm_tn": ("bias_out",), "embed_scatter": ("gword", "gtype", "gpos"), "pair_proj_bwd": ("dW", "db"), "pair_proj_fwd": ("out",),
                "ln_fwd": ("out",),          # (the last two write some rows of a larger matrix: the others keep their values)
                "lora_qkv_fwd": ("qkv",), "lora_qkv_bwd": ("gA", "gB"),    # (colsum_grouped: per problem, like gemm_tn_grouped)
-               "lora_dense_fwd": ("y",), "lora_dense_bwd": ("dx", "gA", "gB")}    # (gA / gB of both adapter backwards: when ``accumulate``)
+               "lora_dense_fwd": ("y",), "lora_dense_bwd": ("dx", "gA", "gB"),    # (gA / gB of both adapter backwards: when ``accumulate``)
+               "heads_step_bwd": tuple(HEAD_GRADS) + ("ws",),   # (ws: backward reads what the forward levels left in the workspace)
+               "prologue": ("bufs",)}                            # (the persistent sets are larger than one step's extent)
 
 # ---- the op sequence of the trunk (check 1): stage names, see ``_stage``
 FWD_LAYER = ("qkv", "attn_fwd", "z1", "ln1", "g", "z2", "ln2")            # model._EncoderFn._layer_forward (z1 .. ln2: _forward_behind_attention)
@@ -210,6 +254,21 @@ def _snap(v, hold=True):
     return v
 
 
+def _snap_prologue(pro, args):
+    """What ``ops.prologue`` returned, as Recs: its named views and the WHOLE ``prologue_sizes`` extent of both buffers (``all_f`` /
+    ``all_i``: every output word, the sequence counts between ``valid`` and ``idx`` included)."""
+    from msa_amd import ops
+    lens, B, rowset = list(args["pass_lens"]), int(args["B"]), bool(args["rowset"])
+    bias_len, _ni = ops.prologue_sizes(lens, B)
+    nf, ni = ops.prologue_sizes(lens, B, rowset)
+    kb = pro.key_bias
+    all_f = torch.as_strided(kb, (nf,), (1,), kb.storage_offset() - (bias_len if rowset else 0))
+    all_i = torch.as_strided(pro.kv_len, (ni,), (1,), pro.kv_len.storage_offset())
+    out = {k: _snap(getattr(pro, k)) for k in ("key_bias", "kv_len", "valid", "idx", "words") + (("rank",) if rowset else ())}
+    out.update(all_f=_snap(all_f), all_i=_snap(all_i))
+    return out
+
+
 def _recs(v):
     if isinstance(v, Rec):
         yield v
@@ -245,7 +304,7 @@ def record(model=None):
             call.meta["stream"] = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0
             call.meta["det"] = bool(ops.deterministic()) if name == "embed_scatter" else None
             out = fn(*args, **kw)
-            call.ret = _snap(out)
+            call.ret = _snap_prologue(out, b.arguments) if name == "prologue" else _snap(out)
             for k in WRITES.get(name, ()):
                 if b.arguments.get(k) is not None and not isinstance(b.arguments[k], bool):
                     call.post[k] = _snap(b.arguments[k])
@@ -274,9 +333,34 @@ def record(model=None):
         calls.append(call)
         return out
 
+    def heads_spy(name, fn):
+        def spy(a, lo=1, hi=7 if name == "heads_step_fwd" else 6):
+            from msa_amd.model import _HeadsStepFn
+            tens = _HeadsStepFn.tensors(a)                       # (raises on a record no train step of the model made)
+            call = Call(name, {k: _snap(v) for k, v in tens.items()})
+            call.a.update({k: getattr(a, k) for k in HEAD_SCALARS}, lo=lo, hi=hi)
+            call.meta["stream"] = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0
+            call.meta["record"] = id(a)
+            # a frozen parameter's gradient is computed into its span of the flat buffer and dropped (model._gv): nothing reads it
+            call.meta["dropped"] = sorted(g for g in HEAD_GRADS if g in tens and not tens[g[1:]].requires_grad)
+            out = fn(a) if name == "heads_step_dmlm" else fn(a, lo, hi)
+            writes = [k for k in WRITES[name] if k in tens and k not in call.meta["dropped"]]
+            if name == "heads_step_fwd" and hi < 7:
+                writes = [k for k in writes if k not in ("loss", "aux", "out5")]
+            for k in writes:
+                call.post[k] = _snap(tens[k])
+            keep.append(a)
+            calls.append(call)
+            return out
+        return spy
+
+    keep = []
     for n in SPIED:
         orig[n] = getattr(ops, n)
         setattr(ops, n, wrap(n, orig[n]))
+    for n in HEADS:
+        orig[n] = getattr(ops, n)
+        setattr(ops, n, heads_spy(n, orig[n]))
     ops.LnDeferred.flush = flush
     try:
         yield calls
@@ -730,7 +814,207 @@ def _r_colsum(c):
     return res
 
 
-ADAPTERS = {"gemm_nt": _r_gemm_nt, "gemm_nt_splitk": _r_splitk, "gemm_tn": _r_gemm_tn, "gemm_tn_grouped": _r_tn_grouped, "attn_fwd": _r_attn_fwd,
+# ---- the level-launch heads: a Case of the reference the record's fields select, judged by that reference's expected / check_all
+def heads_case(c, d=1.0, prior=None):
+    """(reference module, Case, Opts or None) of a recorded heads call: ``first`` = the recorded rows ``first_rows`` of ``y`` as fp32 (or the
+    fp32 ``first`` operand), the recorded fp32 parameters, labels, MLM losses, alpha / beta; the reference by the record's fields --
+    heads_multilabel_ref (``multi_label``), loss_options_ref (an option of the label loss on), heads_cls_ref (``ncls``), else heads_ref."""
+    from tests import heads_cls_ref as HCR, heads_multilabel_ref as HML, heads_ref as HR, loss_options_ref as LOR
+    a = c.a
+    B, H, ncls = int(a["B"]), int(a["H"]), int(a["ncls"])
+    if "y" in a:
+        if int(a["ldy"]) != a["y"].stride[0]:
+            raise NotImplementedError(f"heads: ldy {a['ldy']} is not the row stride of y {a['y'].stride}")
+        first = _c(a["y"])[_c(a["first_rows"]).long()].float()
+    else:
+        first = _c(a["first"]).float()
+    assert tuple(first.shape) == (3 * B, H), f"heads: the [CLS] rows are {tuple(first.shape)}, the record says B = {B}, H = {H}"
+    params = {n: _c(a[f]).float() for f, n in HEAD_PARAM.items()}
+    if "ap2" in a:
+        ap_v, ap_s = _c(a["ap"]).reshape(-1), _c(a["ap2"]).reshape(-1)
+    else:
+        ap_v, ap_s = _c(a["ap"]).reshape(-1)[:B], _c(a["ap"]).reshape(-1)[B:]
+    mlm = _c(a["mlm"]).float() if int(a["nmlm"]) else None
+    assert mlm is None or mlm.numel() == int(a["nmlm"]), "heads: nmlm is not the size of the recorded mlm operand"
+    kw = dict(B=B, H=H, first=first, params=params, ap_v=ap_v, ap_s=ap_s, alpha=float(a["alpha"]), beta=float(a["beta"]), mlm=mlm, d=float(d),
+              prior=dict(prior or {}))
+    opt_on = bool(a["loss_kind"]) or float(a["label_smoothing"]) != 0.0 or "cls_weight" in a
+    if a["multi_label"]:
+        if a["loss_kind"] or "cls_weight" in a or not ncls:
+            raise NotImplementedError("heads: a multi-label record with a loss kind / class weights / no classes")
+        case = HML.Case(sent=None, num_labels=ncls, C=ncls, y=None, t=_c(a["multi_target"]).float().reshape(B, ncls), **kw)
+        return HML, case, HML.Opts(pos_weight=_c(a.get("pos_weight")), eps=float(a["label_smoothing"]), thr=_c(a.get("threshold")))
+    if "pos_weight" in a or "threshold" in a:
+        raise NotImplementedError("heads: pos_weight / threshold outside the multi-label head")
+    if ncls:
+        case = HCR.Case(sent=None, num_labels=ncls, C=ncls, y=_c(a["sent_cls"]).reshape(-1), **kw)
+    else:
+        case = HR.Case(sent=_c(a["sent"]).float().reshape(-1), num_labels=1 if a["tanh_lo"] else 7, **kw)
+    if opt_on:
+        if ncls and a["loss_kind"]:
+            raise NotImplementedError("heads: a loss kind on the class head")
+        o = LOR.Opts(kind=LOR.KINDS[int(a["loss_kind"])], delta=float(a["huber_delta"]) if int(a["loss_kind"]) == 2 else 1.0,
+                     eps=float(a["label_smoothing"]), weight=_c(a.get("cls_weight")))
+        return LOR, case, o
+    return (HCR if ncls else HR), case, None
+
+
+def heads_expected(c, d=1.0, prior=None):
+    """(module, expected) of a recorded heads call.  The references' bounds hold only where fp32 and float64 agree on the side of every
+    kink (relu: heads_ref.kink_ratio; the argmax: heads_cls_ref.gap_ratio; the thresholds: heads_multilabel_ref.decision_ratio; L1 /
+    Huber: loss_options_ref.loss_kink_ratio) -- conditions, not tolerances.  The ratios reached on the recorded operands are left in
+    ``call.meta["precondition"]``; every output is judged whatever they are (no element or sample is ever left out), a miss under a
+    violated condition says that it is one (``_heads_worst``), and ``preconditions(calls)`` asserts them: tests/test_step_seam_gpu.py
+    does, on inputs it chose for that; the suites that record a step at the initialisation scale judge the heads as they find them."""
+    from tests import heads_cls_ref as HCR, heads_multilabel_ref as HML, heads_ref as HR, loss_options_ref as LOR
+    mod, case, o = heads_case(c, d, prior)
+    exp = mod.expected(case) if o is None else mod.expected(case, o)
+    pre = {"kink_ratio": HR.kink_ratio(case)}
+    if mod is HML:
+        pre["decision_ratio"] = HML.decision_ratio(case, o, exp)
+    elif int(c.a["ncls"]):
+        pre["gap_ratio"] = HCR.gap_ratio(case, exp)
+    elif mod is LOR and o.kind != "mse":
+        pre["loss_kink_ratio"] = LOR.loss_kink_ratio(case, o, exp)
+    c.meta["precondition"] = pre
+    return mod, exp
+
+
+def _violated(pre):
+    from tests import heads_ref as HR
+    bad = {k: round(v, 3) for k, v in pre.items() if not v >= HR.KINK}
+    return (f"PRECONDITION of the heads' reference violated: {bad} < {HR.KINK} on the recorded [CLS] rows (fp32 and float64 may take "
+            "different sides of a kink there; the bound does not apply): choose another seed") if bad else ""
+
+
+def preconditions(calls):
+    """{condition: the smallest ratio reached} over the recomputed heads calls; raises where one is below heads_ref.KINK."""
+    pre = {}
+    for c in calls:
+        for k, v in c.meta.get("precondition", {}).items():
+            pre[k] = min(pre.get(k, math.inf), v)
+    assert not _violated(pre), _violated(pre)
+    return pre
+
+
+_HEADS_EXP = {}                                                 # record id -> (module, expected) of its backward (dmlm and the six levels)
+
+
+def _heads_worst(mod, got, exp, what, pre=None):
+    worst = {}
+    try:
+        mod.check_all(got, exp, what, worst)
+    except AssertionError as e:
+        raise AssertionError(f"{e}" + (" -- " + _violated(pre) if pre and _violated(pre) else "")) from None
+    return [(k, max(w[0], w[1])) for k, w in sorted(worst.items())] + ([("pred", 0.0)] if "pred" in got else [])
+
+
+def _r_heads_fwd(c):
+    """Forward outputs are judged once level 7 has run (a levels-1-6 call leaves them half made: ``check_seam`` holds what it wrote to the
+    level-7 recording bit for bit)."""
+    if int(c.a["hi"]) < 7:
+        return []
+    mod, exp = heads_expected(c)
+    got = {k: _c(c.post[k]) for k in ("loss", "aux", "out5") + HEAD_FWD_FINAL}
+    if "pred" in c.post:
+        got["pred"] = _c(c.post["pred"])
+    return _heads_worst(mod, got, exp, "heads_step_fwd", c.meta["precondition"])
+
+
+def _heads_bwd_exp(c):
+    key = c.meta.get("record")
+    if key not in _HEADS_EXP:
+        prior = {n: _c(c.a[g]).float() for g, n in HEAD_GRADS.items()}
+        _HEADS_EXP[key] = heads_expected(c, float(_c(c.a["dloss"]).reshape(-1)[0]), prior) + (c.meta["precondition"],)
+    c.meta["precondition"] = _HEADS_EXP[key][2]
+    return _HEADS_EXP[key][:2]
+
+
+def _r_heads_dmlm(c):
+    mod, exp = _heads_bwd_exp(c)
+    return _heads_worst(mod, {"dmlm": _c(c.post["dmlm"])}, exp, "heads_step_dmlm", c.meta.get("precondition"))
+
+
+def _r_heads_bwd(c):
+    if (int(c.a["lo"]), int(c.a["hi"])) != (1, 6):
+        raise NotImplementedError("heads_step_bwd: a partial range of levels")
+    mod, exp = _heads_bwd_exp(c)
+    _HEADS_EXP.pop(c.meta.get("record"), None)
+    got = {"dfirst": _c(c.post["dfirst"])}
+    if int(c.a["nmlm"]):
+        got["dmlm"] = _c(c.post["dmlm"])
+    got.update({n: _c(c.post[g]) for g, n in HEAD_GRADS.items() if g in c.post})
+    return _heads_worst(mod, got, exp, "heads_step_bwd", c.meta.get("precondition"))
+
+
+# ---- the prologue and the row lists: exact
+def _mask_f32(r):
+    """The fp32 value the prologue reads from a recorded mask: float64 rounds (numpy RNE), every other mask dtype converts exactly."""
+    t = _c(r)
+    return t.numpy().astype(np.float32) if t.dtype == torch.float64 else t.float().numpy()
+
+
+def prologue_words(ref, tokens, rowset):
+    """(fp32 words, int words, mask of the int words the prologue writes) of ``prologue_sizes``'s extent from layout_ref's dict."""
+    f = np.concatenate([ref["key_bias"]] + ([ref["key_bias_perm"]] if rowset else []))
+    n = len(ref["idx"])
+    idx, wrote = np.zeros(max(tokens, 1), dtype=np.int64), np.zeros(max(tokens, 1), dtype=bool)
+    idx[:n], wrote[:n] = ref["idx"], True
+    parts = [ref["kv_len"], ref["valid"], ref["seq_cnt"], idx, ref["words"]] + ([ref["rank"]] if rowset else [])
+    mask = np.concatenate([np.ones(len(p), dtype=bool) if p is not idx else wrote for p in parts])
+    return f, np.concatenate(parts).astype(np.int64), mask
+
+
+def _r_prologue(c, ref_fn=None):
+    a = c.a
+    lens, B, rowset = list(a["pass_lens"]), int(a["B"]), bool(a["rowset"])
+    segs = [(_mask_f32(m), int(p), int(o)) for m, p, o in a["segs"]]
+    labels = None if a["labels"] is None else _c(a["labels"]).numpy()
+    ref = (ref_fn or LR.prologue_ref)(segs, lens, B, labels, int(a["vocab"]), rowset)
+    want_f, want_i, mask = prologue_words(ref, B * sum(lens), rowset)
+    got_f, got_i = _c(c.ret["all_f"]).numpy(), _c(c.ret["all_i"]).numpy().astype(np.int64)
+    assert got_f.size == want_f.size and got_i.size == want_i.size, "prologue: the recorded extent is not prologue_sizes'"
+    bad = np.nonzero(LR.f32_bits(got_f) != LR.f32_bits(want_f))[0]
+    assert bad.size == 0, f"prologue: {bad.size} key-bias words differ from layout_ref.prologue_ref (first at {int(bad[0])})"
+    bad = np.nonzero((got_i != want_i) & mask)[0]
+    assert bad.size == 0, f"prologue: {bad.size} int words differ from layout_ref.prologue_ref (first at {int(bad[0])})"
+    nseq = len(lens) * B
+    for k, want in (("kv_len", ref["kv_len"]), ("valid", ref["valid"]), ("words", ref["words"])):
+        assert np.array_equal(_c(c.ret[k]).numpy().astype(np.int64), want), f"prologue: the view {k}"
+    assert np.array_equal(_c(c.ret["idx"]).numpy()[:len(ref["idx"])].astype(np.int64), ref["idx"]), "prologue: the view idx"
+    kb = ref["key_bias_perm"] if rowset else ref["key_bias"]
+    assert np.array_equal(LR.f32_bits(_c(c.ret["key_bias"]).numpy()), LR.f32_bits(kb)), "prologue: the view key_bias"
+    assert c.ret["kv_len"].shape == (nseq,)
+    return [("out", 0.0)]
+
+
+def _r_active_rows(c):
+    want = LR.active_rows_ref(_c(c.a["labels"]).reshape(-1).numpy(), int(c.a["V"]))
+    idx, cnt = _c(c.ret[0]).numpy().astype(np.int64), int(_c(c.ret[1]).reshape(-1)[0])
+    assert cnt == want.size and np.array_equal(idx[:cnt], want), "active_rows differs from layout_ref.active_rows_ref"
+    return [("out", 0.0)]
+
+
+def _r_compact_rows(c):
+    rm = c.a["row_map"]
+    want = LR.compact_ref(_c(c.a["rows"]).numpy(), _c(c.a["extra"]).numpy(), None if rm is None else _c(rm).numpy())
+    for j, r in enumerate(c.ret):
+        assert np.array_equal(_c(r).numpy().astype(np.int64), want), f"compact_rows: output {j} differs from layout_ref.compact_ref"
+    return [("out", 0.0)]
+
+
+def _r_pack_i64(c):
+    want = LR.pack_ref([s if isinstance(s, tuple) else _c(s).numpy() for s in c.a["segments"]])
+    got = _c(c.ret[0]).numpy()
+    assert got.size >= want.size and np.array_equal(got[:want.size], want), "pack_i64 differs from layout_ref.pack_ref"
+    offs = np.concatenate(([0], np.cumsum([s[0] if isinstance(s, tuple) else s.t.numel() for s in c.a["segments"]])[:-1]))
+    assert list(c.ret[1]) == [int(x) for x in offs], "pack_i64: the start offsets"
+    return [("out", 0.0)]
+
+
+ADAPTERS = {"heads_step_fwd": _r_heads_fwd, "heads_step_dmlm": _r_heads_dmlm, "heads_step_bwd": _r_heads_bwd, "prologue": _r_prologue,
+            "active_rows": _r_active_rows, "compact_rows": _r_compact_rows, "pack_i64": _r_pack_i64,
+            "gemm_nt": _r_gemm_nt, "gemm_nt_splitk": _r_splitk, "gemm_tn": _r_gemm_tn, "gemm_tn_grouped": _r_tn_grouped, "attn_fwd": _r_attn_fwd,
             "attn_bwd": _r_attn_bwd, "attn_q_limit": _r_q_limit, "ln_fwd": _r_ln_fwd, "ln_bwd": _r_ln_bwd, "ln_bwd_reduce": _r_ln_reduce,
             "gelu_bwd": _r_gelu_bwd, "ce_fwd": _r_ce_fwd, "ce_bwd": _r_ce_bwd, "embed_gather": _r_embed_gather, "embed_scatter": _r_embed_scatter,
             "pair_proj_fwd": _r_pair_fwd, "pair_proj_bwd": _r_pair_bwd, "gather_rows": _r_gather_rows, "scatter_rows_zero": _r_scatter_rows,
@@ -749,14 +1033,19 @@ def recompute(call):
         raise AssertionError(f"call {call.index} ({call.op}, stage {call.meta.get('stage')} layer {call.meta.get('layer')}): {e}") from None
 
 
-def recompute_all(calls, model=None):
+SEAM_OPS = HEADS + ("prologue", "active_rows", "compact_rows", "pack_i64")
+
+
+def recompute_all(calls, model=None, only=None):
     """Every call recomputed: {op kind: [number of calls, worst ratio]}.  ``model``: the calls are given their stage names first (a
-    failure then says which stage of which layer it was)."""
+    failure then says which stage of which layer it was).  ``only``: the op kinds to recompute (tests/test_step_seam_gpu.py: ``SEAM_OPS``
+    -- the trunk's launches of the same configurations are recomputed by tests/test_step_stages_gpu.py); the others are counted."""
     if model is not None:
         annotate(calls, model)
     out = {}
+    _HEADS_EXP.clear()
     for c in calls:
-        worst = max([float(r) for _, r in recompute(c)] + [0.0])
+        worst = max([float(r) for _, r in (recompute(c) if only is None or c.op in only else ())] + [0.0])
         n, w = out.get(c.op, (0, 0.0))
         out[c.op] = (n + 1, max(w, worst))
     return out
@@ -982,13 +1271,24 @@ class Shadow:
         k.fill_(True)
 
 
-def check_producers(calls, cls_rows=None):
-    """Check 2, see the module docstring.  One writer is no recorded launch: torch's ``index_add_`` of the heads' [CLS]-row gradients onto
-    the dense output gradient the MLM head returned (model._MLMHeadFn.backward) -- where the top layer's LayerNorm' reads that matrix
-    (stage mlm_dy -> ln2_bwd operand dy), the rows ``cls_rows`` (the first row of every sequence) may differ, no other."""
+def check_producers(calls, expect=None):
+    """Check 2, see the module docstring.  One writer is no recorded launch: the ATen copy / ``index_add_`` that puts the heads' [CLS]-row
+    gradients into the output gradient the trunk's backward reads (model._MLMHeadFn.backward, _ClsRowsFn.backward).  ``expect`` (from
+    ``check_seam``): {call index: [(the recorded operand, its expected contents or None, rows, name)]} -- before that call's operands are
+    read, the expected contents are written into the shadow, so the operand must equal them bit for bit in every row; with None for the
+    contents (a step whose heads are not the level-launch form: no recorded ``dfirst`` to expect anything from) the listed rows may
+    differ, no other."""
     sh = Shadow()
-    top = max([c.meta["layer"] for c in calls if c.meta.get("layer") is not None] + [0])
     for c in calls:
+        allow, named = {}, {}
+        for r, want, rows, name in (expect or {}).get(c.index, ()):
+            named[id(r)] = name + ": "
+            if want is None:
+                allow[id(r)] = rows
+            else:
+                v, k = sh._views(r)
+                v.copy_(_bits(want).view(v.shape))
+                k.fill_(True)
         pure = set(WRITES.get(c.op, ())) - set(ACCUMULATES.get(c.op, ()))
         for k, v in c.a.items():
             if c.op == "gemm_tn_grouped" and k == "problems":
@@ -1009,13 +1309,247 @@ def check_producers(calls, cls_rows=None):
                 continue
             if k in pure:
                 continue
-            allow = cls_rows if (c.meta.get("stage") == "ln2_bwd" and c.meta.get("layer") == top and k == "dy" and c.a.get("dy_rows") is None
-                                 and cls_rows is not None and c.a["dy"].shape[0] > int(cls_rows.max())) else None
             for r in _recs(v):
-                sh.read(r, f"call {c.index} ({c.op}, {c.meta.get('stage')}) operand {k}", allow)
+                sh.read(r, f"{named.get(id(r), '')}call {c.index} ({c.op}, {c.meta.get('stage')}) operand {k}", allow.get(id(r)))
         for r in list(_recs(list(c.post.values()))) + list(_recs(c.ret)):
             if r.sbytes:
                 sh.write(r)
+
+
+def bf16_rne(t):
+    """fp32 -> bf16, round to nearest even, by integer arithmetic on the bit patterns (layout_ref.bf16_rne)."""
+    b = LR.bf16_rne(LR.f32_bits(t.detach().cpu().float().contiguous().numpy()))
+    return torch.from_numpy(b.view(np.int16).copy()).view(torch.bfloat16).reshape(t.shape)
+
+
+def _eq(x, y):
+    x, y = _c(x), _c(y)
+    return x.shape == y.shape and x.dtype == y.dtype and torch.equal(_bits(x), _bits(y))
+
+
+def _view_of(r: Rec, whole: Rec):
+    """The recorded contents of ``whole`` at the elements the contiguous 1-D view ``r`` covers, or None where ``r`` is no such view."""
+    lo = r.off - whole.off
+    if r.sptr != whole.sptr or r.dtype != whole.dtype or lo < 0 or lo + r.t.numel() > whole.t.numel() or r.stride not in ((1,), ()):
+        return None
+    return whole.cpu().reshape(-1)[lo:lo + r.t.numel()]
+
+
+def _ws_views(ws, B, H):
+    """(P, T) of a recorded heads workspace (ops.heads_step_outputs: the library's own offsets), or None where the library is not there."""
+    try:
+        from msa_amd import ops
+        return ops.heads_step_outputs(_c(ws), B, H)
+    except Exception:
+        return None
+
+
+def check_seam(calls, model=None):
+    """The hand-overs between the last encoder LayerNorm of the forward pass and the first launch of the encoder's backward, exact, on
+    annotated calls.  Every check carries its name in its failure message:
+
+      prologue consumers   every attn_fwd / attn_bwd key bias is a view of the step's prologue output and bit-equal to it, ``kv_len`` (an
+                           unsplit layout's) likewise; the MLM head's gather index is a view of the prologue's ``idx``, of its host count
+      alternating buffers  two consecutive prologue calls handed persistent buffers use different sets (a step's backward is held to the
+                           set its own forward wrote by "prologue consumers": the next prologue comes after it)
+      heads y              the heads' ``y`` is the region the top layer's ``ln2`` wrote, bit-equal to what it left
+      heads first_rows     ``first_rows`` is the first row of every sequence of the recorded layout, pass by pass
+      heads forward finals what levels 1 - 6 wrote (logits, t_rel, rel, the workspace's P / T) is what level 7 found and left
+      mlm losses           level 7's ``mlm`` is bit-equal to the per-pass losses ``ce_fwd`` returned, in pass order
+      dmlm twice           ``heads_step_dmlm``'s words and the scratch copy level 6 writes are bit-equal
+      gscale               ``ce_bwd``'s ``gscale`` is bit-equal to what ``heads_step_dmlm`` wrote (without it: to level 6's ``dmlm``)
+      compact row list     ``compact_rows`` is handed the prologue's labelled rows (its host count of them) and ``first_rows``
+      label-only step      a step whose heads carry no MLM loss records no MLM-head op, and its row list is empty plus ``first_rows``
+      heads gradient views each of the 22 gradient operands of ``heads_step_bwd`` is the ``.grad`` of the parameter named for it
+      compact hand-over    (through ``check_producers``) the matrix the top layer's backward reads: rows [:n] the last MLM ``gemm_nt``
+                           output, rows [n:] the round-to-nearest-even bf16 of the recorded ``dfirst`` in ``first_rows`` order
+      dense hand-over      (likewise) the rows ``first_rows`` equal torch's own bf16 ``index_add_`` of bf16(dfirst) onto the matrix the MLM
+                           head left (its dense product, or zeros with the labelled rows copied in), every other row is untouched
+
+    Returns (``expect`` for ``check_producers``, {check name: times it ran})."""
+    top = max([c.meta["layer"] for c in calls if c.meta.get("layer") is not None] + [0])
+    params = dict(model.named_parameters()) if hasattr(model, "named_parameters") else None
+    views = getattr(model, "head_grad_views", None)
+    expect, ran = {}, {}
+    st = {}
+
+    def tick(k):
+        ran[k] = ran.get(k, 0) + 1
+
+    def fresh(pro):
+        return dict(pro=pro, lens=None, lay=None, ln2=None, ce_f=None, heads={}, h7=None, dm=None, hb=None, mlm_dy=None, cr=None, mlm_ops=[], gathered={})
+    st = fresh(None)
+    prev_pro = None
+    for c in calls:
+        stage, l = c.meta.get("stage"), c.meta.get("layer")
+        w = f"call {c.index} ({c.op}, {stage})"
+        if c.op == "prologue":
+            if prev_pro is not None and prev_pro.a["bufs"] is not None and c.a["bufs"] is not None:
+                same = [x.sptr == y.sptr for x, y in zip(prev_pro.a["bufs"], c.a["bufs"])]
+                assert not any(same), f"alternating buffers: {w} writes the buffer set of the previous step's prologue (call {prev_pro.index})"
+                tick("alternating buffers")
+            st, prev_pro = fresh(c), c
+            continue
+        if c.op in ("attn_fwd", "attn_bwd"):
+            st["lens"], st["lay"] = list(c.a["layout"].lens), c.a["layout"]
+            pro = st["pro"]
+            if pro is not None:
+                got = _view_of(c.a["key_bias"], pro.ret["all_f"])
+                assert got is not None, f"prologue consumers: {w}: key_bias is no view of the output of this step's prologue (call {pro.index})"
+                assert _eq(got, _c(c.a["key_bias"]).reshape(-1)), f"prologue consumers: {w}: key_bias differs from what the prologue wrote"
+                kv = None if c.a["layout"].split else c.a.get("kv_len")
+                if kv is not None:
+                    got = _view_of(kv, pro.ret["all_i"])
+                    assert got is not None and kv.off == pro.ret["kv_len"].off, f"prologue consumers: {w}: kv_len is not the prologue's kv_len view"
+                    assert _eq(got, _c(kv).reshape(-1)) and _eq(_c(kv), _c(pro.ret["kv_len"])), f"prologue consumers: {w}: kv_len differs from what the prologue wrote"
+                tick("prologue consumers")
+        if stage == "ln2" and l == top:
+            st["ln2"] = c
+        if stage in ("mlm_t0", "logits", "mlm_dt", "mlm_dy", "mlm_ln", "mlm_ln_bwd") or c.op in ("ce_fwd", "ce_bwd", "gelu_bwd"):
+            st["mlm_ops"].append(c)
+        if c.op == "ce_fwd":
+            st["ce_f"] = c
+        if c.op == "active_rows":
+            st["ar"] = c
+        if stage == "mlm_dy":
+            st["mlm_dy"] = c
+        if c.op == "gather_rows":
+            for s, o in zip(c.a["srcs"], c.ret):
+                st["gathered"][o.region()] = (c, s)
+            if len(c.a["srcs"]) == 6 and st["pro"] is not None:       # the MLM head's gather of its labelled rows
+                pro, ar = st["pro"], st.get("ar")                    # (a caller without the prologue's list: ops.active_rows made one)
+                n = int(_c(pro.ret["words"])[len(_c(pro.ret["kv_len"]))])
+                whole = pro.ret["idx"] if ar is None else ar.ret[0]
+                got = _view_of(c.a["idx32"], whole)
+                assert got is not None and c.a["idx32"].off == whole.off, f"prologue consumers: {w}: the gather index is no prefix view of the prologue's idx"
+                assert c.a["idx32"].t.numel() == n, f"prologue consumers: {w}: {c.a['idx32'].t.numel()} gathered rows, the prologue's host word says {n}"
+                assert _eq(got, _c(c.a["idx32"])), f"prologue consumers: {w}: the gather index differs from the prologue's idx"
+                tick("prologue consumers")
+        if c.op == "heads_step_fwd":
+            a, rec = c.a, c.meta.get("record")
+            if "y" in a:
+                ln2 = st["ln2"]
+                assert ln2 is not None, f"heads y: {w}: no ln2 of the top layer was recorded in front of the heads"
+                out = ln2.ret[0]
+                lay = st.get("lay")
+                if a["y"].sptr != out.sptr and lay is not None and lay.split and lay.inv is not None:
+                    # (the inference packing: the encoder's output is gathered back into the caller's row order by torch, no recorded launch)
+                    want = _unpacked(_c(out), _c(lay.inv).long(), sum(lay.lens))
+                    assert _eq(a["y"], want), f"heads y: {w}: y is not the top layer's ln2 output in the caller's row order"
+                else:
+                    assert a["y"].region() == out.region() and a["y"].shape == out.shape, f"heads y: {w}: y is not the region the top layer's ln2 wrote"
+                    assert _eq(a["y"], out), f"heads y: {w}: y differs from what the top layer's ln2 left"
+                tick("heads y")
+                assert st["lens"] is not None, f"heads first_rows: {w}: no attention layout recorded"
+                want = torch.tensor([0] + st["lens"][:-1]).cumsum(0)
+                fr = _c(a["first_rows"]).reshape(-1).long()
+                assert fr.numel() == want.numel() == 3 * int(a["B"]) and torch.equal(fr, want), \
+                    f"heads first_rows: {w}: {fr.tolist()} is not the first row of every sequence {want.tolist()}"
+                tick("heads first_rows")
+            if int(a["lo"]) > 1:
+                prev = st["heads"].get(rec)
+                assert prev is not None and int(prev.a["hi"]) == int(a["lo"]) - 1, f"heads forward finals: {w}: levels from {a['lo']} without the levels below"
+                for k in HEAD_FWD_FINAL:
+                    assert _eq(prev.post[k], a[k]) and _eq(a[k], c.post[k]), f"heads forward finals: {w}: {k} changed behind levels 1 - {prev.a['hi']}"
+                have_ws = "ws" in prev.post and "ws" in a and "ws" in c.post
+                v0, v1, v2 = (_ws_views(x, int(a["B"]), int(a["H"])) for x in (prev.post["ws"], a["ws"], c.post["ws"])) if have_ws else (None,) * 3
+                if v0 is not None:
+                    for k, x, y, z in zip("PT", v0, v1, v2):
+                        assert _eq(x, y) and _eq(y, z), f"heads forward finals: {w}: the workspace's {k} changed behind levels 1 - {prev.a['hi']}"
+                tick("heads forward finals")
+            if int(a["hi"]) == 7:
+                st["h7"] = c
+                if int(a["nmlm"]):
+                    ce = st["ce_f"]
+                    assert ce is not None, f"mlm losses: {w}: nmlm = {a['nmlm']} and no ce_fwd recorded in this step"
+                    assert _eq(_c(a["mlm"]).reshape(-1), _c(ce.ret[0]).float().reshape(-1)[:int(a["nmlm"])]) and int(a["nmlm"]) == int(ce.a["nseg"]), \
+                        f"mlm losses: {w}: mlm {_c(a['mlm']).tolist()} is not what ce_fwd returned, in pass order {_c(ce.ret[0]).tolist()}"
+                    tick("mlm losses")
+            st["heads"][rec] = c
+        if c.op == "heads_step_dmlm":
+            st["dm"] = c
+        if c.op == "heads_step_bwd":
+            st["hb"] = c
+            if st["dm"] is not None:
+                assert st["dm"].meta.get("record") == c.meta.get("record") and _eq(st["dm"].post["dmlm"], c.post["dmlm"]), \
+                    f"dmlm twice: {w}: level 6's scratch copy differs from what heads_step_dmlm wrote"
+                tick("dmlm twice")
+            have = params is not None or views is not None
+            for g, n in HEAD_GRADS.items() if have else ():
+                if g in c.meta.get("dropped", ()):
+                    continue
+                v = params[n].grad if params is not None else views[n]
+                assert v is not None and g in c.a and c.a[g].ptr == v.data_ptr() and c.a[g].shape == tuple(v.shape), \
+                    f"heads gradient views: {w}: {g} is not the .grad view of {n}"
+            if have:
+                tick("heads gradient views")
+        if c.op == "ce_bwd":
+            src = st["dm"] if st["dm"] is not None else st["hb"]
+            if src is not None:
+                assert _eq(_c(c.a["gscale"]).reshape(-1), _c(src.post["dmlm"]).reshape(-1)), \
+                    f"gscale: {w}: gscale {_c(c.a['gscale']).tolist()} is not what {src.op} (call {src.index}) wrote {_c(src.post['dmlm']).tolist()}"
+                tick("gscale")
+        if c.op == "compact_rows":
+            st["cr"] = c
+            hb, pro = st["hb"], st["pro"]
+            if hb is not None and "first_rows" in hb.a:
+                assert torch.equal(_c(c.a["extra"]).long(), _c(hb.a["first_rows"]).long()), f"compact row list: {w}: the extra rows are not the heads' first_rows"
+                if pro is not None and st.get("ar") is None:
+                    n = int(_c(pro.ret["words"])[len(_c(pro.ret["kv_len"]))])
+                    assert torch.equal(_c(c.a["rows"]).long(), _c(pro.ret["idx"]).long()[:n]), \
+                        f"compact row list: {w}: the labelled rows are not the prologue's idx[:{n}] (its host count)"
+                tick("compact row list")
+        if stage == "ln2_bwd" and l == top:
+            _handover(c, st, expect, tick, w)
+        if c.op == "heads_step_bwd" and not int(c.a["nmlm"]):
+            assert not st["mlm_ops"], f"label-only step: {w}: no MLM loss, yet the step recorded {[x.op for x in st['mlm_ops']]}"
+            tick("label-only step")
+    return expect, ran
+
+
+def _handover(c, st, expect, tick, w):
+    """The output gradient the top layer's backward reads (its ``ln2_bwd``'s ``dy``, or the source of the gather in front of it): what
+    ``check_seam`` expects of it, left in ``expect`` for ``check_producers``."""
+    dy = c.a["dy"]
+    user, m = c, dy
+    if dy.region() in st["gathered"] and len(st["gathered"][dy.region()][0].a["srcs"]) == 1:
+        user, m = st["gathered"][dy.region()]
+    hb, cr, last = st["hb"], st["cr"], st["mlm_dy"]
+    lens = st["lens"] or []
+    cls_rows = torch.tensor([0] + lens[:-1]).cumsum(0) if lens else None
+    if hb is None:                                               # the 19-launch / eager heads: no recorded dfirst to expect anything from
+        if cr is None and cls_rows is not None and c.a.get("dy_rows") is None:
+            expect.setdefault(user.index, []).append((m, None, cls_rows[cls_rows < m.shape[0]], "dense hand-over (heads not recorded)"))
+        return
+    df = bf16_rne(_c(hb.post["dfirst"]))
+    fr = _c(hb.a["first_rows"]).long() if "first_rows" in hb.a else cls_rows
+    if cr is not None and cr.index > hb.index:                   # compact: labelled rows ‖ first_rows
+        n, nf = cr.a["rows"].t.numel(), cr.a["extra"].t.numel()
+        assert m is dy and dy.shape[0] == n + nf, f"compact hand-over: {w}: dy has {dy.shape[0]} rows, the row list {n} + {nf}"
+        assert df.shape[0] == nf, f"compact hand-over: {w}: {df.shape[0]} rows of dfirst for {nf} [CLS] rows"
+        if n:
+            assert last is not None and last.ret.ptr == dy.ptr and last.ret.shape[0] == n, f"compact hand-over: {w}: rows [:{n}] are not the last MLM gemm_nt's output"
+            want = torch.cat((_c(last.ret), df))
+        else:
+            assert not st["mlm_ops"], f"label-only step: {w}: an empty labelled-row list, yet the step recorded {[x.op for x in st['mlm_ops']]}"
+            want = df
+        expect.setdefault(user.index, []).append((m, want, None, "compact hand-over"))
+        tick("compact hand-over")
+        return
+    rows = sum(lens)
+    if last is not None and last.ret.sptr == m.sptr:             # the MLM head's dense product, the [CLS] rows added in place
+        base = _c(last.ret).clone()
+    else:                                                        # zeros, the labelled rows' gradients copied in (none on a label-only step)
+        base = torch.zeros((rows, m.shape[1]), dtype=torch.bfloat16)
+        if last is not None:
+            pro = st["pro"]
+            assert pro is not None, f"dense hand-over: {w}: no prologue recorded to take the labelled rows from"
+            n = int(_c(pro.ret["words"])[len(_c(pro.ret["kv_len"]))])
+            assert last.ret.shape[0] >= n, f"dense hand-over: {w}: {last.ret.shape[0]} rows from the MLM head for {n} labelled rows"
+            base[_c(pro.ret["idx"]).long()[:n]] = _c(last.ret)[:n]
+    base.index_add_(0, fr, df)                                   # torch's own bf16 index_add_ (one rounding of the sum per element)
+    expect.setdefault(user.index, []).append((m, base[:m.shape[0]], None, "dense hand-over"))
+    tick("dense hand-over")
 
 
 def _same(x: Rec, y: Rec, what):
@@ -1227,9 +1761,13 @@ def check_grad_views(calls, names, model):
         for k, pn in _PARAM_OF.items():
             g = params[f"bert.encoder.layer.{i}.{pn}"].grad
             assert g is not None and g.data_ptr() == lw["g_" + k].data_ptr(), f"l{i}.g_{k} is not the .grad of {pn}"
+    label_only = not any(c.op == "ce_fwd" for c in calls)         # (a label-only step: its backward does not reach the MLM-only parameters)
     for k, pn in _PARAM_OF_W.items():
         if "g_" + k in model._w:
             g = params[pn].grad
+            if label_only and k in ("pred_bias", "bt", "mlm_ln_g", "mlm_ln_b", "Wt"):
+                assert g is None, f"a label-only step left a gradient on the MLM-only parameter {pn}"
+                continue
             assert g is not None and g.data_ptr() == model._w["g_" + k].data_ptr(), f"g_{k} is not the .grad of {pn}"
 
 
@@ -1330,8 +1868,8 @@ def check_dataflow(calls, model):
             n += 1
         c.meta["pass"] = n
     passes = check_sequence(calls, L)
-    lens = next((c.a["layout"].lens for c in calls if c.op == "attn_fwd"), None)
-    check_producers(calls, None if lens is None else torch.tensor([0] + lens[:-1]).cumsum(0))
+    expect, _ran = check_seam(calls, model)
+    check_producers(calls, expect)
     _wiring(calls, names, L)
     check_kv_len(calls)
     check_transposes(calls, names, model)
@@ -1406,8 +1944,8 @@ def check_dataflow_frozen(calls, model, plan, lora=None, backward=True):
         c.meta["pass"] = n
     stop = 0 if plan is None else plan.stop
     passes = check_sequence(calls, L, stop, plan is not None and not plan.embedding_stage, lora or (), backward)
-    lens = next((c.a["layout"].lens for c in calls if c.op == "attn_fwd"), None)
-    check_producers(calls, None if lens is None else torch.tensor([0] + lens[:-1]).cumsum(0))
+    expect, _ran = check_seam(calls, model)
+    check_producers(calls, expect)
     check_kv_len(calls)
     check_transposes(calls, names, model)
     sites = check_dropout_sites(calls)

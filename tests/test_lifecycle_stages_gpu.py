@@ -83,10 +83,13 @@ NO_PLAN = ("iii_adapters_on_the_top_layer", "vi_dense_only_dense_top_layer", "vi
 NO_ADAPTERS = ("i_bias_only_top_layer", "iv_behind_a_merge", "x_behind_a_merge_of_all_linear")
 
 
-def expected(plan, lora, L, backward=True, forwards=1):
+def expected(plan, lora, L, backward=True, forwards=1, sparse_top=True):
     """The launch counts the plan (None: nothing frozen) and the adapter record (None: no adapters) decide, for one forward + backward
     (``backward`` False: ``forwards`` forward passes alone): one Q/K/V adapter launch per adapted layer (when a Q/K/V target is there), one dense adapter
-    launch per dense target and adapted layer -- backward on the adapted layers at or above ``stop``."""
+    launch per dense target and adapted layer -- backward on the adapted layers at or above ``stop``.  The seam: one prologue per forward
+    pass, one ``pack_i64`` per model forward, the heads' forward in two calls (levels 1 - 6 prelaunched on the side stream, level 7), with
+    a backward ``heads_step_dmlm`` + ``heads_step_bwd`` and -- where the top layer runs its sparse backward -- one ``compact_rows``; the eval
+    case's ``predict_tokens`` makes its own labelled-row list (``active_rows``)."""
     stop = 0 if plan is None else plan.stop
     emb = plan is None or plan.embedding_stage
     layers = () if lora is None else lora["layers"]
@@ -99,9 +102,12 @@ def expected(plan, lora, L, backward=True, forwards=1):
         colsum += 1 if (not plan.word_table and "cls.predictions.bias" not in plan.frozen) else 0
     want = {"attn_fwd": forwards * L, "attn_bwd": max(0, L - stop), "lora_qkv_fwd": forwards * qkv * len(layers), "lora_qkv_bwd": qkv * above,
             "lora_dense_fwd": forwards * dense * len(layers), "lora_dense_bwd": dense * above,
-            "colsum_grouped": colsum, "embed_scatter": 1 if emb else 0, "pair_proj_bwd": 2 if emb else 0}
+            "colsum_grouped": colsum, "embed_scatter": 1 if emb else 0, "pair_proj_bwd": 2 if emb else 0,
+            "prologue": forwards, "pack_i64": 1, "heads_step_fwd": 2, "heads_step_dmlm": 1, "heads_step_bwd": 1,
+            "compact_rows": 1 if stop < L and sparse_top else 0, "active_rows": 0 if backward else 1}
     if not backward:
-        want.update({k: 0 for k in ("attn_bwd", "lora_qkv_bwd", "lora_dense_bwd", "colsum_grouped", "embed_scatter", "pair_proj_bwd")})
+        want.update({k: 0 for k in ("attn_bwd", "lora_qkv_bwd", "lora_dense_bwd", "colsum_grouped", "embed_scatter", "pair_proj_bwd",
+                                    "heads_step_dmlm", "heads_step_bwd", "compact_rows")})
     return want
 
 
@@ -159,7 +165,7 @@ def test_every_launch_of_a_frozen_or_adapter_step_is_within_its_reference_bound(
     assert (writes > 0) == backward
     folded = [id(x) for c in calls if c.op == "ln_bwd_reduce" for x in c.meta["calls"]]
     assert sorted(folded) == sorted(id(c) for c in calls if c.op == "ln_bwd"), "a LayerNorm' call folded twice or never"
-    want = expected(plan, lora, L, backward, forwards)
+    want = expected(plan, lora, L, backward, forwards, getattr(m, "sparse_top_layer_backward", True))
     got = {k: per.get(k, (0, 0.0))[0] for k in want}
     assert got == want, (case, cfg, got, want)
     # the arguments the model passes: no residual gradient where backward ends, accumulation onto what the optimizer left -- which is

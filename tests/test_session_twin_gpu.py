@@ -253,7 +253,7 @@ def _counts(L, cfg, item):
         c["gemm_nt"] += 1
         c["gemm_nt_splitk"] -= 1
         c["gather_rows"] -= 1
-        del c["scatter_rows_zero"], c["attn_q_limit"]
+        del c["scatter_rows_zero"], c["attn_q_limit"], c["compact_rows"]
     return c, dense_top
 
 

@@ -45,7 +45,7 @@ def _step(m, batch):
     return out
 
 
-def expected_counts(L, shortcuts, steps=1):
+def expected_counts(L, shortcuts, steps=1, side=True):
     """Launches per op kind of one forward + backward, from the model's structure (msa_amd/model.py): three passes, two of them joint
     (one pair projection each); per layer 4 + 4 NT GEMMs, 2 + 2 LayerNorms, attention forward and backward; the MLM head 2 + 2 NT GEMMs
     (the dense one: 3 + 2; the sparse one takes split-K for the vocabulary product), its LayerNorm and GELU'; the embedding LayerNorm in
@@ -54,14 +54,20 @@ def expected_counts(L, shortcuts, steps=1):
     back and asks for the query limit; the MLM head gathers its labelled rows; ALL weight gradients go out in one grouped call (the
     deferred dense ones, the top layer's, the MLM head's two).  Off: one grouped call per layer pair, the MLM head's two through gemm_tn.
     The deferred LayerNorm reduce is not counted here: its workspace grows with the first calls, each growth folds what it holds;
-    ``_judge`` asserts that every LayerNorm' call is folded exactly once."""
+    ``_judge`` asserts that every LayerNorm' call is folded exactly once.
+    The seam: one prologue call and one ``pack_i64`` (ids | token types | labels) per forward; the level-launch heads' forward in two
+    calls with ``heads_side_stream`` (``side``: levels 1 - 6 prelaunched, level 7 behind the MLM head) and in one without, their backward
+    in one call, in front of it ``heads_step_dmlm`` when the six levels go to the side stream; the sparse top layer builds its row list
+    with one ``compact_rows``.  ``active_rows`` does not run: the labelled-row list is the prologue's."""
     on = shortcuts
     c = {"embed_gather": 1, "embed_scatter": 1, "pair_proj_fwd": 2, "pair_proj_bwd": 2, "ce_fwd": 1, "ce_bwd": 1, "gelu_bwd": 1,
          "attn_fwd": L, "attn_bwd": L,
          "ln_fwd": 2 * L + 1 + 2 + 2, "ln_bwd": 2 * L + 1 + 2 + 2,
          "gemm_nt": 8 * L + 2 + (1 if on else 2) - (1 if on else 0), "gemm_nt_splitk": 2 if on else 0,
          "gather_rows": 2 if on else 0, "scatter_rows_zero": 1 if on else 0, "attn_q_limit": 1 if on else 0,
-         "gemm_tn": 0 if on else 2}
+         "gemm_tn": 0 if on else 2,
+         "prologue": 1, "pack_i64": 1, "compact_rows": 1 if on else 0,
+         "heads_step_fwd": 2 if side else 1, "heads_step_dmlm": 1 if side else 0, "heads_step_bwd": 1}
     c["gemm_tn_grouped"] = 1 if on else (L + 1) // 2
     return {k: v * steps for k, v in c.items() if v}
 
@@ -79,6 +85,10 @@ def _judge(calls, m, case, L, shortcuts, steps=1):
     assert len(tied) == steps, tied
     _PARITY[case] = {k: dict(calls=n, worst_ratio=w) for k, (n, w) in sorted(per.items())}
     _PARITY[case]["tied_word_gradient_both_producers"] = dict(calls=steps, worst_ratio=max(tied))
+    # (the heads' references' preconditions as this step met them, at the initialisation scale: a record -- tests/test_step_seam_gpu.py
+    # chooses inputs that meet them and asserts them)
+    _PARITY[case]["heads_preconditions"] = {k: min(c.meta["precondition"][k] for c in calls if k in c.meta.get("precondition", {}))
+                                            for k in sorted({k for c in calls for k in c.meta.get("precondition", {})})}
     _report("step_stage_parity", _PARITY)
     return per, sites
 
