@@ -125,7 +125,7 @@ int mmbert_mlm_mask(mmbert_stream_t stream, int64_t* ids, int64_t* labels, size_
  * fwd: y[out_rows[i]] = dropout(LN(x[in_rows[i]]))              BertEmbeddings HF:104-107,
  *      JointEmbeddings REF:MMBertEmbedding.py:69-70, BertSelfOutput/BertOutput LN HF:292,350.  The dropout mask of row i is the
  *      one of row i + drop_row0 of the dropout site (a launch over a slice of the rows the site covers).
- * bwd: see rowwise.hip; dx2 = dx * (pre-LN branch dropout mask) feeds the dense layer's gradients.  The dropout masks are
+ * bwd: see layernorm.hip; dx2 = dx * (pre-LN branch dropout mask) feeds the dense layer's gradients.  The dropout masks are
  *      functions of (row, column): drop_rows[i] (may be null: i) names the row of the forward pass that compact row i stands for. */
 int mmbert_ln_fwd(mmbert_stream_t stream, const void* x, int ldx, const int* in_rows, void* y, int ldy, const int* out_rows,
                   int M, int H, const float* gamma, const float* beta, float eps, float* mean, float* rstd,

@@ -19,6 +19,7 @@
 // rounded up to 4 (elem_base multiples of 4), so forward and both backward kernels agree.
 #include <cstdlib>
 #include "common.h"
+#include "../../include/mmbert_hip.h"
 #include <type_traits>
 
 #define LOG2E 1.4426950408889634f

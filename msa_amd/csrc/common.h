@@ -50,6 +50,16 @@ static inline int mmb_device_cus() {
     return c;
 }
 
+// workgroups for work_items at per_block each, at most cap
+static inline int grid_for(size_t work_items, int per_block, int cap = 2048) {
+    size_t b = (work_items + per_block - 1) / per_block;
+    if (b < 1) b = 1;
+    return (int)(b > (size_t)cap ? cap : b);
+}
+
+// LayerNorm row width in 256-column chunks (layernorm.hip; mmbert_embed_scatter holds its rows to the same limit)
+#define LN_MAXV 4   // 4 chunks x 64 lanes x 4 elements = 1024 columns max
+
 // mmbert_set_deterministic (rowwise.hip defines the flag; one .so): 1 = every fp32 sum of the library is formed in an order that does not
 // depend on how workgroups are scheduled -- slabs + ordered reduces (or a single adder per address) instead of fp32 atomics whose arrival
 // order varies: the CE loss sums, the heads' skinny products, the weight-gradient kernel's bias sums (no token split), the LayerNorm

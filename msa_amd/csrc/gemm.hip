@@ -14,6 +14,7 @@
 // Operands are staged global -> LDS with 16-byte LDS-DMA (lane-linear writes: the XOR swizzle is applied on the per-lane SOURCE address
 // and again on the LDS read); tile ids are remapped so that each XCD (private L2) works on a contiguous band of the tile walk.
 #include "common.h"
+#include "../../include/mmbert_hip.h"
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>

@@ -13,6 +13,7 @@
 //   nce = sum_m mean_b ( logsumexp_b' <Xn[m,b], XPn[m,b']> - <Xn[m,b], XPn[m,b]> ),  Xn = P/|P|, XPn = XP/|XP|
 //   heads_loss = ap_loss + label_loss - beta * nce                               heads_loss_fwd (+ the backward seeds)
 #include "common.h"
+#include "../../include/mmbert_hip.h"
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {      // 256 threads; red: 4 floats of LDS
     v = wave_sum(v);
@@ -593,11 +594,6 @@ int mmbert_heads_tanh_bwd(hipStream_t stream, const float* dP, const float* P, f
     MMB_CHECK_LAUNCH();
     return 0;
 }
-
-// see include/mmbert_hip.h for the two op structs (mirrored here field by field)
-struct mmbert_skinny_src { const float* X; const float* W; int ldx, ldw, inner, row0, rows, w_inner_major; };
-struct mmbert_skinny_op { float* Y; const float* bias; int ldy, M, N, nsrc, act, accumulate; mmbert_skinny_src src[4]; };
-struct mmbert_skinny_wgrad_op { const float* dY; const float* X; float* dW; float* db; int ldy, ldx, ldw, M, N, K; };
 
 static int skinny_mm_args(int nops, const mmbert_skinny_op* ops, SkArgs& a, int& tiles, long long& elems) {
     if (nops > SK_MAXOPS) return -1;

@@ -1,4 +1,4 @@
-"""A float64 reference for the LayerNorm and cross-entropy kernels (csrc/rowwise.hip) and a scale-aware check of their outputs.
+"""A float64 reference for the LayerNorm and cross-entropy kernels (csrc/layernorm.hip, csrc/rowwise.hip) and a scale-aware check of their outputs.
 
 Not a test module (pytest does not collect it): ``from tests import rowwise_ref as R``.
 
@@ -86,12 +86,12 @@ TAU_OUT, TAU_ACC = 0.8, 0.25
 U_BF16, U_F32 = 2.0 ** -8, 2.0 ** -23
 EPS24 = 2.0 ** -24
 
-LN_MAXV = 4                  # csrc/rowwise.hip: 4 chunks x 256 columns
+LN_MAXV = 4                  # csrc/common.h: 4 chunks x 256 columns
 CE_MAXC = 16                 # csrc/rowwise.hip: register chunks of ce_row_kernel (16 x 256 threads x 8 columns)
 IGNORE = -100
 
 
-# ------------------------------------------------------------------------------------------------ launch geometry (csrc/rowwise.hip)
+# ------------------------------------------------------------------------------------------------ launch geometry (csrc/layernorm.hip, csrc/rowwise.hip)
 def grid_for(work, per_block, cap):
     return max(1, min(cap, (work + per_block - 1) // per_block))
 

@@ -1,4 +1,4 @@
-"""The LayerNorm and cross-entropy kernels (csrc/rowwise.hip) against the float64 reference of tests/rowwise_ref.py through
+"""The LayerNorm and cross-entropy kernels (csrc/layernorm.hip, csrc/rowwise.hip) against the float64 reference of tests/rowwise_ref.py through
 ``rowwise_ref.check``, run through the C ABI (msa_amd.ops): every LayerNorm width and both eps at the trip edges of the lean and
 generic kernels, every reachable lean backward template, row maps and drop_row0 over several trips, the immediate, deferred and
 ordered gamma / beta reduces; the cross-entropy at the model's vocabulary (V = 30 522, ldv = 30 592) with bf16 and fp32 logits,

@@ -3,16 +3,17 @@
 The stamp tools (stamp_attn.py) load THAT file; the product build (msa_amd/build.py) refuses every -DMMB_* define."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from msa_amd.build import CSRC, FLAGS, HIPCC, SOURCES  # noqa: E402
 OUT = os.path.join(ROOT, "tools", "_stamp")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffast-math", "-fno-finite-math-only", "-DMMB_STAMPS"]
 os.makedirs(OUT, exist_ok=True)
 procs, objs = [], []
-for f in ("gemm", "attention", "rowwise", "heads", "heads_coop", "layer"):
-    o = os.path.join(OUT, f + "_stamps.o")
+for s in SOURCES:
+    o = os.path.join(OUT, s.replace(".hip", "_stamps.o"))
     objs.append(o)
-    procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", *FLAGS, "-c", os.path.join(ROOT, "msa_amd", "csrc", f + ".hip"), "-o", o]))
+    procs.append(subprocess.Popen([HIPCC, *FLAGS, "-DMMB_STAMPS", "-c", os.path.join(CSRC, s), "-o", o]))
 for p in procs:
     assert p.wait() == 0
 lib = os.path.join(OUT, "libmmbert_hip_stamps.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs])
+subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs])
 print(lib)
